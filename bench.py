@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the FCVSR per-frame forward hot path on MI355X (contract: see the task prompt / DESIGN.md section 6).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one pass of the hot path (model(lrs)) over one batch of `--batch` synthetic 7-frame windows of
@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_TFLOPS = {"f32": 157.3, "bf16": 2500.0, "f16": 2500.0}   # MI355X dense MFMA peaks (MI355X_MICROARCH.md)
+DUMP_BYTES = 64 * 10 ** 6                                     # --dump-outputs: all files together stay under this
 
 
 def conv_flops_live(model_name: str, H: int, W: int) -> float:
@@ -155,6 +156,29 @@ def self_launch(n: int) -> int:
                     p.kill()
             break
     return rc
+
+
+def dump_outputs(out_dir: str, name: str, y, budget: int = DUMP_BYTES) -> dict:
+    """--dump-outputs: the output of the last timed step as `out_dir/<name>.npy` (float32, shape as returned).  An output larger
+    than `budget` is written as a fixed sample instead: `<name>_sample.npy` (float32 values) and `<name>_sample_index.npy` (their
+    flat indices, float64 - exact below 2**53), drawn from a seeded generator so that every run picks the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    y = y.detach().float()
+    n = y.numel()
+    if n * 4 <= budget - 4096:                                  # 4096: headroom for the .npy header
+        files = {f"{name}.npy": y.cpu().numpy()}
+    else:
+        k = (budget - 8192) // 12                               # 4 bytes per value + 8 per index
+        rs = np.random.RandomState(12345)
+        idx = np.unique(rs.randint(0, n, size=k, dtype=np.int64))
+        vals = y.reshape(-1)[torch.from_numpy(idx).to(y.device)].cpu().numpy()
+        files = {f"{name}_sample.npy": vals, f"{name}_sample_index.npy": idx.astype(np.float64)}
+    for fn, a in files.items():
+        np.save(os.path.join(out_dir, fn), a)
+    return {"dir": out_dir, "files": {fn: list(a.shape) for fn, a in files.items()}, "shape": list(y.shape),
+            "sampled": len(files) > 1}
 
 
 def build_info():
@@ -324,7 +348,14 @@ def main():
     ap.add_argument("--stub", action="store_true",
                     help="launch-plumbing rehearsal without a GPU: the step is a no-op on CPU tensors and the line says so "
                          "(metric 'stub'); used by tests/test_dist_cpu.py with --backend gloo")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's output (rank 0) as DIR/sr.npy in float32 (a seeded "
+                         "sample if it exceeds 64 MB); inputs and weights are seeded, so runs with the same arguments compare")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # The launcher parent imports nothing that could open /dev/kfd (no torch, no HIP): a process that has initialised the
         # GPU must not fork + exec on this pool.  Devices are counted from the environment / sysfs; when neither can tell, the
@@ -405,6 +436,10 @@ def main():
         dt = float(t.item())
     assert bool(torch.isfinite(y).all())
     log(f"timed {args.steps} steps in {dt:.3f} s")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, "sr", y)
+        log(f"outputs dumped: {dumped}")
     frames = world * B * args.steps
     fps = frames / dt
 
@@ -609,6 +644,7 @@ def main():
                      "rccl_world": (dist.get_world_size() if world > 1 and dist.get_backend() == "nccl" else None)},
             "build": build_info(),
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "extras": extras, "train": train,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(line))
     if world > 1:

@@ -194,3 +194,38 @@ def test_bench_train_block_failure_is_collective():
                         "--steps", "2", "--warmup", "0"], env=_bench_env(), capture_output=True, text=True, timeout=300)
     rec = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert rec["train"] == {"steps_done": 3, "world": 2}
+
+
+def test_bench_dump_outputs_full_and_sampled(tmp_path):
+    """--dump-outputs: an output under the budget is written whole in float32; a larger one as the same seeded sample every
+    time, values and float64 flat indices, within the budget."""
+    import importlib.util
+    import numpy as np
+    import torch
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    y = torch.rand(2, 1, 48, 64, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    rec = bench.dump_outputs(str(tmp_path / "full"), "sr", y)
+    a = np.load(tmp_path / "full" / "sr.npy")
+    assert a.dtype == np.float32 and rec["sampled"] is False
+    assert np.array_equal(a, y.float().numpy())
+    budget = 8192 + 12 * 500
+    for d in ("s1", "s2"):
+        rec = bench.dump_outputs(str(tmp_path / d), "sr", y, budget=budget)
+        assert rec["sampled"] is True and rec["shape"] == [2, 1, 48, 64]
+    v1, i1 = np.load(tmp_path / "s1" / "sr_sample.npy"), np.load(tmp_path / "s1" / "sr_sample_index.npy")
+    assert v1.dtype == np.float32 and i1.dtype == np.float64 and 0 < len(v1) == len(i1) <= 500
+    assert np.array_equal(v1, y.float().numpy().reshape(-1)[i1.astype(np.int64)])
+    assert np.array_equal(i1, np.load(tmp_path / "s2" / "sr_sample_index.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= budget
+
+
+def test_bench_rejects_zero_steps():
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--stub", "--steps", "0"], env=_bench_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr
