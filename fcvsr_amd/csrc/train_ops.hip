@@ -58,13 +58,21 @@ __global__ __launch_bounds__(256) void pack_weight_multi_kernel(const long long*
 }
 
 // g_pre = g * act'(y) with y the activation's OUTPUT (LeakyReLU / ReLU: the sign of y is the sign of the pre-activation for a
-// positive slope; for slope 0 the y == 0 entries take the zero-side derivative like torch's threshold_backward).  4 floats per lane.
-__global__ __launch_bounds__(256) void act_bwd_kernel(const float4* __restrict__ g, const float4* __restrict__ y, float4* __restrict__ out,
-                                                      float slope, long long n4) {
+// positive slope; for slope 0 the y == 0 entries take the zero-side derivative like torch's threshold_backward).  4 floats per lane;
+// the n % 4 trailing elements (a layer with an odd number of output values) one per lane of block 0.
+__global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y, float* __restrict__ out,
+                                                      float slope, long long n) {
+  const long long n4 = n / 4;
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  const float4* y4 = reinterpret_cast<const float4*>(y);
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    const float4 a = g[i], b = y[i];
-    out[i] = make_float4(b.x > 0.f ? a.x : a.x * slope, b.y > 0.f ? a.y : a.y * slope, b.z > 0.f ? a.z : a.z * slope,
-                         b.w > 0.f ? a.w : a.w * slope);
+    const float4 a = g4[i], b = y4[i];
+    reinterpret_cast<float4*>(out)[i] = make_float4(b.x > 0.f ? a.x : a.x * slope, b.y > 0.f ? a.y : a.y * slope,
+                                                    b.z > 0.f ? a.z : a.z * slope, b.w > 0.f ? a.w : a.w * slope);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    out[i] = y[i] > 0.f ? g[i] : g[i] * slope;
   }
 }
 
@@ -272,10 +280,11 @@ extern "C" int fcvsr_pack_weights_mfma_multi(const long long* tab, int n_items, 
 
 extern "C" int fcvsr_act_bwd(const float* g, const float* y, float* out, float slope, long long n, void* stream) {
   FCVSR_CHECK_ARG(g && y && out, "null pointer");
-  FCVSR_CHECK_ARG(n % 4 == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)out % 16) == 0, "16-byte aligned, n % 4 == 0");
+  FCVSR_CHECK_ARG(n >= 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)out % 16) == 0, "16-byte aligned, n >= 0");
   const long long n4 = n / 4;
-  const int grid = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-  if (n4 > 0) hipLaunchKernelGGL(act_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float4*)g, (const float4*)y, (float4*)out, slope, n4);
+  const long long nb = (n4 + 255) / 256 > 0 ? (n4 + 255) / 256 : 1;     // block 0 also takes the tail
+  const int grid = (int)(nb < 4096 ? nb : 4096);
+  if (n > 0) hipLaunchKernelGGL(act_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, y, out, slope, n);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

@@ -620,6 +620,8 @@ extern "C" int fcvsr_conv2d_wgrad_mfma_eligible(int cin, int cout, int kh, int k
 // Same contract as fcvsr_conv2d_wgrad (f32 NHWC x / gy views, f32 (cout,cin,kh,kw) result), products in bf16 on the matrix cores.
 extern "C" int fcvsr_conv2d_wgrad_mfma(const fcvsr_view* x, const fcvsr_view* gy, int B, int H, int W, int kh, int kw, int stride, int pad,
                                        float* dw, float* scratch, long long scratch_elems, void* stream) {
+  float* const bias_out = g_wgrad_bias_out;              // one-shot: consumed before any early return, so it never outlives this call
+  g_wgrad_bias_out = nullptr;
   FCVSR_CHECK_ARG(x && gy && dw && scratch, "null argument");
   FCVSR_CHECK_ARG(x->dtype == FCVSR_F32 && gy->dtype == FCVSR_F32 && x->sc == 1 && gy->sc == 1 && x->ptr && gy->ptr,
                   "x and gy must be channel-contiguous f32 views");
@@ -632,8 +634,6 @@ extern "C" int fcvsr_conv2d_wgrad_mfma(const fcvsr_view* x, const fcvsr_view* gy
   a.Ho = H; a.Wo = W; a.cin = x->c; a.cout = gy->c;
   a.npix = (long long)B * H * W;
   a.n_slabs = wgrad_mfma_slabs(B, H, W, a.cin, a.cout);
-  float* const bias_out = g_wgrad_bias_out;
-  g_wgrad_bias_out = nullptr;                            // one-shot
   FCVSR_CHECK_ARG(scratch_elems >= (long long)a.n_slabs * ((long long)kh * kw * a.cin * a.cout + a.cout), "scratch too small (fcvsr_conv2d_wgrad_mfma_scratch_elems)");
   a.slab_pix = 0;
   a.partial = scratch; a.dw = dw; a.accumulate = g_wgrad_accumulate;
@@ -664,6 +664,8 @@ extern "C" long long fcvsr_conv2d_wgrad_mfma_groups_scratch_elems(const int* B, 
 
 extern "C" int fcvsr_conv2d_wgrad_mfma_groups(const fcvsr_view* xs, const fcvsr_view* gys, const int* B, const int* H, const int* W, int n_groups,
                                               int kh, int kw, int pad, float* dw, float* scratch, long long scratch_elems, void* stream) {
+  float* const bias_out = g_wgrad_bias_out;              // one-shot: consumed before any early return
+  g_wgrad_bias_out = nullptr;
   FCVSR_CHECK_ARG(xs && gys && B && H && W && dw && scratch, "null argument");
   FCVSR_CHECK_ARG(n_groups >= 1 && n_groups <= 3, "1..3 problems");
   const int cin = xs[0].c, cout = gys[0].c;
@@ -672,8 +674,6 @@ extern "C" int fcvsr_conv2d_wgrad_mfma_groups(const fcvsr_view* xs, const fcvsr_
   hipStream_t st = (hipStream_t)stream;
   int slab0 = 0, slabs_total = 0;
   for (int g = 0; g < n_groups; ++g) slabs_total += wgrad_mfma_slabs(B[g], H[g], W[g], cin, cout);
-  float* const bias_out = g_wgrad_bias_out;
-  g_wgrad_bias_out = nullptr;                            // one-shot
   FCVSR_CHECK_ARG(scratch_elems >= (long long)slabs_total * (per + cout), "scratch too small (fcvsr_conv2d_wgrad_mfma_groups_scratch_elems)");
   float* const dbp_all = bias_out ? scratch + (long long)slabs_total * per : nullptr;
   WgradArgs a;

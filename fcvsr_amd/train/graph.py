@@ -301,9 +301,10 @@ def forward_train(p: Dict[str, Tensor], x: Tensor, *, precision: str = "f32", fu
     if precision == "f32" or (T * C) % 64 == 0:
         feat = conv2d(x7, p["feat_extract.0.weight"], p["feat_extract.0.bias"], 1, "f32")
     else:
-        # 16-bit modes: the frame stack completed with zero channels to 64 and the weight with zero input columns, products in f16
-        # (8-bit pixel values stay exact, as in the inference engine): forward and weight gradient on the matrix cores - the exact-f32
-        # VALU weight gradient of this 7 -> 448 layer alone cost 1.1 ms per step
+        # 16-bit modes: the frame stack completed with zero channels to 64 and the weight with zero input columns, forward and weight
+        # gradient on the matrix cores - the exact-f32 VALU weight gradient of this 7 -> 448 layer alone cost 1.1 ms per step.  The
+        # forward rounds the inputs k/255 and the weight to f16 (k/255 is not exact in f16, unlike the inference engine's integer pixel
+        # values); the weight gradient's products are bf16 whatever the mode (fcvsr_conv2d_wgrad_mfma)
         cpad = (-(T * C)) % 64
         xz = torch.cat([x7, torch.zeros(B, cpad, H, W, dtype=x7.dtype, device=x7.device)], 1).contiguous(memory_format=torch.channels_last)
         feat = conv2d(xz, F.pad(p["feat_extract.0.weight"], (0, 0, 0, 0, 0, cpad)), p["feat_extract.0.bias"], 1, "f16")

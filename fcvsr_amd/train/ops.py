@@ -118,8 +118,13 @@ def clear_packed_weights(owner=None) -> None:
 
 
 def _nhwc(t: torch.Tensor) -> torch.Tensor:
-    """(B,C,H,W) any layout -> contiguous (B,H,W,C) view of a channels_last tensor."""
-    return t.permute(0, 2, 3, 1).contiguous()           # no copy when t is already channels_last
+    """(B,C,H,W) any layout -> contiguous (B,H,W,C) view of a channels_last tensor, with the dense strides."""
+    v = t.permute(0, 2, 3, 1).contiguous()               # no copy when t is already channels_last
+    # contiguous() keeps any stride of a size-1 dimension (an NCHW (B, C, 1, 1) gradient stays (C, 1, 1, 1)), which the kernels' stride
+    # alignment checks reject: restate the dense ones (same elements, no copy)
+    _, H, W, Cn = v.shape
+    dense = (H * W * Cn, W * Cn, Cn, 1)
+    return v if v.stride() == dense else v.as_strided(v.shape, dense)
 
 
 def packed_weight_mfma(w: torch.Tensor, tdt: torch.dtype, transposed: bool) -> torch.Tensor:
@@ -196,7 +201,9 @@ class _Conv2dFn(torch.autograd.Function):
     def forward(ctx, x, w, bias, stride, precision, act, slope):
         xv = _nhwc(x.float())
         out = _run_conv(xv, w, bias, stride, precision, act=act, slope=slope)
-        ctx.save_for_backward(xv, w, out if act != hip.ACT_NONE else None, bias)
+        # the activation backward reads the saved output as a dense (npix, cout) array: 1-3 output channels in a 16-bit mode come back as
+        # a strided view of a 4-channel buffer, which is compacted here
+        ctx.save_for_backward(xv, w, out.contiguous() if act != hip.ACT_NONE else None, bias)
         ctx.stride, ctx.precision, ctx.has_bias, ctx.act, ctx.slope = stride, precision, bias is not None, act, slope
         return out.permute(0, 3, 1, 2)                    # (B,Cout,Ho,Wo), channels_last in memory
 
@@ -251,6 +258,7 @@ class _Conv2dFn(torch.autograd.Function):
                 hip.check(fn(C.addressof(xd), C.addressof(gd), B, H, W, k, k, stride, k // 2, gw.data_ptr(), scratch.data_ptr(), n,
                              hip.stream_ptr()), "fcvsr_conv2d_wgrad")
         finally:
+            L.fcvsr_wgrad_set_bias_out(None, 0)                       # never leave the one-shot bias request armed
             if sink is not None:
                 L.fcvsr_wgrad_set_accumulate(0)
                 L.fcvsr_colsum_set_accumulate(0)
@@ -344,6 +352,7 @@ class _ConvLevelsFn(torch.autograd.Function):
                 hip.check(L.fcvsr_conv2d_wgrad_mfma_groups(xd, gd, Bs, Hs, Ws, n, k, k, k // 2, gw.data_ptr(), scratch.data_ptr(), ne, st),
                           "fcvsr_conv2d_wgrad_mfma_groups")
             finally:
+                L.fcvsr_wgrad_set_bias_out(None, 0)
                 L.fcvsr_wgrad_set_accumulate(0)
             if sink is not None:
                 gw = None

@@ -52,7 +52,8 @@ class FlatGradAllReduce:
         if self.flat is None or self.flat.device != dev:
             self.flat = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         for v, p in zip(self.flat.split(self.sizes), self.params):
-            if p.grad is None:
+            if p.grad is None:                                   # no gradient this step: the slice must not carry the last one's
+                v.zero_()
                 p.grad = v.view(p.shape)
             elif p.grad.data_ptr() != v.data_ptr():              # a gradient produced elsewhere (plain autograd): adopt its values
                 v.copy_(p.grad.reshape(-1))

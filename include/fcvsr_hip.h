@@ -116,7 +116,7 @@ int fcvsr_conv2d_wgrad_mfma(const fcvsr_view* x, const fcvsr_view* gy, int B, in
  * fcvsr_pack_weight_mfma: nn.Conv2d.weight (cout,cin,kh,kw) f32 -> the 16-bit operand layout of fcvsr_conv2d_mfma,
  *   [kh*kw][rows_pad][cols_pad] zero padded; transposed = 0: rows = cout, cols = cin (forward); transposed = 1: rows = cin,
  *   cols = cout, taps flipped (the input-gradient convolution).  One launch (the weights change every optimizer step).
- * fcvsr_act_bwd: out = g * (y > 0 ? 1 : slope), y = the activation's output (LeakyReLU / ReLU backward), n % 4 == 0, out may alias g.
+ * fcvsr_act_bwd: out = g * (y > 0 ? 1 : slope), y = the activation's output (LeakyReLU / ReLU backward), any n >= 0 (16-byte aligned pointers), out may alias g.
  * fcvsr_colsum: out[c] = sum over the npix rows of a dense (npix, C) f32 matrix (bias gradient), deterministic two-stage. */
 int fcvsr_pack_weight_mfma(const float* w, int cout, int cin, int kh, int kw, void* dst, int rows_pad, int cols_pad, int dtype,
                            int transposed, void* stream);
@@ -182,7 +182,8 @@ int fcvsr_iac_bwd_warp(const float* gv, const fcvsr_view* k1, const float* prev,
 /* One-shot request consumed by the next fcvsr_conv2d_wgrad_mfma / fcvsr_conv2d_wgrad_mfma_groups call of the calling thread: also write
  * (accumulate = 0) or add (1) dL/dbias[cout] = sum over pixels of gy (nn.Conv2d bias gradient; f32, fixed summation order) - the kernel
  * has the gy tiles in registers, the separate fcvsr_colsum launches go away.  Returns 1 if the weight-gradient form in use supports it
- * (default form), 0 otherwise (request ignored). */
+ * (default form), 0 otherwise (request ignored).  The request is consumed even when that call rejects its arguments; dbias = NULL
+ * disarms it. */
 int fcvsr_wgrad_set_bias_out(float* dbias, int accumulate);
 
 /* fcvsr_conv2d_wgrad_mfma summed over 1..3 problems that share the weight (the pyramid levels of a BlockRCB layer): one launch per

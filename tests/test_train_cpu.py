@@ -113,3 +113,29 @@ def test_two_rank_flat_allreduce_reproduces_the_batch_gradient_and_update():
         for a, p in zip(params, net.parameters()):
             assert np.abs(a - p.detach().numpy()).max() <= 1e-6
     assert np.array_equal(res[0][1], res[1][1])              # identical buffers on both ranks after the collective
+
+
+def test_flat_grad_bind_zeroes_the_slice_of_a_parameter_without_gradient():
+    """optimizer.zero_grad() (set_to_none) and then a backward that skips a parameter: bind() must attach a ZERO slice to it, not the
+    previous step's gradient (it would be all-reduced and applied again)."""
+    from fcvsr_amd.train.step import FlatGradAllReduce
+    torch.manual_seed(3)
+    a, b = torch.nn.Linear(5, 4), torch.nn.Linear(4, 3)
+    params = list(a.parameters()) + list(b.parameters())
+    ar = FlatGradAllReduce(params, "sum")
+    opt = torch.optim.SGD(params, lr=0.1)
+    x = torch.randn(6, 5)
+    ar.bind()
+    b(a(x)).square().sum().backward()                      # step 1: every parameter gets a gradient, in the flat buffer
+    flat = ar()
+    assert all(float(p.grad.abs().sum()) > 0 for p in params)
+    assert float(flat.abs().sum()) > 0
+    opt.zero_grad(set_to_none=True)
+    a(x).square().sum().backward()                         # step 2: b gets no gradient
+    ar.bind()
+    for p in b.parameters():
+        assert p.grad is not None and p.grad.data_ptr() >= ar.flat.data_ptr()
+        assert torch.equal(p.grad, torch.zeros_like(p))
+    a_ref = torch.autograd.grad(a(x).square().sum(), list(a.parameters()))
+    for p, r in zip(a.parameters(), a_ref):
+        assert torch.allclose(p.grad, r)
