@@ -186,6 +186,7 @@ class _GShiftBase(nn.Module):
         self.MFFRblock = MultiFreq_Refinment(dim=n, Freq_Inv=Freq_Inv, mode="gaussian")
         self.upconv_fuse = nn.Conv2d(n + n // 4 + n // 16, n, 3, 1, 1, bias=True)
         self._engine = None
+        self._packers = {}          # train precision -> fcvsr_amd.train.ops.WeightPacker of this model's training passes
         # arithmetic of the conv layers: "f32" = exact f32 (parity mode, default); "bf16" / "f16" = matrix cores with
         # 16-bit operands and f32 accumulation (activations stay f32 in HBM).  Not part of state_dict.
         self.precision = os.environ.get("FCVSR_PRECISION", "f32")
@@ -226,6 +227,20 @@ class _GShiftBase(nn.Module):
         if self._engine is not None:
             self._engine.invalidate()
 
+    def _train_precision(self) -> str:
+        return getattr(self, "train_precision", self.precision)
+
+    def train_packer(self):
+        """The packed-weight plan of this model's training passes at the current train precision (one per precision, kept for
+        the model's lifetime: a hipGraph captured by TrainStep points into it)."""
+        from ..train.ops import WeightPacker
+        prec = self._train_precision()
+        packer = self._packers.get(prec)
+        if packer is None or packer.owner() is not self:                   # (a deepcopy carries the source's packers)
+            object.__setattr__(self, "_packers", {**self._packers, prec: WeightPacker(self)})
+            packer = self._packers[prec]
+        return packer
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x: float (B, 7, C, H, W) in [0,1] on a HIP device -> (B, C, 4H, 4W).
 
@@ -237,7 +252,7 @@ class _GShiftBase(nn.Module):
             from ..train.graph import forward_train
             if x.dim() != 5 or x.shape[1] != self._in_frames or x.shape[2] != self._img_ch:
                 raise ValueError(f"expected (B,{self._in_frames},{self._img_ch},H,W) input, got {tuple(x.shape)}")
-            return forward_train(self.state_dict(keep_vars=True), x, precision=getattr(self, "train_precision", self.precision))
+            return forward_train(self.state_dict(keep_vars=True), x, precision=self._train_precision(), packer=self.train_packer())
         from ..engine import Engine
         if self._engine is None or self._engine._model() is not self:      # (a deepcopy carries the source's engine)
             object.__setattr__(self, "_engine", Engine(self))

@@ -112,7 +112,6 @@ __global__ __launch_bounds__(256) void colsum_stage1(const float* __restrict__ x
     __syncthreads();
   }
 }
-static thread_local int g_colsum_accumulate = 0;                // fcvsr_colsum_set_accumulate: out += instead of out = (see wgrad.hip)
 __global__ __launch_bounds__(256) void colsum_stage2(const float* __restrict__ part, int nblk, int C, float* __restrict__ out, int accumulate) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;       // 4 threads per column, fixed combination order
   __shared__ float sm[4][64];
@@ -295,14 +294,15 @@ extern "C" long long fcvsr_colsum_scratch_elems(long long npix, int C) {
   return (nblk > 0 ? nblk : 1) * C;
 }
 
-extern "C" int fcvsr_colsum(const float* x, long long npix, int C, float* out, float* scratch, long long scratch_elems, void* stream) {
+extern "C" int fcvsr_colsum(const float* x, long long npix, int C, float* out, float* scratch, long long scratch_elems, int accumulate,
+                            void* stream) {
   FCVSR_CHECK_ARG(x && out && scratch, "null pointer");
   FCVSR_CHECK_ARG(C >= 1 && npix >= 1, "empty matrix");
   const int rpb = colsum_rows(npix);
   const long long nblk = (npix + rpb - 1) / rpb;
   FCVSR_CHECK_ARG(scratch_elems >= nblk * C, "scratch too small");
   hipLaunchKernelGGL(colsum_stage1, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, x, npix, C, rpb, scratch);
-  hipLaunchKernelGGL(colsum_stage2, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, scratch, (int)nblk, C, out, g_colsum_accumulate);
+  hipLaunchKernelGGL(colsum_stage2, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, scratch, (int)nblk, C, out, accumulate ? 1 : 0);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }
@@ -338,7 +338,7 @@ extern "C" long long fcvsr_wgrad_cout1_scratch_elems(int B, int H, int C) {
 
 /* dw (1, C, 3, 3) of a 3x3 "same" convolution with one output channel; x dense (B,H,W,C) f32, gy dense (B,H,W) f32; C in {16, 32, 64} */
 extern "C" int fcvsr_wgrad_cout1(const float* x, const float* gy, int B, int H, int W, int C, float* dw, float* scratch, long long scratch_elems,
-                                 void* stream) {
+                                 int accumulate, void* stream) {
   FCVSR_CHECK_ARG(x && gy && dw && scratch, "null pointer");
   FCVSR_CHECK_ARG(C == 16 || C == 32 || C == 64, "C in {16, 32, 64}");
   const long long nrows = (long long)B * H;
@@ -349,37 +349,10 @@ extern "C" int fcvsr_wgrad_cout1(const float* x, const float* gy, int B, int H, 
   FCVSR_CHECK_ARG(((uintptr_t)x % 16) == 0, "x 16-byte aligned");
   hipLaunchKernelGGL(wgrad_cout1_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, gy, B, H, W, C, rpb, scratch);
   // column sums of the (nb, C*9) partial matrix in block order = dw in nn.Conv2d's (1, C, 3, 3) layout
-  hipLaunchKernelGGL(colsum_stage2, dim3((9 * C + 63) / 64), dim3(256), 0, (hipStream_t)stream, scratch, nb, 9 * C, dw, g_colsum_accumulate);
+  hipLaunchKernelGGL(colsum_stage2, dim3((9 * C + 63) / 64), dim3(256), 0, (hipStream_t)stream, scratch, nb, 9 * C, dw, accumulate ? 1 : 0);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }
-
-/* column sums over 1..3 dense (npix[g], C) matrices added together (the bias gradient of a layer applied to several pyramid levels):
- * stage 1 per matrix into consecutive block ranges of one scratch buffer, ONE ordered stage 2 */
-extern "C" long long fcvsr_colsum_groups_scratch_elems(const long long* npix, int n_groups, int C) {
-  long long nblk = 0;
-  for (int g = 0; g < n_groups; ++g) { const int rpb = colsum_rows(npix[g]); nblk += (npix[g] + rpb - 1) / rpb; }
-  return (nblk > 0 ? nblk : 1) * C;
-}
-
-extern "C" int fcvsr_colsum_groups(const float* const* xs, const long long* npix, int n_groups, int C, float* out, float* scratch,
-                                   long long scratch_elems, void* stream) {
-  FCVSR_CHECK_ARG(xs && npix && out && scratch && n_groups >= 1 && n_groups <= 3 && C >= 1, "bad arguments");
-  long long blk0 = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    FCVSR_CHECK_ARG(xs[g] && npix[g] >= 1, "empty matrix");
-    const int rpb = colsum_rows(npix[g]);
-    const long long nblk = (npix[g] + rpb - 1) / rpb;
-    FCVSR_CHECK_ARG(scratch_elems >= (blk0 + nblk) * C, "scratch too small");
-    hipLaunchKernelGGL(colsum_stage1, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, xs[g], npix[g], C, rpb, scratch + blk0 * C);
-    blk0 += nblk;
-  }
-  hipLaunchKernelGGL(colsum_stage2, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, scratch, (int)blk0, C, out, g_colsum_accumulate);
-  FCVSR_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" void fcvsr_colsum_set_accumulate(int on) { g_colsum_accumulate = on ? 1 : 0; }
 
 /* backward of fcvsr_corr_lookup: g = dL/dcorr restricted to the first x_count columns (view with >= (2r+1)^2 channels), x1f / x2f as in
  * the forward; gx1 / gx2: dense (B, H, Wf, pix_stride) f32 tensors that the caller has ZEROED (every element is written at most once) */

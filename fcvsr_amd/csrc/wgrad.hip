@@ -23,20 +23,11 @@ struct WgradArgs {
   float* partial;          // [n_slabs][kh*kw][cin][cout]
   float* dw;               // [cout][cin][kh][kw]
   int accumulate;          // 1: dw += the sum (the gradient buffer was zeroed at the start of the pass), 0: dw = the sum
-  // bias gradient fused into the matrix-core form 2 (fcvsr_wgrad_set_bias_out): per-slab column sums of gy [n_slabs][cout] -> dbias
+  // bias gradient fused into the matrix-core kernel (dbias of fcvsr_conv2d_wgrad_mfma): per-slab column sums of gy [n_slabs][cout] -> dbias
   float* dbp;
   float* dbias;
   int db_accumulate;
 };
-
-// Per-thread switch of the three weight-gradient entry points between "dw = sum" and "dw += sum": the training step keeps every
-// parameter gradient in one flat, pre-zeroed buffer and lets the reduction add straight into it, which removes autograd's
-// AccumulateGrad addition per parameter and pass (fcvsr_wgrad_set_accumulate; fcvsr_amd/train/ops.py).
-static thread_local int g_wgrad_accumulate = 0;
-// One-shot request consumed by the next fcvsr_conv2d_wgrad_mfma / _groups call of this thread: also produce dL/dbias = column sums of gy
-// (f32, fixed order) - the kernel has every gy tile in registers anyway, the stand-alone column-sum launches (two per layer) go away.
-static thread_local float* g_wgrad_bias_out = nullptr;
-static thread_local int g_wgrad_bias_accumulate = 0;
 
 constexpr int kWgCo = 16, kWgCi = 64, kWgPx = 32;
 
@@ -229,7 +220,7 @@ extern "C" long long fcvsr_conv2d_wgrad_scratch_elems(int B, int Ho, int Wo, int
 }
 
 extern "C" int fcvsr_conv2d_wgrad(const fcvsr_view* x, const fcvsr_view* gy, int B, int H, int W, int kh, int kw, int stride, int pad,
-                                  float* dw, float* scratch, long long scratch_elems, void* stream) {
+                                  float* dw, float* scratch, long long scratch_elems, int accumulate, void* stream) {
   FCVSR_CHECK_ARG(x && gy && dw && scratch, "null argument");
   FCVSR_CHECK_ARG(x->dtype == FCVSR_F32 && gy->dtype == FCVSR_F32 && x->sc == 1 && gy->sc == 1 && x->ptr && gy->ptr,
                   "x and gy must be channel-contiguous f32 views");
@@ -250,7 +241,7 @@ extern "C" int fcvsr_conv2d_wgrad(const fcvsr_view* x, const fcvsr_view* gy, int
   a.slab_pix = (a.npix + a.n_slabs - 1) / a.n_slabs;
   a.slab_pix = (a.slab_pix + kWgPx - 1) / kWgPx * kWgPx;
   a.partial = scratch;
-  a.dw = dw; a.accumulate = g_wgrad_accumulate;
+  a.dw = dw; a.accumulate = accumulate ? 1 : 0;
   a.dbp = nullptr; a.dbias = nullptr; a.db_accumulate = 0;
   hipStream_t st = (hipStream_t)stream;
   const int nco = (a.cout + kWgCo - 1) / kWgCo, nci = (a.cin + kWgCi - 1) / kWgCi;
@@ -276,12 +267,15 @@ extern "C" int fcvsr_conv2d_wgrad(const fcvsr_view* x, const fcvsr_view* gy, int
 //   dW[tap][co][ci] = sum_p gy[p][co] * x[p + tap][ci]   =  per tap a (64 x K) x (K x 64) GEMM with K = pixels
 //
 // The reduction runs over PIXELS, but NHWC keeps channels contiguous, so both MFMA operands (8 consecutive k per lane) need the
-// transposed image.  A workgroup transposes while staging: f32 -> bf16, ds_write_b16 into [channel][row][x] LDS images whose
-// channel pitch is padded by 16 bytes (conflict-free ds_read_b128 over 32 channels).  A tap's horizontal shift would misalign the
-// 16-byte fragment reads, so the input tile is stored three times, pre-shifted by kx - 1; vertical shifts are row offsets.
+// transposed image.  The workgroup stages its tiles PIXEL-major, as they lie in memory - 8 floats -> one 16-byte ds_write_b128 of
+// bf16 per lane - and lets the LDS do the transpose on the way out: ds_read_b64_tr_b16 hands lane i of a 16-lane group channel i of
+// 4 consecutive pixel records, which is exactly the "8 consecutive k of one row" the MFMA operands want when k runs over pixels.
 //   * workgroup = 256 threads = 4 waves = the 2 x 2 (cout, cin) fragment pairs of a 64 x 64 block, all 9 taps each: 9 f32
 //     accumulator fragments per wave (144 VGPRs) that persist over the workgroup's whole slab of 4 x 32 pixel tiles;
-//   * per 16-pixel k-step: 1 + 9 ds_read_b128 feed 9 MFMAs;
+//   * a tap's shift is a whole number of 128-byte pixel records, so ONE x image serves all nine taps, and a fragment of x row yy is
+//     read once for the (up to three) taps that use it: 88 transposed 8-byte reads per wave and tile feed its 72 MFMAs;
+//   * records are 8 chunks of 16 bytes; chunk c of pixel record P sits in slot c ^ (4 * ((P >> 1) & 1)): the 4 rows x 2 blocks of a
+//     32-lane half then cover all 64 banks once, for any start pixel;
 //   * partial sums per slab go to the same scratch layout as the exact kernel and are added in slab order by
 //     wgrad_reduce_kernel: deterministic, no atomics.
 #include "mfma_util.h"
@@ -289,120 +283,7 @@ extern "C" int fcvsr_conv2d_wgrad(const fcvsr_view* x, const fcvsr_view* gy, int
 namespace fcvsr {
 
 constexpr int kGTY = 4, kGTX = 32;
-constexpr int kGyPitch = kGTY * kGTX * 2 + 16;          // bytes per cout row of the gy^T image (4 rows x 32 px bf16 + pad)
 
-template <int KS>
-__global__ __launch_bounds__(256, 1) void wgrad_mfma_kernel(WgradArgs a, int tiles_x, int tiles_y, int tiles_per_slab) {
-  constexpr int PAD = KS / 2, HY = kGTY + 2 * PAD, NKX = KS;
-  constexpr int kXPitch = HY * kGTX * 2 + 16;           // bytes per cin row of one pre-shifted x^T image
-  extern __shared__ __align__(16) unsigned char lds[];
-  unsigned char* gy_s = lds;                             // [64 co][kGyPitch]
-  unsigned char* x_s = lds + 64 * kGyPitch;              // [NKX][64 ci][kXPitch]
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int mf = wave >> 1, nf = wave & 1;               // this wave's (cout, cin) fragment pair
-  const int nci = a.cin / 64;
-  const int co0 = (blockIdx.y / nci) * 64, ci0 = (blockIdx.y % nci) * 64;
-  const int slab = blockIdx.x;
-  const int total_tiles = a.B * tiles_x * tiles_y;
-  const int t_begin = slab * tiles_per_slab;
-  int t_end = t_begin + tiles_per_slab;
-  if (t_end > total_tiles) t_end = total_tiles;
-
-  f32x16_t acc[KS * KS];
-#pragma unroll
-  for (int t = 0; t < KS * KS; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int b = tile / (tiles_x * tiles_y);
-    const int t2 = tile - b * tiles_x * tiles_y;
-    const int ty0 = (t2 / tiles_x) * kGTY, tx0 = (t2 % tiles_x) * kGTX;
-    __syncthreads();                                     // the previous tile's images are no longer read
-    // ---- gy tile -> gy^T image: thread = (pixel, 4-cout quad), 16 quads per pixel, 16 pixels per pass -----------------------
-    {
-      const int q = tid & 15, p0 = tid >> 4;
-      for (int p = p0; p < kGTY * kGTX; p += 16) {
-        const int y = p >> 5, x = p & 31;
-        const int gyy = ty0 + y, gxx = tx0 + x;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (gyy < a.Ho && gxx < a.Wo)
-          v = *reinterpret_cast<const float4*>(a.gy.p + (long long)b * a.gy.sb + (long long)gyy * a.gy.sy + (long long)gxx * a.gy.sx + co0 + q * 4);
-        const uint2 pk = cvt4<true>(v);
-        unsigned char* d = gy_s + (q * 4) * kGyPitch + (y * kGTX + x) * 2;
-        *reinterpret_cast<uint16_t*>(d) = (uint16_t)(pk.x & 0xffff);
-        *reinterpret_cast<uint16_t*>(d + kGyPitch) = (uint16_t)(pk.x >> 16);
-        *reinterpret_cast<uint16_t*>(d + 2 * kGyPitch) = (uint16_t)(pk.y & 0xffff);
-        *reinterpret_cast<uint16_t*>(d + 3 * kGyPitch) = (uint16_t)(pk.y >> 16);
-      }
-    }
-    // ---- x halo tile -> NKX pre-shifted x^T images: image kx holds x[.., tx0 + xx + kx - PAD] at column xx ---------------------
-    {
-      constexpr int HXW = kGTX + 2 * PAD;                // halo width
-      const int q = tid & 15, p0 = tid >> 4;
-      for (int p = p0; p < HY * HXW; p += 16) {
-        const int hy = p / HXW, hx = p - hy * HXW;
-        const int iy = ty0 + hy - PAD, ix = tx0 + hx - PAD;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-          v = *reinterpret_cast<const float4*>(a.x.p + (long long)b * a.x.sb + (long long)iy * a.x.sy + (long long)ix * a.x.sx + ci0 + q * 4);
-        const uint2 pk = cvt4<true>(v);
-        const uint16_t e0 = (uint16_t)(pk.x & 0xffff), e1 = (uint16_t)(pk.x >> 16), e2 = (uint16_t)(pk.y & 0xffff), e3 = (uint16_t)(pk.y >> 16);
-#pragma unroll
-        for (int kx = 0; kx < NKX; ++kx) {
-          const int xx = hx - kx;                        // column of this halo pixel in image kx
-          if (xx >= 0 && xx < kGTX) {
-            unsigned char* d = x_s + ((kx * 64 + q * 4) * kXPitch) + (hy * kGTX + xx) * 2;
-            *reinterpret_cast<uint16_t*>(d) = e0;
-            *reinterpret_cast<uint16_t*>(d + kXPitch) = e1;
-            *reinterpret_cast<uint16_t*>(d + 2 * kXPitch) = e2;
-            *reinterpret_cast<uint16_t*>(d + 3 * kXPitch) = e3;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    // ---- 8 k-steps of 16 pixels (row y, half s): A = gy^T[co][k], B = x^T[kx][ci][row y + ky][k] ---------------------------------
-    const unsigned char* ga = gy_s + (mf * 32 + r) * kGyPitch + h * 16;
-    const unsigned char* xa = x_s + (nf * 32 + r) * kXPitch + h * 16;
-#pragma unroll
-    for (int ks = 0; ks < kGTY * 2; ++ks) {
-      const int y = ks >> 1, s = ks & 1;
-      const uint4 af = *reinterpret_cast<const uint4*>(ga + (y * kGTX + s * 16) * 2);
-#pragma unroll
-      for (int t = 0; t < KS * KS; ++t) {
-        const int ky = t / KS, kx = t - ky * KS;
-        const uint4 bf = *reinterpret_cast<const uint4*>(xa + kx * 64 * kXPitch + ((y + ky) * kGTX + s * 16) * 2);
-        acc[t] = mfma<true>(af, bf, acc[t]);
-      }
-    }
-  }
-  // ---- partial[slab][tap][ci][co]: lane (r = ci, h) holds couts (i&3) + 8 (i>>2) + 4h of its fragment ---------------------------
-  float* pp = a.partial + ((long long)slab * (KS * KS)) * a.cin * a.cout;
-#pragma unroll
-  for (int t = 0; t < KS * KS; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int co = co0 + mf * 32 + 8 * g + 4 * h, ci = ci0 + nf * 32 + r;
-      *reinterpret_cast<float4*>(pp + ((long long)t * a.cin + ci) * a.cout + co) =
-          make_float4(acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]);
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Second form (round 3): the same products without the transposing stores.  The workgroup stages its tiles PIXEL-major, as they
-// lie in memory - 8 floats -> one 16-byte ds_write_b128 of bf16 per lane (the first form issues four 2-byte ds_write_b16 per
-// 4 channels, three times over for the pre-shifted x images: ~12 us of staging per 4 x 32 tile) - and lets the LDS do the
-// transpose on the way out: ds_read_b64_tr_b16 hands lane i of a 16-lane group channel i of 4 consecutive pixel records, which is
-// exactly the "8 consecutive k of one row" the MFMA operands want when k runs over pixels.  A tap's shift is a whole number of
-// 128-byte pixel records, so ONE x image serves all nine taps, and a fragment of x row yy is read once for the (up to three)
-// taps that use it: 88 transposed 8-byte reads per wave and tile feed its 72 MFMAs (first form: 80 ds_read_b128).
-// Records are 8 chunks of 16 bytes; chunk c of pixel record P sits in slot c ^ (4 * ((P >> 1) & 1)): the 4 rows x 2 blocks of a
-// 32-lane half then cover all 64 banks once, for any start pixel.  Same MFMA instruction, same k order per tap: results are
-// bit-identical to the first form.
 typedef __attribute__((ext_vector_type(4))) short wg_s4_t;
 
 __device__ __forceinline__ uint2 lds_tr16(const unsigned char* p) {
@@ -576,52 +457,24 @@ static int wgrad_mfma_slabs(int B, int Ho, int Wo, int cin, int cout) {
   return n;
 }
 
-// FCVSR_WGRAD_FORM: 2 (default) = wgrad_tr_kernel (pixel-major images, transposing LDS reads), 1 = wgrad_mfma_kernel (transposing stores)
-static int launch_wgrad_mfma(const WgradArgs& a, dim3 grid, int kh, int tiles_x, int tiles_y, int per_slab, hipStream_t st) {
-  static const int form = getenv("FCVSR_WGRAD_FORM") ? atoi(getenv("FCVSR_WGRAD_FORM")) : 2;
-  if (form == 2) {
-    if (kh == 3) hipLaunchKernelGGL(wgrad_tr_kernel<3>, grid, dim3(256), 0, st, a, tiles_x, tiles_y, per_slab);
-    else hipLaunchKernelGGL(wgrad_tr_kernel<1>, grid, dim3(256), 0, st, a, tiles_x, tiles_y, per_slab);
-    return 0;
-  }
-  if (kh == 3) {
-    const size_t ldsb = 64 * kGyPitch + 3 * 64 * ((kGTY + 2) * kGTX * 2 + 16);
-    static DevOnce attr3;
-    hipError_t e = once_per_device(attr3, [&] {
-      return hipFuncSetAttribute((const void*)wgrad_mfma_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    });
-    if (e != hipSuccess) { set_error("fcvsr_conv2d_wgrad_mfma: %s", hipGetErrorString(e)); return (int)e; }
-    hipLaunchKernelGGL(wgrad_mfma_kernel<3>, grid, dim3(256), ldsb, st, a, tiles_x, tiles_y, per_slab);
-  } else {
-    const size_t ldsb = 64 * kGyPitch + 64 * (kGTY * kGTX * 2 + 16);
-    hipLaunchKernelGGL(wgrad_mfma_kernel<1>, grid, dim3(256), ldsb, st, a, tiles_x, tiles_y, per_slab);
-  }
-  return 0;
+static void launch_wgrad_mfma(const WgradArgs& a, dim3 grid, int kh, int tiles_x, int tiles_y, int per_slab, hipStream_t st) {
+  if (kh == 3) hipLaunchKernelGGL(wgrad_tr_kernel<3>, grid, dim3(256), 0, st, a, tiles_x, tiles_y, per_slab);
+  else hipLaunchKernelGGL(wgrad_tr_kernel<1>, grid, dim3(256), 0, st, a, tiles_x, tiles_y, per_slab);
 }
 
 extern "C" long long fcvsr_conv2d_wgrad_mfma_scratch_elems(int B, int Ho, int Wo, int cin, int cout, int kh, int kw) {
   return (long long)wgrad_mfma_slabs(B, Ho, Wo, cin, cout) * ((long long)kh * kw * cin * cout + cout);      // + the bias partials
 }
 
-/* One-shot: the next fcvsr_conv2d_wgrad_mfma / fcvsr_conv2d_wgrad_mfma_groups call of this thread also writes (accumulate = 0) or adds
- * (1) dL/dbias = sum over pixels of gy into dbias[cout].  Returns 1 when the build's weight-gradient form supports it (form 2), else 0
- * (the request is then ignored: use fcvsr_colsum). */
-extern "C" int fcvsr_wgrad_set_bias_out(float* dbias, int accumulate) {
-  static const int form = getenv("FCVSR_WGRAD_FORM") ? atoi(getenv("FCVSR_WGRAD_FORM")) : 2;
-  if (form != 2) return 0;
-  g_wgrad_bias_out = dbias; g_wgrad_bias_accumulate = accumulate ? 1 : 0;
-  return 1;
-}
-
 extern "C" int fcvsr_conv2d_wgrad_mfma_eligible(int cin, int cout, int kh, int kw, int stride, int pad) {
   return (kh == kw && (kh == 1 || kh == 3) && stride == 1 && pad == kh / 2 && cin % 64 == 0 && cout % 64 == 0) ? 1 : 0;
 }
 
-// Same contract as fcvsr_conv2d_wgrad (f32 NHWC x / gy views, f32 (cout,cin,kh,kw) result), products in bf16 on the matrix cores.
+// Same contract as fcvsr_conv2d_wgrad (f32 NHWC x / gy views, f32 (cout,cin,kh,kw) result), products in bf16 on the matrix cores;
+// dbias != NULL: also the column sums of gy (the bias gradient).
 extern "C" int fcvsr_conv2d_wgrad_mfma(const fcvsr_view* x, const fcvsr_view* gy, int B, int H, int W, int kh, int kw, int stride, int pad,
-                                       float* dw, float* scratch, long long scratch_elems, void* stream) {
-  float* const bias_out = g_wgrad_bias_out;              // one-shot: consumed before any early return, so it never outlives this call
-  g_wgrad_bias_out = nullptr;
+                                       float* dw, float* dbias, float* scratch, long long scratch_elems, int dw_accumulate,
+                                       int dbias_accumulate, void* stream) {
   FCVSR_CHECK_ARG(x && gy && dw && scratch, "null argument");
   FCVSR_CHECK_ARG(x->dtype == FCVSR_F32 && gy->dtype == FCVSR_F32 && x->sc == 1 && gy->sc == 1 && x->ptr && gy->ptr,
                   "x and gy must be channel-contiguous f32 views");
@@ -636,15 +489,15 @@ extern "C" int fcvsr_conv2d_wgrad_mfma(const fcvsr_view* x, const fcvsr_view* gy
   a.n_slabs = wgrad_mfma_slabs(B, H, W, a.cin, a.cout);
   FCVSR_CHECK_ARG(scratch_elems >= (long long)a.n_slabs * ((long long)kh * kw * a.cin * a.cout + a.cout), "scratch too small (fcvsr_conv2d_wgrad_mfma_scratch_elems)");
   a.slab_pix = 0;
-  a.partial = scratch; a.dw = dw; a.accumulate = g_wgrad_accumulate;
-  a.dbp = bias_out ? scratch + (long long)a.n_slabs * kh * kw * a.cin * a.cout : nullptr;
-  a.dbias = bias_out; a.db_accumulate = g_wgrad_bias_accumulate;
+  a.partial = scratch; a.dw = dw; a.accumulate = dw_accumulate ? 1 : 0;
+  a.dbp = dbias ? scratch + (long long)a.n_slabs * kh * kw * a.cin * a.cout : nullptr;
+  a.dbias = dbias; a.db_accumulate = dbias_accumulate ? 1 : 0;
   const int tiles_x = cdiv(W, kGTX), tiles_y = cdiv(H, kGTY);
   const int total = B * tiles_x * tiles_y;
   const int per_slab = (total + a.n_slabs - 1) / a.n_slabs;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a.n_slabs, (a.cin / 64) * (a.cout / 64));
-  { const int e = launch_wgrad_mfma(a, grid, kh, tiles_x, tiles_y, per_slab, st); if (e) return e; }
+  launch_wgrad_mfma(a, grid, kh, tiles_x, tiles_y, per_slab, st);
   FCVSR_LAUNCH_CHECK();
   const long long n = (long long)a.cout * a.cin * kh * kw;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 63) / 64 + (a.dbp ? (a.cout + 63) / 64 : 0))), dim3(256), 0, st, a);
@@ -663,9 +516,8 @@ extern "C" long long fcvsr_conv2d_wgrad_mfma_groups_scratch_elems(const int* B, 
 }
 
 extern "C" int fcvsr_conv2d_wgrad_mfma_groups(const fcvsr_view* xs, const fcvsr_view* gys, const int* B, const int* H, const int* W, int n_groups,
-                                              int kh, int kw, int pad, float* dw, float* scratch, long long scratch_elems, void* stream) {
-  float* const bias_out = g_wgrad_bias_out;              // one-shot: consumed before any early return
-  g_wgrad_bias_out = nullptr;
+                                              int kh, int kw, int pad, float* dw, float* dbias, float* scratch, long long scratch_elems,
+                                              int dw_accumulate, int dbias_accumulate, void* stream) {
   FCVSR_CHECK_ARG(xs && gys && B && H && W && dw && scratch, "null argument");
   FCVSR_CHECK_ARG(n_groups >= 1 && n_groups <= 3, "1..3 problems");
   const int cin = xs[0].c, cout = gys[0].c;
@@ -675,7 +527,7 @@ extern "C" int fcvsr_conv2d_wgrad_mfma_groups(const fcvsr_view* xs, const fcvsr_
   int slab0 = 0, slabs_total = 0;
   for (int g = 0; g < n_groups; ++g) slabs_total += wgrad_mfma_slabs(B[g], H[g], W[g], cin, cout);
   FCVSR_CHECK_ARG(scratch_elems >= (long long)slabs_total * (per + cout), "scratch too small (fcvsr_conv2d_wgrad_mfma_groups_scratch_elems)");
-  float* const dbp_all = bias_out ? scratch + (long long)slabs_total * per : nullptr;
+  float* const dbp_all = dbias ? scratch + (long long)slabs_total * per : nullptr;
   WgradArgs a;
   for (int g = 0; g < n_groups; ++g) {
     const fcvsr_view* x = xs + g, *gy = gys + g;
@@ -690,13 +542,13 @@ extern "C" int fcvsr_conv2d_wgrad_mfma_groups(const fcvsr_view* xs, const fcvsr_
     a.n_slabs = wgrad_mfma_slabs(B[g], H[g], W[g], cin, cout);
     FCVSR_CHECK_ARG(scratch_elems >= (long long)(slab0 + a.n_slabs) * per, "scratch too small (fcvsr_conv2d_wgrad_mfma_groups_scratch_elems)");
     a.slab_pix = 0;
-    a.partial = scratch + (long long)slab0 * per; a.dw = dw; a.accumulate = g_wgrad_accumulate;
-    a.dbp = dbp_all ? dbp_all + (long long)slab0 * cout : nullptr; a.dbias = bias_out; a.db_accumulate = g_wgrad_bias_accumulate;
+    a.partial = scratch + (long long)slab0 * per; a.dw = dw; a.accumulate = dw_accumulate ? 1 : 0;
+    a.dbp = dbp_all ? dbp_all + (long long)slab0 * cout : nullptr; a.dbias = dbias; a.db_accumulate = dbias_accumulate ? 1 : 0;
     const int tiles_x = cdiv(W[g], kGTX), tiles_y = cdiv(H[g], kGTY);
     const int total = B[g] * tiles_x * tiles_y;
     const int per_slab = (total + a.n_slabs - 1) / a.n_slabs;
     const dim3 grid(a.n_slabs, (cin / 64) * (cout / 64));
-    { const int e = launch_wgrad_mfma(a, grid, kh, tiles_x, tiles_y, per_slab, st); if (e) return e; }
+    launch_wgrad_mfma(a, grid, kh, tiles_x, tiles_y, per_slab, st);
     FCVSR_LAUNCH_CHECK();
     slab0 += a.n_slabs;
   }
@@ -707,6 +559,3 @@ extern "C" int fcvsr_conv2d_wgrad_mfma_groups(const fcvsr_view* xs, const fcvsr_
   FCVSR_LAUNCH_CHECK();
   return 0;
 }
-
-extern "C" void fcvsr_wgrad_set_accumulate(int on) { g_wgrad_accumulate = on ? 1 : 0; }
-extern "C" int fcvsr_wgrad_get_accumulate(void) { return g_wgrad_accumulate; }

@@ -74,11 +74,11 @@ SIGNATURES = {
     "fcvsr_debug_res_stamps": [C.c_void_p, C.c_size_t],
     "fcvsr_conv2d_wgrad_scratch_elems": [C.c_int] * 7,
     "fcvsr_conv2d_wgrad": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                           C.c_longlong, C.c_void_p],
+                           C.c_longlong, C.c_int, C.c_void_p],
     "fcvsr_conv2d_wgrad_mfma_eligible": [C.c_int] * 6,
     "fcvsr_conv2d_wgrad_mfma_scratch_elems": [C.c_int] * 7,
     "fcvsr_conv2d_wgrad_mfma": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                C.c_longlong, C.c_void_p],
+                                C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p],
     "fcvsr_abi_version": [],
     "fcvsr_device_count": [],
     "fcvsr_conv2d": [C.POINTER(ConvDesc), _VP],
@@ -123,23 +123,17 @@ SIGNATURES = {
     "fcvsr_pack_weights_mfma_multi": [_VP, _I, _I, _I, _VP],
     "fcvsr_act_bwd": [_VP, _VP, _VP, _F, C.c_longlong, _VP],
     "fcvsr_colsum_scratch_elems": [C.c_longlong, _I],
-    "fcvsr_colsum": [_VP, C.c_longlong, _I, _VP, _VP, C.c_longlong, _VP],
+    "fcvsr_colsum": [_VP, C.c_longlong, _I, _VP, _VP, C.c_longlong, _I, _VP],
     "fcvsr_iac_bwd_sac": [_VP, _VP, _VP, _VP, _PV, _F, _I, _I, _I, _I, _VP, _I, _VP, _PV, _I, _VP],
     "fcvsr_iac_bwd_warp": [_VP, _PV, _VP, _PV, _I, _I, _I, _I, _VP, _VP, _VP],
     "fcvsr_prelu_fwd": [_VP, _VP, _VP, C.c_longlong, _VP],
     "fcvsr_prelu_bwd": [_VP, _VP, _VP, _VP, _VP, _VP, C.c_longlong, _VP],
     "fcvsr_wgrad_cout1_scratch_elems": [_I, _I, _I],
-    "fcvsr_wgrad_cout1": [_VP, _VP, _I, _I, _I, _I, _VP, _VP, C.c_longlong, _VP],
-    "fcvsr_wgrad_set_bias_out": [_VP, _I],
+    "fcvsr_wgrad_cout1": [_VP, _VP, _I, _I, _I, _I, _VP, _VP, C.c_longlong, _I, _VP],
     "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": [_VP, _VP, _VP, _I, _I, _I, _I, _I],
-    "fcvsr_conv2d_wgrad_mfma_groups": [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.c_longlong, _VP],
-    "fcvsr_colsum_groups_scratch_elems": [_VP, _I, _I],
-    "fcvsr_colsum_groups": [_VP, _VP, _I, _I, _VP, _VP, C.c_longlong, _VP],
+    "fcvsr_conv2d_wgrad_mfma_groups": [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, C.c_longlong, _I, _I, _VP],
     "fcvsr_up2_adjoint": [_VP, _VP, _I, _I, _I, _I, _VP],
     "fcvsr_pool2_adjoint": [_VP, _VP, _I, _I, _I, _I, _VP],
-    "fcvsr_wgrad_set_accumulate": [_I],
-    "fcvsr_wgrad_get_accumulate": [],
-    "fcvsr_colsum_set_accumulate": [_I],
     "fcvsr_rcbt_nblk": [_I],
     "fcvsr_rcbt_stat_elems": [],
     "fcvsr_rcbt_forward": [_VP, _VP, _VP, _VP, _VP, _F, _I, _I, _I, _VP, _VP, _VP, C.c_longlong, _VP],
@@ -151,10 +145,9 @@ SIGNATURES = {
                                    C.c_longlong, _I, _VP],
     "fcvsr_corr_lookup_bwd": [_VP, _VP, _I64, _I, _I, _I, _I, _I, _I, _PV, _VP, _VP, _VP],
 }
-_RESTYPES = {"fcvsr_wgrad_set_accumulate": None, "fcvsr_colsum_set_accumulate": None, "fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
+_RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
-             "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong,
-             "fcvsr_colsum_groups_scratch_elems": C.c_longlong}
+             "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong}
 
 
 def lib() -> C.CDLL:

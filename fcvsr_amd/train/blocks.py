@@ -6,6 +6,7 @@ from __future__ import annotations
 import torch
 
 from .. import hip
+from .ops import grad_destinations
 
 
 def _nhwc(t: torch.Tensor) -> torch.Tensor:
@@ -29,7 +30,7 @@ class _RcbTailFn(torch.autograd.Function):
                                        out.data_ptr(), stats.data_ptr(), scratch.data_ptr(), scratch.numel(), hip.stream_ptr()),
                   "fcvsr_rcbt_forward")
         ctx.save_for_backward(rv, wm, a1, a2, stats, wmask, w1, w2)
-        ctx.slope, ctx.shapes = slope, (wmask.shape, w1.shape, w2.shape)
+        ctx.slope = slope
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -40,24 +41,13 @@ class _RcbTailFn(torch.autograd.Function):
         L = hip.lib()
         nblk = L.fcvsr_rcbt_nblk(H * W)
         gr = torch.empty_like(rv)
-        from .ops import _grad_sink
-        sinks = [_grad_sink(p) for p in (p_wm, p_w1, p_w2)]
-        inplace = all(s_ is not None for s_ in sinks)                      # add into the flat gradient buffer (ops.accumulate_into_grad)
-        if inplace:
-            dwm, dw1, dw2 = sinks
-        else:
-            dwm = torch.empty(Cn, dtype=torch.float32, device=rv.device)
-            dw1 = torch.empty(Cn * Cn, dtype=torch.float32, device=rv.device)
-            dw2 = torch.empty(Cn * Cn, dtype=torch.float32, device=rv.device)
+        (dwm, dw1, dw2), acc, grads = grad_destinations(p_wm, p_w1, p_w2)   # one kernel, one accumulate flag: all parameters or none
         n = B * nblk * Cn + B * (Cn + 1) + 4 + 2 * B * Cn * Cn
         scratch = torch.empty(n, dtype=torch.float32, device=rv.device)
         hip.check(L.fcvsr_rcbt_backward(rv.data_ptr(), gv.data_ptr(), wm.data_ptr(), a1.data_ptr(), a2.data_ptr(), stats.data_ptr(), ctx.slope,
                                         B, H * W, Cn, gr.data_ptr(), dwm.data_ptr(), dw1.data_ptr(), dw2.data_ptr(), scratch.data_ptr(), n,
-                                        int(inplace), hip.stream_ptr()), "fcvsr_rcbt_backward")
-        if inplace:
-            return gr.permute(0, 3, 1, 2), g, None, None, None, None
-        s0, s1, s2 = ctx.shapes
-        return gr.permute(0, 3, 1, 2), g, dwm.reshape(s0), dw1.reshape(s1), dw2.reshape(s2), None
+                                        acc, hip.stream_ptr()), "fcvsr_rcbt_backward")
+        return (gr.permute(0, 3, 1, 2), g, *grads, None)
 
 
 def rcb_tail(r: torch.Tensor, z: torch.Tensor, wmask: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, slope: float = 0.2) -> torch.Tensor:
@@ -97,27 +87,15 @@ class _DivEnhBandFn(torch.autograd.Function):
         L = hip.lib()
         nblk = L.fcvsr_divenh_band_nblk(H * W)
         gf, gsf_o, gso_o = torch.empty_like(fv), torch.empty_like(fv), torch.empty_like(fv)
-        from .ops import _grad_sink
-        sinks = [_grad_sink(p) for p in (p_a, p_b, p_w1, p_w2)]
-        inplace = all(s_ is not None for s_ in sinks)
-        if inplace:
-            ga, gb, dw1, dw2 = sinks
-        else:
-            ga = torch.empty(Cn, dtype=torch.float32, device=fv.device)
-            gb = torch.empty(Cn, dtype=torch.float32, device=fv.device)
-            dw1 = torch.empty(CR * Cn, dtype=torch.float32, device=fv.device)
-            dw2 = torch.empty(Cn * CR, dtype=torch.float32, device=fv.device)
+        (ga, gb, dw1, dw2), acc, grads = grad_destinations(p_a, p_b, p_w1, p_w2)
         n = B * nblk * 2 * Cn + 2 * B * Cn + 2 * B * Cn * CR
         scratch = torch.empty(n, dtype=torch.float32, device=fv.device)
         hip.check(L.fcvsr_divenh_band_backward(fv.data_ptr(), sfv.data_ptr(), sov.data_ptr(), av.data_ptr(), bv.data_ptr(), a1.data_ptr(),
                                                a2.data_ptr(), stats.data_ptr(), hv.data_ptr(), ov.data_ptr(), B, H * W, Cn, gf.data_ptr(),
                                                gsf_o.data_ptr(), gso_o.data_ptr(), ga.data_ptr(), gb.data_ptr(), dw1.data_ptr(),
-                                               dw2.data_ptr(), scratch.data_ptr(), n, int(inplace), hip.stream_ptr()),
+                                               dw2.data_ptr(), scratch.data_ptr(), n, acc, hip.stream_ptr()),
                   "fcvsr_divenh_band_backward")
-        outs = tuple(t.permute(0, 3, 1, 2) for t in (gf, gsf_o, gso_o))
-        if inplace:
-            return outs + (None, None, None, None)
-        return outs + (ga.reshape(p_a.shape), gb.reshape(p_b.shape), dw1.reshape(p_w1.shape), dw2.reshape(p_w2.shape))
+        return (*(t.permute(0, 3, 1, 2) for t in (gf, gsf_o, gso_o)), *grads)
 
 
 def divenh_band(f, sf, so, a, b, w1, w2):

@@ -3,8 +3,13 @@ through (`sr = model(frames)`; `loss.backward()`, CVSR_train/train_LD_freqCVSR_S
 CVSR_train/arch/CVSR_freq.py:2611-2646 / :2688-2756, specification SURVEY.md Appendix A).
 
 Every nn.Conv2d of the path (98 % of the FLOPs) runs on the HIP kernels in all three directions through
-`fcvsr_amd.train.ops.conv2d`; the remaining operators (FFTs, CorrBlock lookup, bilinear warp, separable adaptive 3-tap
-convolution, ContextBlock softmax pool, bilinear resampling) are device-side torch operators whose backward torch derives.
+`fcvsr_amd.train.ops.conv2d` / `conv2d_levels`.  Most other operators are HIP autograd Functions too, forward and backward:
+the frequency transforms (`fft.py`: spectrum packing, the offset-field inverse transform, the band split), the CorrBlock lookup,
+both IAC alignment directions (warp + separable adaptive 3-tap convolution), the RCB tail with its ContextBlock, the DivEnh bands,
+PReLU and BlockRCB's cross-scale sums (`blocks.py`).  What is left to torch operators (and torch's derived backward) is light
+elementwise and layout work: concatenations, slices, PixelShuffle, sums and products of whole tensors, the CALayer vectors, the
+first DivEnh band and the bilinear up-sampling of the base image.  `fused_blocks=False` runs every non-convolution operator as
+torch ops instead (the tests' reference).
 This is the training counterpart of `fcvsr_amd.engine` (inference: every operator a hand-written kernel, no autograd); it is
 selected automatically by the drop-in modules when gradients are required.  Device tensors only - no CPU fallback.
 
@@ -13,7 +18,7 @@ selected automatically by the drop-in modules when gradients are required.  Devi
 from __future__ import annotations
 
 import math
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 import torch.nn.functional as F
@@ -21,19 +26,19 @@ import torch.nn.functional as F
 from ..engine import band_masks_half
 from .blocks import corr_lookup, divenh_band, iac_both, prelu, rcb_tail, xscale
 from .fft import irfft_pair, spec_pack, split_bands
-from .ops import clear_packed_weights, conv2d, conv2d_levels
+from .ops import WeightPacker, conv2d, conv2d_levels
 
 Tensor = torch.Tensor
 
 
 class _Ctx:
-    def __init__(self, p: Dict[str, Tensor], precision: str, fused_blocks: bool = True):
-        self.p, self.precision = p, precision
+    def __init__(self, p: Dict[str, Tensor], precision: str, fused_blocks: bool = True, packer: Optional[WeightPacker] = None):
+        self.p, self.precision, self.packer = p, precision, packer
         self.fused_blocks = fused_blocks                # False: every non-convolution operator as torch ops (the test reference)
 
     def conv(self, key: str, x: Tensor, stride: int = 1, act=None, slope: float = 0.0) -> Tensor:
         """nn.Conv2d + optional LeakyReLU / ReLU evaluated in the HIP kernel's epilogue (one launch)."""
-        return conv2d(x, self.p[key + ".weight"], self.p.get(key + ".bias"), stride, self.precision, act, slope)
+        return conv2d(x, self.p[key + ".weight"], self.p.get(key + ".bias"), stride, self.precision, act, slope, self.packer)
 
     def conv_padded(self, key: str, parts: List[Tensor], act=None, slope: float = 0.0) -> Tensor:
         """conv(cat(parts)) for a layer whose input-channel count is not a multiple of 64 (upconv_fuse 84, upconv1_L2_2 80, convcorr.0
@@ -44,10 +49,10 @@ class _Ctx:
         cin = w.shape[1]
         cpad = (-cin) % 64
         if self.precision == "f32" or cpad == 0 or w.shape[2] not in (1, 3):
-            return conv2d(torch.cat(parts, 1), w, b, 1, self.precision, act, slope)
+            return conv2d(torch.cat(parts, 1), w, b, 1, self.precision, act, slope, self.packer)
         ref = parts[0]
         z = torch.zeros(ref.shape[0], cpad, ref.shape[2], ref.shape[3], dtype=ref.dtype, device=ref.device)
-        return conv2d(torch.cat(list(parts) + [z], 1), F.pad(w, (0, 0, 0, 0, 0, cpad)), b, 1, self.precision, act, slope)
+        return conv2d(torch.cat(list(parts) + [z], 1), F.pad(w, (0, 0, 0, 0, 0, cpad)), b, 1, self.precision, act, slope, self.packer)
 
     def conv_s2(self, key: str, x: Tensor) -> Tensor:
         """3x3 stride-2 convolution (rconcat1/2, :2594-2595).  16-bit modes: the stride-1 layer on the matrix cores, sub-sampled - 4x
@@ -59,7 +64,7 @@ class _Ctx:
     def chain(self, key: str, t: Tensor, n: int) -> Tensor:
         """n bias-free 1x1 convolutions with ReLU in between (convfuse / convcrt / convcorr, CVSR_freq.py:1371-1396)."""
         for li in range(n):
-            t = conv2d(t, self.p[f"{key}.{2 * li}.weight"], None, 1, self.precision, "relu" if li < n - 1 else None)
+            t = conv2d(t, self.p[f"{key}.{2 * li}.weight"], None, 1, self.precision, "relu" if li < n - 1 else None, packer=self.packer)
         return t
 
     def ca(self, key: str, z: Tensor) -> Tensor:
@@ -164,8 +169,8 @@ def _mgaa(c: _Ctx, key: str, x: Tensor, A: int) -> Tensor:
     corr = corr_lookup(x1f, x2f) if c.fused_blocks else _corr_lookup(x1f, x2f)   # forward pair only, reused for both directions (:1487-1488)
     flow0 = torch.zeros(2 * B, 2, H, x1f.shape[-1], dtype=x.dtype, device=x.device)
     t = c.conv_padded(key + ".convcorr.0", [off, torch.cat([corr, corr], 0), flow0], act="relu")       # 211 -> 64 (:1379-1385)
-    t = conv2d(t, c.p[key + ".convcorr.2.weight"], None, 1, c.precision, "relu")
-    off = conv2d(t, c.p[key + ".convcorr.4.weight"], None, 1, c.precision)
+    t = conv2d(t, c.p[key + ".convcorr.2.weight"], None, 1, c.precision, "relu", packer=c.packer)
+    off = conv2d(t, c.p[key + ".convcorr.4.weight"], None, 1, c.precision, packer=c.packer)
     sim2 = torch.cat([sim, sim], 0)
     offs: List[List[Tensor]] = [[], []]
     for i in range(A):
@@ -247,7 +252,7 @@ def _context_block(c: _Ctx, key: str, r: Tensor) -> Tensor:
 def _block_rcb(c: _Ctx, key: str, xs: List[Tensor]) -> List[Tensor]:
     def lv(name, ts, act=None, slope=0.0):
         """one nn.Conv2d on every pyramid level (shared weights): grouped launches where the layer allows"""
-        return conv2d_levels(ts, c.p[name + ".weight"], c.p.get(name + ".bias"), c.precision, act, slope)
+        return conv2d_levels(ts, c.p[name + ".weight"], c.p.get(name + ".bias"), c.precision, act, slope, c.packer)
 
     zs = lv(key + ".body.2", lv(key + ".body.0", xs, "lrelu", 0.1))
     rs = lv(key + ".RCB.body.2", lv(key + ".RCB.body.0", zs, "lrelu", 0.2))
@@ -274,13 +279,16 @@ def _scnet(c: _Ctx, key: str, xs: List[Tensor], G: int) -> List[Tensor]:
         t = cur
         for k in range(3):
             t = _block_rcb(c, f"{key}.body.{g}.body.{k}", t)
-        cv = conv2d_levels(t, c.p[f"{key}.body.{g}.conv.weight"], c.p.get(f"{key}.body.{g}.conv.bias"), c.precision)
+        cv = conv2d_levels(t, c.p[f"{key}.body.{g}.conv.weight"], c.p.get(f"{key}.body.{g}.conv.bias"), c.precision, packer=c.packer)
         cur = [a + r for a, r in zip(cur, cv)]
     return [x + r for x, r in zip(xs, cur)]
 
 
-def forward_train(p: Dict[str, Tensor], x: Tensor, *, precision: str = "f32", fused_blocks: bool = True) -> Tensor:
-    """x: (B,7,C,H,W) device tensor in [0,1] -> (B,C,4H,4W), differentiable w.r.t. every live parameter in `p`."""
+def forward_train(p: Dict[str, Tensor], x: Tensor, *, precision: str = "f32", fused_blocks: bool = True,
+                  packer: Optional[WeightPacker] = None) -> Tensor:
+    """x: (B,7,C,H,W) device tensor in [0,1] -> (B,C,4H,4W), differentiable w.r.t. every live parameter in `p`.
+    `packer`: the WeightPacker of this parameter set at this precision (one per model and train precision, kept across passes: it
+    replays the 16-bit weight packings of a pass as one launch).  None: every convolution packs its weight per call."""
     if not x.is_cuda:
         raise RuntimeError("fcvsr_amd.train needs device tensors (the HIP path has no CPU fallback)")
     n = p["conv_last0.weight"].shape[1]
@@ -290,16 +298,12 @@ def forward_train(p: Dict[str, Tensor], x: Tensor, *, precision: str = "f32", fu
     B, T, C, H, W = x.shape
     if H % 4 or W % 4:
         raise ValueError("H and W must be multiples of 4 (3-level pyramid, reference BlockRCB :766-777)")
-    # The packed 16-bit weight operands are cached per (storage pointer, version) for the duration of ONE forward + backward pass (a
-    # layer applied several times packs once).  Across passes the cache must not survive: the optimizer rewrites every weight, and a
-    # freed model's storage can be handed to another parameter of the same shape and version.  Clearing here also guarantees that a
-    # hipGraph capture records the packing kernels of its pass.
-    first, last = next(iter(p.values())), p["conv_last0.weight"]
-    clear_packed_weights(owner=(first.data_ptr(), last.data_ptr(), len(p), precision, str(first.device)))
-    c = _Ctx(p, precision, fused_blocks)
+    if packer is not None:
+        packer.begin_pass()
+    c = _Ctx(p, precision, fused_blocks, packer)
     x7 = x.reshape(B, T * C, H, W).float()
     if precision == "f32" or (T * C) % 64 == 0:
-        feat = conv2d(x7, p["feat_extract.0.weight"], p["feat_extract.0.bias"], 1, "f32")
+        feat = conv2d(x7, p["feat_extract.0.weight"], p["feat_extract.0.bias"], 1, "f32", packer=packer)
     else:
         # 16-bit modes: the frame stack completed with zero channels to 64 and the weight with zero input columns, forward and weight
         # gradient on the matrix cores - the exact-f32 VALU weight gradient of this 7 -> 448 layer alone cost 1.1 ms per step.  The
@@ -307,7 +311,7 @@ def forward_train(p: Dict[str, Tensor], x: Tensor, *, precision: str = "f32", fu
         # values); the weight gradient's products are bf16 whatever the mode (fcvsr_conv2d_wgrad_mfma)
         cpad = (-(T * C)) % 64
         xz = torch.cat([x7, torch.zeros(B, cpad, H, W, dtype=x7.dtype, device=x7.device)], 1).contiguous(memory_format=torch.channels_last)
-        feat = conv2d(xz, F.pad(p["feat_extract.0.weight"], (0, 0, 0, 0, 0, cpad)), p["feat_extract.0.bias"], 1, "f16")
+        feat = conv2d(xz, F.pad(p["feat_extract.0.weight"], (0, 0, 0, 0, 0, cpad)), p["feat_extract.0.bias"], 1, "f16", packer=packer)
     f1, f2, f3 = feat[:, :3 * n], feat[:, 3 * n:4 * n], feat[:, 4 * n:]
     a13 = _mgaa(c, "MGAA", torch.cat([f1, f3], 0), A)               # the two outer calls share the weights: one call on 2B samples
     a1, a3 = a13[:B], a13[B:]
@@ -325,6 +329,6 @@ def forward_train(p: Dict[str, Tensor], x: Tensor, *, precision: str = "f32", fu
     fz = c.conv("recorb0", c.conv_padded("upconv_fuse", [o0, l2, l3_2]))
     u = _ps2(_prelu(c.conv("upconv1", fz), a))                      # PReLU (one shared slope) commutes with the shuffle: same values,
     u = _ps2(_prelu(c.conv("upconv2", u), a))                       # and the activation then runs on the dense conv output
-    out = conv2d(u, p["conv_last0.weight"], p["conv_last0.bias"], 1, precision)   # (16-bit modes: a 4-channel MFMA layer, rows 1..3 zero)
+    out = conv2d(u, p["conv_last0.weight"], p["conv_last0.bias"], 1, precision, packer=packer)   # (16-bit modes: 4-channel MFMA layer, rows 1..3 zero)
     base = F.interpolate(x[:, T // 2].float(), scale_factor=4, mode="bilinear", align_corners=False)
     return out + base

@@ -107,7 +107,7 @@ class TrainStep:
         self.allreduce.zero()                              # one fill: every .grad is a view of the flat buffer
         sr = self.model(lr_frames)
         loss = self.loss_fn(sr, hr)
-        with accumulate_into_grad():                       # the HIP reductions add weight / bias gradients straight into it
+        with accumulate_into_grad(self.allreduce.flat):    # the HIP reductions add weight / bias gradients straight into it
             loss.backward()
         return loss
 
@@ -135,17 +135,20 @@ class TrainStep:
             with torch.cuda.stream(side):
                 for _ in range(2):
                     self.allreduce.zero()
-                    with accumulate_into_grad():
+                    with accumulate_into_grad(self.allreduce.flat):
                         self.loss_fn(self.model(sx), sh).backward()
             torch.cuda.current_stream(lr_frames.device).wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 self.allreduce.flat.zero_()                  # gradients accumulate into the static flat buffer
                 loss = self.loss_fn(self.model(sx), sh)
-                with accumulate_into_grad():
+                with accumulate_into_grad(self.allreduce.flat):
                     loss.backward()
-            ent = self._graphs[key] = (graph, sx, sh, loss)
-        graph, sx, sh, loss = ent
+            # the graph holds raw pointers into the packed-weight plan that was live at capture (fcvsr_amd.train.ops.WeightPacker):
+            # keep that plan alive with the graph, whatever the model's packer does later
+            packer = self.model.train_packer() if hasattr(self.model, "train_packer") else None
+            ent = self._graphs[key] = (graph, sx, sh, loss, packer.plan if packer is not None else None)
+        graph, sx, sh, loss, _ = ent
         sx.copy_(lr_frames)
         sh.copy_(hr)
         graph.replay()

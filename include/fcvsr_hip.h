@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define FCVSR_ABI_VERSION 1
+#define FCVSR_ABI_VERSION 2
 
 enum { FCVSR_E_ARG = -1, FCVSR_E_UNSUPPORTED = -2, FCVSR_E_NOGPU = -3 };
 enum { FCVSR_F32 = 0, FCVSR_BF16 = 1, FCVSR_F16 = 2 };
@@ -102,16 +102,21 @@ int fcvsr_conv2d_f32mfma(const fcvsr_conv_desc* d, void* stream);
  * tap-flipped weight, so it goes through fcvsr_conv2d / fcvsr_conv2d_mfma; the weight gradient is this entry point:
  *   dw[co][ci][ky][kx] = sum_{b,oy,ox} gy[b,oy,ox,co] * x[b, oy*stride - pad + ky, ox*stride - pad + kx, ci]
  * x: (B,H,W,cin), gy: (B,Ho,Wo,cout), both channel-contiguous f32 views; dw: f32 (cout,cin,kh,kw) = nn.Conv2d.weight layout;
- * scratch: >= fcvsr_conv2d_wgrad_scratch_elems(...) floats.  Exact f32, fixed summation order (bit-reproducible). */
+ * scratch: >= fcvsr_conv2d_wgrad_scratch_elems(...) floats.  Exact f32, fixed summation order (bit-reproducible).
+ * accumulate = 1 ADDS the sum to dw instead of overwriting it (the same for every `accumulate` argument of the training path: the
+ * training step keeps every parameter gradient in one flat, pre-zeroed buffer and lets the reductions add straight into it). */
 long long fcvsr_conv2d_wgrad_scratch_elems(int B, int Ho, int Wo, int cin, int cout, int kh, int kw);
 int fcvsr_conv2d_wgrad(const fcvsr_view* x, const fcvsr_view* gy, int B, int H, int W, int kh, int kw, int stride, int pad,
-                       float* dw, float* scratch, long long scratch_elems, void* stream);
+                       float* dw, float* scratch, long long scratch_elems, int accumulate, void* stream);
 /* The same weight gradient with bf16 products on the matrix cores (f32 accumulation, deterministic slab order): 3x3 / 1x1,
- * stride 1, cin and cout multiples of 64 (fcvsr_conv2d_wgrad_mfma_eligible); same arguments and result layout. */
+ * stride 1, cin and cout multiples of 64 (fcvsr_conv2d_wgrad_mfma_eligible); same arguments and result layout.  dbias != NULL: the
+ * kernel also writes (dbias_accumulate = 0) or adds (1) dL/dbias[cout] = sum over pixels of gy (nn.Conv2d bias gradient; f32, fixed
+ * summation order) - it has the gy tiles in registers anyway.  dbias = NULL: no bias gradient. */
 int fcvsr_conv2d_wgrad_mfma_eligible(int cin, int cout, int kh, int kw, int stride, int pad);
 long long fcvsr_conv2d_wgrad_mfma_scratch_elems(int B, int Ho, int Wo, int cin, int cout, int kh, int kw);
 int fcvsr_conv2d_wgrad_mfma(const fcvsr_view* x, const fcvsr_view* gy, int B, int H, int W, int kh, int kw, int stride, int pad,
-                            float* dw, float* scratch, long long scratch_elems, void* stream);
+                            float* dw, float* dbias, float* scratch, long long scratch_elems, int dw_accumulate, int dbias_accumulate,
+                            void* stream);
 /* Training-path helpers (reference: the per-layer work of `loss.backward()` + `optimizer.step()`, train_LD_freqCVSR_S_22.py:244-251).
  * fcvsr_pack_weight_mfma: nn.Conv2d.weight (cout,cin,kh,kw) f32 -> the 16-bit operand layout of fcvsr_conv2d_mfma,
  *   [kh*kw][rows_pad][cols_pad] zero padded; transposed = 0: rows = cout, cols = cin (forward); transposed = 1: rows = cin,
@@ -127,7 +132,7 @@ int fcvsr_pack_weights_multi_block_elems(void);
 int fcvsr_pack_weights_mfma_multi(const long long* tab, int n_items, int total_blocks, int dtype, void* stream);
 int fcvsr_act_bwd(const float* g, const float* y, float* out, float slope, long long n, void* stream);
 long long fcvsr_colsum_scratch_elems(long long npix, int C);
-int fcvsr_colsum(const float* x, long long npix, int C, float* out, float* scratch, long long scratch_elems, void* stream);
+int fcvsr_colsum(const float* x, long long npix, int C, float* out, float* scratch, long long scratch_elems, int accumulate, void* stream);
 /* RCB tail with the ContextBlock under training (CVSR_freq.py:657-701 inside RCB.forward :705-725), dense (B, HW, 64) f32:
  *   out = LeakyReLU_slope(r + add(r)) + z,  add = W2 . LeakyReLU_slope(W1 . ctx),  ctx = sum_p softmax_p(wmask . r[p]) r[p].
  * forward: three launches; stats (B x fcvsr_rcbt_stat_elems() floats) is what the backward needs besides r;
@@ -158,9 +163,6 @@ int fcvsr_divenh_band_backward(const float* f, const float* sf, const float* so,
 /* backward of fcvsr_corr_lookup: g = dL/dcorr on the first x_count columns; gx1 / gx2 dense (B,H,Wf,pix_stride), ZEROED by the caller */
 int fcvsr_corr_lookup_bwd(const float* x1f, const float* x2f, int64_t pix_stride, int B, int H, int Wf, int C, int radius, int x_count,
                           const fcvsr_view* g, float* gx1_zeroed, float* gx2_zeroed, void* stream);
-long long fcvsr_colsum_groups_scratch_elems(const long long* npix, int n_groups, int C);
-int fcvsr_colsum_groups(const float* const* xs, const long long* npix, int n_groups, int C, float* out, float* scratch,
-                        long long scratch_elems, void* stream);   /* column sums of 1..3 matrices added together, one ordered second stage */
 /* PReLU with one shared slope (nn.PReLU(), CVSR_freq.py:2590 / ConvBlk :349), slope in device memory:
  *   fcvsr_prelu_fwd: y = x > 0 ? x : slope[0] * x;   fcvsr_prelu_bwd: gx and gslope[0] (two-stage sum; scratch >= 2048 floats). */
 int fcvsr_prelu_fwd(const float* x, const float* slope, float* y, long long n, void* stream);
@@ -168,7 +170,8 @@ int fcvsr_prelu_bwd(const float* g, const float* x, const float* slope, float* g
 /* Weight gradient of a 3x3 "same" convolution with ONE output channel (conv_last0, :2607): x dense (B,H,W,C) f32, gy dense (B,H,W) f32,
  * dw (1,C,3,3); C in {16, 32, 64}; x is read once; fixed summation order. */
 long long fcvsr_wgrad_cout1_scratch_elems(int B, int H, int C);
-int fcvsr_wgrad_cout1(const float* x, const float* gy, int B, int H, int W, int C, float* dw, float* scratch, long long scratch_elems, void* stream);
+int fcvsr_wgrad_cout1(const float* x, const float* gy, int B, int H, int W, int C, float* dw, float* scratch, long long scratch_elems,
+                      int accumulate, void* stream);
 /* Backward of one IAC iteration under training (CVSR_freq.py:1230-1250; forward = fcvsr_warp, fcvsr_sac_v, fcvsr_sac_h, which leave
  * s = flow_warp(prev, off) and v = SAC_v(s) in memory).  All tensors f32 NHWC; gy, yout (the iteration's output), v, s, gfin, gv, prev,
  * gprev dense (B,H,W,C); k1 / gk: views of the iteration's 3*C kernel channels inside the predictor output / its gradient.
@@ -179,30 +182,18 @@ int fcvsr_iac_bwd_sac(const float* gy, const float* yout, const float* v, const 
                       int W, int C, float* gfin, int fin_accumulate, float* gv, const fcvsr_view* gk, int k_accumulate, void* stream);
 int fcvsr_iac_bwd_warp(const float* gv, const fcvsr_view* k1, const float* prev, const fcvsr_view* off, int B, int H, int W, int C,
                        float* gprev_zeroed, float* goff, void* stream);
-/* One-shot request consumed by the next fcvsr_conv2d_wgrad_mfma / fcvsr_conv2d_wgrad_mfma_groups call of the calling thread: also write
- * (accumulate = 0) or add (1) dL/dbias[cout] = sum over pixels of gy (nn.Conv2d bias gradient; f32, fixed summation order) - the kernel
- * has the gy tiles in registers, the separate fcvsr_colsum launches go away.  Returns 1 if the weight-gradient form in use supports it
- * (default form), 0 otherwise (request ignored).  The request is consumed even when that call rejects its arguments; dbias = NULL
- * disarms it. */
-int fcvsr_wgrad_set_bias_out(float* dbias, int accumulate);
-
 /* fcvsr_conv2d_wgrad_mfma summed over 1..3 problems that share the weight (the pyramid levels of a BlockRCB layer): one launch per
  * problem into consecutive slab ranges of one scratch buffer and ONE ordered reduction (no per-level gradient tensors). */
 long long fcvsr_conv2d_wgrad_mfma_groups_scratch_elems(const int* B, const int* H, const int* W, int n_groups, int cin, int cout, int kh,
                                                        int kw);
 int fcvsr_conv2d_wgrad_mfma_groups(const fcvsr_view* xs, const fcvsr_view* gys, const int* B, const int* H, const int* W, int n_groups, int kh,
-                                   int kw, int pad, float* dw, float* scratch, long long scratch_elems, void* stream);
+                                   int kw, int pad, float* dw, float* dbias, float* scratch, long long scratch_elems, int dw_accumulate,
+                                   int dbias_accumulate, void* stream);
 /* Adjoints of the two resamplings inside fcvsr_xscale (BlockRCB cross-scale sum under training), f32 NHWC:
  *   fcvsr_up2_adjoint:   g (B,2H,2W,C) -> (B,H,W,C), transposed x2 bilinear up-sampling (align_corners = False, clamped);
  *   fcvsr_pool2_adjoint: g (B,H,W,C) -> (B,2H,2W,C), transposed 2x2 mean. */
 int fcvsr_up2_adjoint(const float* g, float* out, int B, int H, int W, int C, void* stream);
 int fcvsr_pool2_adjoint(const float* g, float* out, int B, int H, int W, int C, void* stream);
-/* Per-thread switches: while on, fcvsr_conv2d_wgrad / _mfma / _mfma_groups (dw) and fcvsr_colsum / _groups / fcvsr_wgrad_cout1 (out, dw)
- * ADD their result to the destination instead of overwriting it.  The training step keeps every parameter gradient in one flat,
- * pre-zeroed buffer and lets the reductions add straight into it (no AccumulateGrad addition per parameter and pass). */
-void fcvsr_wgrad_set_accumulate(int on);
-int fcvsr_wgrad_get_accumulate(void);
-void fcvsr_colsum_set_accumulate(int on);
 /* Diagnostic (FCVSR_RES_STAMPS=1 in the environment): copies the in-kernel cycle stamps the last resident-weight convolution
  * launch recorded for one workgroup, [wave 8][phase 64][slot 8] uint64, to host memory.  Not part of the data path. */
 int fcvsr_debug_res_stamps(void* host_out, size_t bytes);

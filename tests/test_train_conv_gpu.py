@@ -19,9 +19,6 @@ next to tau(n) (run with -s)."""
 import ctypes as C
 import contextlib
 import math
-import os
-import subprocess
-import sys
 import zlib
 
 import pytest
@@ -30,7 +27,6 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MMA = {"bf16": torch.bfloat16, "f16": torch.float16}
 SLOPE = 0.1
 
@@ -147,7 +143,8 @@ def run(prec, x, w, b, gy, stride, act, *, g0w=None, g0b=None, accumulate=False,
     if g0b is not None:
         bd.grad = g0b.cuda().clone()
     y = conv2d(xd, wd, bd, stride, prec, act, SLOPE if act == "lrelu" else 0.0)
-    with (accumulate_into_grad() if accumulate else contextlib.nullcontext()):
+    preset = [t.grad for t in (wd, bd) if t is not None and t.grad is not None]
+    with (accumulate_into_grad(*preset) if accumulate else contextlib.nullcontext()):
         y.backward(gy.cuda())
     torch.cuda.synchronize()
     yc = y.detach().float().cpu()
@@ -273,7 +270,8 @@ def run_levels(prec, xs, w, b, gys, *, g0w=None, g0b=None, accumulate=False, x_g
     ys = conv2d_levels(xds, wd, bd, prec, "lrelu", SLOPE)
     if prec in MMA:
         assert type(ys[0].grad_fn).__name__ == "_ConvLevelsFnBackward", "expected the grouped launches"
-    with (accumulate_into_grad() if accumulate else contextlib.nullcontext()):
+    preset = [t.grad for t in (wd, bd) if t.grad is not None]
+    with (accumulate_into_grad(*preset) if accumulate else contextlib.nullcontext()):
         torch.autograd.backward(ys, [gy.cuda() for gy in gys])
     torch.cuda.synchronize()
     yks = [y.detach().float().cpu() for y in ys]
@@ -364,65 +362,6 @@ def test_conv_levels_accumulate_mode_adds_into_existing_grad(prec):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# weight-gradient form 1 (FCVSR_WGRAD_FORM=1: wgrad_mfma_kernel, bias through fcvsr_colsum / fcvsr_colsum_groups) in a child process
-
-_FORM1_CHILD = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[1])
-from fcvsr_amd import hip
-from fcvsr_amd.train.ops import conv2d, conv2d_levels
-from fcvsr_amd.train.ops import accumulate_into_grad
-assert hip.lib().fcvsr_wgrad_set_bias_out(None, 0) == 0, "form 1 has no fused bias"
-d = torch.load(sys.argv[2])
-out = {}
-x = d["x"].cuda().contiguous(memory_format=torch.channels_last)
-w, b = d["w"].cuda().requires_grad_(True), d["b"].cuda().requires_grad_(True)
-conv2d(x, w, b, 1, "bf16", "lrelu", 0.1).backward(d["gy"].cuda())
-out["dw"], out["db"] = w.grad.cpu(), b.grad.cpu()
-xs = [t.cuda().contiguous(memory_format=torch.channels_last) for t in d["xs"]]
-lw, lb = d["lw"].cuda().requires_grad_(True), d["lb"].cuda().requires_grad_(True)
-ys = conv2d_levels(xs, lw, lb, "bf16", "lrelu", 0.1)
-assert type(ys[0].grad_fn).__name__ == "_ConvLevelsFnBackward"
-torch.autograd.backward(ys, [t.cuda() for t in d["gys"]])
-out["ldw"], out["ldb"] = lw.grad.cpu(), lb.grad.cpu()
-lw.grad, lb.grad = None, d["g0b"].cuda().clone()                  # fcvsr_colsum_groups in accumulate mode
-ys = conv2d_levels(xs, lw, lb, "bf16", "lrelu", 0.1)
-with accumulate_into_grad():
-    torch.autograd.backward(ys, [t.cuda() for t in d["gys"]])
-out["ldb_acc"] = lb.grad.cpu()
-torch.cuda.synchronize()
-torch.save(out, sys.argv[3])
-"""
-
-
-def test_weight_gradient_form1_matches_form2(tmp_path):
-    """FCVSR_WGRAD_FORM=1 (read once per process, so a fresh child): dw bit-identical to the default form, db (from fcvsr_colsum /
-    fcvsr_colsum_groups) within the bound, also in accumulate mode."""
-    assert os.environ.get("FCVSR_WGRAD_FORM", "2") == "2", "the parent must run the default form"
-    cin, cout, k, stride, B, H, W, _, _ = CASES["64-64-k3"]
-    g, x, w, b = make(21, B, cin, cout, k, H, W, True)
-    gy = torch.randn(B, cout, H, W, generator=g)
-    xs, lw, lb, gys = levels_inputs("64-64-k3", seed=22)
-    g0b = torch.randn(lb.shape, generator=g)
-    inp, res = tmp_path / "in.pt", tmp_path / "out.pt"
-    torch.save(dict(x=x, w=w, b=b, gy=gy, xs=xs, lw=lw, lb=lb, gys=gys, g0b=g0b), inp)
-    env = dict(os.environ, FCVSR_WGRAD_FORM="1")
-    p = subprocess.run([sys.executable, "-c", _FORM1_CHILD, ROOT, str(inp), str(res)], env=env, capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    f1 = torch.load(res)
-
-    got2, yk = run("bf16", x, w, b, gy, 1, "lrelu")
-    lgot2, lyks = run_levels("bf16", xs, lw, lb, gys)
-    assert torch.equal(f1["dw"], got2["dw"]), "form 1 and form 2 weight gradients differ"
-    assert torch.equal(f1["ldw"], lgot2["dw"]), "form 1 and form 2 grouped weight gradients differ"
-    db = reference("bf16", x, w, b, gy, yk, 1, "lrelu")["db"]
-    ldb = levels_reference("bf16", xs, lw, lb, gys, lyks)["db"]
-    check("form1 db", {"db": f1["db"], "ldb": f1["ldb"], "ldb_acc": f1["ldb_acc"]},
-          {"db": db, "ldb": ldb, "ldb_acc": (ldb[0] + g0b.double(), ldb[1] + g0b.double().abs(), ldb[2])})
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
 
 def test_first_layer_f16_training_path():
     """feat_extract in the 16-bit training modes (graph.forward_train): inputs k/255 zero-padded from 7 to 64 channels, precision "f16":
@@ -452,14 +391,13 @@ def test_first_layer_f16_training_path():
     print(f"[first layer f16] against the unrounded f64 result: forward max-abs / max {ey:.2e}, dw {edw:.2e}")
 
 
-def test_bias_request_never_outlives_a_rejected_call():
-    """fcvsr_wgrad_set_bias_out arms a one-shot request; a matrix-core weight gradient that rejects its arguments (cin = 48) must consume
-    it, so that the next, bias-free call does not write column sums into the stale buffer."""
+def test_rejected_wgrad_call_writes_neither_dw_nor_dbias():
+    """The bias gradient of the matrix-core weight gradient is an argument of the call: a call that rejects its arguments (cin = 48)
+    writes neither dw nor dbias, and the next call without a bias (dbias = NULL) leaves that buffer alone and gives the right dw."""
     from fcvsr_amd import hip
     L = hip.lib()
     st = hip.stream_ptr()
     sentinel = torch.full((256,), 7.0, device="cuda")
-    assert L.fcvsr_wgrad_set_bias_out(sentinel.data_ptr(), 0) == 1
     B, H, W, cout = 1, 8, 32, 64
     x48 = torch.randn(B, H, W, 48, device="cuda")
     gy = torch.randn(B, H, W, cout, device="cuda")
@@ -467,19 +405,21 @@ def test_bias_request_never_outlives_a_rejected_call():
     n48 = 4 * (9 * 64 * cout + cout)
     scratch48 = torch.zeros(n48, device="cuda")
     xv, gv = hip.view(x48), hip.view(gy)
-    rc = L.fcvsr_conv2d_wgrad_mfma(C.addressof(xv), C.addressof(gv), B, H, W, 3, 3, 1, 1, dw48.data_ptr(), scratch48.data_ptr(), n48, st)
+    rc = L.fcvsr_conv2d_wgrad_mfma(C.addressof(xv), C.addressof(gv), B, H, W, 3, 3, 1, 1, dw48.data_ptr(), sentinel.data_ptr(),
+                                   scratch48.data_ptr(), n48, 0, 0, st)
     assert rc != 0, "cin = 48 must be rejected"
     torch.cuda.synchronize()
     assert torch.equal(dw48, torch.zeros_like(dw48))        # nothing launched
+    assert torch.equal(sentinel, torch.full_like(sentinel, 7.0))
     x64 = torch.randn(B, H, W, 64, device="cuda")
     dw = torch.empty(cout * 64 * 9, device="cuda")
     n = L.fcvsr_conv2d_wgrad_mfma_scratch_elems(B, H, W, 64, cout, 3, 3)
     scratch = torch.empty(n, device="cuda")
     xv = hip.view(x64)
-    hip.check(L.fcvsr_conv2d_wgrad_mfma(C.addressof(xv), C.addressof(gv), B, H, W, 3, 3, 1, 1, dw.data_ptr(), scratch.data_ptr(), n, st),
-              "fcvsr_conv2d_wgrad_mfma")
+    hip.check(L.fcvsr_conv2d_wgrad_mfma(C.addressof(xv), C.addressof(gv), B, H, W, 3, 3, 1, 1, dw.data_ptr(), None, scratch.data_ptr(), n,
+                                        0, 0, st), "fcvsr_conv2d_wgrad_mfma")
     torch.cuda.synchronize()
-    assert torch.equal(sentinel, torch.full_like(sentinel, 7.0)), "the rejected call left the bias request armed"
+    assert torch.equal(sentinel, torch.full_like(sentinel, 7.0)), "a call without a bias wrote into the earlier call's bias buffer"
     ref = torch.nn.grad.conv2d_weight(x64.cpu().permute(0, 3, 1, 2).to(torch.bfloat16).double(), (cout, 64, 3, 3),
                                       gy.cpu().permute(0, 3, 1, 2).to(torch.bfloat16).double(), 1, 1)
     S = torch.nn.grad.conv2d_weight(x64.cpu().permute(0, 3, 1, 2).to(torch.bfloat16).double().abs(), (cout, 64, 3, 3),

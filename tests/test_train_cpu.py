@@ -139,3 +139,33 @@ def test_flat_grad_bind_zeroes_the_slice_of_a_parameter_without_gradient():
     a_ref = torch.autograd.grad(a(x).square().sum(), list(a.parameters()))
     for p, r in zip(a.parameters(), a_ref):
         assert torch.allclose(p.grad, r)
+
+
+def test_accumulate_into_grad_sinks_only_views_of_the_active_buffers():
+    """ops.accumulate_into_grad(flat): the reductions add into a parameter's .grad in place only while the context is open and only
+    if that .grad is a view of `flat` - not for a parameter with a dense f32 .grad of its own (another model's backward), and not
+    outside the context.  A kernel that writes several parameters with one flag gets all of them in place or none."""
+    from fcvsr_amd.train.ops import accumulate_into_grad, grad_destinations
+    flat = torch.zeros(17)
+    a, b = torch.nn.Parameter(torch.zeros(4, 3)), torch.nn.Parameter(torch.zeros(5))
+    a.grad = flat[5:].view(4, 3)                           # a slice of the flat buffer, not at its start
+    b.grad = torch.zeros(5)                                # dense f32, but its own storage
+
+    def sunk(p):
+        (d,), acc, (ret,) = grad_destinations(p)
+        if acc:
+            assert d.data_ptr() == p.grad.data_ptr() and ret is None
+        else:
+            assert ret is d and d.shape == p.shape and d.dtype == torch.float32 and d.data_ptr() != p.grad.data_ptr()
+        return bool(acc)
+
+    assert not sunk(a) and not sunk(b)
+    with accumulate_into_grad(flat):
+        assert sunk(a)
+        assert not sunk(b)
+        dests, acc, rets = grad_destinations(a, b)
+        assert acc == 0 and all(r is d for r, d in zip(rets, dests))
+        with accumulate_into_grad(b.grad):
+            assert sunk(a) and sunk(b)
+        assert not sunk(b)
+    assert not sunk(a) and not sunk(b)
