@@ -195,26 +195,14 @@ class _GShiftBase(nn.Module):
         # 16-bit modes only: store the spatial activations (extracted features, aligned features, SCNetbk trunk) in the
         # MFMA dtype instead of f32 - half the HBM bytes and staging instructions.  Spectra, offsets, MultiFreq_Refinment
         # internals, ContextBlock statistics and all accumulation stay f32.
-        self.trunk16 = os.environ.get("FCVSR_TRUNK16", "1") == "1"
+        self.trunk16 = True
+        # Fused forms of launch sequences (tests/test_hip_model_parity.py switches them off to compare):
         # 16-bit modes, n_features == 64: compute the adaptive kernels (F[1]) inside the IAC kernel instead of storing them
-        self.fold_f1 = os.environ.get("FCVSR_FOLD_F1", "1") == "1"
+        self.fold_f1 = True
         # 16-bit modes, S model (1x1 up-convs), one image channel: upconv2 + PixelShuffle + PReLU + conv_last0 in one kernel
-        self.fuse_tail = os.environ.get("FCVSR_FUSE_TAIL", "1") == "1"
-        # 16-bit modes: BlockRCB's down path as conv1x1(avgpool2(R)) (they commute) and level-grouped elementwise launches
-        self.pool_first = os.environ.get("FCVSR_POOL_FIRST", "1") == "1"
-        # 16-bit modes, n_features == 64: the convfuse 1x1 stack of MGAAbk as one kernel (hidden tensors stay on chip)
-        self.fuse_freq_mlp = os.environ.get("FCVSR_FUSE_FREQ_MLP", "1") == "1"
-        # 16-bit modes, 9*Cin <= 64 (the Y models): feat_extract as a single-K-step GEMM kernel
-        self.fast_feat = os.environ.get("FCVSR_FAST_FEAT", "1") == "1"
-        # 16-bit modes, n_features == 64: convcrt and (away from the CorrBlock strip) convcorr as one launch each
-        self.fuse_freq_head = os.environ.get("FCVSR_FUSE_FREQ_HEAD", "1") == "1"
-        # 16-bit modes, 16-bit trunk: ContextBlock partials from the stored r in their own launch (the conv then runs on the
-        # resident-weight kernel) instead of from the lean kernel's epilogue
-        self.gc_separate = os.environ.get("FCVSR_GC_SEPARATE", "1") == "1"
-        # MultiFreq_Refinment band split: all masked inverse transforms in one call (spectrum columns read once)
-        self.fuse_bands = os.environ.get("FCVSR_FUSE_BANDS", "1") == "1"
+        self.fuse_tail = True
         # 16-bit modes: BlockRCB's full-resolution level in one pass (R0 is never stored)
-        self.fuse_rcb_l0 = os.environ.get("FCVSR_FUSE_RCB_L0", "1") == "1"
+        self.fuse_rcb_l0 = True
         # capture the launch sequence of a forward in a hipGraph (per input shape) and replay it
         self.use_graph = os.environ.get("FCVSR_GRAPH", "0") == "1"
         # captured graphs kept per (shape, precision, streams, flags): least-recently-used entries beyond this are freed

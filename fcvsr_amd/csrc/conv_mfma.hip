@@ -29,7 +29,9 @@
 
 namespace fcvsr {
 
-constexpr int kTW = 32, kCK = 64, kLD = kCK + 8;  // tile cols, channel chunk, padded LDS row (halfwords); tile rows = 4*MW
+// tile rows (one per wave: 4-row tiles leave room for more co-resident workgroups in different phases; 8-row tiles measured
+// 0.85-1.0x), tile cols, channel chunk, padded LDS row (halfwords)
+constexpr int kTH = 4, kTW = 32, kCK = 64, kLD = kCK + 8;
 
 struct MGroup {
   View src[3];
@@ -62,7 +64,6 @@ struct MfmaArgs {
   const float* gc_wmask;   // ContextBlock fusion: per-wave online-softmax partials of the output (cout <= 64, 3x3)
   int planar;          // single f32 source with arbitrary channel stride (the NCHW frames of feat_extract), cin <= 64
   int sub2;            // stride-2 convolution: evaluate at full resolution, keep the even output pixels only
-  int dbg;             // ablation switches for profiling builds (FCVSR_MFMA_DBG): 1 skip staging, 2 skip MFMA, 4 skip stores, 8 skip weight loads
 };
 
 struct EpiCtx {
@@ -220,10 +221,9 @@ typedef __attribute__((address_space(1))) cm_f32x4_t cm_gfloat4_t;
 __device__ __forceinline__ uint4 gld_u4(long long addr) { const cm_u32x4_t v = *reinterpret_cast<const cm_guint4_t*>((unsigned long long)addr); return make_uint4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ float4 gld_f4(long long addr) { const cm_f32x4_t v = *reinterpret_cast<const cm_gfloat4_t*>((unsigned long long)addr); return make_float4(v.x, v.y, v.z, v.w); }
 
-template <bool BF16, int NT, int KS, int MW, bool WD>
-__global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 128 ? 3 : 4)) : 2) void conv_mfma_kernel(MfmaArgs a) {
+template <bool BF16, int NT, int KS>
+__global__ __launch_bounds__(256, 4) void conv_mfma_kernel(MfmaArgs a) {
   constexpr bool FLAT = KS == 1;                     // the host sets a.flat exactly for the 1x1 kernels
-  constexpr int kTH = 4 * MW;                       // MW tile rows (M-fragments) per wave
   constexpr int PAD = KS / 2;
   constexpr int HH = kTH + 2 * PAD, HWD = kTW + 2 * PAD;
   constexpr int NF = NT / 32;
@@ -267,13 +267,11 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
     tx0 = (t2 % G.tiles_x) * kTW;
   }
 
-  f32x16_t acc[MW][NF];
+  f32x16_t acc[NF];
 #pragma unroll
-  for (int m = 0; m < MW; ++m)
+  for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
-    for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[m][nf][i] = 0.f;
+    for (int i = 0; i < 16; ++i) acc[nf][i] = 0.f;
 
   for (int c0 = 0; c0 < a.cin16; c0 += kCK) {
     const int ck = (a.cin16 - c0) < kCK ? (a.cin16 - c0) : kCK;       // multiple of 16
@@ -289,7 +287,7 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
         const int hy = hp / HWD, hx = hp - hy * HWD;
         const int iy = ty0 + hy - PAD, ix = tx0 + hx - PAD;
         float v = 0.f;
-        if (c < a.cin_total && iy >= 0 && iy < G.H && ix >= 0 && ix < G.W && !(a.dbg & 1))
+        if (c < a.cin_total && iy >= 0 && iy < G.H && ix >= 0 && ix < G.W)
           v = sv.p[(long long)b * sv.sb + (long long)iy * sv.sy + (long long)ix * sv.sx + (long long)c * sv.sc];
         const uint2 pk = cvt4<BF16>(make_float4(v, 0.f, 0.f, 0.f));
         A_s[hp * kLD + c] = (uint16_t)(pk.x & 0xffff);
@@ -299,7 +297,7 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
       constexpr int ITERS = (NHP * 16 + 255) / 256;    // 16 channel-quads per pixel, 256 threads
       const int q = tid & 15;
       const int c = c0 + q * 4;
-      const bool cok = (c < a.cin_total) && !(a.dbg & 1);
+      const bool cok = c < a.cin_total;
       int s_ = 0, cl = c;
       if (cl >= a.seg_c[0]) { cl -= a.seg_c[0]; s_ = 1; if (cl >= a.seg_c[1]) { cl -= a.seg_c[1]; s_ = 2; } }
       // The lane's source depends on its channel quad: G.src[s_] with a lane-dependent index is a VECTOR load from the
@@ -349,7 +347,7 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
       constexpr int ITERS = (NHP * 8 + 255) / 256;
       const int q = tid & 7;
       const int c = c0 + q * 8;
-      const bool cok = (c < a.cin_total) && !(a.dbg & 1);
+      const bool cok = c < a.cin_total;
       int s_ = 0, cl = c;
       if (cl >= a.seg_c[0]) { cl -= a.seg_c[0]; s_ = 1; if (cl >= a.seg_c[1]) { cl -= a.seg_c[1]; s_ = 2; } }
       const int si = cok ? s_ : 0;                     // scalar view fields selected per lane, unconditional loads (see above)
@@ -390,50 +388,6 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
         }
       }
     }
-    if (WD) {
-      // ---- weights straight from L2/L1 into the MFMA B-operand registers: no LDS staging, NO barriers in the tap loop.
-      // Lane (r,h) of N-fragment nf needs W[tap][n0+nf*32+r][c0+kk*16+h*8 .. +8]: one 16-byte load.  The flattened
-      // (tap,kk) sequence is software-pipelined PD steps ahead through a register ring; waves free-run through the taps.
-      constexpr int S = KS * KS * 4;
-      constexpr int PD = NT == 128 ? 3 : 4;
-      const long long wtap = (long long)a.cout_pad * a.cin_pad;
-      const long long wrow32 = 32ll * a.cin_pad;
-      const uint16_t* wl = a.w + ((long long)n0 + r) * a.cin_pad + c0 + h * 8;
-      uint4 bq[PD][NF];
-#pragma unroll
-      for (int s0 = 0; s0 < PD && s0 < S; ++s0) {
-        const int tap = s0 >> 2, kk = s0 & 3;
-        if (kk * 16 < ck && !(a.dbg & 8)) {
-#pragma unroll
-          for (int nf = 0; nf < NF; ++nf)
-            bq[s0][nf] = *reinterpret_cast<const uint4*>(wl + tap * wtap + nf * wrow32 + kk * 16);
-        }
-      }
-      __syncthreads();                     // A_s visible
-#pragma unroll
-      for (int s1 = 0; s1 < S; ++s1) {
-        const int tap = s1 >> 2, kk = s1 & 3;
-        const int ky = tap / KS, kx = tap - ky * KS;
-        if (kk * 16 < ck && !(a.dbg & 2)) {
-          const uint16_t* arow0 = A_s + ((MW * wave + ky) * HWD + r + kx) * kLD + h * 8;
-          uint4 af[MW];
-#pragma unroll
-          for (int m = 0; m < MW; ++m) af[m] = *reinterpret_cast<const uint4*>(arow0 + m * HWD * kLD + kk * 16);
-#pragma unroll
-          for (int m = 0; m < MW; ++m)
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf) acc[m][nf] = mfma<BF16>(af[m], bq[s1 % PD][nf], acc[m][nf]);
-        }
-        if (s1 + PD < S) {
-          const int tap2 = (s1 + PD) >> 2, kk2 = (s1 + PD) & 3;
-          if (kk2 * 16 < ck && !(a.dbg & 8)) {
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf)
-              bq[s1 % PD][nf] = *reinterpret_cast<const uint4*>(wl + tap2 * wtap + nf * wrow32 + kk2 * 16);
-          }
-        }
-      }
-    } else {
     // ---- taps: weights global -> regs -> LDS, then MFMA ---------------------------------------------------------------
     uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0, w2 = w0, w3 = w0;   // named (not an array): must stay in VGPRs
     // weights for chunk columns beyond ck are never read by the MFMA loop (kk*16 < ck), but the 16-byte loads must stay
@@ -444,7 +398,6 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
 #define FCVSR_FETCH_W(TAP)                                                                             \
   do {                                                                                                 \
     const uint16_t* wp_ = wbase + (TAP) * wtap;                                                        \
-    if (a.dbg & 8) break;                                                                              \
     w0 = *reinterpret_cast<const uint4*>(wp_);                                                         \
     if (WLOADS > 1) w1 = *reinterpret_cast<const uint4*>(wp_ + wrow32);                                \
     if (WLOADS > 2) w2 = *reinterpret_cast<const uint4*>(wp_ + 2 * wrow32);                            \
@@ -464,23 +417,19 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
       __syncthreads();                   // A_s (first tap) and B_s visible
       if (tap + 1 < KS * KS) FCVSR_FETCH_W(tap + 1);
       const int ky = tap / KS, kx = tap - ky * KS;
-      const uint16_t* arow0 = A_s + ((MW * wave + ky) * HWD + r + kx) * kLD + h * 8;
+      const uint16_t* arow = A_s + ((wave + ky) * HWD + r + kx) * kLD + h * 8;
       const uint16_t* brow = B_s + r * kLD + h * 8;
 #pragma unroll
       for (int kk = 0; kk < kCK / 16; ++kk) {
-        if (kk * 16 < ck && !(a.dbg & 2)) {
-          uint4 af[MW], bf[NF];
-#pragma unroll
-          for (int m = 0; m < MW; ++m) af[m] = *reinterpret_cast<const uint4*>(arow0 + m * HWD * kLD + kk * 16);
+        if (kk * 16 < ck) {
+          const uint4 af = *reinterpret_cast<const uint4*>(arow + kk * 16);
+          uint4 bf[NF];
 #pragma unroll
           for (int nf = 0; nf < NF; ++nf) bf[nf] = *reinterpret_cast<const uint4*>(brow + nf * 32 * kLD + kk * 16);
 #pragma unroll
-          for (int m = 0; m < MW; ++m)
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf) acc[m][nf] = mfma<BF16>(af[m], bf[nf], acc[m][nf]);
+          for (int nf = 0; nf < NF; ++nf) acc[nf] = mfma<BF16>(af, bf[nf], acc[nf]);
         }
       }
-    }
     }
   }
 
@@ -500,89 +449,84 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
   __syncthreads();                              // every wave is done with A_s / B_s
   float* E_s = reinterpret_cast<float*>(lds) + wave * (32 * EROW);
   const bool oct_path = a.dst16 && !a.ps && !a.gc_wmask && (a.cout % 8 == 0) && G.dst.sc == 1;
+  const int yo = wave;                          // the wave's tile row
 #pragma unroll
-  for (int m = 0; m < MW; ++m) {
-    const int yo = MW * wave + m;
+  for (int nh = 0; nh < NT / EW; ++nh) {
 #pragma unroll
-    for (int nh = 0; nh < NT / EW; ++nh) {
+    for (int nf2 = 0; nf2 < EW / 32; ++nf2) {
 #pragma unroll
-      for (int nf2 = 0; nf2 < EW / 32; ++nf2) {
+      for (int i = 0; i < 16; ++i)
+        E_s[((i & 3) + 8 * (i >> 2) + 4 * h) * EROW + nf2 * 32 + r] = acc[nh * (EW / 32) + nf2][i];
+    }
+    __builtin_amdgcn_wave_barrier();
+    float gm = -INFINITY, gs = 0.f;                     // ContextBlock partials of this lane group (online softmax)
+    float4 ga = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (oct_path) {
+      constexpr int OPR = EW / 8;                       // lanes per pixel at 8 couts per lane
 #pragma unroll
-        for (int i = 0; i < 16; ++i)
-          E_s[((i & 3) + 8 * (i >> 2) + 4 * h) * EROW + nf2 * 32 + r] = acc[m][nh * (EW / 32) + nf2][i];
-      }
-      __builtin_amdgcn_wave_barrier();
-      float gm = -INFINITY, gs = 0.f;                     // ContextBlock partials of this lane group (online softmax)
-      float4 ga = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (oct_path) {
-        constexpr int OPR = EW / 8;                       // lanes per pixel at 8 couts per lane
-#pragma unroll
-        for (int j = 0; j < 32 * OPR / 64; ++j) {
-          const int idx = j * 64 + lane;
-          const int co = idx % OPR, p = idx / OPR;
-          const float4 va = *reinterpret_cast<const float4*>(E_s + p * EROW + co * 8);
-          const float4 vb = *reinterpret_cast<const float4*>(E_s + p * EROW + co * 8 + 4);
-          const int n = n0 + nh * EW + co * 8;
-          if (n < a.cout && (!(a.dbg & 4) || va.x == 12345.678f))
-            epilogue_oct<BF16>(e, va, vb, a.bias, n, ty0 + yo, tx0 + p, flat0 + yo * kTW + p);
-          asm volatile("" ::: "memory");
-        }
-      } else
-#pragma unroll
-      for (int j = 0; j < 32 * QPR / 64; ++j) {
+      for (int j = 0; j < 32 * OPR / 64; ++j) {
         const int idx = j * 64 + lane;
-        const int cq = idx % QPR, p = idx / QPR;
-        const float4 v = *reinterpret_cast<const float4*>(E_s + p * EROW + cq * 4);
-        const int n = n0 + nh * EW + cq * 4;
-        float4 xo = make_float4(0.f, 0.f, 0.f, 0.f);
-        bool valid = false;
-        if (!(a.dbg & 4) || v.x == 12345.678f)
-          valid = epilogue_quad<BF16>(e, v, a.bias, a.cout, n, ty0 + yo, tx0 + p, flat0 + yo * kTW + p, &xo);
-        if (a.gc_wmask) {
-          // logit of pixel p = <r_p, wmask> summed over the QPR lanes that hold the pixel (ContextBlock.conv_mask, :676)
-          float part = 0.f;
-          if (valid) {
-            const float4 wm = *reinterpret_cast<const float4*>(a.gc_wmask + n);
-            part = xo.x * wm.x + (n + 1 < a.cout ? xo.y * wm.y : 0.f) + (n + 2 < a.cout ? xo.z * wm.z : 0.f) +
-                   (n + 3 < a.cout ? xo.w * wm.w : 0.f);
-          }
-#pragma unroll
-          for (int o = QPR / 2; o >= 1; o >>= 1) part += __shfl_xor(part, o);
-          const bool pval = (ty0 + yo < G.H) && (tx0 + p < G.W);
-          if (pval) {
-            const float mn = fmaxf(gm, part);
-            const float sc = expf(gm - mn);                 // gm = -inf on the first valid pixel -> 0
-            const float ee = expf(part - mn);
-            gs = gs * sc + ee;
-            ga.x = ga.x * sc + ee * xo.x; ga.y = ga.y * sc + ee * xo.y; ga.z = ga.z * sc + ee * xo.z; ga.w = ga.w * sc + ee * xo.w;
-            gm = mn;
-          }
-        }
+        const int co = idx % OPR, p = idx / OPR;
+        const float4 va = *reinterpret_cast<const float4*>(E_s + p * EROW + co * 8);
+        const float4 vb = *reinterpret_cast<const float4*>(E_s + p * EROW + co * 8 + 4);
+        const int n = n0 + nh * EW + co * 8;
+        if (n < a.cout)
+          epilogue_oct<BF16>(e, va, vb, a.bias, n, ty0 + yo, tx0 + p, flat0 + yo * kTW + p);
         asm volatile("" ::: "memory");
       }
-      if (a.gc_wmask && G.gc_partial) {
-        // combine the 64/QPR lane groups of the wave, then lanes 0..QPR-1 write the wave's partial
+    } else
 #pragma unroll
-        for (int o = QPR; o < 64; o <<= 1) {
-          const float om = __shfl_xor(gm, o), os = __shfl_xor(gs, o);
-          const float ox = __shfl_xor(ga.x, o), oy = __shfl_xor(ga.y, o), oz = __shfl_xor(ga.z, o), ow = __shfl_xor(ga.w, o);
-          const float mn = fmaxf(gm, om);
-          const float s1 = (gm == -INFINITY) ? 0.f : expf(gm - mn), s2 = (om == -INFINITY) ? 0.f : expf(om - mn);
-          gs = gs * s1 + os * s2;
-          ga.x = ga.x * s1 + ox * s2; ga.y = ga.y * s1 + oy * s2; ga.z = ga.z * s1 + oz * s2; ga.w = ga.w * s1 + ow * s2;
+    for (int j = 0; j < 32 * QPR / 64; ++j) {
+      const int idx = j * 64 + lane;
+      const int cq = idx % QPR, p = idx / QPR;
+      const float4 v = *reinterpret_cast<const float4*>(E_s + p * EROW + cq * 4);
+      const int n = n0 + nh * EW + cq * 4;
+      float4 xo = make_float4(0.f, 0.f, 0.f, 0.f);
+      const bool valid = epilogue_quad<BF16>(e, v, a.bias, a.cout, n, ty0 + yo, tx0 + p, flat0 + yo * kTW + p, &xo);
+      if (a.gc_wmask) {
+        // logit of pixel p = <r_p, wmask> summed over the QPR lanes that hold the pixel (ContextBlock.conv_mask, :676)
+        float part = 0.f;
+        if (valid) {
+          const float4 wm = *reinterpret_cast<const float4*>(a.gc_wmask + n);
+          part = xo.x * wm.x + (n + 1 < a.cout ? xo.y * wm.y : 0.f) + (n + 2 < a.cout ? xo.z * wm.z : 0.f) +
+                 (n + 3 < a.cout ? xo.w * wm.w : 0.f);
+        }
+#pragma unroll
+        for (int o = QPR / 2; o >= 1; o >>= 1) part += __shfl_xor(part, o);
+        const bool pval = (ty0 + yo < G.H) && (tx0 + p < G.W);
+        if (pval) {
+          const float mn = fmaxf(gm, part);
+          const float sc = expf(gm - mn);                 // gm = -inf on the first valid pixel -> 0
+          const float ee = expf(part - mn);
+          gs = gs * sc + ee;
+          ga.x = ga.x * sc + ee * xo.x; ga.y = ga.y * sc + ee * xo.y; ga.z = ga.z * sc + ee * xo.z; ga.w = ga.w * sc + ee * xo.w;
           gm = mn;
         }
-        // per-wave partial -> LDS (behind the 4 transpose areas); combined across the 4 waves below
-        float* gw = reinterpret_cast<float*>(lds) + 4 * 32 * EROW + wave * (EW + 4);
-        if (lane < QPR) {
-          *reinterpret_cast<float4*>(gw + lane * 4) = ga;
-          if (lane == 0) { gw[EW] = gm; gw[EW + 1] = gs; }
-        }
       }
-      __builtin_amdgcn_wave_barrier();
+      asm volatile("" ::: "memory");
     }
+    if (a.gc_wmask && G.gc_partial) {
+      // combine the 64/QPR lane groups of the wave, then lanes 0..QPR-1 write the wave's partial
+#pragma unroll
+      for (int o = QPR; o < 64; o <<= 1) {
+        const float om = __shfl_xor(gm, o), os = __shfl_xor(gs, o);
+        const float ox = __shfl_xor(ga.x, o), oy = __shfl_xor(ga.y, o), oz = __shfl_xor(ga.z, o), ow = __shfl_xor(ga.w, o);
+        const float mn = fmaxf(gm, om);
+        const float s1 = (gm == -INFINITY) ? 0.f : expf(gm - mn), s2 = (om == -INFINITY) ? 0.f : expf(om - mn);
+        gs = gs * s1 + os * s2;
+        ga.x = ga.x * s1 + ox * s2; ga.y = ga.y * s1 + oy * s2; ga.z = ga.z * s1 + oz * s2; ga.w = ga.w * s1 + ow * s2;
+        gm = mn;
+      }
+      // per-wave partial -> LDS (behind the 4 transpose areas); combined across the 4 waves below
+      float* gw = reinterpret_cast<float*>(lds) + 4 * 32 * EROW + wave * (EW + 4);
+      if (lane < QPR) {
+        *reinterpret_cast<float4*>(gw + lane * 4) = ga;
+        if (lane == 0) { gw[EW] = gm; gw[EW + 1] = gs; }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
   }
-  if (a.gc_wmask && G.gc_partial && NT <= 64 && MW == 1) {
+  if (a.gc_wmask && G.gc_partial && NT <= 64) {
     // one partial per workgroup: waves combined in fixed order (deterministic), written by wave 0
     __syncthreads();
     if (wave == 0 && lane < QPR) {
@@ -613,7 +557,7 @@ __global__ __launch_bounds__(256, MW == 1 ? (WD ? (NT == 128 ? 2 : 3) : (NT == 1
 }
 
 // =====================================================================================================================
-// Lean 3x3 kernel: the same algorithm as conv_mfma_kernel<.., KS=3, MW=1> specialised for the layers that carry the FLOPs
+// Lean 3x3 kernel: the same algorithm as conv_mfma_kernel<.., KS=3> specialised for the layers that carry the FLOPs
 // (one dense NHWC source, stride 1, no pixel shuffle, channel-contiguous destination, cin % 64 == 0).  PMC showed the generic
 // kernel is instruction-issue bound (1431 VALU + 1031 SALU instructions per wave for 72 MFMAs, SIMD issue 96 % busy):
 // here every per-element index computation is hoisted - halo staging walks (row, col) incrementally with 32-bit offsets and
@@ -1161,49 +1105,34 @@ static hipError_t dispatch_lean(const MfmaArgs& a, int nt, int total_tiles, hipS
 #undef FCVSR_LEAN
 }
 
-template <bool BF16, int NT, int KS, int MW, bool WD>
+template <bool BF16, int NT, int KS>
 static hipError_t launch_mfma(const MfmaArgs& a, int total_tiles, hipStream_t st) {
   constexpr int PAD = KS / 2;
-  constexpr int kTH = 4 * MW;
   size_t lds = ((size_t)(kTH + 2 * PAD) * (kTW + 2 * PAD) * kLD + (size_t)NT * kLD) * sizeof(uint16_t);
   const size_t epi = (4ull * 32 + 4) * ((NT >= 64 ? 64 : 32) + 4) * sizeof(float);   // epilogue transpose + GC partial areas
   if (lds < epi) lds = epi;
   static DevOnce attr;
   hipError_t e = once_per_device(attr, [&] {
-    return hipFuncSetAttribute((const void*)conv_mfma_kernel<BF16, NT, KS, MW, WD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return hipFuncSetAttribute((const void*)conv_mfma_kernel<BF16, NT, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((conv_mfma_kernel<BF16, NT, KS, MW, WD>), dim3(total_tiles * a.n_nblk), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((conv_mfma_kernel<BF16, NT, KS>), dim3(total_tiles * a.n_nblk), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
-template <bool BF16, int MW, bool WD>
-static hipError_t dispatch2(const MfmaArgs& a, int nt, int ks, int total_tiles, hipStream_t st) {
-  if (ks == 3) {
-    if (nt == 64) return launch_mfma<BF16, 64, 3, MW, WD>(a, total_tiles, st);
-    return launch_mfma<BF16, 32, 3, MW, WD>(a, total_tiles, st);
-  }
-  if (nt == 64) return launch_mfma<BF16, 64, 1, MW, WD>(a, total_tiles, st);
-  return launch_mfma<BF16, 32, 1, MW, WD>(a, total_tiles, st);
-}
-
 template <bool BF16>
-static hipError_t dispatch(const MfmaArgs& a, int nt, int ks, int mw, int wd, int total_tiles, hipStream_t st) {
-  (void)mw;      // (8-row tiles - MW = 2 - measured 0.85-1.0x and their 128-cout instances spilled 176 scratch operations: not built)
-  return wd ? dispatch2<BF16, 1, true>(a, nt, ks, total_tiles, st) : dispatch2<BF16, 1, false>(a, nt, ks, total_tiles, st);
+static hipError_t dispatch(const MfmaArgs& a, int nt, int ks, int total_tiles, hipStream_t st) {
+  if (ks == 3) {
+    if (nt == 64) return launch_mfma<BF16, 64, 3>(a, total_tiles, st);
+    return launch_mfma<BF16, 32, 3>(a, total_tiles, st);
+  }
+  if (nt == 64) return launch_mfma<BF16, 64, 1>(a, total_tiles, st);
+  return launch_mfma<BF16, 32, 1>(a, total_tiles, st);
 }
 
 }  // namespace fcvsr
 
 using namespace fcvsr;
-
-// diagnostic stamp buffer of the resident-weight kernel (FCVSR_RES_STAMPS=1): [wave 8][phase 64][slot 8] u64
-static void* g_res_stamps = nullptr;
-static const size_t kResStampBytes = 8 * 64 * 8 * sizeof(unsigned long long);
-extern "C" int fcvsr_debug_res_stamps(void* host_out, size_t bytes) {
-  if (!g_res_stamps || bytes > kResStampBytes) return FCVSR_E_ARG;
-  return (int)hipMemcpy(host_out, g_res_stamps, bytes, hipMemcpyDeviceToHost);
-}
 
 // name of the kernel the last fcvsr_conv2d_mfma call of this thread launched (bench.py groups its per-launch timings by it)
 static thread_local char g_last_kernel[96] = "";
@@ -1224,6 +1153,9 @@ static bool src_ok(const fcvsr_view& v, int mma_dtype) {
   if (v.dtype != FCVSR_F32 && v.dtype != mma_dtype) return false;
   return v.c % g == 0 && v.sx % g == 0 && v.sy % g == 0 && v.sb % g == 0;
 }
+
+// the resident-weight kernel pays once a launch has this many workgroup-tiles (tiles x cout blocks): below it, the lean kernel
+static constexpr int kResMinTiles = 768;
 
 extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int mma_dtype, void* stream) {
   FCVSR_CHECK_ARG(descs != nullptr && n_groups >= 1 && n_groups <= 3, "1..3 problem groups");
@@ -1261,8 +1193,8 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
   a.cout = d0.cout;
   a.cout_pad = d0.cout_pad;
   // N tile: measured faster with <= 64 couts per workgroup (register pressure of 128-cout accumulators costs more than
-  // re-staging the input tile for the second N-block); FCVSR_MFMA_NTMAX=128 restores the wide tile for experiments.
-  int nt = d0.cout > 32 ? 64 : 32;
+  // re-staging the input tile for the second N-block)
+  const int nt = d0.cout > 32 ? 64 : 32;
   a.n_nblk = (d0.cout + nt - 1) / nt;
   a.w = (const uint16_t*)d0.weight;
   a.bias = d0.bias;
@@ -1277,19 +1209,6 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
   FCVSR_CHECK_ARG(d0.gc_wmask == nullptr || (d0.kh == 3 && d0.stride == 1 && d0.cout <= 64 && !d0.pixel_shuffle &&
                                              ((uintptr_t)d0.gc_wmask % 16) == 0),
                   "ContextBlock fusion: 3x3 stride-1 layer with cout <= 64");
-  {
-    const char* dbg = getenv("FCVSR_MFMA_DBG");
-    a.dbg = dbg ? atoi(dbg) : 0;
-  }
-  // tile rows per workgroup: 8 (2 per wave) or 4 (1 per wave: half the LDS -> more co-resident workgroups in
-  // different phases).  FCVSR_MFMA_MW overrides for experiments.
-  const int mw = 1;   // measured: 4-row tiles (more co-resident workgroups in different phases) win for 3x3 and 1x1 alike
-  int wd = 0;     // weights straight from L2 into the B-operand registers (no LDS staging / tap barriers)
-  {
-    const char* e = getenv("FCVSR_MFMA_WD");
-    if (e) wd = atoi(e) ? 1 : 0;
-  }
-  const int kTH = 4 * mw;
   int tiles = 0;
   for (int g = 0; g < n_groups; ++g) {
     const fcvsr_conv_desc& d = descs[g];
@@ -1337,7 +1256,7 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
   for (int g = n_groups; g < 3; ++g) a.g[g] = a.g[0];
   hipStream_t st = (hipStream_t)stream;
   // lean fast path: 3x3 stride 1, one dense source, cin multiple of 64, plain channel-contiguous destination and residuals
-  bool lean = dst_native && d0.kh == 3 && d0.stride == 1 && mw == 1 && !wd && d0.n_src == 1 && !a.planar && !a.ps && (cin % 64 == 0) &&
+  bool lean = dst_native && d0.kh == 3 && d0.stride == 1 && d0.n_src == 1 && !a.planar && !a.ps && (cin % 64 == 0) &&
               (!a.dst16 || d0.cout % 8 == 0) && (d0.gc_wmask == nullptr || d0.cout % 4 == 0);
   for (int g = 0; g < n_groups && lean; ++g) {
     const fcvsr_conv_desc& d = descs[g];
@@ -1362,7 +1281,7 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
   }
   // lean 1x1 (flat) path: every source a multiple of 64 channels, channel-contiguous destination, f32 residuals;
   // pixel shuffle only without residuals
-  bool lean1 = dst_native && d0.kh == 1 && mw == 1 && !wd && nt <= 64 && (d0.cout % 8 == 0) && !a.planar;
+  bool lean1 = dst_native && d0.kh == 1 && (d0.cout % 8 == 0) && !a.planar;
   for (int s2 = 0; s2 < d0.n_src && lean1; ++s2) lean1 = lean1 && (d0.src[s2].c % 64 == 0);
   lean1 = lean1 && (!a.ps || (d0.n_res == 0 && (d0.cout / 4) % 8 == 0));
   for (int g = 0; g < n_groups && lean1; ++g) {
@@ -1392,7 +1311,7 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
   // amortises its 72 KiB weight copy over a few 8 x 32 tiles; small launches stay on the lean kernel.
   // Pixel-shuffled layers (the 3x3 up-convs of the full / RGB models, 64 -> 256) qualify too: with sub-pixel-major rows a
   // 64-cout block is one sub-pixel, so PixelShuffle is only a different destination pixel (no residuals, 16-bit destination).
-  const bool res_ps = a.ps && dst_native && d0.kh == 3 && d0.stride == 1 && mw == 1 && !wd && d0.n_src == 1 && !a.planar && cin == 64 &&
+  const bool res_ps = a.ps && dst_native && d0.kh == 3 && d0.stride == 1 && d0.n_src == 1 && !a.planar && cin == 64 &&
                       d0.cout % 256 == 0 && d0.n_res == 0 && a.dst16 && a.src16 && d0.gc_wmask == nullptr;
   bool res = (lean || res_ps) && a.src16 && conv3_res_supports(cin, d0.cout) && d0.gc_wmask == nullptr && d0.cout == d0.cout / 64 * 64;
   int rtiles = 0;
@@ -1413,12 +1332,10 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
                       d.src[0].sc == 1 && ((uintptr_t)d.src[0].ptr % 16) == 0;
   }
   {
-    // FCVSR_MFMA_RES: 0 never, 1 always (when eligible), unset: by size (FCVSR_MFMA_RES_MIN workgroup-tiles)
+    // FCVSR_MFMA_RES: 0 never, 1 always (when eligible), unset: by size (kResMinTiles workgroup-tiles)
     const char* e3 = getenv("FCVSR_MFMA_RES");
     const int res_mode = e3 ? (atoi(e3) ? 1 : 0) : 2;
-    const char* e4 = getenv("FCVSR_MFMA_RES_MIN");
-    const int res_min = e4 ? atoi(e4) : 768;
-    if (res_mode == 0 || (res_mode == 2 && rtiles * (cin == 64 ? d0.cout / 64 : d0.cout / 32) < res_min)) res = false;
+    if (res_mode == 0 || (res_mode == 2 && rtiles * (cin == 64 ? d0.cout / 64 : d0.cout / 32) < kResMinTiles)) res = false;
   }
   if (res) {
     // 256 zero bytes per DEVICE (the source of halo pixels outside the image), created on first use.  hipMalloc / hipMemset are
@@ -1460,16 +1377,6 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
     wa.cin = cin; wa.cout = d0.cout; wa.cout_pad = d0.cout_pad; wa.cin_pad = a.cin_pad;
     wa.w = a.w; wa.bias = a.bias; wa.act = a.act; wa.slope = a.slope; wa.slope_ptr = a.slope_ptr;
     wa.rs[0] = a.rs[0]; wa.rs[1] = a.rs[1]; wa.n_res = a.n_res; wa.res16 = a.res16; wa.ps = a.ps; wa.zeros = zeros;
-    { const char* wd_ = getenv("FCVSR_RES_DBG"); wa.dbg = wd_ ? atoi(wd_) : 0; }
-    wa.stamps = nullptr;
-    {
-      const char* ws_ = getenv("FCVSR_RES_STAMPS");       // diagnostic: in-kernel cycle stamps of one workgroup (scripts/res_stamps.py)
-      if (ws_ && atoi(ws_)) {
-        if (!g_res_stamps && hipMalloc(&g_res_stamps, kResStampBytes) != hipSuccess) g_res_stamps = nullptr;
-        if (g_res_stamps) (void)hipMemsetAsync(g_res_stamps, 0, kResStampBytes, st);
-        wa.stamps = (unsigned long long*)g_res_stamps;
-      }
-    }
     FCVSR_NOTE_KERNEL("conv3_res_kernel<%s, %d, %d, %d>", tf(mma_dtype == FCVSR_BF16), !a.dst16 ? 0 : (a.n_res == 0 ? 2 : 1), cin / 64,
                       a.act == FCVSR_ACT_NONE ? 2 : ((a.act == FCVSR_ACT_RELU || (a.act == FCVSR_ACT_LEAKY && a.slope >= 0.f && a.slope <= 1.f)) ? 1 : 0));
     e = launch_conv3_res(wa, mma_dtype == FCVSR_BF16, a.dst16 != 0, st);
@@ -1479,14 +1386,10 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
     }
     return 0;
   }
-  if (lean && nt > 64) {      // measured: two 64-cout workgroups per tile beat one 128-cout workgroup (register pressure)
-    nt = 64;
-    a.n_nblk = (d0.cout + nt - 1) / nt;
-  }
   if (lean) FCVSR_NOTE_KERNEL("conv3_lean_kernel<%s, %d, %s, %s>%s", tf(mma_dtype == FCVSR_BF16), nt, tf(a.src16), tf(a.dst16), a.gc_wmask ? " +gc" : "");
-  else FCVSR_NOTE_KERNEL("conv_mfma_kernel<%s, %d, %d, %d, %s>", tf(mma_dtype == FCVSR_BF16), nt, d0.kh, mw, tf(wd));
+  else FCVSR_NOTE_KERNEL("conv_mfma_kernel<%s, %d, %d>", tf(mma_dtype == FCVSR_BF16), nt, d0.kh);
   if (lean) e = (mma_dtype == FCVSR_BF16) ? dispatch_lean<true>(a, nt, tiles, st) : dispatch_lean<false>(a, nt, tiles, st);
-  else e = (mma_dtype == FCVSR_BF16) ? dispatch<true>(a, nt, d0.kh, mw, wd, tiles, st) : dispatch<false>(a, nt, d0.kh, mw, wd, tiles, st);
+  else e = (mma_dtype == FCVSR_BF16) ? dispatch<true>(a, nt, d0.kh, tiles, st) : dispatch<false>(a, nt, d0.kh, tiles, st);
   if (e != hipSuccess) {
     set_error("fcvsr_conv2d_mfma: launch failed: %s", hipGetErrorString(e));
     return (int)e;

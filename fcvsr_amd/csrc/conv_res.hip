@@ -25,7 +25,6 @@
 //   * the 32 workgroups of one XCD (blockIdx % 8) share a contiguous range of tiles, so halo rows and both cout blocks of a
 //     tile hit in that XCD's L2.
 // LDS: 73,728 (weights) + 2 x 44,032 (halo tiles) + 256 (bias) + 384 (group parameters) = 162,432 of 163,840 bytes.
-#include <stdlib.h>
 #include <type_traits>
 #include "conv_res.h"
 #include "mfma_util.h"
@@ -60,13 +59,12 @@ enum {
 };
 
 struct ResK {                                        // kernel arguments
-  int n_groups, total_tiles, cout, cout_pad, cin_pad, act, n_res, res16, dbg, ps;
+  int n_groups, total_tiles, cout, cout_pad, cin_pad, act, n_res, res16, ps;
   float slope, rs[2];
   const float* slope_ptr;
   const uint16_t* w;
   const float* bias;
   const void* zeros;
-  unsigned long long* stamps;
   int tab[3][32];
 };
 
@@ -139,14 +137,6 @@ __device__ __forceinline__ void res_stage(const int* tabL, const void* zeros, co
   }
 }
 
-// Diagnostic build switch only (a.stamps != nullptr): in-kernel cycle stamps of one workgroup, written to a buffer nothing else
-// reads (scripts/res_stamps.py prints where a phase spends its cycles).  No stamp executes in the normal path.
-#define FCVSR_RES_STAMP(SLOT)                                                                                          \
-  do {                                                                                                                 \
-    if (a.stamps && blockIdx.x == 8 && p < 64 && lane == 0)                                                            \
-      a.stamps[(wave * 64 + p) * 8 + (SLOT)] = __builtin_amdgcn_s_memtime();                                           \
-  } while (0)
-
 // NCH = input-channel chunks of 64 (1 or 2); a workgroup owns CO = 64 / NCH output channels of every tile it visits.
 // MODE: 0 = f32 destination, 1 = 16-bit destination, 2 = 16-bit destination without residuals (the multiplying wave packs).
 // NSU: 1 = the activation's negative-side factor lies in [0, 1] (ReLU, LeakyReLU): act(x) = max(x, ns * x); 2 = no activation at
@@ -197,7 +187,7 @@ __global__ __launch_bounds__(512, 2) void conv3_res_kernel(ResK a) {
   const unsigned xoff = lds0 + kRWBytes + grp * kRXBytes;                // my group's halo buffer
   __syncthreads();                                   // the parameter table is in LDS
   ResTile tcur = res_decode(tabL, a.n_groups, tb + slot + grp * nslots < te ? tb + slot + grp * nslots : tb + slot);   // the tile my group staged last
-  if (grp == 0 && !(a.dbg & 1)) res_stage(tabL, a.zeros, tcur, 0, xoff, wq, lane);
+  if (grp == 0) res_stage(tabL, a.zeros, tcur, 0, xoff, wq, lane);
 
   // Activation as max(x, ns * x) (0 <= ns <= 1) or max(x, 0) + ns * min(x, 0) with ns = 0 (ReLU), slope (LeakyReLU / PReLU) or 1 (none): the same values as the
   // branchy form, and no per-element scalar branch on `act` (hipcc does not unswitch it: 64 branches per tile row).
@@ -228,7 +218,6 @@ __global__ __launch_bounds__(512, 2) void conv3_res_kernel(ResK a) {
   int k = 0;                                         // my next unit to multiply
 #pragma unroll 1
   for (int p = 0;; ++p) {
-    FCVSR_RES_STAMP(0);
     if ((p & 1) == grp) {
       // ================= multiply unit k: tile list index 2 * (k / NCH) + grp, chunk k % NCH ==========================
       if (k < NU) {
@@ -239,11 +228,10 @@ __global__ __launch_bounds__(512, 2) void conv3_res_kernel(ResK a) {
 #pragma unroll
             for (int nf = 0; nf < 4; ++nf) acc[mf][nf] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         }
-        if (!(a.dbg & 2)) {
-          __builtin_amdgcn_s_setprio(2);   // the multiplying wave wins VALU/MFMA issue over its SIMD partner's epilogue
-          const unsigned wch = ch * (9 * CO * 128);
-          uint4 wf[3][MF16], xf[3][4];                 // fragments are read two 32-deep steps ahead of their MFMAs
-          // step S = 2 tap + ks: channels 32 ks + [0, 32) of tap (ky, kx), tap-major, ascending channels
+        __builtin_amdgcn_s_setprio(2);   // the multiplying wave wins VALU/MFMA issue over its SIMD partner's epilogue
+        const unsigned wch = ch * (9 * CO * 128);
+        uint4 wf[3][MF16], xf[3][4];                 // fragments are read two 32-deep steps ahead of their MFMAs
+        // step S = 2 tap + ks: channels 32 ks + [0, 32) of tap (ky, kx), tap-major, ascending channels
 #define FCVSR_RES_LOAD(S, SLOT)                                                                                  \
   do {                                                                                                           \
     constexpr int tap_ = (S) / 2, ks_ = (S) % 2, ky_ = tap_ / 3, kx_ = tap_ % 3;                                 \
@@ -269,20 +257,18 @@ __global__ __launch_bounds__(512, 2) void conv3_res_kernel(ResK a) {
       __builtin_amdgcn_sched_group_barrier(0x008, 4 * MF16, 0);                                                  \
     }                                                                                                            \
   } while (0)
-          FCVSR_RES_LOAD(0, 0);
-          FCVSR_RES_LOAD(1, 1);
-          __builtin_amdgcn_sched_barrier(0);
-          FCVSR_RES_STEP(0);  FCVSR_RES_STEP(1);  FCVSR_RES_STEP(2);  FCVSR_RES_STEP(3);  FCVSR_RES_STEP(4);  FCVSR_RES_STEP(5);
-          FCVSR_RES_STEP(6);  FCVSR_RES_STEP(7);  FCVSR_RES_STEP(8);  FCVSR_RES_STEP(9);  FCVSR_RES_STEP(10); FCVSR_RES_STEP(11);
-          FCVSR_RES_STEP(12); FCVSR_RES_STEP(13); FCVSR_RES_STEP(14); FCVSR_RES_STEP(15); FCVSR_RES_STEP(16); FCVSR_RES_STEP(17);
+        FCVSR_RES_LOAD(0, 0);
+        FCVSR_RES_LOAD(1, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        FCVSR_RES_STEP(0);  FCVSR_RES_STEP(1);  FCVSR_RES_STEP(2);  FCVSR_RES_STEP(3);  FCVSR_RES_STEP(4);  FCVSR_RES_STEP(5);
+        FCVSR_RES_STEP(6);  FCVSR_RES_STEP(7);  FCVSR_RES_STEP(8);  FCVSR_RES_STEP(9);  FCVSR_RES_STEP(10); FCVSR_RES_STEP(11);
+        FCVSR_RES_STEP(12); FCVSR_RES_STEP(13); FCVSR_RES_STEP(14); FCVSR_RES_STEP(15); FCVSR_RES_STEP(16); FCVSR_RES_STEP(17);
 #undef FCVSR_RES_STEP
 #undef FCVSR_RES_LOAD
-          __builtin_amdgcn_s_setprio(0);
-        }
-        FCVSR_RES_STAMP(1);
+        __builtin_amdgcn_s_setprio(0);
         // Bias and activation on the multiplying side, in the accumulator layout (lane = pixel p16 of fragment nf, registers
         // 0..3 = couts mf*16 + 4G + [0, 4)).  With a 16-bit destination and no residual the values are packed into registers 0, 1.
-        if (ch == NCH - 1 && !(a.dbg & 8)) {
+        if (ch == NCH - 1) {
           const float* bias_a = reinterpret_cast<const float*>(lds + kRBiasOff) + 4 * G;
 #pragma unroll
           for (int mf = 0; mf < MF16; ++mf) {
@@ -307,18 +293,16 @@ __global__ __launch_bounds__(512, 2) void conv3_res_kernel(ResK a) {
       }
       ++k;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // my LDS reads are complete before the other phase's copy overwrites
-      FCVSR_RES_STAMP(2);
     } else {
       // ================= copy unit k into my buffer; store the tile whose last chunk was unit k - 1 =======================
       ResTile tn = tcur;                             // one decode per tile: the copy below and the stores two phases later share it
       if (k < NU) {
         const int ch = (NCH == 1) ? 0 : (k & (NCH - 1));
         if (ch == 0 && k > 0) tn = res_decode(tabL, a.n_groups, tb + slot + (2 * (k / NCH) + grp) * nslots);
-        if (!(a.dbg & 1)) res_stage(tabL, a.zeros, tn, ch, xoff, wq, lane);
+        res_stage(tabL, a.zeros, tn, ch, xoff, wq, lane);
       }
-      FCVSR_RES_STAMP(3);
       int nst = 0;                                   // store wave-instructions issued below (wave-uniform)
-      if (k >= 1 && k <= NU && ((k - 1) & (NCH - 1)) == NCH - 1 && !(a.dbg & 8)) {
+      if (k >= 1 && k <= NU && ((k - 1) & (NCH - 1)) == NCH - 1) {
         // Branch-free up to the stores: every load of a tile row (bias from LDS, residuals from HBM) is issued before the first
         // use, so a row costs one memory round trip instead of one per 8-channel chunk.
         const ResTile t = tcur;
@@ -341,7 +325,7 @@ __global__ __launch_bounds__(512, 2) void conv3_res_kernel(ResK a) {
 #pragma unroll
           for (int hf = 0; hf < 2; ++hf) {
             const int px = t.tx0 + 16 * hf + p16;
-            ok[hf] = (py < GH) && (px < GW) && !(a.dbg & 4);
+            ok[hf] = (py < GH) && (px < GW);
             // lanes outside the image read the residuals of the image's first pixel (always a valid address) and store nothing
             const int pyc = ok[hf] ? py : 0, pxc = ok[hf] ? px : 0;
             // PixelShuffle(2): rows are packed sub-pixel-major, so this workgroup's 64 couts are 64 consecutive channels of ONE
@@ -437,7 +421,6 @@ __global__ __launch_bounds__(512, 2) void conv3_res_kernel(ResK a) {
         }
       }
       tcur = tn;
-      FCVSR_RES_STAMP(4);
       // My copies must have landed before the barrier; my stores need not have.  vmcnt counts loads, LDS-DMA and stores
       // together in issue order, and the stores are the youngest operations: leave exactly them outstanding (waiting for them
       // too exposes a full HBM write round trip per phase - measured 78 vs 54 us on a 64->64 layer).
@@ -447,9 +430,7 @@ __global__ __launch_bounds__(512, 2) void conv3_res_kernel(ResK a) {
       else if (nst == 2 * SH) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * SH) : "memory");
       else if (nst == 3 * SH) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * SH) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * SH) : "memory");
-      FCVSR_RES_STAMP(5);
     }
-    FCVSR_RES_STAMP(6);
     __builtin_amdgcn_s_barrier();
     if (p >= plast) break;
   }
@@ -468,11 +449,7 @@ static hipError_t launch_res(const ResArgs& a, hipStream_t st) {
   if (e != hipSuccess) return e;
   const int cus = device_cu_count(dev);
   if (cus <= 0) return hipErrorInvalidDevice;
-  int n_cu = cus > 8 ? cus / 8 * 8 : 8;
-  {                                                      // experiment: leave CUs to the other stream's kernels (FCVSR_RES_CUS < CU count)
-    static const int lim = getenv("FCVSR_RES_CUS") ? atoi(getenv("FCVSR_RES_CUS")) : 0;
-    if (lim >= 8 && lim < n_cu) n_cu = lim / 8 * 8;
-  }
+  const int n_cu = cus > 8 ? cus / 8 * 8 : 8;
   const int NB = a.cout / (64 / NCH);
   // one persistent workgroup per CU; the grid is a multiple of 8 * NB (every XCD gets whole slots of NB cout blocks)
   int grid = n_cu / (8 * NB) * (8 * NB);
@@ -481,8 +458,8 @@ static hipError_t launch_res(const ResArgs& a, hipStream_t st) {
   if (grid > need) grid = need;
   ResK k;
   k.n_groups = a.n_groups; k.total_tiles = a.total_tiles; k.cout = a.cout; k.cout_pad = a.cout_pad; k.cin_pad = a.cin_pad;
-  k.act = a.act; k.n_res = a.n_res; k.res16 = a.res16; k.dbg = a.dbg; k.ps = a.ps; k.slope = a.slope; k.rs[0] = a.rs[0]; k.rs[1] = a.rs[1];
-  k.slope_ptr = a.slope_ptr; k.w = a.w; k.bias = a.bias; k.zeros = a.zeros; k.stamps = a.stamps;
+  k.act = a.act; k.n_res = a.n_res; k.res16 = a.res16; k.ps = a.ps; k.slope = a.slope; k.rs[0] = a.rs[0]; k.rs[1] = a.rs[1];
+  k.slope_ptr = a.slope_ptr; k.w = a.w; k.bias = a.bias; k.zeros = a.zeros;
   for (int g = 0; g < 3; ++g) {
     const ResGroup& G = a.g[g < a.n_groups ? g : 0];
     int* T = k.tab[g];

@@ -856,8 +856,6 @@ struct TwoStage { int N, R1, R2; };
 static const TwoStage kTwoStage[] = {{64, 8, 8},    {72, 8, 9},    {80, 8, 10},   {96, 8, 12},   {128, 8, 16},  {144, 12, 12},
                                      {160, 10, 16}, {180, 12, 15}, {192, 12, 16}, {240, 15, 16}, {256, 16, 16}, {320, 16, 20}};
 static const TwoStage* two_stage(int N) {
-  static const bool off = getenv("FCVSR_FFT_2S") && atoi(getenv("FCVSR_FFT_2S")) == 0;
-  if (off) return nullptr;
   for (const TwoStage& t : kTwoStage)
     if (t.N == N) return &t;
   return nullptr;
@@ -979,10 +977,7 @@ static int launch_rfft_rows2(const TwoStage& ts, const fcvsr_view* src, int n, i
                              int re_off, hipStream_t st) {
   const float2* tw = twiddle_table(ts.N, st);
   if (!tw) return FCVSR_E_ARG;
-  static const int envL = getenv("FCVSR_FFT_ROWL") ? atoi(getenv("FCVSR_FFT_ROWL")) : 0;
-  int L = pick_lanes2(ts, n / 2);
-  if (envL > 0 && envL < L) L = envL;
-  const int logL = ilog2(L);
+  const int L = pick_lanes2(ts, n / 2), logL = ilog2(L);
   const int rmax = ts.R1 > ts.R2 ? ts.R1 : ts.R2;
   const dim3 grid(cdiv(n, 2 * L), (B * H + 7) / 8 * 8), block((rmax * L + 63) / 64 * 64);
   const size_t lds = 8ull * ts.N * L + 8ull * ts.N;
@@ -1005,10 +1000,7 @@ static int launch_irfft_rows2(const TwoStage& ts, const float* spec, long long p
                               const fcvsr_view* dst, float scale, hipStream_t st) {
   const float2* tw = twiddle_table(ts.N, st);
   if (!tw) return FCVSR_E_ARG;
-  static const int envL = getenv("FCVSR_FFT_ROWL") ? atoi(getenv("FCVSR_FFT_ROWL")) : 0;
-  int L = pick_lanes2(ts, n / 2);
-  if (envL > 0 && envL < L) L = envL;
-  const int logL = ilog2(L);
+  const int L = pick_lanes2(ts, n / 2), logL = ilog2(L);
   const int rmax = ts.R1 > ts.R2 ? ts.R1 : ts.R2;
   const dim3 grid(cdiv(n, 2 * L), (B * H + 7) / 8 * 8), block((rmax * L + 63) / 64 * 64);
   const size_t lds = 8ull * ts.N * L + 8ull * ts.N;
@@ -1025,19 +1017,13 @@ static bool pair_ok(const fcvsr_view* v) {
   return v->sc == 1 && v->sx % 2 == 0 && v->sy % 2 == 0 && v->sb % 2 == 0 && ((uintptr_t)v->ptr % al) == 0;
 }
 
-static long long lds_budget() {
-  static long long b = -1;
-  if (b < 0) {
-    const char* e = getenv("FCVSR_FFT_LDS_KB");
-    b = (e ? atoll(e) : 64) * 1024;   // measured: 48-64 KiB (2-3 workgroups per CU) is 1.5x faster than 1 fat workgroup
-  }
-  return b;
-}
+// LDS budget of the plan kernels: measured, 48-64 KiB (2-3 workgroups per CU) is 1.5x faster than 1 fat workgroup
+constexpr long long kFftLdsBudget = 64 * 1024;
 
 static int pick_lanes(int N, int n_lanes_needed) {
   // LDS bytes = 16*N*L + 8*N within the budget; L power of two in [1,32]
   int L = 32;
-  while (L > 1 && (16ll * N * L + 8ll * N) > lds_budget()) L >>= 1;
+  while (L > 1 && (16ll * N * L + 8ll * N) > kFftLdsBudget) L >>= 1;
   while (L > 1 && L / 2 >= n_lanes_needed) L >>= 1;
   return L;
 }
@@ -1099,6 +1085,31 @@ extern "C" int fcvsr_rfft2(const fcvsr_view* src, int B, int H, int W, int n, fl
   return 0;
 }
 
+// Inverse row pass of fcvsr_irfft2 / fcvsr_irfft2_bands: the transformed columns `mid` -> the real output dst (scaled by
+// 1 / (H W)).  Two-stage kernel for the listed lengths, else the plan kernel; mid_vec: `mid` may be read 16 bytes at a time.
+static int irfft_rows(const float* mid, long long pix_stride, int im_off, int re_off, int n, int B, int H, int W, const FftPlan& pw,
+                      bool mid_vec, const fcvsr_view* dst, hipStream_t st) {
+  const TwoStage* tsw = two_stage(W);
+  const bool mid_pair = pix_stride % 2 == 0 && im_off % 2 == 0 && re_off % 2 == 0 && ((uintptr_t)mid % 8) == 0;
+  if (tsw && n % 2 == 0 && pair_ok(dst) && mid_pair) {
+    const int rc = launch_irfft_rows2(*tsw, mid, pix_stride, im_off, re_off, n, B, H, dst, 1.0f / ((float)H * (float)W), st);
+    if (rc) return rc;
+    FCVSR_LAUNCH_CHECK();
+  } else {
+    const int L = pick_lanes(W, (n + 1) / 2);
+    FCVSR_CHECK_ARG(16ll * W * L + 8ll * W <= 160 * 1024, "row too long for LDS");
+    const size_t lds = 16ull * W * L + 8ull * W;
+    (void)allow_lds(irfft_rows_kernel, lds);
+    dim3 grid(cdiv(n, 2 * L), (B * H + 7) / 8 * 8);
+    const int vec = (L >= 4 && n % (2 * L) == 0 && mid_vec && dst->sc == 1 && dst->sx % 4 == 0 && dst->sy % 4 == 0 &&
+                     dst->sb % 4 == 0 && ((uintptr_t)dst->ptr % 16) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(irfft_rows_kernel, grid, dim3(512), lds, st, mid, pix_stride, im_off, re_off, n, H, W, L, to_view(*dst),
+                       1.0f / ((float)H * (float)W), pw, vec, B);
+    FCVSR_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 extern "C" int fcvsr_irfft2(const float* spec, int64_t pix_stride, int im_off, int re_off, int B, int H, int W, int n,
                             const float* mask, float* work, const fcvsr_view* dst, void* stream) {
   FCVSR_CHECK_ARG(spec && dst && dst->ptr, "null pointer");
@@ -1110,8 +1121,6 @@ extern "C" int fcvsr_irfft2(const float* spec, int64_t pix_stride, int im_off, i
   hipStream_t st = (hipStream_t)stream;
   float* mid = work ? work : const_cast<float*>(spec);
   const bool spec_ok = pix_stride % 4 == 0 && im_off % 4 == 0 && re_off % 4 == 0 && ((uintptr_t)spec % 16) == 0;
-  const bool mid_pair = pix_stride % 2 == 0 && im_off % 2 == 0 && re_off % 2 == 0 && ((uintptr_t)mid % 8) == 0;
-  const TwoStage* tsw = two_stage(W);
   const TwoStage* tsh = two_stage_cols(H);
   if (tsh) {
     const int rc = launch_cols2(*tsh, spec, mid, (long long)pix_stride, im_off, re_off, n, Wf, B, true, mask, st);
@@ -1128,24 +1137,7 @@ extern "C" int fcvsr_irfft2(const float* spec, int64_t pix_stride, int im_off, i
                        Wf, L, 1, mask, ph, vec, B);
     FCVSR_LAUNCH_CHECK();
   }
-  if (tsw && n % 2 == 0 && pair_ok(dst) && mid_pair) {
-    const int rc = launch_irfft_rows2(*tsw, mid, (long long)pix_stride, im_off, re_off, n, B, H, dst,
-                                      1.0f / ((float)H * (float)W), st);
-    if (rc) return rc;
-    FCVSR_LAUNCH_CHECK();
-  } else {
-    const int L = pick_lanes(W, (n + 1) / 2);
-    FCVSR_CHECK_ARG(16ll * W * L + 8ll * W <= 160 * 1024, "row too long for LDS");
-    const size_t lds = 16ull * W * L + 8ull * W;
-    (void)allow_lds(irfft_rows_kernel, lds);
-    dim3 grid(cdiv(n, 2 * L), (B * H + 7) / 8 * 8);
-    const int vec = (L >= 4 && n % (2 * L) == 0 && spec_ok && ((uintptr_t)mid % 16) == 0 && dst->sc == 1 && dst->sx % 4 == 0 &&
-                     dst->sy % 4 == 0 && dst->sb % 4 == 0 && ((uintptr_t)dst->ptr % 16) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(irfft_rows_kernel, grid, dim3(512), lds, st, (const float*)mid, (long long)pix_stride, im_off,
-                       re_off, n, H, W, L, to_view(*dst), 1.0f / ((float)H * (float)W), pw, vec, B);
-    FCVSR_LAUNCH_CHECK();
-  }
-  return 0;
+  return irfft_rows(mid, (long long)pix_stride, im_off, re_off, n, B, H, W, pw, spec_ok && ((uintptr_t)mid % 16) == 0, dst, st);
 }
 
 extern "C" int fcvsr_irfft2_bands(const float* spec, int64_t pix_stride, int im_off, int re_off, int B, int H, int W, int n,
@@ -1156,8 +1148,7 @@ extern "C" int fcvsr_irfft2_bands(const float* spec, int64_t pix_stride, int im_
   const long long band = (long long)B * H * Wf * pix_stride;           // floats per band of `work`
   hipStream_t st = (hipStream_t)stream;
   const TwoStage* tsh = two_stage_bands(H);
-  static const bool off = getenv("FCVSR_FFT_BANDS") && atoi(getenv("FCVSR_FFT_BANDS")) == 0;
-  if (!tsh || off) {                                                    // no fused column pass for this height: band by band
+  if (!tsh) {                                 // no fused column pass for this height: band by band
     for (int m = 0; m < n_bands; ++m) {
       const int rc = fcvsr_irfft2(spec, pix_stride, im_off, re_off, B, H, W, n, masks + (long long)m * H * Wf, work, &dst[m], stream);
       if (rc) return rc;
@@ -1171,31 +1162,13 @@ extern "C" int fcvsr_irfft2_bands(const float* spec, int64_t pix_stride, int im_
     if (rc) return rc;
     FCVSR_LAUNCH_CHECK();
   }
-  // row passes: the inverse column pass of fcvsr_irfft2 is skipped by handing it each band's transformed columns... the row
-  // kernels are launched directly here (same dispatch as fcvsr_irfft2)
   FftPlan pw;
   FCVSR_CHECK_ARG(make_plan(W, &pw), "length has too many factors");
-  const TwoStage* tsw = two_stage(W);
   for (int m = 0; m < n_bands; ++m) {
     const float* mid = work + (long long)m * band;
-    const bool mid_pair = pix_stride % 2 == 0 && im_off % 2 == 0 && re_off % 2 == 0 && ((uintptr_t)mid % 8) == 0;
-    const bool spec_ok = pix_stride % 4 == 0 && im_off % 4 == 0 && re_off % 4 == 0 && ((uintptr_t)mid % 16) == 0;
-    if (tsw && n % 2 == 0 && pair_ok(&dst[m]) && mid_pair) {
-      const int rc = launch_irfft_rows2(*tsw, mid, (long long)pix_stride, im_off, re_off, n, B, H, &dst[m], 1.0f / ((float)H * (float)W), st);
-      if (rc) return rc;
-      FCVSR_LAUNCH_CHECK();
-    } else {
-      const int L = pick_lanes(W, (n + 1) / 2);
-      FCVSR_CHECK_ARG(16ll * W * L + 8ll * W <= 160 * 1024, "row too long for LDS");
-      const size_t lds = 16ull * W * L + 8ull * W;
-      (void)allow_lds(irfft_rows_kernel, lds);
-      dim3 grid(cdiv(n, 2 * L), (B * H + 7) / 8 * 8);
-      const int vec = (L >= 4 && n % (2 * L) == 0 && spec_ok && dst[m].sc == 1 && dst[m].sx % 4 == 0 && dst[m].sy % 4 == 0 &&
-                       dst[m].sb % 4 == 0 && ((uintptr_t)dst[m].ptr % 16) == 0) ? 1 : 0;
-      hipLaunchKernelGGL(irfft_rows_kernel, grid, dim3(512), lds, st, mid, (long long)pix_stride, im_off, re_off, n, H, W, L,
-                         to_view(dst[m]), 1.0f / ((float)H * (float)W), pw, vec, B);
-      FCVSR_LAUNCH_CHECK();
-    }
+    const bool mid_vec = pix_stride % 4 == 0 && im_off % 4 == 0 && re_off % 4 == 0 && ((uintptr_t)mid % 16) == 0;
+    const int rc = irfft_rows(mid, (long long)pix_stride, im_off, re_off, n, B, H, W, pw, mid_vec, &dst[m], st);
+    if (rc) return rc;
   }
   return 0;
 }

@@ -8,7 +8,6 @@
 // quads of a pixel are 8 consecutive lanes, so feature accesses are 128-byte runs and the per-pixel adaptive kernels
 // (12 values per quad, channel index c*3+t) are 192/384-byte runs.  HBM-bound: the dominant traffic is K1
 // (3*C values per pixel per step), read once from HBM (second touch hits L2) in f32 or the 16-bit MFMA dtype.
-#include <stdlib.h>
 #include "common.h"
 #include "mfma_util.h"
 
@@ -292,20 +291,11 @@ constexpr int kKtRow = 3 * kJC + 8;                   // halfwords per pixel row
 // (192 x 64) x (64 x 72): 18 MFMA tiles spread over the 4 waves, operands straight from L2 (weights) / HBM (the 64-channel
 // predictor features), result rounded to the MFMA dtype into LDS - exactly what the stand-alone F[1] launch would have
 // stored, minus 1152 bytes written and 2 x 1152 bytes read per pixel and iteration set.
-#ifndef FCVSR_IAC_PIPE
-#define FCVSR_IAC_PIPE 1
-#endif
-// Ablation builds (-DFCVSR_IAC_ABL=bits, one library per value run through scripts/ab_lib.sh; profiles/r03_iac_ablation.txt):
-// 1 no gather loads, 2 no SAC arithmetic / LDS reads, 4 no predictor GEMM, 8 no stores, 16 no offset loads.  0 in every shipped build.
-#ifndef FCVSR_IAC_ABL
-#define FCVSR_IAC_ABL 0
-#endif
 // Persistent workgroups (the host launches two per CU): each walks a contiguous run of tiles, so the predictor weights of
 // its waves (FK: 4 or 8 MFMA A-fragments) and the bias are fetched once per workgroup instead of once per tile (24 KB per
 // tile was a quarter of what a tile pulled through L2), and consecutive tiles of a workgroup share their halo columns in L1.
 template <int KDT, int ADT, int ND, bool FK>
 __global__ __launch_bounds__(256, 2) void iac_step64_kernel(IacArgs a) {
-  constexpr bool PIPE = FCVSR_IAC_PIPE != 0;
   const View k1 = a.k1;
   const float slope = a.slope;
   const int H = a.H, W = a.W, tiles_x = a.tiles_x, tiles_y = a.tiles_y;
@@ -367,7 +357,6 @@ __global__ __launch_bounds__(256, 2) void iac_step64_kernel(IacArgs a) {
     const long long osb = d1 ? a.d[1].off.sb : a.d[0].off.sb, osy = d1 ? a.d[1].off.sy : a.d[0].off.sy;
     const long long osx = d1 ? a.d[1].off.sx : a.d[0].off.sx, osc = d1 ? a.d[1].off.sc : a.d[0].off.sc;
     const float* op = op0 + (long long)bb * osb + (long long)gy * osy + (long long)gx * osx;
-    if (FCVSR_IAC_ABL & 16) return make_float2(0.25f, 0.25f);
     return make_float2(op[0], op[osc]);
   };
   float2 off_next = make_float2(0.f, 0.f);
@@ -410,7 +399,7 @@ __global__ __launch_bounds__(256, 2) void iac_step64_kernel(IacArgs a) {
   // The 12 pixel fragments are requested here, with the offsets; the MFMAs run after the first direction's taps have been
   // issued, so the gather latency hides behind them.
   uint4 kf[3][4];
-  if (FK && !(FCVSR_IAC_ABL & 4)) {
+  if (FK) {
     const uint16_t* k0p = reinterpret_cast<const uint16_t*>(a.k0.p) + (long long)b * a.k0.sb + hh * 8;
 #pragma unroll
     for (int nt = 0; nt < 3; ++nt) {
@@ -520,8 +509,7 @@ __global__ __launch_bounds__(256, 2) void iac_step64_kernel(IacArgs a) {
       const int src = dir * 32 + it * 8 + (lane >> 3);  // the lane that owns (dir, it, this lane's pixel)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        if (FCVSR_IAC_ABL & 1) tap[dir][it][q] = Pack8<ADT>{};
-        else tap[dir][it][q] = ld_p8<ADT>(pb, __shfl(my_eo[q], src));
+        tap[dir][it][q] = ld_p8<ADT>(pb, __shfl(my_eo[q], src));
       }
     }
   };
@@ -564,7 +552,7 @@ __global__ __launch_bounds__(256, 2) void iac_step64_kernel(IacArgs a) {
         unpack_k24<KDT>(j < 2 ? kin[j] : khal, k);
         float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int tt = 0; tt < ((FCVSR_IAC_ABL & 2) ? 0 : 3); ++tt) {
+        for (int tt = 0; tt < 3; ++tt) {
           const int sp = (y + tt) * kIHX + hx;
           const float4 va = *reinterpret_cast<const float4*>(s_s + rec(sp, 0)), vb = *reinterpret_cast<const float4*>(s_s + rec(sp, 1));
           const float v[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
@@ -589,7 +577,7 @@ __global__ __launch_bounds__(256, 2) void iac_step64_kernel(IacArgs a) {
         unpack8<ADT>(fpk[dir][j], f);
         float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int tt = 0; tt < ((FCVSR_IAC_ABL & 2) ? 0 : 3); ++tt) {
+        for (int tt = 0; tt < 3; ++tt) {
           const int vp = y * kIHX + x + tt;
           const float4 va = *reinterpret_cast<const float4*>(v_s + rec(vp, 0)), vb = *reinterpret_cast<const float4*>(v_s + rec(vp, 1));
           const float v[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
@@ -601,14 +589,13 @@ __global__ __launch_bounds__(256, 2) void iac_step64_kernel(IacArgs a) {
           acc[c] += f[c];
           acc[c] = acc[c] >= 0.f ? acc[c] : acc[c] * slope;
         }
-        if (!(FCVSR_IAC_ABL & 8) || acc[0] == 1234.5f)
-          st_p8<ADT>(dst.p, (long long)b * dst.sb + (long long)gy * dst.sy + (long long)gx * dst.sx + c0, acc);
+        st_p8<ADT>(dst.p, (long long)b * dst.sb + (long long)gy * dst.sy + (long long)gx * dst.sx + c0, acc);
       }
     }
   };
 
   issue_taps(0);
-  if (FK && !(FCVSR_IAC_ABL & 4)) {                                            // the predicted kernels of the lane's pixels: LDS -> registers, once
+  if (FK) {                                            // the predicted kernels of the lane's pixels: LDS -> registers, once
     predictor_gemm();                                  // kf requested before the taps: in flight since the tile began
     __syncthreads();                                   // GEMM results of all four waves are in kt_s
 #pragma unroll
@@ -624,13 +611,12 @@ __global__ __launch_bounds__(256, 2) void iac_step64_kernel(IacArgs a) {
     __syncthreads();                                   // kt_s is dead: its bytes become s_s / v_s
   }
   warp_store(0);
-  if (ND > 1 && PIPE) { issue_taps(1); issue_fin(1); } // in flight during direction 0's LDS phases
+  if (ND > 1) { issue_taps(1); issue_fin(1); }        // in flight during direction 0's LDS phases
   if (t + 1 < t_end) off_next = load_off(t + 1, tid);
   __syncthreads();
   sac_phases(0);
   if (ND > 1) {
     // s_s was last read in phase 2 of direction 0, which every wave has left (barrier inside sac_phases)
-    if (!PIPE) { issue_taps(1); issue_fin(1); }
     warp_store(1);
     __syncthreads();
     sac_phases(1);
@@ -680,9 +666,6 @@ struct Iac2Args {        // compact: both directions share every stride (host-ch
 #ifndef FCVSR_IAC2_WGS
 #define FCVSR_IAC2_WGS 3
 #endif
-#ifndef FCVSR_IAC2_EARLY
-#define FCVSR_IAC2_EARLY 2
-#endif
 // (Tried and dropped, round 3: 8-wave workgroups - two 4-row tiles over one weight copy, 16 waves per CU: 252 vs 248 us; one 8-row tile
 // (warped halo 1.43 instead of 1.71 pixels per output pixel) needs <= 128 registers for two workgroups per CU and spilled 49.)
 template <int KDT, int ADT>
@@ -692,7 +675,7 @@ __global__ __launch_bounds__(256, FCVSR_IAC2_WGS) void iac_fused2_kernel(Iac2Arg
   constexpr bool BF = KDT == FCVSR_BF16;
   constexpr int SPP = 32 * NG;                           // pixel slots per gather pass
   constexpr int ND = 2, NP = (kQNS + SPP - 1) / SPP;     // 3 gather passes
-  constexpr int EARLY = FCVSR_IAC2_EARLY;                // passes of direction 1 requested before direction 0's LDS phases
+  constexpr int EARLY = 2;                               // passes of direction 1 requested before direction 0's LDS phases
   __shared__ __align__(16) float s_all[kQNS * kJC];      // 24,576 B (4 rows) / 40,960 B (8 rows); v = the first kQY * 16 records
   __shared__ __align__(16) uint16_t w_s[3 * kJC * kJC];  // 24,576 B, 16-byte segments XOR (row & 7)
   __shared__ __align__(16) float kb_s[3 * kJC];
@@ -856,10 +839,7 @@ __global__ __launch_bounds__(256, FCVSR_IAC2_WGS) void iac_fused2_kernel(Iac2Arg
     __builtin_amdgcn_sched_barrier(0);
     // ---- predictor GEMM of the wave's pixel row: K1p[t*4 + cb] = kernels of channels q*16 + cb*4 .. +3, tap t (16-bit, what
     // the stand-alone F[1] launch would have stored) ----
-#ifndef FCVSR_IAC2_KF32
-#define FCVSR_IAC2_KF32 1
-#endif
-    constexpr bool KF = FCVSR_IAC2_KF32 != 0 && NG == 1 && BF;   // kernels kept as (rounded) f32: 24 more registers, 144 fewer conversions per tile (bf16: two VALU ops per pair)
+    constexpr bool KF = NG == 1 && BF;   // kernels kept as (rounded) f32: 24 more registers, 144 fewer conversions per tile (bf16: two VALU ops per pair)
     uint2 K1p[KF ? 1 : 12];
     float K1f[KF ? 12 : 1][4];
     {
@@ -1001,12 +981,9 @@ static void launch_iac64(int adt, dim3 grid, hipStream_t st, IacArgs a) {
   a.ntiles = (int)grid.x;
   // Tile runs pay off for the fused-predictor kernel only (its workgroups stage 24 KB of weights first: 384 -> 350 us per
   // 16 x 180 x 320 iteration); the others lose 3-8 % to a run of any length (measured with 2...28 tiles per workgroup) and
-  // keep one tile per workgroup.  FCVSR_IAC_PERSIST: bit 0 = fused-predictor kernel, bit 1 = the others (experiments).
-  static const int persist = getenv("FCVSR_IAC_PERSIST") ? atoi(getenv("FCVSR_IAC_PERSIST")) : 1;
-  static const int tpw = getenv("FCVSR_IAC_TPW") ? atoi(getenv("FCVSR_IAC_TPW")) : 0;
-  if (persist & (FK ? 1 : 2)) {
+  // keep one tile per workgroup.
+  if (FK) {
     int nwg = iac_persistent_wgs() / (int)grid.y;
-    if (tpw > 0) nwg = ((int)grid.x + tpw - 1) / tpw;
     nwg = nwg < 8 ? 8 : nwg / 8 * 8;
     if (nwg < (int)grid.x) grid.x = nwg;
   }
@@ -1049,10 +1026,9 @@ extern "C" int fcvsr_iac_step(const fcvsr_view* prev, const fcvsr_view* off, con
   FCVSR_CHECK_ARG(((uintptr_t)k1->ptr % 16) == 0 && k1->sx % g == 0 && k1->sy % g == 0 && k1->sb % g == 0, "k1 alignment");
   const int tx = cdiv(W, kIX), ty = cdiv(H, kIY);
   // 64-channel kernel: 16-byte accesses of 8 channels (features) / 24 kernel values
-  static const bool no_wide = getenv("FCVSR_IAC_WIDE") && atoi(getenv("FCVSR_IAC_WIDE")) == 0;
   const int fa = adt == FCVSR_F32 ? 4 : 8;
   auto wide_ok = [&](const fcvsr_view* v) { return ((uintptr_t)v->ptr % 16) == 0 && v->sx % fa == 0 && v->sy % fa == 0 && v->sb % fa == 0; };
-  const bool wide = !no_wide && prev->c % kJC == 0 && wide_ok(prev) && wide_ok(feat_in) && wide_ok(dst) &&
+  const bool wide = prev->c % kJC == 0 && wide_ok(prev) && wide_ok(feat_in) && wide_ok(dst) &&
                     (long long)H * prev->sy < (1ll << 31);
   dim3 grid(B * tx * ty, prev->c / (wide ? kJC : kIC));
   hipStream_t st = (hipStream_t)stream;
@@ -1133,14 +1109,13 @@ extern "C" int fcvsr_iac_step2_fused(const fcvsr_view* prev, const fcvsr_view* o
   a.k1 = to_view(*k0); a.k0 = to_view(*k0); a.wk = (const uint16_t*)wk; a.kbias = kbias;
   a.slope = slope; a.B = B; a.H = H; a.W = W; a.tiles_x = tx; a.tiles_y = ty;
   hipStream_t st = (hipStream_t)stream;
-  static const int form = getenv("FCVSR_IAC_FORM") ? atoi(getenv("FCVSR_IAC_FORM")) : 2;   // 1 = iac_step64_kernel (kernels through LDS)
   bool same = adt != FCVSR_F32 && adt == k0->dtype && (long long)H * k0->sy < (1ll << 31);
   {
     const fcvsr_view* sets[4] = {prev, off, feat_in, dst};
     for (const fcvsr_view* v : sets)
       same = same && v[0].sb == v[1].sb && v[0].sy == v[1].sy && v[0].sx == v[1].sx && v[0].sc == v[1].sc && (long long)H * v[0].sy < (1ll << 31);
   }
-  if (form == 2 && same && slope >= 0.f && slope <= 1.f) {   // kernels in registers, three workgroups per CU (iac_fused2_kernel)
+  if (same && slope >= 0.f && slope <= 1.f) {   // kernels in registers, three workgroups per CU (iac_fused2_kernel)
     Iac2Args q;
     for (int d = 0; d < 2; ++d) {
       q.prev[d] = (const uint16_t*)prev[d].ptr; q.off[d] = (const float*)off[d].ptr;

@@ -10,7 +10,6 @@
 //      the 340 halo pixels - 44 small MFMAs instead of 576 multiply-adds per output pixel on the vector ALU.
 //   3. out[y][x] += bias + sum_tap P[y+dy][x+dx][tap]   (out holds the bilinear x4 base skip).
 // HBM traffic per output pixel: 14 bytes of u1 (with halo) + 8 bytes of out, instead of 128 written + ~170 read.
-#include <stdlib.h>
 #include "common.h"
 #include "mfma_util.h"
 
@@ -221,8 +220,7 @@ extern "C" int fcvsr_tail_fused(const fcvsr_view* u1, const void* w2, const floa
     hipDeviceProp_t prop;
     wgs[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? 3 * prop.multiProcessorCount : 768;
   }
-  static const int tpw = getenv("FCVSR_TAIL_TPW") ? atoi(getenv("FCVSR_TAIL_TPW")) : 0;   // tiles per workgroup (experiments)
-  int nwg = tpw > 0 ? cdiv(a.ntiles, tpw) : wgs[dev];
+  int nwg = wgs[dev];
   nwg = nwg < 8 ? 8 : nwg / 8 * 8;
   dim3 grid(nwg < a.ntiles ? nwg : a.ntiles);
   hipStream_t st = (hipStream_t)stream;

@@ -181,7 +181,7 @@ class Engine:
         """Storage dtype of the SCNetbk trunk (x, t2, R, cross-scale terms, block outputs): f32, or - with
         model.trunk16 in the 16-bit modes - the MFMA operand dtype (halves the bytes and the staging instructions of
         every SCNet kernel; f16 recommended: each block rounds the trunk once)."""
-        if self.precision == "f32" or not getattr(self._model(), "trunk16", False):
+        if self.precision == "f32" or not self._model().trunk16:
             return torch.float32
         return self._adt()
 
@@ -292,8 +292,8 @@ class Engine:
         fdt = self._adt(freq=True)
         # the offset spectra feed only convcorr.0: stored in its operand dtype (bit-identical results, half the bytes)
         off = self._new(dev, 2 * B, H, Wf, 2 * n, dtype=fdt)
-        fuse_mlp = fdt != torch.float32 and n == 64 and getattr(m, "fuse_freq_mlp", True)
-        if fuse_mlp:
+        fused = fdt != torch.float32 and n == 64               # convfuse, convcrt and convcorr as fused kernels
+        if fused:
             # the whole convfuse stack for both directions in one kernel: hidden tensors never leave the CU
             ws = [self._weights(f"MGAA.convfuse.{i}", torch.bfloat16)[0] for i in (0, 2, 4)]
             P2 = C.c_void_p * 2
@@ -312,8 +312,7 @@ class Engine:
                                             for d, xa in dirs], res_scale=[1.0, -1.0], freq=True)
         sim = self._new(dev, B, H, Wf, 4)
         off4 = self._new(dev, 2 * B, H, Wf, 4)
-        fuse_head = fuse_mlp and getattr(m, "fuse_freq_head", True)
-        if fuse_head:
+        if fused:
             # convcrt (128 -> 64 -> 4 on the centre spectrum) as one launch
             check(L.fcvsr_freq_head(x2f.data_ptr(), hip.F32, fs, B * H * Wf,
                                     self._weights("MGAA.convcrt.0", torch.bfloat16)[0].data_ptr(), None,
@@ -340,7 +339,7 @@ class Engine:
             # CVSR_freq.py:1318-1337), so its 81 input channels contribute exact zeros to convcorr.0 everywhere else:
             # the stack runs over both directions on the offset spectra alone, then the narrow strip x < 8 is recomputed
             # with the lookup channels and pasted over - the same sums as the full concat (zeros add nothing to an f32 chain).
-            if fuse_head:
+            if fused:
                 check(L.fcvsr_freq_head(off.data_ptr(), hip.BF16, 2 * n, 2 * B * H * Wf,
                                         self._weights("MGAA.convcorr.0", torch.bfloat16, cols=(0, 2 * n))[0].data_ptr(),
                                         self._weights("MGAA.convcorr.2", torch.bfloat16)[0].data_ptr(),
@@ -360,7 +359,7 @@ class Engine:
             for d in range(2):
                 self._conv("MGAA.convcorr.0", [off_s[d * B:(d + 1) * B], corr], c0_s[d * B:(d + 1) * B], act=ACT_RELU,
                            freq=True)
-            if fuse_head:
+            if fused:
                 c1_s = self._new(dev, 2 * B, H, xs, n, dtype=fdt)
                 off4_s = self._new(dev, 2 * B, H, xs, 4)
                 self._conv("MGAA.convcorr.2", [c0_s], c1_s, act=ACT_RELU, freq=True)
@@ -400,7 +399,7 @@ class Engine:
         self._conv("MGAA.F.0", [kp], k0)
         # 16-bit modes, n = 64: F[1] (a 1x1 convolution) is folded into the IAC kernel - the A*3n adaptive-kernel channels
         # (1152 bytes per pixel) are computed per tile and never stored
-        fold_f1 = fused_iac and n == 64 and self.precision != "f32" and getattr(self._model(), "fold_f1", True)
+        fold_f1 = fused_iac and n == 64 and self.precision != "f32" and self._model().fold_f1
         if not fold_f1:
             K = self._new(dev, B, H, W, A * 3 * n, dtype=self._adt() if fused_iac else torch.float32)
             self._conv("MGAA.F.1", [k0], K)
@@ -487,21 +486,14 @@ class Engine:
         par = self._par
         masks = self._mask(Q, H, W, dev)
         spec = self._new(dev, B, H, Wf, 2 * n)
-        work = self._new(dev, B, H, Wf, 2 * n)                   # (band-by-band path)
         xv = view(x)
         check(L.fcvsr_rfft2(C.byref(xv), B, H, W, n, spec.data_ptr(), 2 * n, 0, n, st), "fcvsr_rfft2")
         bands = self._new(dev, Q, B, H, W, n)
-        if masks.is_contiguous() and getattr(m, "fuse_bands", True):
-            # all Q masked inverse transforms in one call: the spectrum columns are read once (fcvsr_irfft2_bands)
-            work = self._new(dev, Q, B, H, Wf, 2 * n)
-            bvs = (hip.View * Q)(*[view(bands[q]) for q in range(Q)])
-            check(L.fcvsr_irfft2_bands(spec.data_ptr(), 2 * n, 0, n, B, H, W, n, masks.data_ptr(), Q, work.data_ptr(), bvs, st),
-                  "fcvsr_irfft2_bands")
-        else:
-            for q in range(Q):
-                bv = view(bands[q])
-                check(L.fcvsr_irfft2(spec.data_ptr(), 2 * n, 0, n, B, H, W, n, masks[q].data_ptr(), work.data_ptr(),
-                                     C.byref(bv), st), "fcvsr_irfft2")
+        # all Q masked inverse transforms in one call: the spectrum columns are read once (fcvsr_irfft2_bands)
+        work = self._new(dev, Q, B, H, Wf, 2 * n)
+        bvs = (hip.View * Q)(*[view(bands[q]) for q in range(Q)])
+        check(L.fcvsr_irfft2_bands(spec.data_ptr(), 2 * n, 0, n, B, H, W, n, masks.data_ptr(), Q, work.data_ptr(), bvs, st),
+              "fcvsr_irfft2_bands")
         freq = [bands[Q - 1 - i] for i in range(Q)]               # 'l2h' => reversed band list (:2204-2205)
         s_f = self._new(dev, B, H, W, n)
         s_o = self._new(dev, B, H, W, n)
@@ -557,7 +549,7 @@ class Engine:
         t2 = [like(x, n, tdt) for x in xs]
         r1 = [like(x, n, self._adt()) for x in xs]
         # RCB.body.2's output r is read once more (gc_apply): with the level-grouped tail it is stored like the trunk
-        r16 = self.precision != "f32" and tdt != torch.float32 and getattr(m, "pool_first", True)
+        r16 = self.precision != "f32" and tdt != torch.float32
         rr = [like(x, n, tdt if r16 else torch.float32) for x in xs]
         self._convg(pre + ".body.0", [dict(srcs=[x], dst=t) for x, t in zip(xs, t1)], act=ACT_LEAKY, slope=0.1)
         self._convg(pre + ".body.2", [dict(srcs=[a], dst=t) for a, t in zip(t1, t2)])
@@ -567,7 +559,7 @@ class Engine:
         w1g, w2g = par[pre + ".RCB.gcnet.channel_add_conv.0.weight"], par[pre + ".RCB.gcnet.channel_add_conv.2.weight"]
         nparts = [((x.shape[1] + 3) // 4) * ((x.shape[2] + 31) // 32) for x in xs]
         parts = [self._new(x.device, x.shape[0], npt, n + 2) for x, npt in zip(xs, nparts)]
-        if r16 and n == 64 and getattr(m, "gc_separate", True):
+        if r16 and n == 64:
             # r is stored in 16 bit anyway: run the layer without the ContextBlock epilogue (it then goes to the resident-weight
             # kernel: 102 vs 185 us) and compute the softmax-pool partials from the stored r in one launch for all levels
             self._convg(pre + ".RCB.body.2", [dict(srcs=[a], dst=t) for a, t in zip(r1, rr)])
@@ -580,7 +572,7 @@ class Engine:
         else:
             fused_gc = self._convg(pre + ".RCB.body.2", [dict(srcs=[a], dst=t, gc_partial=pt) for a, t, pt in zip(r1, rr, parts)],
                                    gc_wmask=wmask if self.precision != "f32" else None)
-        if fused_gc and getattr(m, "pool_first", True):
+        if fused_gc:
             return self._block_rcb_tail_levels(pre, xs, t2, rr, parts, nparts, w1g, w2g, tdt)
         R = []
         for l, x in enumerate(xs):
@@ -588,14 +580,10 @@ class Engine:
             B, H, W, _ = x.shape
             r = rr[l]
             add = self._new(dev, B, n)
-            if fused_gc:
-                check(L.fcvsr_gc_finish(parts[l].data_ptr(), nparts[l], w1g.data_ptr(), w2g.data_ptr(), B, n,
-                                        add.data_ptr(), st), "fcvsr_gc_finish")
-            else:
-                nblk = (H * W + 255) // 256
-                scratch = self._new(dev, B * nblk * (n + 2))
-                check(L.fcvsr_gc_context(r.data_ptr(), wmask.data_ptr(), w1g.data_ptr(), w2g.data_ptr(), B, H, W, n,
-                                         add.data_ptr(), scratch.data_ptr(), scratch.numel(), st), "fcvsr_gc_context")
+            nblk = (H * W + 255) // 256
+            scratch = self._new(dev, B * nblk * (n + 2))
+            check(L.fcvsr_gc_context(r.data_ptr(), wmask.data_ptr(), w1g.data_ptr(), w2g.data_ptr(), B, H, W, n,
+                                     add.data_ptr(), scratch.data_ptr(), scratch.numel(), st), "fcvsr_gc_context")
             Rl = self._new(dev, B, H, W, n, dtype=tdt)
             check(L.fcvsr_gc_apply(r.data_ptr(), add.data_ptr(), t2[l].data_ptr(), Rl.data_ptr(), self._code(tdt), 0.2, B,
                                    H, W, n, st), "fcvsr_gc_apply")
@@ -633,7 +621,7 @@ class Engine:
             fl[l].partial, fl[l].add, fl[l].nparts = parts[l].data_ptr(), adds[l].data_ptr(), nparts[l]
         check(L.fcvsr_gc_finish_levels(fl, 3, w1g.data_ptr(), w2g.data_ptr(), B, n, st), "fcvsr_gc_finish_levels")
         P = [self._new(dev, B, xs[l].shape[1] // 2, xs[l].shape[2] // 2, n, dtype=tdt) for l in (0, 1)]
-        if (getattr(m, "fuse_rcb_l0", True) and tdt != torch.float32 and rr[0].dtype == tdt and xs[0].dtype == tdt
+        if (m.fuse_rcb_l0 and tdt != torch.float32 and rr[0].dtype == tdt and xs[0].dtype == tdt
                 and n % 8 == 0):
             return self._block_rcb_tail_l0(pre, xs, t2, rr, adds, P, tdt)
         R = [torch.empty_like(t) for t in t2]
@@ -735,9 +723,7 @@ class Engine:
             x = x.contiguous().float()
             self._refresh(dev)
             ns = max(1, min(int(getattr(m, "streams", 1)), B))
-            flags = tuple(bool(getattr(m, f, True)) for f in ("trunk16", "fold_f1", "fuse_tail", "pool_first", "fuse_freq_mlp",
-                                                              "fuse_freq_head", "fast_feat", "fuse_rcb_tail", "gc_separate", "fast_last",
-                                                              "fuse_rcb_l0", "fuse_bands"))
+            flags = (bool(m.trunk16), bool(m.fold_f1), bool(m.fuse_tail), bool(m.fuse_rcb_l0))
             cfg = (tuple(x.shape[1:]), self.precision, str(dev), self._pack_epoch, flags)
             if ns > 1 and cfg not in self._warm:
                 # First pass of a configuration: re-packed weights, band masks and per-kernel attributes are created lazily
@@ -812,7 +798,7 @@ class Engine:
         adt = self._tdt()
         f2 = self._new(dev, B, H, W, n, dtype=adt)
         cin = T * Cimg
-        if adt != torch.float32 and cin == 7 and n == 64 and getattr(m, "fast_feat", True):
+        if adt != torch.float32 and cin == 7 and n == 64:
             # the whole 3x3 patch fits one K = 64 GEMM step: dedicated kernel, the 7 output blocks go straight to their tensors.
             # The three inputs of the stacked MGAA call are three DENSE tensors (2B,H,W,n) = [clip's group 1 | clip's group 3],
             # not channel slices of one 3n-channel tensor: every later reader (FFT rows, IAC taps, conv_KP, conv3's residual)
@@ -877,7 +863,7 @@ class Engine:
         cv, ov = view(centre), view(out_v)
         check(L.fcvsr_bilinear_up4(C.byref(cv), B, H, W, C.byref(ov), st), "fcvsr_bilinear_up4")
         fuse_tail = (self.precision != "f32" and n == 64 and Cimg == 1 and self._par["upconv2.weight"].shape[-1] == 1
-                     and getattr(m, "fuse_tail", True))
+                     and m.fuse_tail)
         if fuse_tail:
             # upconv2 (1x1) + PixelShuffle + PReLU + conv_last0 in one kernel: the 64-channel tensor at 4H x 4W is never stored
             dt = self._adt()
@@ -890,7 +876,7 @@ class Engine:
         else:
             u2 = self._new(dev, B, 4 * H, 4 * W, n, dtype=self._adt())
             self._conv("upconv2", [u1], u2, act=ACT_PRELU, slope_t=a_t, ps=True)
-            if self.precision != "f32" and n == 64 and Cimg <= 3 and getattr(m, "fast_last", True):
+            if self.precision != "f32" and n == 64 and Cimg <= 3:
                 # 3x3 up-convs (full / RGB models): conv_last0 as a memory-bound "taps are MFMA columns" pass over u2
                 wl = self._last_weights("conv_last0", self._adt(), Cimg)
                 u2v = view(u2)

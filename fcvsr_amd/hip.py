@@ -71,7 +71,6 @@ _PV = C.POINTER(View)
 SIGNATURES = {
     "fcvsr_last_error": [],
     "fcvsr_last_conv_kernel": [],
-    "fcvsr_debug_res_stamps": [C.c_void_p, C.c_size_t],
     "fcvsr_conv2d_wgrad_scratch_elems": [C.c_int] * 7,
     "fcvsr_conv2d_wgrad": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_longlong, C.c_int, C.c_void_p],
@@ -307,9 +306,6 @@ def conv2d_mfma(groups, wpacked: torch.Tensor, ksize: int, cout: int, mma_dtype:
     check(lib().fcvsr_conv2d_mfma(descs, n, mma_dtype, stream_ptr()), "fcvsr_conv2d_mfma")
 
 
-F32_MFMA = os.environ.get("FCVSR_F32_MFMA", "1") == "1"     # exact-f32 layers on the matrix cores where eligible
-
-
 def conv2d(srcs: Sequence[torch.Tensor], wpacked: torch.Tensor, ksize: int, cout: int, dst: torch.Tensor, *,
            bias: Optional[torch.Tensor] = None, stride: int = 1, act: int = ACT_NONE, slope: float = 0.0,
            slope_t: Optional[torch.Tensor] = None, res: Sequence[torch.Tensor] = (),
@@ -317,7 +313,7 @@ def conv2d(srcs: Sequence[torch.Tensor], wpacked: torch.Tensor, ksize: int, cout
            w_f32mfma: Optional[torch.Tensor] = None, bias_f32mfma: Optional[torch.Tensor] = None) -> torch.Tensor:
     """srcs / res / dst are (b,y,x,c)-ordered tensors (any strides).  Exact f32: the direct VALU kernel, or - when
     `w_f32mfma` (pack_conv_weight_f32mfma) is given and the layer qualifies - the f32-operand matrix-core kernel."""
-    if w_f32mfma is not None and F32_MFMA and len(srcs) == 1 and stride == 1 and PROFILE is None:
+    if w_f32mfma is not None and len(srcs) == 1 and stride == 1 and PROFILE is None:
         dm = ConvDesc()              # (pixel-shuffled layers: w_f32mfma / bias_f32mfma are in sub-pixel-major row order)
         _fill_desc(dm, srcs, w_f32mfma, ksize, cout, w_f32mfma.shape[1], dst, bias_f32mfma if pixel_shuffle else bias, stride, act,
                    slope, slope_t, res, res_scale, pixel_shuffle)

@@ -20,7 +20,6 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-import os
 import weakref
 from typing import Dict, List, Optional, Tuple
 
@@ -87,9 +86,6 @@ def pack_weight_mfma(w: torch.Tensor, tdt: torch.dtype, transposed: bool) -> tor
     return out
 
 
-_PLAN_ENABLED = os.environ.get("FCVSR_PACK_PLAN", "1") == "1"
-
-
 class WeightPacker:
     """The 16-bit weight operands of ONE parameter set's training passes (a model at one train precision, see
     _GShiftBase.train_packer).  Within a pass a packing is cached per (storage pointer, parameter version, dtype, transposed), so a
@@ -114,8 +110,6 @@ class WeightPacker:
         (same storage), re-pack all of its weights from their current values in one launch.  Also guarantees that a hipGraph
         capture records the packing kernels of its pass."""
         self._packed.clear()
-        if not _PLAN_ENABLED:
-            return
         if self.plan is None and self._record and not torch.cuda.is_current_stream_capturing():
             self.plan = _build_plan(self._record)            # (uploads the table: never inside a capture)
         self._record = []
@@ -138,7 +132,7 @@ class WeightPacker:
         out = self._packed.get(key)
         if out is None:
             out = self._packed[key] = pack_weight_mfma(w, tdt, transposed)
-            if _PLAN_ENABLED and self.plan is None and w.is_leaf and w.dtype == torch.float32 and w.is_contiguous():
+            if self.plan is None and w.is_leaf and w.dtype == torch.float32 and w.is_contiguous():
                 self._record.append((w, tdt, transposed, out))   # a parameter in stable storage: part of the next passes' one launch
         return out
 

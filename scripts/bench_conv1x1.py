@@ -33,17 +33,12 @@ def run(name, B, H, W, cin, cout, src16, dst16, ps=False, pix_stride=None, iters
 
 
 B = 4
-for dbg in os.environ.get("DBGS", "0").split(","):
-    os.environ["FCVSR_MFMA_DBG"] = dbg
-    for mw in os.environ.get("MWS", "2,1").split(","):
-        os.environ["FCVSR_MFMA_MW"] = mw
-        print(f"--- dbg={dbg} MW={mw}")
-        run("F1 64->576 src f32 dst f32", B, 180, 320, 64, 576, False, False)
-        run("F1 64->576 src bf16 dst f32", B, 180, 320, 64, 576, True, False)
-        run("F1 64->576 src bf16 dst bf16", B, 180, 320, 64, 576, True, True)
-        run("upconv2 64->256 PS f32->f32", B, 360, 640, 64, 256, False, False, ps=True, iters=5)
-        run("upconv2 64->256 PS bf16->bf16", B, 360, 640, 64, 256, True, True, ps=True, iters=5)
-        run("upconv2-like 64->256 noPS bf16->bf16", B, 360, 640, 64, 256, True, True, ps=False, iters=5)
-        run("convfuse.0-like 128->128 strided f32", B, 180, 161, 128, 128, False, True, pix_stride=384)
-        run("convfuse.0-like 128->128 dense f32", B, 180, 161, 128, 128, False, True)
-        run("down.0 64->64 f32->f32", B, 180, 320, 64, 64, False, False)
+run("F1 64->576 src f32 dst f32", B, 180, 320, 64, 576, False, False)
+run("F1 64->576 src bf16 dst f32", B, 180, 320, 64, 576, True, False)
+run("F1 64->576 src bf16 dst bf16", B, 180, 320, 64, 576, True, True)
+run("upconv2 64->256 PS f32->f32", B, 360, 640, 64, 256, False, False, ps=True, iters=5)
+run("upconv2 64->256 PS bf16->bf16", B, 360, 640, 64, 256, True, True, ps=True, iters=5)
+run("upconv2-like 64->256 noPS bf16->bf16", B, 360, 640, 64, 256, True, True, ps=False, iters=5)
+run("convfuse.0-like 128->128 strided f32", B, 180, 161, 128, 128, False, True, pix_stride=384)
+run("convfuse.0-like 128->128 dense f32", B, 180, 161, 128, 128, False, True)
+run("down.0 64->64 f32->f32", B, 180, 320, 64, 64, False, False)

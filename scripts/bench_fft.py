@@ -20,4 +20,4 @@ def t(fn, iters=20):
 f = lambda: hip.check(L.fcvsr_rfft2(C.byref(sv), B, H, W, n, spec.data_ptr(), 2 * n, 0, n, hip.stream_ptr()), "r")
 g = lambda: hip.check(L.fcvsr_irfft2(spec.data_ptr(), 2 * n, 0, n, B, H, W, n, mask.data_ptr(), work.data_ptr(), C.byref(dv), hip.stream_ptr()), "i")
 byts = src.numel() * 4 + 3 * spec.numel() * 4
-print(f"LDS budget {os.environ.get('FCVSR_FFT_LDS_KB','128')} KB: rfft2 {t(f):8.1f} us  irfft2(mask) {t(g):8.1f} us   (ideal @4.5TB/s: {byts/4.5e6:.0f} us each)")
+print(f"rfft2 {t(f):8.1f} us  irfft2(mask) {t(g):8.1f} us   (ideal @4.5TB/s: {byts/4.5e6:.0f} us each)")
