@@ -9,6 +9,7 @@ GPUs, sharded by `fcvsr_amd.harness.sharding`.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Iterable, List, Optional
 
 import numpy as np
@@ -44,6 +45,52 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
         sr = sr.round() if quantise == "round" else sr            # uint8 cast truncates
         out.append(sr.to(torch.uint8).cpu().numpy())
     return np.concatenate(out, 0)
+
+
+@dataclass
+class SequenceScores:
+    """Per-frame PSNR / SSIM (f64) of one sequence, their means, and the uint8 SR frames when they were asked for."""
+    psnr: np.ndarray
+    ssim: np.ndarray
+    psnr_mean: float
+    ssim_mean: float
+    frames: Optional[np.ndarray] = None
+
+
+@torch.no_grad()
+def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
+                      quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False) -> SequenceScores:
+    """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
+    eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
+
+    lr: (N,C,H,W) float in [0,1]; hr: uint8 (N,C,4H,4W) (host or device).  Windows, padding, crop and quantisation are those of
+    `super_resolve_sequence`; each batch is scored straight from the model output (cropped by view, quantised in the metric
+    kernel) by `device_metrics.frame_metrics`.  Without `return_frames` no SR frame leaves the device."""
+    from .device_metrics import frame_metrics
+    N, C, H, W = lr.shape
+    if tuple(hr.shape) != (N, C, 4 * H, 4 * W):
+        raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, 4 * H, 4 * W)}, got {tuple(hr.shape)}")
+    if hr.dtype != torch.uint8:
+        raise ValueError(f"hr must be uint8, got {hr.dtype}")
+    if quantise not in ("truncate", "round"):
+        raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+    dev = next(model.parameters()).device
+    x = pad_to_multiple(lr.float(), 4).to(dev)
+    p_dev, s_dev, frames = [], [], []                             # per-batch device results, fetched once at the end
+    for s in range(0, N, batch):
+        idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
+        win = torch.stack([x[j] for j in idx], 0)                 # (b, 7, C, Hp, Wp)
+        sr = model(win)[:, :, :4 * H, :4 * W]
+        p, q = frame_metrics(sr, hr[s:s + len(idx)].to(dev), crop_border=crop_border, quantise=quantise, convert_to=convert_to)
+        p_dev.append(p)
+        s_dev.append(q)
+        if return_frames:
+            sr = sr.clamp(0, 1) * 255.0
+            sr = sr.round() if quantise == "round" else sr
+            frames.append(sr.to(torch.uint8).cpu().numpy())
+    psnr_np, ssim_np = torch.cat(p_dev).cpu().numpy(), torch.cat(s_dev).cpu().numpy()
+    return SequenceScores(psnr_np, ssim_np, float(np.mean(psnr_np)), float(np.mean(ssim_np)),
+                          np.concatenate(frames, 0) if return_frames else None)
 
 
 def sequence_psnr(sr_u8: np.ndarray, hr_u8: np.ndarray, crop_border: int = 4) -> float:

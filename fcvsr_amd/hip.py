@@ -143,10 +143,14 @@ SIGNATURES = {
     "fcvsr_divenh_band_backward": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                    C.c_longlong, _I, _VP],
     "fcvsr_corr_lookup_bwd": [_VP, _VP, _I64, _I, _I, _I, _I, _I, _I, _PV, _VP, _VP, _VP],
+    "fcvsr_frame_metrics_scratch_bytes": [_I] * 6,
+    "fcvsr_frame_metrics": [_VP, C.POINTER(C.c_int64), _I, _VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I,
+                            C.POINTER(C.c_double), _VP, _VP, C.c_longlong, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
-             "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong}
+             "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong,
+             "fcvsr_frame_metrics_scratch_bytes": C.c_longlong}
 
 
 def lib() -> C.CDLL:
@@ -335,3 +339,23 @@ def conv2d(srcs: Sequence[torch.Tensor], wpacked: torch.Tensor, ksize: int, cout
         return dst
     check(lib().fcvsr_conv2d(C.byref(d), stream_ptr()), "fcvsr_conv2d")
     return dst
+
+
+QUANT_NONE, QUANT_TRUNCATE, QUANT_ROUND = 0, 1, 2
+
+
+def frame_metric_sums(sr: torch.Tensor, hr: torch.Tensor, quantise: int, crop_border: int, to_y: bool,
+                      window: Sequence[float]) -> torch.Tensor:
+    """fcvsr_frame_metrics: sr (N,C,H,W) uint8 (QUANT_NONE) or f32 (any strides), hr uint8 (N,C,H,W) on the same device.
+    Returns f64 (N, 2) on the device: per frame the squared-error sum over the PSNR region and the SSIM-map sum, both over all
+    scored planes.  Arguments are checked by the library (FCVSR_E_ARG -> HipError)."""
+    N, Cc, H, W = sr.shape
+    to_y = int(bool(to_y))
+    nbytes = lib().fcvsr_frame_metrics_scratch_bytes(N, Cc, H, W, crop_border, to_y)
+    scratch = torch.empty((max(1, nbytes) + 7) // 8, dtype=torch.float64, device=sr.device)
+    out = torch.empty((N, 2), dtype=torch.float64, device=sr.device)
+    s_st, h_st = (C.c_int64 * 4)(*sr.stride()), (C.c_int64 * 4)(*hr.stride())
+    win = (C.c_double * 11)(*[float(v) for v in window])
+    check(lib().fcvsr_frame_metrics(sr.data_ptr(), s_st, quantise, hr.data_ptr(), h_st, N, Cc, H, W, crop_border, to_y, win,
+                                    out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, stream_ptr()), "fcvsr_frame_metrics")
+    return out

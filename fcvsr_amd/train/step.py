@@ -184,10 +184,18 @@ def to_tensor(sample: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
 
 def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torch.Tensor]]], *, epochs: int, device,
         lr: float = 1e-4, weight_decay: float = 1e-5, milestones: Sequence[int] = (2000, 8000, 12000, 20000), gamma: float = 0.5,
-        val_itv: int = 1, ckpt_dir: Optional[str] = None, warm_start_epoch: int = 0, log: Callable[[str], None] = print) -> List[float]:
+        val_itv: int = 1, ckpt_dir: Optional[str] = None, warm_start_epoch: int = 0, log: Callable[[str], None] = print,
+        val_sequences: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None,
+        on_validate: Optional[Callable[[int, float, float], None]] = None) -> List[float]:
     """Epoch loop of the reference (train_LD_freqCVSR_S_22.py:239-266): MultiStepLR stepped at the START of every epoch,
     Charbonnier-sum loss, Adam, `epoch-%d.pth` state_dict checkpoints every `val_itv` epochs (rank 0).
-    `batches(epoch)` yields {'lr_imgs': (b,C,7,h,w), 'hr_imgs': (b,C,f',4h,4w)} like the reference DataLoader."""
+    `batches(epoch)` yields {'lr_imgs': (b,C,7,h,w), 'hr_imgs': (b,C,f',4h,4w)} like the reference DataLoader.
+
+    val_sequences: (lr (N,C,H,W) in [0,1], hr uint8 (N,C,4H,4W)) pairs scored after the checkpoint of every `val_itv`-th epoch
+    on rank 0 (the reference's eval_seq, :263-280): the average over the sequences of each one's mean per-frame PSNR / SSIM
+    (`harness.infer.evaluate_sequence` with its defaults: crop border 4, truncating quantisation) is logged as
+    `PSNR:%f, SSIM: %f` and passed to `on_validate(epoch, psnr, ssim)` (epoch counted from 1).  It runs under no_grad:
+    parameters, gradients and optimizer state are not touched."""
     step = TrainStep(model, lr=lr, weight_decay=weight_decay)
     sched = torch.optim.lr_scheduler.MultiStepLR(step.optimizer, milestones=list(milestones), gamma=gamma)
     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
@@ -209,4 +217,18 @@ def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torc
         if (epoch + 1) % val_itv == 0 and ckpt_dir is not None and rank == 0:
             os.makedirs(ckpt_dir, exist_ok=True)
             torch.save(model.state_dict(), os.path.join(ckpt_dir, "epoch-%d.pth" % (epoch + 1 + warm_start_epoch)))
+        if (epoch + 1) % val_itv == 0 and val_sequences and rank == 0:
+            psnr, ssim = validate(model, val_sequences)
+            log("PSNR:%f, SSIM: %f" % (psnr, ssim))
+            if on_validate is not None:
+                on_validate(epoch + 1, psnr, ssim)
     return history
+
+
+@torch.no_grad()
+def validate(model: torch.nn.Module, sequences: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> Tuple[float, float]:
+    """Mean over `sequences` of each sequence's mean per-frame PSNR and SSIM, scored on the device (reference
+    test_LD_freqCVSR_S_22.py:118-119)."""
+    from ..harness.infer import evaluate_sequence
+    scores = [evaluate_sequence(model, lr, hr) for lr, hr in sequences]
+    return float(np.mean([s.psnr_mean for s in scores])), float(np.mean([s.ssim_mean for s in scores]))

@@ -396,6 +396,25 @@ int fcvsr_tail_fused(const fcvsr_view* u1, const void* w2, const float* b2, cons
  * row tap*C + c (tap = ky*3 + kx), zero rows past 9C.  Used where fcvsr_tail_fused does not apply (3x3 up-convs). */
 int fcvsr_conv_last(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C, const fcvsr_view* out, void* stream);
 
+/* ---- quality metrics of the evaluation harness (reference CVSR_train/metric/psnr_ssim.py:278-398 calculate_psnr / _ssim /
+ * calculate_ssim, applied per frame by cal_psnr_ssim :447-485; the contract is fcvsr_amd/harness/metrics.py) ----------------
+ * N frame pairs (N,C,H,W) with element strides host_*_strides[4] = {n, c, y, x}:
+ *   sr: quantise = FCVSR_QUANT_NONE: uint8 frames; FCVSR_QUANT_TRUNCATE / _ROUND: f32 in [0,1], quantised in the kernel as
+ *       clamp(v, 0, 1) * 255.0f (f32), then truncated toward zero / rounded half-to-even;
+ *   hr: uint8 frames.
+ * to_y = 1 (C = 3, RGB channel order): both are scored on Y = (65.481 R + 128.553 G + 24.966 B) / 255 + 16 (f64); otherwise every
+ * channel is a plane.  PSNR region: crop_border pixels removed on each side; SSIM region: that, shrunk by 5 more per side.
+ *   out[2n]   = sum over the PSNR region and the planes of frame n of (sr - hr)^2;
+ *   out[2n+1] = sum over the SSIM region and the planes of the SSIM map (11x11 Gaussian host_window[11], C1 = (0.01*255)^2,
+ *               C2 = (0.03*255)^2);
+ * all in f64.  Per-tile partials go to scratch (>= fcvsr_frame_metrics_scratch_bytes(...) bytes) and are added in a fixed order:
+ * two calls on the same input give the same bits.  FCVSR_E_ARG when the SSIM region is empty. */
+enum { FCVSR_QUANT_NONE = 0, FCVSR_QUANT_TRUNCATE = 1, FCVSR_QUANT_ROUND = 2 };
+long long fcvsr_frame_metrics_scratch_bytes(int N, int C, int H, int W, int crop_border, int to_y);
+int fcvsr_frame_metrics(const void* sr, const int64_t* host_sr_strides, int quantise, const uint8_t* hr,
+                        const int64_t* host_hr_strides, int N, int C, int H, int W, int crop_border, int to_y,
+                        const double* host_window, double* out, void* scratch, long long scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
