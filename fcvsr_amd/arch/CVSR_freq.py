@@ -201,7 +201,7 @@ class _GShiftBase(nn.Module):
         self.fold_f1 = True
         # 16-bit modes, S model (1x1 up-convs), one image channel: upconv2 + PixelShuffle + PReLU + conv_last0 in one kernel
         self.fuse_tail = True
-        # 16-bit modes: BlockRCB's full-resolution level in one pass (R0 is never stored)
+        # 16-bit modes, n_features == 64: BlockRCB's second half in two launches (fcvsr_rcb_tail)
         self.fuse_rcb_l0 = True
         # capture the launch sequence of a forward in a hipGraph (per input shape) and replay it
         self.use_graph = os.environ.get("FCVSR_GRAPH", "0") == "1"

@@ -409,23 +409,32 @@ struct XsArgs { XsLv lv[3]; int n; };
 // V quads (4 V channels) per thread: V = 2 in the 16-bit modes makes every access 16 bytes per lane
 template <int V> struct QuadV { float4 p[V]; };
 
+// 8 channels of 16-bit storage (one 16-byte access) widened to f32
+template <int DT>
+__device__ __forceinline__ QuadV<2> unpack8(const uint4 v) {
+  QuadV<2> r;
+  if (DT == FCVSR_BF16) {
+    r.p[0] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
+                         __uint_as_float(v.y & 0xffff0000u));
+    r.p[1] = make_float4(__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16),
+                         __uint_as_float(v.w & 0xffff0000u));
+  } else {
+    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+    const h2 a = __builtin_bit_cast(h2, v.x), b = __builtin_bit_cast(h2, v.y), c = __builtin_bit_cast(h2, v.z),
+             d = __builtin_bit_cast(h2, v.w);
+    r.p[0] = make_float4((float)a[0], (float)a[1], (float)b[0], (float)b[1]);
+    r.p[1] = make_float4((float)c[0], (float)c[1], (float)d[0], (float)d[1]);
+  }
+  return r;
+}
+
 template <int DT, int V>
 __device__ __forceinline__ QuadV<V> ldq(const void* base, long long idx) {       // idx counts groups of V quads
   QuadV<V> r;
   if (V == 2 && DT != FCVSR_F32) {
-    const uint4 v = reinterpret_cast<const uint4*>(base)[idx];
-    if (DT == FCVSR_BF16) {
-      r.p[0] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
-                           __uint_as_float(v.y & 0xffff0000u));
-      r.p[V - 1] = make_float4(__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16),
-                               __uint_as_float(v.w & 0xffff0000u));
-    } else {
-      typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-      const h2 a = __builtin_bit_cast(h2, v.x), b = __builtin_bit_cast(h2, v.y), c = __builtin_bit_cast(h2, v.z),
-               d = __builtin_bit_cast(h2, v.w);
-      r.p[0] = make_float4((float)a[0], (float)a[1], (float)b[0], (float)b[1]);
-      r.p[V - 1] = make_float4((float)c[0], (float)c[1], (float)d[0], (float)d[1]);
-    }
+    const QuadV<2> u = unpack8<DT>(reinterpret_cast<const uint4*>(base)[idx]);
+    r.p[0] = u.p[0];
+    r.p[V - 1] = u.p[1];
     return r;
   }
 #pragma unroll
@@ -433,24 +442,27 @@ __device__ __forceinline__ QuadV<V> ldq(const void* base, long long idx) {      
   return r;
 }
 
+// 8 channels rounded to the 16-bit storage type, packed as they are stored (one 16-byte access)
+template <int DT>
+__device__ __forceinline__ uint4 pack8(const float4& lo, const float4& hi) {
+  if (DT == FCVSR_BF16) {
+    typedef __attribute__((ext_vector_type(4))) __bf16 b4;
+    const b4 c0 = {(__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w};
+    const b4 c1 = {(__bf16)hi.x, (__bf16)hi.y, (__bf16)hi.z, (__bf16)hi.w};
+    const uint2 u0 = __builtin_bit_cast(uint2, c0), u1 = __builtin_bit_cast(uint2, c1);
+    return make_uint4(u0.x, u0.y, u1.x, u1.y);
+  }
+  typedef __attribute__((ext_vector_type(4))) _Float16 h4;
+  const h4 c0 = {(_Float16)lo.x, (_Float16)lo.y, (_Float16)lo.z, (_Float16)lo.w};
+  const h4 c1 = {(_Float16)hi.x, (_Float16)hi.y, (_Float16)hi.z, (_Float16)hi.w};
+  const uint2 u0 = __builtin_bit_cast(uint2, c0), u1 = __builtin_bit_cast(uint2, c1);
+  return make_uint4(u0.x, u0.y, u1.x, u1.y);
+}
+
 template <int DT, int V>
 __device__ __forceinline__ void stq(void* base, long long idx, const QuadV<V>& x) {
   if (V == 2 && DT != FCVSR_F32) {
-    uint4 o;
-    if (DT == FCVSR_BF16) {
-      typedef __attribute__((ext_vector_type(4))) __bf16 b4;
-      const b4 c0 = {(__bf16)x.p[0].x, (__bf16)x.p[0].y, (__bf16)x.p[0].z, (__bf16)x.p[0].w};
-      const b4 c1 = {(__bf16)x.p[V - 1].x, (__bf16)x.p[V - 1].y, (__bf16)x.p[V - 1].z, (__bf16)x.p[V - 1].w};
-      const uint2 u0 = __builtin_bit_cast(uint2, c0), u1 = __builtin_bit_cast(uint2, c1);
-      o = make_uint4(u0.x, u0.y, u1.x, u1.y);
-    } else {
-      typedef __attribute__((ext_vector_type(4))) _Float16 h4;
-      const h4 c0 = {(_Float16)x.p[0].x, (_Float16)x.p[0].y, (_Float16)x.p[0].z, (_Float16)x.p[0].w};
-      const h4 c1 = {(_Float16)x.p[V - 1].x, (_Float16)x.p[V - 1].y, (_Float16)x.p[V - 1].z, (_Float16)x.p[V - 1].w};
-      const uint2 u0 = __builtin_bit_cast(uint2, c0), u1 = __builtin_bit_cast(uint2, c1);
-      o = make_uint4(u0.x, u0.y, u1.x, u1.y);
-    }
-    reinterpret_cast<uint4*>(base)[idx] = o;
+    reinterpret_cast<uint4*>(base)[idx] = pack8<DT>(x.p[0], x.p[V - 1]);
     return;
   }
 #pragma unroll
@@ -472,6 +484,27 @@ __device__ __forceinline__ QuadV<V> qv_half_sum(const QuadV<V>& a, const QuadV<V
     r.p[i] = make_float4(0.5f * a.p[i].x + 0.5f * b.p[i].x, 0.5f * a.p[i].y + 0.5f * b.p[i].y,
                          0.5f * a.p[i].z + 0.5f * b.p[i].z, 0.5f * a.p[i].w + 0.5f * b.p[i].w);
   return r;
+}
+
+// acc + bilinear_x2(up) at pixel (yy, xx) of an H x W level, up being (B, H/2, W/2, C) (F.interpolate align_corners=False
+// semantics; taps added in the order 00, 01, 10, 11)
+template <int DT, int V>
+__device__ __forceinline__ QuadV<V> add_up2(QuadV<V> acc, const void* up, int b, int yy, int xx, int H, int W, int cq, int Cq) {
+  const int Hh = H / 2, Wh = W / 2;
+  float sy = 0.5f * ((float)yy + 0.5f) - 0.5f; sy = sy < 0.f ? 0.f : sy;
+  float sx = 0.5f * ((float)xx + 0.5f) - 0.5f; sx = sx < 0.f ? 0.f : sx;
+  const int y0 = (int)sy, x0 = (int)sx;
+  const int y1 = y0 + (y0 < Hh - 1 ? 1 : 0), x1 = x0 + (x0 < Wh - 1 ? 1 : 0);
+  const float ly = sy - (float)y0, lx = sx - (float)x0;
+  const long long u0 = ((long long)b * Hh * Wh) * Cq + cq;
+  const QuadV<V> u00 = ldq<DT, V>(up, u0 + ((long long)y0 * Wh + x0) * Cq), u01 = ldq<DT, V>(up, u0 + ((long long)y0 * Wh + x1) * Cq);
+  const QuadV<V> u10 = ldq<DT, V>(up, u0 + ((long long)y1 * Wh + x0) * Cq), u11 = ldq<DT, V>(up, u0 + ((long long)y1 * Wh + x1) * Cq);
+  const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
+  acc = qv_axpy<V>(w00, u00, acc);
+  acc = qv_axpy<V>(w01, u01, acc);
+  acc = qv_axpy<V>(w10, u10, acc);
+  acc = qv_axpy<V>(w11, u11, acc);
+  return acc;
 }
 
 // Cq counts the per-pixel groups of V quads (C / (4 V))
@@ -509,22 +542,7 @@ __global__ void xscale_levels_kernel(XsArgs a, int Cq) {
       acc = qv_axpy<V>(0.5f, bot, acc);
     }
   }
-  if (L.up) {
-    const int Hh = H / 2, Wh = W / 2;
-    float sy = 0.5f * ((float)yy + 0.5f) - 0.5f; sy = sy < 0.f ? 0.f : sy;
-    float sx = 0.5f * ((float)xx + 0.5f) - 0.5f; sx = sx < 0.f ? 0.f : sx;
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = y0 + (y0 < Hh - 1 ? 1 : 0), x1 = x0 + (x0 < Wh - 1 ? 1 : 0);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    const long long u0 = ((long long)b * Hh * Wh) * Cq + cq;
-    const QuadV<V> u00 = ldq<DT, V>(L.up, u0 + ((long long)y0 * Wh + x0) * Cq), u01 = ldq<DT, V>(L.up, u0 + ((long long)y0 * Wh + x1) * Cq);
-    const QuadV<V> u10 = ldq<DT, V>(L.up, u0 + ((long long)y1 * Wh + x0) * Cq), u11 = ldq<DT, V>(L.up, u0 + ((long long)y1 * Wh + x1) * Cq);
-    const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-    acc = qv_axpy<V>(w00, u00, acc);
-    acc = qv_axpy<V>(w01, u01, acc);
-    acc = qv_axpy<V>(w10, u10, acc);
-    acc = qv_axpy<V>(w11, u11, acc);
-  }
+  if (L.up) acc = add_up2<DT, V>(acc, L.up, b, yy, xx, H, W, cq, Cq);
   stq<DT, V>(L.out, t, acc);
 }
 
@@ -542,15 +560,26 @@ struct Rcb0Args {
   int B, H, W;
 };
 
+// R = lrelu(r + add) + z for 8 channels, rounded to the storage type (what gc_apply_levels stores)
 template <int DT>
-__global__ void __launch_bounds__(256) rcb_level0_kernel(Rcb0Args a, int Cq) {      // Cq = C / 8
+__device__ __forceinline__ QuadV<2> rcb_r(const QuadV<2>& rr, const QuadV<2>& zz, float4 ad0, float4 ad1, float slope) {
+  QuadV<2> R;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float4 av = h ? ad1 : ad0, rv = rr.p[h], zv = zz.p[h];
+    float4 v = make_float4(rv.x + av.x, rv.y + av.y, rv.z + av.z, rv.w + av.w);
+    v.x = v.x >= 0.f ? v.x : v.x * slope; v.y = v.y >= 0.f ? v.y : v.y * slope;
+    v.z = v.z >= 0.f ? v.z : v.z * slope; v.w = v.w >= 0.f ? v.w : v.w * slope;
+    R.p[h] = as_stored<DT>(make_float4(v.x + zv.x, v.y + zv.y, v.z + zv.z, v.w + zv.w));
+  }
+  return R;
+}
+
+// One (2x2 level-0 block over half-resolution pixel (y2, x2), 8 channels cq) of rcb_level0: writes the 2x2 average of the
+// rounded R values (rounded again) to *pool (global memory or LDS), then the four outputs.
+template <int DT>
+__device__ __forceinline__ void rcb0_block(const Rcb0Args& a, int b, int y2, int x2, int cq, int Cq, uint4* pool) {
   const int H2 = a.H >> 1, W2 = a.W >> 1;
-  const long long total = (long long)a.B * H2 * W2 * Cq;
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int cq = (int)(t % Cq);
-  const long long pg = t / Cq;
-  const int x2 = (int)(pg % W2), y2 = (int)((pg / W2) % H2), b = (int)(pg / ((long long)W2 * H2));
   const float* ad = a.add + (long long)b * Cq * 8 + cq * 8;
   const float4 ad0 = *reinterpret_cast<const float4*>(ad), ad1 = *reinterpret_cast<const float4*>(ad + 4);
   const long long q00 = (((long long)b * a.H + 2 * y2) * a.W + 2 * x2) * Cq + cq;
@@ -569,19 +598,10 @@ __global__ void __launch_bounds__(256) rcb_level0_kernel(Rcb0Args a, int Cq) {  
     for (int j = 0; j < 3; ++j) U[i][j] = ldq<DT, 2>(a.up, u0 + ((long long)ys[i] * W2 + xs[j]) * Cq);
   QuadV<2> R[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float4 av = h ? ad1 : ad0, rv = rr[i].p[h], zv = zz[i].p[h];
-      float4 v = make_float4(rv.x + av.x, rv.y + av.y, rv.z + av.z, rv.w + av.w);
-      v.x = v.x >= 0.f ? v.x : v.x * a.slope; v.y = v.y >= 0.f ? v.y : v.y * a.slope;
-      v.z = v.z >= 0.f ? v.z : v.z * a.slope; v.w = v.w >= 0.f ? v.w : v.w * a.slope;
-      R[i].p[h] = as_stored<DT>(make_float4(v.x + zv.x, v.y + zv.y, v.z + zv.z, v.w + zv.w));
-    }
-  }
+  for (int i = 0; i < 4; ++i) R[i] = rcb_r<DT>(rr[i], zz[i], ad0, ad1, a.slope);
   {
-    const QuadV<2> top = qv_half_sum<2>(R[0], R[1]), bot = qv_half_sum<2>(R[2], R[3]);
-    stq<DT, 2>(a.pool, t, qv_half_sum<2>(top, bot));
+    const QuadV<2> p = qv_half_sum<2>(qv_half_sum<2>(R[0], R[1]), qv_half_sum<2>(R[2], R[3]));
+    *pool = pack8<DT>(p.p[0], p.p[1]);
   }
 #pragma unroll
   for (int dy = 0; dy < 2; ++dy) {
@@ -599,6 +619,18 @@ __global__ void __launch_bounds__(256) rcb_level0_kernel(Rcb0Args a, int Cq) {  
       stq<DT, 2>(a.out, qs[dy * 2 + dx], acc);
     }
   }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(256) rcb_level0_kernel(Rcb0Args a, int Cq) {      // Cq = C / 8
+  const int H2 = a.H >> 1, W2 = a.W >> 1;
+  const long long total = (long long)a.B * H2 * W2 * Cq;
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int cq = (int)(t % Cq);
+  const long long pg = t / Cq;
+  const int x2 = (int)(pg % W2), y2 = (int)((pg / W2) % H2), b = (int)(pg / ((long long)W2 * H2));
+  rcb0_block<DT>(a, b, y2, x2, cq, Cq, reinterpret_cast<uint4*>(a.pool) + t);
 }
 
 }  // namespace fcvsr
@@ -880,6 +912,227 @@ extern "C" int fcvsr_gc_partial_levels(const fcvsr_gc_partial_level* lv, int n_l
   }
   if (r_dtype == FCVSR_BF16) hipLaunchKernelGGL(fcvsr::gc_partial16_levels_kernel<true>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(fcvsr::gc_partial16_levels_kernel<false>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
+
+// =====================================================================================================================
+// BlockRCB's second half after the ContextBlock terms in two launches (16-bit storage modes, 64 channels).  The generic
+// sequence is gc_apply_levels (R1, R2, pooled R1) -> 1x1 up.0 (U1, U2) -> rcb_level0 (out0, pooled R0) -> 1x1 down.0 (Dn0,
+// Dn1) -> xscale_levels (out1, out2): five launches whose intermediates make a round trip through HBM.  Here
+//   rcb_tail_l12_kernel, tiles of level 1 (8 x 16 pixels, the 4 x 8 level-2 pixels under them): forms R1 (stored: the second
+//     kernel reads it), U1 = up.0(R1), Dn1 = down.0(pool(R1)), R2, U2 = up.0(R2) and out2 = x2 + 2 R2 + Dn1; neither the
+//     pooled R1, Dn1 nor R2 leave the workgroup.
+//   rcb_tail_l01_kernel, tiles of level 0 (8 x 32 pixels, the 4 x 16 level-1 pixels under them): out0 as rcb_level0 does,
+//     Dn0 = down.0(pool(R0)) and out1 = x1 + R1 + Dn0 + bilinear_x2(U2); neither the pooled R0 nor Dn0 leave the workgroup.
+// Results are bit-identical to the five-launch sequence: every value is rounded to the storage type where that sequence
+// stores it, the elementwise arithmetic is the same code (rcb_r, rcb0_block, add_up2), and the 1x1 convolutions run
+// conv1_lean_kernel's MFMA sequence (mm1x1_frag) on LDS tiles, followed by its bias-then-round epilogue.
+// Occupancy (LDS-bound for the first kernel): l12 uses 45 KiB of LDS per 256-thread workgroup -> 3 workgroups (12 waves) per
+// CU; l01 uses 18 KiB per 512-thread workgroup and is bound by its VGPRs (see the contract in fcvsr_hip.h).
+namespace fcvsr {
+
+constexpr int kT1LD = 72;      // LDS row of one pixel / one cout: 64 channels + 8 halfwords of padding (conv_mfma.hip's kLD)
+
+struct RcbTailArgs {
+  const void* x[3]; const void* r[3]; const void* z[3]; const float* add[3]; void* out[3];
+  void* r1; void* u1; void* u2;
+  const uint16_t* w_up; const float* b_up; const uint16_t* w_dn; const float* b_dn;
+  float slope;
+  int B, H0, W0, H1, W1, H2, W2;
+  int tiles_x, tiles_y;
+};
+
+// 64 x 64 weights of a 1x1 layer ([cout][cin], row stride 64 halfwords) into an LDS tile with kT1LD rows
+template <int NTHR>
+__device__ __forceinline__ void load_w1x1(const uint16_t* w, uint16_t* W_s, int tid) {
+#pragma unroll
+  for (int i = tid; i < 64 * 8; i += NTHR)
+    *reinterpret_cast<uint4*>(W_s + (i >> 3) * kT1LD + (i & 7) * 8) = *reinterpret_cast<const uint4*>(w + (i >> 3) * 64 + (i & 7) * 8);
+}
+
+// One 32-pixel x 32-cout fragment of a 64 -> 64 1x1 convolution of an LDS tile, in conv1_lean_kernel's exact sequence: four
+// v_mfma_f32_32x32x16 from zero over ascending 16-channel steps, lane half h holding channels 8h..8h+7 of a step.
+// Lane (r, h) returns D[m0 + (i & 3) + 8 (i >> 2) + 4 h][n0 + r] in element i.
+template <bool BF16>
+__device__ __forceinline__ f32x16_t mm1x1_frag(const uint16_t* A_s, int m0, const uint16_t* W_s, int n0, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  const uint16_t* arow = A_s + (m0 + r) * kT1LD + h * 8;
+  const uint16_t* brow = W_s + (n0 + r) * kT1LD + h * 8;
+  f32x16_t acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk)
+    acc = mfma<BF16>(*reinterpret_cast<const uint4*>(arow + kk * 16), *reinterpret_cast<const uint4*>(brow + kk * 16), acc);
+  return acc;
+}
+
+// conv1_lean_kernel's epilogue for a layer without activation: bias added, rounded to the storage type, into an LDS tile
+template <int DT>
+__device__ __forceinline__ void frag_to_lds(const f32x16_t& acc, uint16_t* D_s, int m0, int n0, const float* bias, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  const float bv = bias ? bias[n0 + r] : 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float v = acc[i] + bv;
+    uint16_t o;
+    if (DT == FCVSR_BF16) o = __builtin_bit_cast(uint16_t, (__bf16)v);
+    else o = __builtin_bit_cast(uint16_t, (_Float16)v);
+    D_s[(m0 + (i & 3) + 8 * (i >> 2) + 4 * h) * kT1LD + n0 + r] = o;
+  }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(256) rcb_tail_l12_kernel(RcbTailArgs a) {
+  constexpr bool BF = DT == FCVSR_BF16;
+  __shared__ __align__(16) uint16_t A1_s[128 * kT1LD];    // R1 of the 8 x 16 tile, then U1
+  __shared__ __align__(16) uint16_t P_s[32 * kT1LD];      // pooled R1 (the 4 x 8 level-2 tile), then Dn1
+  __shared__ __align__(16) uint16_t R2_s[32 * kT1LD];     // R2, then U2
+  __shared__ __align__(16) uint16_t Wu_s[64 * kT1LD];
+  __shared__ __align__(16) uint16_t Wd_s[64 * kT1LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int t = blockIdx.x;
+  const int tx = t % a.tiles_x; t /= a.tiles_x;
+  const int ty = t % a.tiles_y;
+  const int b = t / a.tiles_y;
+  load_w1x1<256>(a.w_up, Wu_s, tid);
+  load_w1x1<256>(a.w_dn, Wd_s, tid);
+  // thread = (level-2 pixel k of the tile, 8 channels cq); level 1 holds the 2 x 2 block under it (H1 = 2 H2, W1 = 2 W2)
+  const int k = tid >> 3, cq = tid & 7;
+  const int by = k >> 3, bx = k & 7;
+  const int y2 = ty * 4 + by, x2 = tx * 8 + bx;
+  const bool live = y2 < a.H2 && x2 < a.W2;
+  const long long q2 = (((long long)b * a.H2 + y2) * a.W2 + x2) * 8 + cq;
+  QuadV<2> acc2;
+  if (live) {
+    const float* ad = a.add[1] + b * 64 + cq * 8;
+    const float4 ad0 = *reinterpret_cast<const float4*>(ad), ad1 = *reinterpret_cast<const float4*>(ad + 4);
+    const long long q00 = (((long long)b * a.H1 + 2 * y2) * a.W1 + 2 * x2) * 8 + cq;
+    const long long qs[4] = {q00, q00 + 8, q00 + (long long)a.W1 * 8, q00 + (long long)a.W1 * 8 + 8};
+    QuadV<2> rr[4], zz[4], R[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { rr[i] = ldq<DT, 2>(a.r[1], qs[i]); zz[i] = ldq<DT, 2>(a.z[1], qs[i]); }
+    const float* ad2 = a.add[2] + b * 64 + cq * 8;
+    const float4 ae0 = *reinterpret_cast<const float4*>(ad2), ae1 = *reinterpret_cast<const float4*>(ad2 + 4);
+    const QuadV<2> rr2 = ldq<DT, 2>(a.r[2], q2), zz2 = ldq<DT, 2>(a.z[2], q2), xx2 = ldq<DT, 2>(a.x[2], q2);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      R[i] = rcb_r<DT>(rr[i], zz[i], ad0, ad1, a.slope);
+      stq<DT, 2>(a.r1, qs[i], R[i]);
+      *reinterpret_cast<uint4*>(A1_s + ((2 * by + (i >> 1)) * 16 + 2 * bx + (i & 1)) * kT1LD + cq * 8) = pack8<DT>(R[i].p[0], R[i].p[1]);
+    }
+    const QuadV<2> pool = qv_half_sum<2>(qv_half_sum<2>(R[0], R[1]), qv_half_sum<2>(R[2], R[3]));
+    *reinterpret_cast<uint4*>(P_s + k * kT1LD + cq * 8) = pack8<DT>(pool.p[0], pool.p[1]);
+    const QuadV<2> R2 = rcb_r<DT>(rr2, zz2, ae0, ae1, a.slope);
+    *reinterpret_cast<uint4*>(R2_s + k * kT1LD + cq * 8) = pack8<DT>(R2.p[0], R2.p[1]);
+    acc2 = qv_axpy<2>(2.f, R2, xx2);
+  }
+  __syncthreads();
+  // U1: wave = 32-pixel row pair of the tile, both 32-cout halves; then U2 (waves 0, 1) or Dn1 (waves 2, 3), one half each
+  const f32x16_t u1a = mm1x1_frag<BF>(A1_s, wave * 32, Wu_s, 0, lane);
+  const f32x16_t u1b = mm1x1_frag<BF>(A1_s, wave * 32, Wu_s, 32, lane);
+  const bool up_side = wave < 2;
+  uint16_t* S_s = up_side ? R2_s : P_s;
+  const f32x16_t s = mm1x1_frag<BF>(S_s, 0, up_side ? Wu_s : Wd_s, (wave & 1) * 32, lane);
+  __syncthreads();
+  frag_to_lds<DT>(u1a, A1_s, wave * 32, 0, a.b_up, lane);
+  frag_to_lds<DT>(u1b, A1_s, wave * 32, 32, a.b_up, lane);
+  frag_to_lds<DT>(s, S_s, 0, (wave & 1) * 32, up_side ? a.b_up : a.b_dn, lane);
+  __syncthreads();
+#pragma unroll
+  for (int i = tid; i < 128 * 8; i += 256) {
+    const int lp = i >> 3, oc = i & 7;
+    const int y = ty * 8 + (lp >> 4), x = tx * 16 + (lp & 15);
+    if (y < a.H1 && x < a.W1)
+      reinterpret_cast<uint4*>(a.u1)[(((long long)b * a.H1 + y) * a.W1 + x) * 8 + oc] =
+          *reinterpret_cast<const uint4*>(A1_s + lp * kT1LD + oc * 8);
+  }
+  if (live) {
+    reinterpret_cast<uint4*>(a.u2)[q2] = *reinterpret_cast<const uint4*>(R2_s + k * kT1LD + cq * 8);
+    const QuadV<2> d = unpack8<DT>(*reinterpret_cast<const uint4*>(P_s + k * kT1LD + cq * 8));
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      acc2.p[i] = make_float4(acc2.p[i].x + d.p[i].x, acc2.p[i].y + d.p[i].y, acc2.p[i].z + d.p[i].z, acc2.p[i].w + d.p[i].w);
+    stq<DT, 2>(a.out[2], q2, acc2);
+  }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(512, 4) rcb_tail_l01_kernel(RcbTailArgs a) {
+  constexpr bool BF = DT == FCVSR_BF16;
+  __shared__ __align__(16) uint16_t P_s[64 * kT1LD];      // pooled R0 of the 4 x 16 level-1 tile, then Dn0
+  __shared__ __align__(16) uint16_t Wd_s[64 * kT1LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int t = blockIdx.x;
+  const int tx = t % a.tiles_x; t /= a.tiles_x;
+  const int ty = t % a.tiles_y;
+  const int b = t / a.tiles_y;
+  load_w1x1<512>(a.w_dn, Wd_s, tid);
+  // thread = (level-1 pixel k of the tile, 8 channels cq); level 0 holds the 2 x 2 block under it (H0 = 2 H1, W0 = 2 W1)
+  const int k = tid >> 3, cq = tid & 7;
+  const int y1 = ty * 4 + (k >> 4), x1 = tx * 16 + (k & 15);
+  const bool live = y1 < a.H1 && x1 < a.W1;
+  if (live) {
+    const Rcb0Args r0{a.x[0], a.r[0], a.add[0], a.z[0], a.u1, a.out[0], nullptr, a.slope, 2.f, a.B, a.H0, a.W0};
+    rcb0_block<DT>(r0, b, y1, x1, cq, 8, reinterpret_cast<uint4*>(P_s + k * kT1LD + cq * 8));
+  }
+  __syncthreads();
+  f32x16_t d;
+  if (wave < 4) d = mm1x1_frag<BF>(P_s, (wave >> 1) * 32, Wd_s, (wave & 1) * 32, lane);
+  __syncthreads();
+  if (wave < 4) frag_to_lds<DT>(d, P_s, (wave >> 1) * 32, (wave & 1) * 32, a.b_dn, lane);
+  __syncthreads();
+  if (live) {
+    const long long q1 = (((long long)b * a.H1 + y1) * a.W1 + x1) * 8 + cq;
+    QuadV<2> acc = qv_axpy<2>(1.f, ldq<DT, 2>(a.r1, q1), ldq<DT, 2>(a.x[1], q1));
+    const QuadV<2> dn = unpack8<DT>(*reinterpret_cast<const uint4*>(P_s + k * kT1LD + cq * 8));
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      acc.p[i] = make_float4(acc.p[i].x + dn.p[i].x, acc.p[i].y + dn.p[i].y, acc.p[i].z + dn.p[i].z, acc.p[i].w + dn.p[i].w);
+    acc = add_up2<DT, 2>(acc, a.u2, b, y1, x1, a.H1, a.W1, cq, 8);
+    stq<DT, 2>(a.out[1], q1, acc);
+  }
+}
+
+}  // namespace fcvsr
+
+extern "C" int fcvsr_rcb_tail(const fcvsr_rcb_tail_args* t, float slope, int io_dtype, int C, void* stream) {
+  FCVSR_CHECK_ARG(t != nullptr, "null args");
+  FCVSR_CHECK_ARG(io_dtype == FCVSR_BF16 || io_dtype == FCVSR_F16, "16-bit storage modes only");
+  FCVSR_CHECK_ARG(C == 64, "64 channels only");
+  FCVSR_CHECK_ARG(t->B > 0 && t->H >= 4 && t->W >= 4 && t->H % 4 == 0 && t->W % 4 == 0, "H, W multiples of 4 (even levels 0 and 1)");
+  FCVSR_CHECK_ARG(t->w_up && t->w_dn && t->r1 && t->u1 && t->u2, "null pointer");
+  FCVSR_CHECK_ARG(al16(t->w_up) && al16(t->w_dn) && al16(t->r1) && al16(t->u1) && al16(t->u2) && al16(t->b_up) && al16(t->b_dn),
+                  "16-byte alignment");
+  const void* reads[9];
+  for (int l = 0; l < 3; ++l) {
+    FCVSR_CHECK_ARG(t->x[l] && t->r[l] && t->z[l] && t->add[l] && t->out[l], "null level pointer");
+    FCVSR_CHECK_ARG(al16(t->x[l]) && al16(t->r[l]) && al16(t->z[l]) && al16(t->add[l]) && al16(t->out[l]), "16-byte alignment");
+    reads[3 * l] = t->x[l]; reads[3 * l + 1] = t->r[l]; reads[3 * l + 2] = t->z[l];
+  }
+  // workgroups read halos of u1 / u2 written by others: every written tensor is distinct from the others and from the inputs
+  const void* writes[6] = {t->out[0], t->out[1], t->out[2], t->r1, t->u1, t->u2};
+  for (int i = 0; i < 6; ++i) {
+    for (int j = 0; j < 9; ++j) FCVSR_CHECK_ARG(writes[i] != reads[j], "outputs must not alias inputs");
+    for (int j = 0; j < i; ++j) FCVSR_CHECK_ARG(writes[i] != writes[j], "outputs must be distinct");
+  }
+  RcbTailArgs a;
+  for (int l = 0; l < 3; ++l) { a.x[l] = t->x[l]; a.r[l] = t->r[l]; a.z[l] = t->z[l]; a.add[l] = t->add[l]; a.out[l] = t->out[l]; }
+  a.r1 = t->r1; a.u1 = t->u1; a.u2 = t->u2;
+  a.w_up = (const uint16_t*)t->w_up; a.b_up = t->b_up; a.w_dn = (const uint16_t*)t->w_dn; a.b_dn = t->b_dn;
+  a.slope = slope;
+  a.B = t->B; a.H0 = t->H; a.W0 = t->W; a.H1 = t->H / 2; a.W1 = t->W / 2; a.H2 = t->H / 4; a.W2 = t->W / 4;
+  hipStream_t st = (hipStream_t)stream;
+  a.tiles_y = cdiv(a.H2, 4); a.tiles_x = cdiv(a.W2, 8);
+  const int g12 = t->B * a.tiles_y * a.tiles_x;
+  if (io_dtype == FCVSR_BF16) hipLaunchKernelGGL(rcb_tail_l12_kernel<FCVSR_BF16>, dim3(g12), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(rcb_tail_l12_kernel<FCVSR_F16>, dim3(g12), dim3(256), 0, st, a);
+  FCVSR_LAUNCH_CHECK();
+  a.tiles_y = cdiv(a.H1, 4); a.tiles_x = cdiv(a.W1, 16);
+  const int g01 = t->B * a.tiles_y * a.tiles_x;
+  if (io_dtype == FCVSR_BF16) hipLaunchKernelGGL(rcb_tail_l01_kernel<FCVSR_BF16>, dim3(g01), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL(rcb_tail_l01_kernel<FCVSR_F16>, dim3(g01), dim3(512), 0, st, a);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

@@ -620,10 +620,13 @@ class Engine:
         for l in range(3):
             fl[l].partial, fl[l].add, fl[l].nparts = parts[l].data_ptr(), adds[l].data_ptr(), nparts[l]
         check(L.fcvsr_gc_finish_levels(fl, 3, w1g.data_ptr(), w2g.data_ptr(), B, n, st), "fcvsr_gc_finish_levels")
+        H0, W0 = xs[0].shape[1], xs[0].shape[2]
+        if (m.fuse_rcb_l0 and tdt != torch.float32 and n == 64 and H0 % 4 == 0 and W0 % 4 == 0
+                and all(t.dtype == tdt for t in list(xs) + list(rr) + list(t2))
+                and all(tuple(xs[l].shape) == (B, H0 >> l, W0 >> l, n) for l in range(3))
+                and B * (H0 // 2) * (W0 // 2) * n * 4 < 2 ** 31):      # the shapes on which the 1x1 layers run the lean kernel
+            return self._block_rcb_tail_fused(pre, xs, t2, rr, adds, tdt)
         P = [self._new(dev, B, xs[l].shape[1] // 2, xs[l].shape[2] // 2, n, dtype=tdt) for l in (0, 1)]
-        if (m.fuse_rcb_l0 and tdt != torch.float32 and rr[0].dtype == tdt and xs[0].dtype == tdt
-                and n % 8 == 0):
-            return self._block_rcb_tail_l0(pre, xs, t2, rr, adds, P, tdt)
         R = [torch.empty_like(t) for t in t2]
         al = (hip.GcApplyLevel * 3)()
         for l in range(3):
@@ -647,40 +650,24 @@ class Engine:
         check(L.fcvsr_xscale_levels(xl, 3, code, n, st), "fcvsr_xscale_levels")
         return outs
 
-    def _block_rcb_tail_l0(self, pre, xs, t2, rr, adds, P, tdt):
-        """Same result as the generic sequence above (bit for bit), with level 0's R never stored: levels 1 and 2 go through
-        gc_apply / xscale as before, level 0 through fcvsr_rcb_level0 once up.0(R1) exists (832 -> 576 bytes per level-0
-        pixel at 64 channels)."""
-        m = self._model()
-        n = m.n_feats
-        L = lib()
-        st = stream_ptr()
+    def _block_rcb_tail_fused(self, pre, xs, t2, rr, adds, tdt):
+        """Same result as the generic sequence above (bit for bit) in two launches (fcvsr_rcb_tail): one over level-1 tiles
+        (R1, up.0 of R1 and R2, out2), one over level-0 tiles (out0, out1).  The pooled R, down.0's outputs and R0, R2 never
+        leave the workgroups; the 1x1 layers run as MFMA GEMMs on LDS tiles."""
+        n = self._model().n_feats
         B = xs[0].shape[0]
-        code = self._code(tdt)
-        R = [None, torch.empty_like(t2[1]), torch.empty_like(t2[2])]
-        al = (hip.GcApplyLevel * 3)()
-        for i, l in enumerate((1, 2)):
-            al[i].r, al[i].add, al[i].z, al[i].out = rr[l].data_ptr(), adds[l].data_ptr(), t2[l].data_ptr(), R[l].data_ptr()
-            al[i].pool = P[1].data_ptr() if l == 1 else None
-            al[i].B, al[i].H, al[i].W = B, xs[l].shape[1], xs[l].shape[2]
-        check(L.fcvsr_gc_apply_levels(al, 2, code, code, 0.2, n, st), "fcvsr_gc_apply_levels")
-        up = [torch.empty_like(R[l]) for l in (1, 2)]
-        self._convg(pre + ".up.0", [dict(srcs=[R[l]], dst=up[l - 1]) for l in (1, 2)])
+        wu, bu, _, _ = self._weights(pre + ".up.0", tdt)
+        wd, bd, _, _ = self._weights(pre + ".down.0", tdt)
+        R1, U1, U2 = torch.empty_like(t2[1]), torch.empty_like(t2[1]), torch.empty_like(t2[2])
         outs = [torch.empty_like(x) for x in xs]
-        check(L.fcvsr_rcb_level0(xs[0].data_ptr(), rr[0].data_ptr(), adds[0].data_ptr(), t2[0].data_ptr(), up[0].data_ptr(),
-                                 outs[0].data_ptr(), P[0].data_ptr(), 0.2, 2.0, code, B, xs[0].shape[1], xs[0].shape[2], n, st),
-              "fcvsr_rcb_level0")
-        dn = [torch.empty_like(P[l]) for l in (0, 1)]
-        self._convg(pre + ".down.0", [dict(srcs=[P[l]], dst=dn[l]) for l in (0, 1)])
-        xl = (hip.XscaleLevel * 3)()
-        for i, l in enumerate((1, 2)):
-            xl[i].x, xl[i].r, xl[i].out = xs[l].data_ptr(), R[l].data_ptr(), outs[l].data_ptr()
-            xl[i].dn = dn[l - 1].data_ptr()
-            xl[i].up = up[1].data_ptr() if l == 1 else None
-            xl[i].r_scale = 2.0 if l == 2 else 1.0
-            xl[i].dn_pooled = 1
-            xl[i].B, xl[i].H, xl[i].W = B, xs[l].shape[1], xs[l].shape[2]
-        check(L.fcvsr_xscale_levels(xl, 2, code, n, st), "fcvsr_xscale_levels")
+        a = hip.RcbTailArgs()
+        for l in range(3):
+            a.x[l], a.r[l], a.z[l] = xs[l].data_ptr(), rr[l].data_ptr(), t2[l].data_ptr()
+            a.add[l], a.out[l] = adds[l].data_ptr(), outs[l].data_ptr()
+        a.r1, a.u1, a.u2 = R1.data_ptr(), U1.data_ptr(), U2.data_ptr()
+        a.w_up, a.b_up, a.w_dn, a.b_dn = wu.data_ptr(), ptr(bu), wd.data_ptr(), ptr(bd)
+        a.B, a.H, a.W = B, xs[0].shape[1], xs[0].shape[2]
+        check(lib().fcvsr_rcb_tail(C.byref(a), 0.2, self._code(tdt), n, stream_ptr()), "fcvsr_rcb_tail")
         return outs
 
     def _scnet(self, xs):

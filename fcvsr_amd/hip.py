@@ -43,6 +43,13 @@ class XscaleLevel(C.Structure):
                 ("r_scale", C.c_float), ("dn_pooled", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
 
 
+class RcbTailArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p * 3), ("r", C.c_void_p * 3), ("z", C.c_void_p * 3), ("add", C.c_void_p * 3),
+                ("out", C.c_void_p * 3), ("r1", C.c_void_p), ("u1", C.c_void_p), ("u2", C.c_void_p), ("w_up", C.c_void_p),
+                ("b_up", C.c_void_p), ("w_dn", C.c_void_p), ("b_dn", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("n_src", C.c_int32), ("src", View * 3), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
@@ -113,6 +120,7 @@ SIGNATURES = {
     "fcvsr_gc_apply_levels": [C.POINTER(GcApplyLevel), _I, _I, _I, _F, _I, _VP],
     "fcvsr_xscale_levels": [C.POINTER(XscaleLevel), _I, _I, _I, _VP],
     "fcvsr_rcb_level0": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _F, _I, _I, _I, _I, _I, _VP],
+    "fcvsr_rcb_tail": [C.POINTER(RcbTailArgs), _F, _I, _I, _VP],
     "fcvsr_pixel_shuffle": [_VP, _VP, _I, _I, _I, _I, _VP],
     "fcvsr_bilinear_up4": [_PV, _I, _I, _I, _PV, _VP],
     "fcvsr_tail_fused": [_PV, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _PV, _VP],

@@ -366,6 +366,34 @@ int fcvsr_xscale_levels(const fcvsr_xscale_level* lv, int n_levels, int io_dtype
 int fcvsr_rcb_level0(const void* x, const void* r, const float* add, const void* z, const void* up, void* out, void* pool,
                      float slope, float r_scale, int io_dtype, int B, int H, int W, int C, void* stream);
 
+/* All of BlockRCB's second half after the ContextBlock terms in two launches (reference :722-725, :766-777; 16-bit storage
+ * modes, C = 64).  With R_l = lrelu(r_l + add_l[b], slope) + z_l rounded to the storage type at each level l:
+ *   launch 1 (tiles of level 1):  r1 = R1,  u1 = up.0(R1),  u2 = up.0(R2),  out2 = x2 + 2 R2 + down.0(avg_pool2x2(R1))
+ *   launch 2 (tiles of level 0):  out0 = x0 + 2 R0 + bilinear_x2(u1),  out1 = x1 + R1 + down.0(avg_pool2x2(R0)) + bilinear_x2(u2)
+ * Bit-identical to fcvsr_gc_apply_levels (levels 1, 2, pooled R1) -> fcvsr_conv2d_mfma (up.0 on R1, R2) -> fcvsr_rcb_level0 ->
+ * fcvsr_conv2d_mfma (down.0 on the pooled R0, R1) -> fcvsr_xscale_levels (levels 1, 2): values are rounded where that
+ * sequence stores them and the 1x1 layers run its lean 1x1 kernel's MFMA sequence.  Level 0 is (B, H, W, 64), level 1
+ * (B, H/2, W/2, 64), level 2 (B, H/4, W/4, 64), H and W multiples of 4; every tensor NHWC in io_dtype (FCVSR_BF16 /
+ * FCVSR_F16), 16-byte aligned; add[l] f32 [B][64].  w_up / w_dn: the layers' weights as packed for fcvsr_conv2d_mfma in
+ * io_dtype (row co = cout co, 64 cin per row); b_up / b_dn f32 [64] or NULL.  r1, u1, u2 are scratch of levels 1, 1, 2
+ * written by launch 1 and read by launch 2; no written tensor may alias another tensor of the call. */
+typedef struct {
+  const void*  x[3];      /* block inputs */
+  const void*  r[3];      /* RCB.body.2 outputs */
+  const void*  z[3];      /* body.2 outputs */
+  const float* add[3];    /* ContextBlock terms */
+  void*        out[3];
+  void*        r1;
+  void*        u1;
+  void*        u2;
+  const void*  w_up;
+  const float* b_up;
+  const void*  w_dn;
+  const float* b_dn;
+  int32_t      B, H, W;   /* level 0 */
+} fcvsr_rcb_tail_args;
+int fcvsr_rcb_tail(const fcvsr_rcb_tail_args* a, float slope, int io_dtype, int C, void* stream);
+
 /* ---- tail ------------------------------------------------------------------------------------------------------ */
 /* nn.PixelShuffle(2) of a dense NHWC tensor (B,H,W,C) -> (B,2H,2W,C/4) (:2634-2635) */
 /* ContextBlock softmax-pool partials (:657-701) from a STORED 16-bit r, all pyramid levels in one launch: one [C+2] record per
