@@ -17,7 +17,8 @@
 //   * 1x1 convolutions run in "flat" mode: the B*H*W pixels are tiled as a 1-D list, so odd widths (Wf = W/2+1) cost nothing.
 //   * Up to 3 "groups" (e.g. the three pyramid levels of BlockRCB, which share weights) run in ONE launch so that the small
 //     levels do not leave most of the 256 CUs idle.
-// Replaces nn.Conv2d(+bias+activation+residual+cat+PixelShuffle) for every stride-1 layer of the path (see fcvsr_hip.h).
+// Replaces nn.Conv2d(+bias+activation+residual+cat+PixelShuffle) for every layer of the path (see fcvsr_hip.h); the stride-2 layers
+// with a dense 64-multiple source run conv3s2_lean_kernel, the generic kernel's sub2 mode serves the rest.
 // The 3x3 16-bit paths here (conv3_lean_kernel, conv_mfma_kernel with KS = 3) and conv3_res_kernel (conv_res.hip) must agree bit
 // for bit (tests/test_hip_ops.py, tests/test_conv_mfma_shape_gpu.py).  All three sum tap-major with ascending channels; conv3_res
 // issues v_mfma_f32_16x16x32 over 32 channels where these kernels chain two 32x32x16 over 16 each, and on gfx950 the two give the
@@ -877,6 +878,191 @@ __global__ __launch_bounds__(256, NT == 128 ? 2 : 4) void conv3_lean_kernel(Mfma
   }
 }
 
+// =====================================================================================================================
+// Lean stride-2 3x3 kernel (the pyramid builders rconcat1 / rconcat2): only the output pixels that exist are computed (the
+// generic kernel's sub2 mode evaluates at full resolution and keeps the even outputs: 4x the MFMA and LDS work).  Summation
+// order of that path: 64-channel chunks outermost, taps in (ky, kx) order, ascending 16-channel steps - the same bits.
+//   * output tile 2 rows x 32 pixels x 64 couts; wave w computes output row w >> 1, couts (w & 1) * 32 .. +32 (one fragment);
+//   * the 5 x 65 input halo of a 64-channel chunk is staged split by column parity: LDS row hy holds the 33 even halo columns,
+//     then the 32 odd ones (33 slots each, the last odd slot is never read).  Tap (ky, kx) of output column x reads halo
+//     column 2x + kx = plane kx & 1, slot x + (kx >> 1), i.e. 32 consecutive kLD-padded slots: the stride-1 kernel's A read.
+//     Lane r reads dword 36 r + (a base shared by the phase: plane / row / tap / h * 8 / kk), and 36 r mod 64 = 4 (9 r mod 16):
+//     the 16 lanes of each ds_read_b128 phase ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, see conv_res.hip) have distinct
+//     r mod 16, so they hit 16 distinct 4-bank groups: conflict-free;
+//   * LDS 47,520 (halo) + 9,216 (weights of one tap) bytes: 2 workgroups per CU.
+// =====================================================================================================================
+template <bool BF16, bool SRC16, bool DST16>
+__global__ __launch_bounds__(256, 2) void conv3s2_lean_kernel(MfmaArgs a) {
+  constexpr int NS = 33, HRW = 65, NHP = 5 * HRW;      // slots per parity plane, halo columns, halo pixels (5 rows)
+  extern __shared__ __align__(16) uint16_t lds[];
+  uint16_t* A_s = lds;                                 // [5][2][NS][kLD]
+  uint16_t* B_s = lds + 5 * 2 * NS * kLD;              // [64][kLD]
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+
+  int wid = blockIdx.x;
+  {
+    const int nwg = gridDim.x, q = nwg >> 3, rr = nwg & 7, xcd = wid & 7, loc = wid >> 3;
+    wid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
+  }
+  const int nb = wid % a.n_nblk;
+  const int tflat = wid / a.n_nblk;
+  int gi = 0;
+  if (a.n_groups > 1 && tflat >= a.g[1].tile_begin) gi = 1;
+  if (a.n_groups > 2 && tflat >= a.g[2].tile_begin) gi = 2;
+  const MGroup& G = a.g[gi];
+  const int tl = tflat - G.tile_begin;
+  const int n0 = nb * 64;
+  const int per_img = G.tiles_x * G.tiles_y;            // tiles of the OUTPUT
+  const int b = tl / per_img;
+  const int t2 = tl - b * per_img;
+  const int oy0 = (t2 / G.tiles_x) * 2, ox0 = (t2 % G.tiles_x) * kTW;
+  const int H = G.H, W = G.W;                           // input size
+  const int Ho = (H + 1) >> 1, Wo = (W + 1) >> 1;
+  const int iy0 = 2 * oy0 - 1, ix0 = 2 * ox0 - 1;       // input pixel of halo (0, 0)
+
+  f32x16_t acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+
+  constexpr int EPL = SRC16 ? 8 : 4;                  // source elements per 16-byte load
+  constexpr int LPP = 64 / EPL;                       // lanes per halo pixel
+  constexpr int STEP = 256 / LPP;                     // halo pixels per iteration
+  constexpr int ITERS = (NHP + STEP - 1) / STEP;
+  constexpr int ESZ = SRC16 ? 2 : 4;
+  const int q = tid & (LPP - 1);
+  const int p0 = tid / LPP;
+  const View sv = G.src[0];
+  const int ssx = (int)sv.sx, ssy = (int)sv.sy;
+  const char* sbase = reinterpret_cast<const char*>(sv.p) + ((long long)b * sv.sb) * ESZ;
+
+  for (int c0 = 0; c0 < a.cin16; c0 += kCK) {
+    __syncthreads();
+    {
+      const bool cok = (c0 + q * EPL) < a.cin_total;
+      constexpr int SB = 7;                           // loads in flight per thread
+#pragma unroll
+      for (int i0 = 0; i0 < ITERS; i0 += SB) {
+        uint4 v[SB];
+        int slot[SB];
+#pragma unroll
+        for (int u = 0; u < SB; ++u) {
+          const int i = i0 + u;
+          v[u] = make_uint4(0, 0, 0, 0);
+          slot[u] = -1;
+          if (i < ITERS) {
+            const int hp = p0 + i * STEP;
+            const int hy = hp / HRW, hx = hp - hy * HRW;
+            const int iy = iy0 + hy, ix = ix0 + hx;
+            const bool ok = cok && (hp < NHP) && ((unsigned)iy < (unsigned)H) && ((unsigned)ix < (unsigned)W);
+            const int off = (iy * ssy + ix * ssx + c0 + q * EPL) * ESZ;
+            // unconditional (out-of-image / dead lanes read the image's first pixel and discard it)
+            const uint4 ld = *reinterpret_cast<const uint4*>(sbase + (ok ? (unsigned)off : 0u));
+            if (ok) v[u] = ld;
+            if (hp < NHP) slot[u] = (2 * hy + (hx & 1)) * NS + (hx >> 1);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < SB; ++u) {
+          if (i0 + u < ITERS && slot[u] >= 0) {
+            uint16_t* dst = A_s + slot[u] * kLD + q * EPL;
+            if (SRC16) *reinterpret_cast<uint4*>(dst) = v[u];
+            else *reinterpret_cast<uint2*>(dst) = cvt4<BF16>(__builtin_bit_cast(float4, v[u]));
+          }
+        }
+      }
+    }
+    // ---- taps: weights global -> regs -> LDS (one tap ahead), MFMA ---------------------------------------------------
+    uint4 w0, w1;
+    const uint16_t* wbase = a.w + ((long long)n0 + (tid >> 3)) * a.cin_pad + c0 + (tid & 7) * 8;
+    const long long wtap = (long long)a.cout_pad * a.cin_pad;
+    const long long wrow32 = 32ll * a.cin_pad;
+    w0 = *reinterpret_cast<const uint4*>(wbase);
+    w1 = *reinterpret_cast<const uint4*>(wbase + wrow32);
+    uint16_t* bp = B_s + (tid >> 3) * kLD + (tid & 7) * 8;
+    const uint16_t* abase = A_s + (4 * (wave >> 1) * NS + r) * kLD + h * 8;     // halo row 2 * (wave >> 1) + ky
+    const uint16_t* brow = B_s + ((wave & 1) * 32 + r) * kLD + h * 8;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      if (tap > 0) __syncthreads();
+      *reinterpret_cast<uint4*>(bp) = w0;
+      *reinterpret_cast<uint4*>(bp + 32 * kLD) = w1;
+      __syncthreads();
+      if (tap + 1 < 9) {
+        w0 = *reinterpret_cast<const uint4*>(wbase + (tap + 1) * wtap);
+        w1 = *reinterpret_cast<const uint4*>(wbase + (tap + 1) * wtap + wrow32);
+      }
+      const int ky = tap / 3, kx = tap % 3;            // compile-time after unrolling
+      const uint16_t* ap = abase + ((2 * ky + (kx & 1)) * NS + (kx >> 1)) * kLD;
+#pragma unroll
+      for (int kk = 0; kk < kCK / 16; ++kk) {
+        const uint4 af = *reinterpret_cast<const uint4*>(ap + kk * 16);
+        const uint4 bf = *reinterpret_cast<const uint4*>(brow + kk * 16);
+        acc = mfma<BF16>(af, bf, acc);
+      }
+    }
+  }
+
+  // ---- epilogue: per-wave LDS transpose, then 16-byte (8 x 16-bit) or float4 stores of one output row ------------------
+  float slope = a.slope;
+  if (a.act == FCVSR_ACT_PRELU) slope = *reinterpret_cast<const __attribute__((address_space(1))) float*>(reinterpret_cast<uintptr_t>(a.slope_ptr));   // global, not flat: a flat_load turns every later counted lgkmcnt into lgkmcnt(0)
+  const float nsf = a.act == FCVSR_ACT_RELU ? 0.f : (a.act == FCVSR_ACT_NONE ? 1.f : slope);   // negative-side factor
+  constexpr int EROW = 32 + 4;
+  __syncthreads();
+  float* E_s = reinterpret_cast<float*>(lds) + wave * (32 * EROW);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) E_s[((i & 3) + 8 * (i >> 2) + 4 * h) * EROW + r] = acc[i];
+  __builtin_amdgcn_wave_barrier();
+  const int oy = oy0 + (wave >> 1);
+  const bool rowok = oy < Ho;
+  const View dv = G.dst;
+  const long long drow = (long long)b * dv.sb + (long long)oy * dv.sy;
+  const int dsx = (int)dv.sx;
+  constexpr int VPL = DST16 ? 8 : 4;                  // couts per lane
+  constexpr int LPR = 32 / VPL;                       // lanes per pixel
+  constexpr int PPI = 64 / LPR;                       // pixels per iteration
+  const int co = lane & (LPR - 1), psub = lane / LPR;
+  const int n = n0 + (wave & 1) * 32 + co * VPL;
+  float bb[VPL];
+#pragma unroll
+  for (int k = 0; k < VPL; ++k) bb[k] = 0.f;
+  if (a.bias) {
+#pragma unroll
+    for (int k = 0; k < VPL; k += 4) {
+      const float4 t = *reinterpret_cast<const float4*>(a.bias + n + k);
+      bb[k] = t.x; bb[k + 1] = t.y; bb[k + 2] = t.z; bb[k + 3] = t.w;
+    }
+  }
+  const float* es = E_s + psub * EROW + co * VPL;
+#pragma unroll
+  for (int j = 0; j < 32 / PPI; ++j) {
+    const int px = ox0 + j * PPI + psub;
+    if (rowok && px < Wo) {
+      float x[VPL];
+#pragma unroll
+      for (int k = 0; k < VPL; k += 4) {
+        const float4 t = *reinterpret_cast<const float4*>(es + j * PPI * EROW + k);
+        x[k] = t.x; x[k + 1] = t.y; x[k + 2] = t.z; x[k + 3] = t.w;
+      }
+      if (a.bias) {                                   // (no "+ 0.f" without bias: it would turn -0 into +0)
+#pragma unroll
+        for (int k = 0; k < VPL; ++k) x[k] += bb[k];
+      }
+#pragma unroll
+      for (int k = 0; k < VPL; ++k) x[k] = x[k] >= 0.f ? x[k] : x[k] * nsf;
+      const long long o = drow + (long long)px * dsx + n;
+      if (DST16) {
+        const uint2 lo = cvt4<BF16>(make_float4(x[0], x[1], x[2], x[3]));
+        const uint2 hi = cvt4<BF16>(make_float4(x[VPL - 4], x[VPL - 3], x[VPL - 2], x[VPL - 1]));
+        *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(dv.p) + o) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+      } else {
+        *reinterpret_cast<float4*>(dv.p + o) = make_float4(x[0], x[1], x[2], x[3]);
+      }
+    }
+  }
+}
+
 // Lean 1x1 kernel: flat list of pixels (128 per workgroup), up to 3 concatenated sources whose channel counts are
 // multiples of 64 (a 64-channel chunk never straddles two sources), optional pixel-shuffle destination (no residuals then).
 template <bool BF16, int NT, bool SRC16, bool DST16, bool PS>
@@ -1056,6 +1242,162 @@ __global__ __launch_bounds__(256, 4) void conv1_lean_kernel(MfmaArgs a) {
       }
     }
   }
+}
+
+// =====================================================================================================================
+// Pixel-shuffle 1x1 up-convolution, 64 -> cout (cout % 32 == 0, <= 256), 16-bit source and destination, with LDS-resident
+// weights (upconv1; upconv2 of the models whose tail is not fused).  conv1_lean_kernel re-reads its input tile once per
+// 64-cout block and a workgroup lives ~9 us for 8 K outputs.  Here the input is read once:
+//   * persistent workgroups (2 per CU); the packed weights (cout x 64) are copied into LDS once per workgroup;
+//   * every wave walks 32-pixel rows of the flat pixel list on its own, without workgroup barriers: it copies the row into
+//     its own LDS slice, reads its 4 A fragments once, then issues the loads of its next row before the multiplies;
+//   * per 32-cout fragment: 4 x v_mfma_f32_32x32x16 over K = 64 (one chunk, ascending 16-channel steps: the lean kernel's
+//     bits), then a per-wave LDS transpose so that a lane stores 8 consecutive channels of one sub-pixel (16 bytes).
+//   * the bias is staged in LDS too: a global load in the fragment loop made every fragment wait for vmcnt(0), i.e. for the
+//     next row's loads and all stores still in flight.
+// LDS: cout x 144 (weights) + 4 waves x (4,608 A + 4,608 transpose) + 1,024 (bias) bytes = 74,752 at cout 256.
+// =====================================================================================================================
+constexpr int kR1ERow = 32 + 4;                      // transpose row (floats)
+inline size_t conv1ps_res_lds(int cout) {
+  return ((size_t)cout * kLD + 4 * 32 * kLD) * sizeof(uint16_t) + 4ull * 32 * kR1ERow * sizeof(float) + 256 * sizeof(float);
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(256, 2) void conv1ps_res_kernel(MfmaArgs a, int nrows) {
+  extern __shared__ __align__(16) uint16_t lds[];
+  const int cout = a.cout;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  uint16_t* W_s = lds;                                                       // [cout][kLD]
+  uint16_t* A_w = lds + cout * kLD + wave * (32 * kLD);                      // this wave's 32 pixels x 64 channels
+  float* E_w = reinterpret_cast<float*>(lds + cout * kLD + 4 * 32 * kLD) + wave * (32 * kR1ERow);
+  float* bias_s = reinterpret_cast<float*>(lds + cout * kLD + 4 * 32 * kLD) + 4 * 32 * kR1ERow;    // [cout]
+
+  for (int idx = tid; idx < cout * 8; idx += 256) {
+    const int row = idx >> 3, c = (idx & 7) * 8;
+    *reinterpret_cast<uint4*>(W_s + row * kLD + c) = *reinterpret_cast<const uint4*>(a.w + (long long)row * a.cin_pad + c);
+  }
+  if (tid < cout) bias_s[tid] = a.bias ? a.bias[tid] : 0.f;
+  float slope = a.slope;
+  if (a.act == FCVSR_ACT_PRELU) slope = *reinterpret_cast<const __attribute__((address_space(1))) float*>(reinterpret_cast<uintptr_t>(a.slope_ptr));   // global, not flat: a flat_load turns every later counted lgkmcnt into lgkmcnt(0)
+  const float nsf = a.act == FCVSR_ACT_RELU ? 0.f : (a.act == FCVSR_ACT_NONE ? 1.f : slope);   // negative-side factor
+  const MGroup& G = a.g[0];
+  const int npix = G.B * G.H * G.W;                   // host guarantees < 2^29
+  const View sv = G.src[0], dv = G.dst;
+  const int ssx = (int)sv.sx, dsx = (int)dv.sx;
+  const int cq4 = cout >> 2;
+  // staging: lane loads pixel (lane >> 3) + 8 i, channels (lane & 7) * 8 .. +8
+  const char* sbase = reinterpret_cast<const char*>(sv.p) + (lane & 7) * 16;
+  uint16_t* a_dst = A_w + (lane >> 3) * kLD + (lane & 7) * 8;
+  const uint16_t* arow = A_w + r * kLD + h * 8;
+  // epilogue: 4 lanes per pixel (8 couts each), 16 pixels per pass
+  const int co = lane & 3, psub = lane >> 2;
+  const float* es = E_w + psub * kR1ERow + co * 8;
+  __syncthreads();
+
+  const int nw = gridDim.x * 4;
+  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);     // wave-uniform: scalar loop control
+  // the next row's pixels, 16 bytes per lane each (named, not an array: an array carried around the loop went to scratch)
+  uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0, v2 = v0, v3 = v0;
+#define FCVSR_R1_LOAD(ROW)                                                                                        \
+  do {                                                                                                            \
+    const int pix_ = (ROW) * 32 + (lane >> 3);                                                                    \
+    const unsigned c0_ = (unsigned)(pix_ < npix ? pix_ : npix - 1), c1_ = (unsigned)(pix_ + 8 < npix ? pix_ + 8 : npix - 1);   \
+    const unsigned c2_ = (unsigned)(pix_ + 16 < npix ? pix_ + 16 : npix - 1), c3_ = (unsigned)(pix_ + 24 < npix ? pix_ + 24 : npix - 1); \
+    v0 = *reinterpret_cast<const uint4*>(sbase + (size_t)(c0_ * (unsigned)ssx) * 2);   /* clamped, never stored */ \
+    v1 = *reinterpret_cast<const uint4*>(sbase + (size_t)(c1_ * (unsigned)ssx) * 2);                              \
+    v2 = *reinterpret_cast<const uint4*>(sbase + (size_t)(c2_ * (unsigned)ssx) * 2);                              \
+    v3 = *reinterpret_cast<const uint4*>(sbase + (size_t)(c3_ * (unsigned)ssx) * 2);                              \
+  } while (0)
+  if (row < nrows) FCVSR_R1_LOAD(row);
+#pragma unroll 1
+  for (; row < nrows; row += nw) {
+    *reinterpret_cast<uint4*>(a_dst) = v0;
+    *reinterpret_cast<uint4*>(a_dst + 8 * kLD) = v1;
+    *reinterpret_cast<uint4*>(a_dst + 16 * kLD) = v2;
+    *reinterpret_cast<uint4*>(a_dst + 24 * kLD) = v3;
+    __builtin_amdgcn_wave_barrier();
+    const uint4 af0 = *reinterpret_cast<const uint4*>(arow), af1 = *reinterpret_cast<const uint4*>(arow + 16);
+    const uint4 af2 = *reinterpret_cast<const uint4*>(arow + 32), af3 = *reinterpret_cast<const uint4*>(arow + 48);
+    if (row + nw < nrows) FCVSR_R1_LOAD(row + nw);
+    // destination pixel (2 qy, 2 qx) of the lane's two pixels (the sub-pixel offset is added per fragment)
+    const int pixa = row * 32 + psub, pixb = pixa + 16;
+    const bool oka = pixa < npix, okb = pixb < npix;
+    size_t oba, obb;
+    {
+      const int qx = pixa % G.W, t1 = pixa / G.W, qy = t1 % G.H, qb = t1 / G.H;
+      oba = (size_t)qb * dv.sb + (size_t)(2 * qy) * dv.sy + (size_t)(2 * qx) * dsx;
+    }
+    {
+      const int qx = pixb % G.W, t1 = pixb / G.W, qy = t1 % G.H, qb = t1 / G.H;
+      obb = (size_t)qb * dv.sb + (size_t)(2 * qy) * dv.sy + (size_t)(2 * qx) * dsx;
+    }
+#pragma unroll 1
+    for (int f = 0; f < cout / 32; ++f) {
+      f32x16_t acc;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+      const uint16_t* brow = W_s + (f * 32 + r) * kLD + h * 8;
+      acc = mfma<BF16>(af0, *reinterpret_cast<const uint4*>(brow), acc);
+      acc = mfma<BF16>(af1, *reinterpret_cast<const uint4*>(brow + 16), acc);
+      acc = mfma<BF16>(af2, *reinterpret_cast<const uint4*>(brow + 32), acc);
+      acc = mfma<BF16>(af3, *reinterpret_cast<const uint4*>(brow + 48), acc);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) E_w[((i & 3) + 8 * (i >> 2) + 4 * h) * kR1ERow + r] = acc[i];
+      __builtin_amdgcn_wave_barrier();
+      const int n = f * 32 + co * 8;                  // packed row: sub-pixel-major, n = sp * (cout / 4) + c
+      const int sp = n / cq4, nn = n - sp * cq4;
+      const float4 b0 = *reinterpret_cast<const float4*>(bias_s + n), b1 = *reinterpret_cast<const float4*>(bias_s + n + 4);
+      const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};    // 0 without bias, as in conv1_lean_kernel
+      const size_t osp = (size_t)(sp >> 1) * dv.sy + (size_t)(sp & 1) * dsx + nn;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if (j == 0 ? oka : okb) {
+          const float4 t0 = *reinterpret_cast<const float4*>(es + j * 16 * kR1ERow);
+          const float4 t1 = *reinterpret_cast<const float4*>(es + j * 16 * kR1ERow + 4);
+          float x[8] = {t0.x + bb[0], t0.y + bb[1], t0.z + bb[2], t0.w + bb[3], t1.x + bb[4], t1.y + bb[5], t1.z + bb[6], t1.w + bb[7]};
+#pragma unroll
+          for (int k = 0; k < 8; ++k) x[k] = x[k] >= 0.f ? x[k] : x[k] * nsf;
+          const uint2 lo = cvt4<BF16>(make_float4(x[0], x[1], x[2], x[3])), hi = cvt4<BF16>(make_float4(x[4], x[5], x[6], x[7]));
+          *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(dv.p) + (j == 0 ? oba : obb) + osp) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+#undef FCVSR_R1_LOAD
+}
+
+template <bool BF16>
+static hipError_t launch_conv1ps_res(const MfmaArgs& a, int nrows, hipStream_t st) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const int cus = device_cu_count(dev);
+  int grid = (nrows + 3) / 4;
+  const int cap = 2 * (cus > 0 ? cus : 256);
+  if (grid > cap) grid = cap;
+  static DevOnce attr;
+  e = once_per_device(attr, [&] {
+    return hipFuncSetAttribute((const void*)conv1ps_res_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv1ps_res_lds(256));
+  });
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((conv1ps_res_kernel<BF16>), dim3(grid), dim3(256), conv1ps_res_lds(a.cout), st, a, nrows);
+  return hipGetLastError();
+}
+
+template <bool BF16, bool SRC16, bool DST16>
+static hipError_t launch_lean_s2(const MfmaArgs& a, int total_tiles, hipStream_t st) {
+  const size_t lds = ((size_t)5 * 2 * 33 * kLD + (size_t)64 * kLD) * sizeof(uint16_t);     // > the 18,432-byte transpose area
+  hipLaunchKernelGGL((conv3s2_lean_kernel<BF16, SRC16, DST16>), dim3(total_tiles * a.n_nblk), dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+template <bool BF16>
+static hipError_t dispatch_lean_s2(const MfmaArgs& a, int total_tiles, hipStream_t st) {
+  if (a.src16) return a.dst16 ? launch_lean_s2<BF16, true, true>(a, total_tiles, st) : launch_lean_s2<BF16, true, false>(a, total_tiles, st);
+  return a.dst16 ? launch_lean_s2<BF16, false, true>(a, total_tiles, st) : launch_lean_s2<BF16, false, false>(a, total_tiles, st);
 }
 
 template <bool BF16, int NT, bool SRC16, bool DST16, bool PS>
@@ -1297,6 +1639,58 @@ extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int
     if (e2 && atoi(e2) == 0) lean1 = false;
   }
   hipError_t e;
+  // pixel-shuffle 1x1 up-convolution 64 -> cout (<= 256) with resident weights: one 16-bit source, 16-bit destination.
+  // FCVSR_MFMA_RES=0 leaves it to the lean 1x1 kernel (the tests' reference for it).
+  bool res1 = lean1 && a.ps && a.src16 && a.dst16 && n_groups == 1 && cin == 64 && d0.cout % 32 == 0 && d0.cout <= 256 &&
+              d0.dst.sx % 8 == 0 && d0.dst.sy % 8 == 0 && d0.dst.sb % 8 == 0 && ((uintptr_t)d0.dst.ptr % 16) == 0;
+  {
+    const char* e4 = getenv("FCVSR_MFMA_RES");
+    if (e4 && atoi(e4) == 0) res1 = false;
+  }
+  if (res1) {
+    FCVSR_NOTE_KERNEL("conv1ps_res_kernel<%s>", tf(mma_dtype == FCVSR_BF16));
+    const int nrows = (int)cdiv((long long)d0.B * d0.H * d0.W, 32);
+    e = (mma_dtype == FCVSR_BF16) ? launch_conv1ps_res<true>(a, nrows, st) : launch_conv1ps_res<false>(a, nrows, st);
+    if (e != hipSuccess) {
+      set_error("fcvsr_conv2d_mfma: launch failed: %s", hipGetErrorString(e));
+      return (int)e;
+    }
+    return 0;
+  }
+  // lean stride-2 3x3 path: one dense source of a multiple of 64 channels, cout a multiple of 64, channel-contiguous
+  // destination, no residuals.  Tiles are 2 x 32 pixels of the OUTPUT.
+  bool s2 = dst_native && d0.kh == 3 && d0.stride == 2 && d0.n_src == 1 && !a.planar && (cin % 64 == 0) && d0.cout % 64 == 0 &&
+            d0.n_res == 0 && d0.gc_wmask == nullptr;
+  for (int g = 0; g < n_groups && s2; ++g) {
+    const fcvsr_conv_desc& d = descs[g];
+    const int dg = a.dst16 ? 8 : 4;
+    s2 = s2 && d.dst.sc == 1 && d.dst.sx % dg == 0 && d.dst.sy % dg == 0 && d.dst.sb % dg == 0 && ((uintptr_t)d.dst.ptr % 16) == 0 &&
+         (long long)d.B * d.H * d.W * d.src[0].sx < (1ll << 29);
+  }
+  {
+    const char* e5 = getenv("FCVSR_MFMA_LEAN");
+    if (e5 && atoi(e5) == 0) s2 = false;
+  }
+  if (s2) {
+    MfmaArgs a2 = a;
+    a2.n_nblk = d0.cout / 64;
+    int t2 = 0;
+    for (int g = 0; g < n_groups; ++g) {
+      MGroup& G = a2.g[g];
+      G.tiles_x = cdiv((G.W + 1) / 2, kTW);
+      G.tiles_y = cdiv((G.H + 1) / 2, 2);
+      G.tile_begin = t2;
+      t2 += G.B * G.tiles_x * G.tiles_y;
+    }
+    for (int g = n_groups; g < 3; ++g) a2.g[g] = a2.g[0];
+    FCVSR_NOTE_KERNEL("conv3s2_lean_kernel<%s, %s, %s>", tf(mma_dtype == FCVSR_BF16), tf(a.src16), tf(a.dst16));
+    e = (mma_dtype == FCVSR_BF16) ? dispatch_lean_s2<true>(a2, t2, st) : dispatch_lean_s2<false>(a2, t2, st);
+    if (e != hipSuccess) {
+      set_error("fcvsr_conv2d_mfma: launch failed: %s", hipGetErrorString(e));
+      return (int)e;
+    }
+    return 0;
+  }
   if (lean1) {
     FCVSR_NOTE_KERNEL("conv1_lean_kernel<%s, %d, %s, %s, %s>", tf(mma_dtype == FCVSR_BF16), nt, tf(a.src16), tf(a.dst16), tf(a.ps));
     e = (mma_dtype == FCVSR_BF16) ? dispatch_lean1<true>(a, nt, tiles, st) : dispatch_lean1<false>(a, nt, tiles, st);

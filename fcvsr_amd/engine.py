@@ -670,7 +670,7 @@ class Engine:
         check(lib().fcvsr_rcb_tail(C.byref(a), 0.2, self._code(tdt), n, stream_ptr()), "fcvsr_rcb_tail")
         return outs
 
-    def _scnet(self, xs):
+    def _scnet(self, xs, out_dtype=torch.float32):
         m = self._model()
         cur = xs
         for g in range(m.SCGroupN):
@@ -678,10 +678,9 @@ class Engine:
             for k in range(3):
                 t = self._block_rcb(f"recorb1.body.{g}.body.{k}", t)
             last = g == m.SCGroupN - 1
-            # the trunk may be 16-bit (trunk16); SCNetbk's outputs leave in f32
-            # (the net outputs stay f32: upconv_fuse concatenates o0 with two narrow f32 tensors and a launch takes sources
-            # of one dtype)
-            nxt = [torch.empty_like(c, dtype=torch.float32 if last else c.dtype) for c in cur]
+            # the trunk may be 16-bit (trunk16); SCNetbk's outputs o0..o2 leave in out_dtype (their only readers are the MFMA
+            # convolutions upconv_fuse, upconv1_L2 and upconv1_L3)
+            nxt = [torch.empty_like(c, dtype=out_dtype if last else c.dtype) for c in cur]
             # fold SCNetbk's outer skip (x + body(x), :817-821) into the last group conv's epilogue
             grp = [dict(srcs=[t[l]], dst=nxt[l], res=([cur[l], xs[l]] if last else [cur[l]])) for l in range(3)]
             self._convg(f"recorb1.body.{g}.conv", grp)
@@ -821,18 +820,30 @@ class Engine:
         d2 = self._new(dev, B, H // 4, W // 4, n, dtype=tdt)
         self._conv("rconcat1", [d0], d1, stride=2)
         self._conv("rconcat2", [d1], d2, stride=2)
-        o0, o1, o2 = self._scnet([d0, d1, d2])
+        # In the 16-bit modes the three sources of upconv_fuse (o0, l2p, l3_2) are stored in the MFMA dtype: they are read only as
+        # MFMA operands (also o1 / o2), and their producers round as upconv_fuse's staging of f32 sources would (bit-identical,
+        # half the bytes).  l3_2 (n/16 channels) is stored with zero channels up to a multiple of 8 (16-bit sources are 16-byte
+        # pixels); the packed weights are zero past the real input channels and the channel count rounded to 16 is unchanged, so
+        # the MFMA operands are those of the f32 concatenation.
+        fuse16 = self._adt() != torch.float32 and n % 32 == 0
+        o0, o1, o2 = self._scnet([d0, d1, d2], self._adt() if fuse16 else torch.float32)
         self._tap("sc.o0", o0), self._tap("sc.o1", o1), self._tap("sc.o2", o2)
 
         # pyramid fuse (:2633-2639); PReLU commutes with PixelShuffle (one shared scalar slope)
         l3_1 = self._new(dev, B, H // 2, W // 2, n // 4)
         self._conv("upconv1_L3", [o2], l3_1, act=ACT_PRELU, slope_t=a_t, ps=True)
-        l3_2 = self._new(dev, B, H, W, n // 16)
-        check(L.fcvsr_pixel_shuffle(l3_1.data_ptr(), l3_2.data_ptr(), B, H // 2, W // 2, n // 4, st),
-              "fcvsr_pixel_shuffle")
+        if fuse16:
+            l3_2 = self._new(dev, B, H, W, (n // 16 + 7) // 8 * 8, dtype=self._adt())
+            l3v = view(l3_2)
+            check(L.fcvsr_pixel_shuffle16(l3_1.data_ptr(), C.byref(l3v), B, H // 2, W // 2, n // 4, st),
+                  "fcvsr_pixel_shuffle16")
+        else:
+            l3_2 = self._new(dev, B, H, W, n // 16)
+            check(L.fcvsr_pixel_shuffle(l3_1.data_ptr(), l3_2.data_ptr(), B, H // 2, W // 2, n // 4, st),
+                  "fcvsr_pixel_shuffle")
         l2 = self._new(dev, B, H // 2, W // 2, n)
         self._conv("upconv1_L2", [o1], l2, act=ACT_PRELU, slope_t=a_t)
-        l2p = self._new(dev, B, H, W, n // 4)
+        l2p = self._new(dev, B, H, W, n // 4, dtype=self._adt() if fuse16 else torch.float32)
         self._conv("upconv1_L2_2", [l2, l3_1], l2p, res=[l2], ps=True)
         fz0 = self._new(dev, B, H, W, n, dtype=self._adt())
         fz = self._new(dev, B, H, W, n, dtype=self._adt())          # read only by upconv1 (MFMA)

@@ -122,6 +122,7 @@ SIGNATURES = {
     "fcvsr_rcb_level0": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _F, _I, _I, _I, _I, _I, _VP],
     "fcvsr_rcb_tail": [C.POINTER(RcbTailArgs), _F, _I, _I, _VP],
     "fcvsr_pixel_shuffle": [_VP, _VP, _I, _I, _I, _I, _VP],
+    "fcvsr_pixel_shuffle16": [_VP, _PV, _I, _I, _I, _I, _VP],
     "fcvsr_bilinear_up4": [_PV, _I, _I, _I, _PV, _VP],
     "fcvsr_tail_fused": [_PV, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _PV, _VP],
     "fcvsr_conv_last": [_PV, _VP, _VP, _I, _I, _I, _I, _PV, _VP],

@@ -408,6 +408,9 @@ typedef struct {
 int fcvsr_gc_partial_levels(const fcvsr_gc_partial_level* lv, int n_levels, int r_dtype, const float* wmask, int C, void* stream);
 
 int fcvsr_pixel_shuffle(const float* src, float* dst, int B, int H, int W, int C, void* stream);
+/* PixelShuffle(2) of a dense f32 (B,H,W,C) tensor into channels [0, C/4) of a 16-bit (bf16 / f16) view (B,2H,2W,dst.c);
+ * channels [C/4, dst.c) of the view are written as zeros.  dst.c % 8 == 0, 16-byte-aligned channel-contiguous pixels. */
+int fcvsr_pixel_shuffle16(const float* src, const fcvsr_view* dst, int B, int H, int W, int C, void* stream);
 /* F.interpolate(scale_factor=4, bilinear, align_corners=False) (:2644): src view (B,H,W,c) -> dst view (B,4H,4W,c) */
 int fcvsr_bilinear_up4(const fcvsr_view* src, int B, int H, int W, const fcvsr_view* dst, void* stream);
 
