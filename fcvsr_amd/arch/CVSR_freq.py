@@ -241,10 +241,23 @@ class _GShiftBase(nn.Module):
             if x.dim() != 5 or x.shape[1] != self._in_frames or x.shape[2] != self._img_ch:
                 raise ValueError(f"expected (B,{self._in_frames},{self._img_ch},H,W) input, got {tuple(x.shape)}")
             return forward_train(self.state_dict(keep_vars=True), x, precision=self._train_precision(), packer=self.train_packer())
+        return self._get_engine().forward(x)
+
+    def super_resolve_u8(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
+        """8-bit frames in, 8-bit SR frames out: x uint8 (B, 7, C, H, W) on a HIP device -> uint8 (B, C, 4H, 4W).
+
+        The bytes equal those of ``q(clamp(self(x.float() / 255), 0, 1) * 255)`` with the division done on the host and q =
+        truncation toward zero ("truncate", the reference evaluation's ``.astype(np.uint8)``) or rounding half to even
+        ("round", mmedit's ``tensor2img``).  The uint8 window is read by the first kernels and the last kernel stores the
+        quantised frames: no f32 copy of the input or the output crosses PCIe or HBM.  Always runs without autograd; hipGraph
+        capture and ``streams`` apply as in ``forward``."""
+        return self._get_engine().forward_u8(x, quantise)
+
+    def _get_engine(self):
         from ..engine import Engine
         if self._engine is None or self._engine._model() is not self:      # (a deepcopy carries the source's engine)
             object.__setattr__(self, "_engine", Engine(self))
-        return self._engine.forward(x)
+        return self._engine
 
 
 class GShiftNet_S(_GShiftBase):
@@ -269,6 +282,10 @@ class GShiftNet_ETC(GShiftNet):
     ``(out_seq, x_up)``, both ``(B, 7, C, 4H, 4W)``: the SR frames and the bilinear x4 bases of the window centres.
     The windows are independent, so they are stacked on the batch axis and run as ONE forward instead of the reference's loop."""
     _windows = 7
+
+    def super_resolve_u8(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
+        raise NotImplementedError("GShiftNet_ETC returns (out_seq, x_up) for a 13-frame input: run its 7-frame windows through "
+                                  "a GShiftNet with the same state_dict for uint8 frames")
 
     def forward(self, x: torch.Tensor):
         if x.dim() != 5 or x.shape[1] != self._in_frames + self._windows - 1 or x.shape[2] != self._img_ch:

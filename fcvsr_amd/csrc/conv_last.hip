@@ -7,8 +7,10 @@
 //   * "taps are output columns": P[pixel][tap*C + c] = sum_k u2[pixel][k] * w[c][k][tap] is a (340 x 64) x (64 x 9C) GEMM on
 //     v_mfma_f32_16x16x32 (2 MFMAs per 16 pixels and 16 columns) instead of 576 C multiply-adds per pixel on the vector ALU;
 //   * out[c][y][x] += bias[c] + sum_tap P[(y+dy, x+dx)][tap*C + c]  - 9 LDS reads per output value.
+// Q != 0 (fcvsr_conv_last_u8): `out` is only read (the f32 base) and the sum goes, quantised (u8.h), to the uint8 frames out8.
 #include "common.h"
 #include "mfma_util.h"
+#include "u8.h"
 
 namespace fcvsr {
 
@@ -22,7 +24,8 @@ struct ClArgs {
   View u;                  // (B, H, W, 64) 16-bit, dense
   const uint16_t* w;       // [16 * NT][64]: row = tap * C + c (tap = ky*3 + kx), zero rows past 9 C; MFMA dtype
   const float* bias;       // C floats or null
-  View out;                // (B, H, W, C) f32 view of the NCHW result, read-modify-write
+  View out;                // (B, H, W, C) f32 view of the NCHW result, read-modify-write (Q != 0: read only)
+  View out8;               // Q != 0: (B, H, W, C) uint8 destination
   int B, H, W, C, tiles_x, tiles_y;
 };
 
@@ -35,7 +38,7 @@ __device__ __forceinline__ f32x4v_t mfma16cl(uint4 a, uint4 b, f32x4v_t c) {
 }
 
 // NT = column tiles of 16 (C = 1: 9 columns -> NT = 1; C = 3: 27 columns -> NT = 2)
-template <bool BF16, int NT>
+template <bool BF16, int NT, int Q = 0>
 __global__ __launch_bounds__(256, 3) void conv_last_kernel(ClArgs a) {
   constexpr int PROW = 16 * NT + 1;                          // floats per pixel of the tap table (odd stride)
   __shared__ __align__(16) uint16_t u_s[kClNHP * kClRow];    // 48,960 bytes; the tap table overwrites it
@@ -127,7 +130,12 @@ __global__ __launch_bounds__(256, 3) void conv_last_kernel(ClArgs a) {
         for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
           for (int dx = 0; dx < 3; ++dx) s += p_s[((ty + dy) * kClHW + tx + dx) * PROW + (dy * 3 + dx) * a.C + c];
-        op[(long long)c * a.out.sc] = s;
+        if constexpr (Q == 0) {
+          op[(long long)c * a.out.sc] = s;
+        } else {
+          reinterpret_cast<uint8_t*>(a.out8.p)[(long long)b * a.out8.sb + (long long)oy * a.out8.sy + (long long)ox * a.out8.sx +
+                                               (long long)c * a.out8.sc] = quantise_u8<Q>(s);
+        }
       }
     }
   }
@@ -137,10 +145,9 @@ __global__ __launch_bounds__(256, 3) void conv_last_kernel(ClArgs a) {
 
 using namespace fcvsr;
 
-// out (B,H,W,C view, f32, any strides) += bias + conv3x3(u) with u (B,H,W,64) dense 16-bit; w: [16 or 32][64] rows tap*C + c in
-// u's dtype (rows past 9C zero); C in 1..3.
-extern "C" int fcvsr_conv_last(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C, const fcvsr_view* out,
-                               void* stream) {
+template <int Q>
+static int conv_last_launch(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C, const fcvsr_view* out,
+                            const fcvsr_view* out8, void* stream) {
   FCVSR_CHECK_ARG(u && u->ptr && w && out && out->ptr, "null argument");
   FCVSR_CHECK_ARG((u->dtype == FCVSR_BF16 || u->dtype == FCVSR_F16) && u->c == 64 && u->sc == 1 && ((uintptr_t)u->ptr % 16) == 0 &&
                       u->sx % 8 == 0 && u->sy % 8 == 0 && u->sb % 8 == 0, "u: 64 contiguous 16-bit channels, 16-byte aligned");
@@ -148,18 +155,34 @@ extern "C" int fcvsr_conv_last(const fcvsr_view* u, const void* w, const float* 
   FCVSR_CHECK_ARG(((uintptr_t)w % 16) == 0 && B > 0 && H > 0 && W > 0, "bad arguments");
   ClArgs a;
   a.u = to_view(*u); a.w = (const uint16_t*)w; a.bias = bias; a.out = to_view(*out);
+  a.out8 = out8 ? to_view(*out8) : a.out;
   a.B = B; a.H = H; a.W = W; a.C = C;
   a.tiles_x = cdiv(W, kClTW); a.tiles_y = cdiv(H, kClTH);
   const dim3 grid(B * a.tiles_x * a.tiles_y);
   hipStream_t st = (hipStream_t)stream;
   const bool bf = u->dtype == FCVSR_BF16;
   if (C == 1) {
-    if (bf) hipLaunchKernelGGL((conv_last_kernel<true, 1>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_last_kernel<false, 1>), grid, dim3(256), 0, st, a);
+    if (bf) hipLaunchKernelGGL((conv_last_kernel<true, 1, Q>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_last_kernel<false, 1, Q>), grid, dim3(256), 0, st, a);
   } else {
-    if (bf) hipLaunchKernelGGL((conv_last_kernel<true, 2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_last_kernel<false, 2>), grid, dim3(256), 0, st, a);
+    if (bf) hipLaunchKernelGGL((conv_last_kernel<true, 2, Q>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_last_kernel<false, 2, Q>), grid, dim3(256), 0, st, a);
   }
   FCVSR_LAUNCH_CHECK();
   return 0;
+}
+
+// out (B,H,W,C view, f32, any strides) += bias + conv3x3(u) with u (B,H,W,64) dense 16-bit; w: [16 or 32][64] rows tap*C + c in
+// u's dtype (rows past 9C zero); C in 1..3.
+extern "C" int fcvsr_conv_last(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C, const fcvsr_view* out,
+                               void* stream) {
+  return conv_last_launch<0>(u, w, bias, B, H, W, C, out, nullptr, stream);
+}
+
+extern "C" int fcvsr_conv_last_u8(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C,
+                                  const fcvsr_view* base, const fcvsr_view* out, int quantise, void* stream) {
+  FCVSR_CHECK_ARG(out && out->ptr && out->dtype == FCVSR_U8 && out->c == C, "out: C uint8 channels");
+  FCVSR_CHECK_ARG(quantise == FCVSR_QUANT_TRUNCATE || quantise == FCVSR_QUANT_ROUND, "quantise: FCVSR_QUANT_TRUNCATE or _ROUND");
+  if (quantise == FCVSR_QUANT_TRUNCATE) return conv_last_launch<FCVSR_QUANT_TRUNCATE>(u, w, bias, B, H, W, C, base, out, stream);
+  return conv_last_launch<FCVSR_QUANT_ROUND>(u, w, bias, B, H, W, C, base, out, stream);
 }

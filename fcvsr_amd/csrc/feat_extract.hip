@@ -9,9 +9,13 @@
 //     wave-private LDS tile so that every store is 16 bytes in a 128-byte run;
 //   * the output channel blocks go to up to three destination tensors (the frame groups f1 | f2 | f3 of the reference's
 //     channel split, :2617-2619), in the storage dtype of the activations.
+// The U8 variant gathers uint8 frames instead (fcvsr_feat_extract_u8): pixel k enters as tab[k] (u8.h), the f32 the f32 variant is
+// fed by a caller that converts on the host, so both variants build the same f16 im2col tile.  The table sits in the LDS of the
+// epilogue tile, which is not written before the tile barrier.
 #include <type_traits>
 #include "common.h"
 #include "mfma_util.h"
+#include "u8.h"
 
 namespace fcvsr {
 
@@ -22,7 +26,8 @@ constexpr int kFeERow = 64 + 4;                    // floats per pixel row of th
 constexpr int kFeMaxBlk = 16;
 
 struct FeatArgs {
-  View x;                   // (B, H, W, Cin) logical view of the planar frames, f32
+  View x;                   // (B, H, W, Cin) logical view of the planar frames, f32 (uint8 in the U8 variant)
+  const float* tab;         // U8 variant: [256] value of pixel k
   int B, H, W, cin;
   const uint16_t* w;        // [n_blk*64][64] f16: k = tap*cin + c (zero beyond 9*cin)
   const float* bias;        // [n_blk*64] or null
@@ -32,7 +37,7 @@ struct FeatArgs {
   int dch[kFeMaxBlk];
 };
 
-template <bool DSTBF, int CIN>
+template <bool DSTBF, int CIN, bool U8 = false>
 __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
   extern __shared__ __align__(16) unsigned char lds[];
   uint16_t* A_s = reinterpret_cast<uint16_t*>(lds);
@@ -42,6 +47,11 @@ __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
   float* E_s = reinterpret_cast<float*>(lds + kFePix * kFeLD * 2) + wave * (32 * kFeERow);
   const long long npix = (long long)a.B * a.H * a.W;
   const long long flat0 = (long long)blockIdx.x * kFePix;
+  float* tab_s = reinterpret_cast<float*>(lds + kFePix * kFeLD * 2);
+  if constexpr (U8) {
+    tab_s[tid] = a.tab[tid];                            // 256 threads, 256 entries
+    __syncthreads();
+  }
 
   // ---- im2col: thread = (pixel, half of k).  k, tap and channel are compile-time inside each half; the 32 loads of a thread
   // are unconditional (clamped address, value zeroed when the tap is outside the image) so that they are issued as one batch.
@@ -54,6 +64,7 @@ __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
     const int yy = (int)((pc / a.W) % a.H);
     const int b = (int)(pc / ((long long)a.W * a.H));
     const float* xb = a.x.p + (long long)b * a.x.sb;
+    const uint8_t* xb8 = reinterpret_cast<const uint8_t*>(a.x.p) + (long long)b * a.x.sb;
     const int sy = (int)a.x.sy, sx = (int)a.x.sx, sc = (int)a.x.sc;   // one image spans < 2^31 elements (host check)
     float f[32];
     auto gather = [&](auto koff) {
@@ -66,7 +77,10 @@ __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
         const int iy = yy + tap / 3 - 1, ix = xx + tap % 3 - 1;
         const bool in = pok && k < 9 * CIN && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
         const int iyc = iy < 0 ? 0 : (iy > a.H - 1 ? a.H - 1 : iy), ixc = ix < 0 ? 0 : (ix > a.W - 1 ? a.W - 1 : ix);
-        const float v = xb[iyc * sy + ixc * sx + (k < 9 * CIN ? c : 0) * sc];
+        const int off = iyc * sy + ixc * sx + (k < 9 * CIN ? c : 0) * sc;
+        float v;
+        if constexpr (U8) v = tab_s[xb8[off]];
+        else v = xb[off];
         f[j] = in ? v : 0.f;
       }
     };
@@ -141,17 +155,15 @@ __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
 
 using namespace fcvsr;
 
-extern "C" int fcvsr_feat_extract(const fcvsr_view* x, int B, int H, int W, const void* w, const float* bias, int n_blk,
-                                  void* const* dst, const int64_t* dst_pix_stride, const int32_t* dst_ch_off, int dst_dtype,
-                                  void* stream) {
-  FCVSR_CHECK_ARG(x && x->ptr && w && dst && dst_pix_stride && dst_ch_off, "null argument");
-  FCVSR_CHECK_ARG(x->dtype == FCVSR_F32 && x->c == 7, "x: f32, 7 channels (the Y models' frame stack)");
+template <bool U8>
+static int feat_extract_launch(const fcvsr_view* x, const float* tab, int B, int H, int W, const void* w, const float* bias, int n_blk,
+                               void* const* dst, const int64_t* dst_pix_stride, const int32_t* dst_ch_off, int dst_dtype, void* stream) {
   FCVSR_CHECK_ARG((long long)H * x->sy < (1ll << 31) && 7ll * x->sc < (1ll << 31), "image too large for 32-bit offsets");
   FCVSR_CHECK_ARG(B > 0 && H > 0 && W > 0 && n_blk >= 1 && n_blk <= kFeMaxBlk, "bad sizes");
   FCVSR_CHECK_ARG(dst_dtype == FCVSR_BF16 || dst_dtype == FCVSR_F16, "16-bit destinations");
   FCVSR_CHECK_ARG(((uintptr_t)w % 16) == 0 && (bias == nullptr || ((uintptr_t)bias % 16) == 0), "weights / bias 16-byte aligned");
   FeatArgs a;
-  a.x = to_view(*x); a.B = B; a.H = H; a.W = W; a.cin = x->c;
+  a.x = to_view(*x); a.tab = tab; a.B = B; a.H = H; a.W = W; a.cin = x->c;
   a.w = (const uint16_t*)w; a.bias = bias; a.n_blk = n_blk;
 
   for (int i = 0; i < kFeMaxBlk; ++i) {
@@ -164,9 +176,9 @@ extern "C" int fcvsr_feat_extract(const fcvsr_view* x, int B, int H, int W, cons
   static DevOnce attr;
   {
     hipError_t e = once_per_device(attr, [&] {
-      hipError_t e1 = hipFuncSetAttribute((const void*)feat_extract_kernel<true, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipError_t e1 = hipFuncSetAttribute((const void*)feat_extract_kernel<true, 7, U8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e1 == hipSuccess)
-        e1 = hipFuncSetAttribute((const void*)feat_extract_kernel<false, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        e1 = hipFuncSetAttribute((const void*)feat_extract_kernel<false, 7, U8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       return e1;
     });
     if (e != hipSuccess) {
@@ -177,8 +189,24 @@ extern "C" int fcvsr_feat_extract(const fcvsr_view* x, int B, int H, int W, cons
   const long long npix = (long long)B * H * W;
   dim3 grid(cdiv(npix, kFePix));
   hipStream_t st = (hipStream_t)stream;
-  if (dst_dtype == FCVSR_BF16) hipLaunchKernelGGL((feat_extract_kernel<true, 7>), grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((feat_extract_kernel<false, 7>), grid, dim3(256), lds, st, a);
+  if (dst_dtype == FCVSR_BF16) hipLaunchKernelGGL((feat_extract_kernel<true, 7, U8>), grid, dim3(256), lds, st, a);
+  else hipLaunchKernelGGL((feat_extract_kernel<false, 7, U8>), grid, dim3(256), lds, st, a);
   FCVSR_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fcvsr_feat_extract(const fcvsr_view* x, int B, int H, int W, const void* w, const float* bias, int n_blk,
+                                  void* const* dst, const int64_t* dst_pix_stride, const int32_t* dst_ch_off, int dst_dtype,
+                                  void* stream) {
+  FCVSR_CHECK_ARG(x && x->ptr && w && dst && dst_pix_stride && dst_ch_off, "null argument");
+  FCVSR_CHECK_ARG(x->dtype == FCVSR_F32 && x->c == 7, "x: f32, 7 channels (the Y models' frame stack)");
+  return feat_extract_launch<false>(x, nullptr, B, H, W, w, bias, n_blk, dst, dst_pix_stride, dst_ch_off, dst_dtype, stream);
+}
+
+extern "C" int fcvsr_feat_extract_u8(const fcvsr_view* x, const float* tab, int B, int H, int W, const void* w, const float* bias,
+                                     int n_blk, void* const* dst, const int64_t* dst_pix_stride, const int32_t* dst_ch_off,
+                                     int dst_dtype, void* stream) {
+  FCVSR_CHECK_ARG(x && x->ptr && tab && w && dst && dst_pix_stride && dst_ch_off, "null argument");
+  FCVSR_CHECK_ARG(x->dtype == FCVSR_U8 && x->c == 7, "x: uint8, 7 channels (the Y models' frame stack)");
+  return feat_extract_launch<true>(x, tab, B, H, W, w, bias, n_blk, dst, dst_pix_stride, dst_ch_off, dst_dtype, stream);
 }

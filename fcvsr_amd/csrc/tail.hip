@@ -47,7 +47,9 @@ __global__ void pixel_shuffle16_kernel(const float* src, View dst, int B, int H,
       make_uint4(lo.x, lo.y, hi.x, hi.y);
 }
 
-__global__ void bilinear_up4_kernel(View src, int B, int H, int W, View dst) {
+// U8: src holds uint8 frames, pixel k read as tab[k] (u8.h) - the same arithmetic on the same f32 values as the f32 source
+template <bool U8>
+__device__ __forceinline__ void bilinear_up4_px(View src, const float* tab, int B, int H, int W, View dst) {
   const int Ho = 4 * H, Wo = 4 * W;
   const long long total = (long long)B * Ho * Wo * dst.c;
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -62,11 +64,24 @@ __global__ void bilinear_up4_kernel(View src, int B, int H, int W, View dst) {
   const int y0 = (int)sy, x0 = (int)sx;
   const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
   const float ly = sy - (float)y0, lx = sx - (float)x0;
-  const float* sp = src.p + (long long)b * src.sb + (long long)c * src.sc;
-  const float v00 = sp[(long long)y0 * src.sy + (long long)x0 * src.sx], v01 = sp[(long long)y0 * src.sy + (long long)x1 * src.sx];
-  const float v10 = sp[(long long)y1 * src.sy + (long long)x0 * src.sx], v11 = sp[(long long)y1 * src.sy + (long long)x1 * src.sx];
+  const long long o00 = (long long)y0 * src.sy + (long long)x0 * src.sx, o01 = (long long)y0 * src.sy + (long long)x1 * src.sx;
+  const long long o10 = (long long)y1 * src.sy + (long long)x0 * src.sx, o11 = (long long)y1 * src.sy + (long long)x1 * src.sx;
+  float v00, v01, v10, v11;
+  if constexpr (U8) {
+    const uint8_t* sp = reinterpret_cast<const uint8_t*>(src.p) + (long long)b * src.sb + (long long)c * src.sc;
+    v00 = tab[sp[o00]]; v01 = tab[sp[o01]]; v10 = tab[sp[o10]]; v11 = tab[sp[o11]];
+  } else {
+    const float* sp = src.p + (long long)b * src.sb + (long long)c * src.sc;
+    v00 = sp[o00]; v01 = sp[o01]; v10 = sp[o10]; v11 = sp[o11];
+  }
   const float v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
   dst.p[(long long)b * dst.sb + (long long)oy * dst.sy + (long long)ox * dst.sx + (long long)c * dst.sc] = v;
+}
+
+__global__ void bilinear_up4_kernel(View src, int B, int H, int W, View dst) { bilinear_up4_px<false>(src, nullptr, B, H, W, dst); }
+
+__global__ void bilinear_up4_u8_kernel(View src, const float* tab, int B, int H, int W, View dst) {
+  bilinear_up4_px<true>(src, tab, B, H, W, dst);
 }
 
 }  // namespace fcvsr
@@ -104,6 +119,17 @@ extern "C" int fcvsr_bilinear_up4(const fcvsr_view* src, int B, int H, int W, co
   const long long total = (long long)B * 16 * H * W * dst->c;
   hipLaunchKernelGGL(bilinear_up4_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, to_view(*src), B, H, W,
                      to_view(*dst));
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fcvsr_bilinear_up4_u8(const fcvsr_view* src, const float* tab, int B, int H, int W, const fcvsr_view* dst, void* stream) {
+  FCVSR_CHECK_ARG(src && dst && src->ptr && dst->ptr && tab, "null pointer");
+  FCVSR_CHECK_ARG(src->dtype == FCVSR_U8 && dst->dtype == FCVSR_F32, "uint8 source, f32 destination");
+  FCVSR_CHECK_ARG(B > 0 && H > 0 && W > 0 && src->c == dst->c && dst->c > 0, "bad sizes");
+  const long long total = (long long)B * 16 * H * W * dst->c;
+  hipLaunchKernelGGL(bilinear_up4_u8_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, to_view(*src), tab, B, H,
+                     W, to_view(*dst));
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

@@ -10,8 +10,10 @@
 //      the 340 halo pixels - 44 small MFMAs instead of 576 multiply-adds per output pixel on the vector ALU.
 //   3. out[y][x] += bias + sum_tap P[y+dy][x+dx][tap]   (out holds the bilinear x4 base skip).
 // HBM traffic per output pixel: 14 bytes of u1 (with halo) + 8 bytes of out, instead of 128 written + ~170 read.
+// Q != 0 (fcvsr_tail_fused_u8): `out` is only read (the f32 base) and the sum goes, quantised (u8.h), to the uint8 frame out8.
 #include "common.h"
 #include "mfma_util.h"
+#include "u8.h"
 
 namespace fcvsr {
 
@@ -33,7 +35,8 @@ struct TailArgs {
   const float* slope;      // PReLU slope (one shared scalar, :2609)
   const uint16_t* wl;      // [16][64] conv_last0: row = tap (ky*3+kx), rows 9..15 zero
   const float* bl;         // conv_last0 bias (1 value, may be null)
-  View out;                // (B, 2*H2, 2*W2, 1) f32, read-modify-write
+  View out;                // (B, 2*H2, 2*W2, 1) f32, read-modify-write (Q != 0: read only)
+  View out8;               // Q != 0: (B, 2*H2, 2*W2, 1) uint8 destination
   int B, H2, W2, tiles_x, tiles_y;
   int ntiles;              // B * tiles_x * tiles_y, split into contiguous runs over the launched workgroups
 };
@@ -46,7 +49,7 @@ __device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
 }
 
-template <bool BF16>
+template <bool BF16, int Q = 0>
 __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
   // 48 KiB: the tap table P of step 2 overwrites the u2 tile it was computed from (3 workgroups per CU)
   __shared__ __align__(16) uint16_t u2_s[kTfNHP * kTfRow];
@@ -186,7 +189,12 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
       for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) s += p_s[((ty + dy) * kTfHW + tx + dx) * kTfPRow + dy * 3 + dx];
-      *op = s;
+      if constexpr (Q == 0) {
+        *op = s;
+      } else {
+        reinterpret_cast<uint8_t*>(a.out8.p)[(long long)b * a.out8.sb + (long long)oy * a.out8.sy + (long long)ox * a.out8.sx] =
+            quantise_u8<Q>(s);
+      }
     }
   }
   __syncthreads();                                         // the tap table is read: the next tile's u2 overwrites it
@@ -197,8 +205,9 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
 
 using namespace fcvsr;
 
-extern "C" int fcvsr_tail_fused(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
-                                const float* bl, int B, int H2, int W2, const fcvsr_view* out, void* stream) {
+template <int Q>
+static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl, const float* bl,
+                             int B, int H2, int W2, const fcvsr_view* out, const fcvsr_view* out8, void* stream) {
   FCVSR_CHECK_ARG(u1 && u1->ptr && w2 && slope && wl && out && out->ptr, "null argument");
   FCVSR_CHECK_ARG((u1->dtype == FCVSR_BF16 || u1->dtype == FCVSR_F16) && u1->c == 64 && u1->sc == 1 &&
                       ((uintptr_t)u1->ptr % 16) == 0 && u1->sx % 8 == 0 && u1->sy % 8 == 0 && u1->sb % 8 == 0,
@@ -210,6 +219,7 @@ extern "C" int fcvsr_tail_fused(const fcvsr_view* u1, const void* w2, const floa
   TailArgs a;
   a.u1 = to_view(*u1); a.w2 = (const uint16_t*)w2; a.b2 = b2; a.slope = slope; a.wl = (const uint16_t*)wl; a.bl = bl;
   a.out = to_view(*out); a.B = B; a.H2 = H2; a.W2 = W2;
+  a.out8 = out8 ? to_view(*out8) : a.out;
   a.tiles_x = cdiv(2 * W2, kTfTW);
   a.tiles_y = cdiv(2 * H2, kTfTH);
   a.ntiles = B * a.tiles_x * a.tiles_y;
@@ -224,8 +234,23 @@ extern "C" int fcvsr_tail_fused(const fcvsr_view* u1, const void* w2, const floa
   nwg = nwg < 8 ? 8 : nwg / 8 * 8;
   dim3 grid(nwg < a.ntiles ? nwg : a.ntiles);
   hipStream_t st = (hipStream_t)stream;
-  if (u1->dtype == FCVSR_BF16) hipLaunchKernelGGL(tail_fused_kernel<true>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(tail_fused_kernel<false>, grid, dim3(256), 0, st, a);
+  if (u1->dtype == FCVSR_BF16) hipLaunchKernelGGL((tail_fused_kernel<true, Q>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((tail_fused_kernel<false, Q>), grid, dim3(256), 0, st, a);
   FCVSR_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fcvsr_tail_fused(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                                const float* bl, int B, int H2, int W2, const fcvsr_view* out, void* stream) {
+  return tail_fused_launch<0>(u1, w2, b2, slope, wl, bl, B, H2, W2, out, nullptr, stream);
+}
+
+extern "C" int fcvsr_tail_fused_u8(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                                   const float* bl, int B, int H2, int W2, const fcvsr_view* base, const fcvsr_view* out, int quantise,
+                                   void* stream) {
+  FCVSR_CHECK_ARG(out && out->ptr && out->dtype == FCVSR_U8 && out->c == 1, "out: one uint8 channel");
+  FCVSR_CHECK_ARG(quantise == FCVSR_QUANT_TRUNCATE || quantise == FCVSR_QUANT_ROUND, "quantise: FCVSR_QUANT_TRUNCATE or _ROUND");
+  if (quantise == FCVSR_QUANT_TRUNCATE)
+    return tail_fused_launch<FCVSR_QUANT_TRUNCATE>(u1, w2, b2, slope, wl, bl, B, H2, W2, base, out, stream);
+  return tail_fused_launch<FCVSR_QUANT_ROUND>(u1, w2, b2, slope, wl, bl, B, H2, W2, base, out, stream);
 }

@@ -693,7 +693,21 @@ class Engine:
         with torch.no_grad():
             return self._forward_checked(x, m)
 
-    def _forward_checked(self, x, m):
+    def forward_u8(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
+        """uint8 frames in, uint8 SR frames out: x (B,T,C,H,W) uint8 -> (B,C,4H,4W) uint8, the bytes of
+        ``q(clamp(forward(x_f32), 0, 1) * 255)`` with x_f32 = ``x.float() / 255`` computed on the host and q = truncation
+        ("truncate", the reference's ``.astype(np.uint8)``) or rounding half to even ("round").  The first kernels read the
+        uint8 window (pixel k through the table of ``hip.u8_table``) and the last one quantises its f32 result; configurations
+        whose first or last layer has no uint8 variant convert in one small kernel on that side."""
+        if quantise not in hip.QUANTISE:
+            raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+            raise ValueError(f"expected a uint8 tensor, got {getattr(x, 'dtype', type(x))}")
+        m = self._model()
+        with torch.no_grad():
+            return self._forward_checked(x, m, hip.QUANTISE[quantise])
+
+    def _forward_checked(self, x, m, quant=None):
         if x.dim() != 5:
             raise ValueError(f"expected (B,T,C,H,W) input, got {tuple(x.shape)}")
         if not x.is_cuda:
@@ -706,23 +720,26 @@ class Engine:
             raise ValueError("H and W must be multiples of 4 (3-level pyramid, reference BlockRCB :766-777)")
         dev = x.device
         with torch.cuda.device(dev):
-            x = x.contiguous().float()
+            x = x.contiguous() if quant is not None else x.contiguous().float()
             self._refresh(dev)
+            if quant is not None:
+                hip.u8_table(dev)                   # built once, on the caller's stream and outside any capture
             ns = max(1, min(int(getattr(m, "streams", 1)), B))
             flags = (bool(m.trunk16), bool(m.fold_f1), bool(m.fuse_tail), bool(m.fuse_rcb_l0))
-            cfg = (tuple(x.shape[1:]), self.precision, str(dev), self._pack_epoch, flags)
+            # the input dtype and the quantise mode are part of every key: a uint8 call never replays an f32 call's graph
+            cfg = (tuple(x.shape[1:]), self.precision, str(dev), self._pack_epoch, flags, x.dtype, quant)
             if ns > 1 and cfg not in self._warm:
                 # First pass of a configuration: re-packed weights, band masks and per-kernel attributes are created lazily
                 # inside the forward.  They must be built on the CALLER's stream, before the fan-out: side streams are only
                 # ordered after the caller's stream, not after each other, so a tensor first written on side stream 0
                 # would be read by the other side streams with no dependency (and would live in stream 0's allocator pool).
-                out = self._run(x, m, 1, dev)
+                out = self._run(x, m, 1, dev, quant)
                 self._warm.add(cfg)
                 if not getattr(m, "use_graph", False) or self.taps is not None or hip.PROFILE is not None:
                     return out
             self._warm.add(cfg)
             if not getattr(m, "use_graph", False) or self.taps is not None or hip.PROFILE is not None:
-                return self._run(x, m, ns, dev)
+                return self._run(x, m, ns, dev, quant)
             # hipGraph mode: the ~650 launches of one forward are captured once per (shape, precision, streams, weights
             # version) and replayed, which removes the host launch cost (~9 us per ctypes launch) from the critical path.
             key = (tuple(x.shape), ns) + cfg[1:]
@@ -730,11 +747,11 @@ class Engine:
             if ent is None:
                 sx = x.clone()
                 for _ in range(2):                       # eager warm-up on the capture configuration
-                    self._run(sx, m, ns, dev)
+                    self._run(sx, m, ns, dev, quant)
                 torch.cuda.synchronize(dev)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    so = self._run(sx, m, ns, dev)
+                    so = self._run(sx, m, ns, dev, quant)
                 # bounded cache: each entry pins a captured graph, its private memory pool and static in/out tensors
                 # (ragged last batches and new resolutions would otherwise grow it without bound)
                 while len(self._graphs) >= max(1, int(getattr(m, "graph_cache_size", 4))):
@@ -747,16 +764,16 @@ class Engine:
             graph.replay()
             return so.clone()
 
-    def _run(self, x, m, ns, dev):
+    def _run(self, x, m, ns, dev, quant=None):
         B, T, Cimg, H, W = x.shape
         if ns == 1:
-            return self._forward(x, m, B, T, Cimg, H, W, dev)
+            return self._forward(x, m, B, T, Cimg, H, W, dev, quant=quant)
         # Clips are independent: run sub-batches on separate HIP streams.  Every kernel of the path has serial phases
         # (stage -> MFMA -> store); with several forwards in flight the hardware interleaves workgroups of different
         # kernels, so HBM-bound and MFMA-bound phases of different sub-batches overlap and launch tails are filled.
         # Worth +4-5 % at B=16.  (Kernels of several HW queues then share the CUs: see DESIGN.md "Multi-stream replays" for
         # the packed-FP32 / LDS hazard this exposed and how the build avoids it.)
-        out = self._new(dev, B, Cimg, 4 * H, 4 * W)
+        out = self._new(dev, B, Cimg, 4 * H, 4 * W, dtype=torch.float32 if quant is None else torch.uint8)
         cur = torch.cuda.current_stream(dev)
         while len(self._streams) < ns:
             self._streams.append(torch.cuda.Stream(device=dev))
@@ -766,25 +783,32 @@ class Engine:
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 xs = x[bounds[i]:bounds[i + 1]]
-                self._forward(xs, m, xs.shape[0], T, Cimg, H, W, dev, out=out[bounds[i]:bounds[i + 1]])
+                self._forward(xs, m, xs.shape[0], T, Cimg, H, W, dev, out=out[bounds[i]:bounds[i + 1]], quant=quant)
         for i in range(ns):
             cur.wait_stream(self._streams[i])
         return out
 
-    def _forward(self, x, m, B, T, Cimg, H, W, dev, out=None):
+    def _forward(self, x, m, B, T, Cimg, H, W, dev, out=None, quant=None):
+        """x: f32 frames, or uint8 frames with quant = hip.QUANT_TRUNCATE / QUANT_ROUND (the result is then uint8)."""
         n = m.n_feats
         L = lib()
         st = stream_ptr()
         a_t = m.lrelu.weight
-        xin = x.view(B, T * Cimg, H, W).permute(0, 2, 3, 1)      # (b,y,x,c) strided view of the NCHW frames
         # 16-bit activation storage with trunk16 (feat_extract multiplies in f16 - 8-bit pixels stay exact - and stores its
         # output in the mode's activation dtype)
         # feat_extract is launched per frame group so that the two outer groups land in ONE batch-stacked tensor: the first
         # two MGAA calls of the reference (same weights, independent inputs f1 and f3, :2623-2624) run as one call on 2B.
         adt = self._tdt()
-        f2 = self._new(dev, B, H, W, n, dtype=adt)
         cin = T * Cimg
-        if adt != torch.float32 and cin == 7 and n == 64:
+        fe_dedicated = adt != torch.float32 and cin == 7 and n == 64
+        if x.dtype == torch.uint8 and not fe_dedicated:
+            # the generic feat_extract reads f32: the window is converted once (the same floats as a host-side conversion)
+            xf = self._new(dev, *x.shape)
+            check(L.fcvsr_u8_to_f32(x.data_ptr(), hip.u8_table(dev).data_ptr(), x.numel(), xf.data_ptr(), st), "fcvsr_u8_to_f32")
+            x = xf
+        xin = x.view(B, T * Cimg, H, W).permute(0, 2, 3, 1)      # (b,y,x,c) strided view of the NCHW frames
+        f2 = self._new(dev, B, H, W, n, dtype=adt)
+        if fe_dedicated:
             # the whole 3x3 patch fits one K = 64 GEMM step: dedicated kernel, the 7 output blocks go straight to their tensors.
             # The three inputs of the stacked MGAA call are three DENSE tensors (2B,H,W,n) = [clip's group 1 | clip's group 3],
             # not channel slices of one 3n-channel tensor: every later reader (FFT rows, IAC taps, conv_KP, conv3's residual)
@@ -795,9 +819,14 @@ class Engine:
             nb = 7 * n // 64
             P = C.c_void_p * nb
             ptrs = [p13[k, :B].data_ptr() for k in range(3)] + [f2.data_ptr()] + [p13[k, B:].data_ptr() for k in range(3)]
-            check(L.fcvsr_feat_extract(C.byref(xv), B, H, W, wf.data_ptr(), ptr(bf), nb, P(*ptrs),
-                                       (C.c_int64 * nb)(*([n] * nb)), (C.c_int32 * nb)(*([0] * nb)), self._code(adt), st),
-                  "fcvsr_feat_extract")
+            if x.dtype == torch.uint8:
+                check(L.fcvsr_feat_extract_u8(C.byref(xv), hip.u8_table(dev).data_ptr(), B, H, W, wf.data_ptr(), ptr(bf), nb,
+                                              P(*ptrs), (C.c_int64 * nb)(*([n] * nb)), (C.c_int32 * nb)(*([0] * nb)),
+                                              self._code(adt), st), "fcvsr_feat_extract_u8")
+            else:
+                check(L.fcvsr_feat_extract(C.byref(xv), B, H, W, wf.data_ptr(), ptr(bf), nb, P(*ptrs),
+                                           (C.c_int64 * nb)(*([n] * nb)), (C.c_int32 * nb)(*([0] * nb)), self._code(adt), st),
+                      "fcvsr_feat_extract")
             x1s, x2s, x3s = p13[0], p13[1], p13[2]
         else:
             f13 = self._new(dev, 2 * B, H, W, 3 * n, dtype=adt)  # [f1 of every clip | f3 of every clip]
@@ -854,12 +883,19 @@ class Engine:
         # up-sampler (:2641-2645)
         u1 = self._new(dev, B, 2 * H, 2 * W, n, dtype=self._adt())
         self._conv("upconv1", [fz], u1, act=ACT_PRELU, slope_t=a_t, ps=True)
-        if out is None:
-            out = self._new(dev, B, Cimg, 4 * H, 4 * W)           # NCHW boundary tensor
-        out_v = out.permute(0, 2, 3, 1)
+        if out is None:                                           # NCHW boundary tensor
+            out = self._new(dev, B, Cimg, 4 * H, 4 * W, dtype=torch.float32 if quant is None else torch.uint8)
+        # uint8 result: the f32 base and, where the last layer has no uint8 variant, the f32 result live in a scratch
+        res = out if quant is None else self._new(dev, B, Cimg, 4 * H, 4 * W)
+        out_v = res.permute(0, 2, 3, 1)
         centre = x[:, T // 2].permute(0, 2, 3, 1)                 # (B,H,W,Cimg) view of the centre LR frame
         cv, ov = view(centre), view(out_v)
-        check(L.fcvsr_bilinear_up4(C.byref(cv), B, H, W, C.byref(ov), st), "fcvsr_bilinear_up4")
+        qv = view(out.permute(0, 2, 3, 1)) if quant is not None else None
+        if x.dtype == torch.uint8:
+            check(L.fcvsr_bilinear_up4_u8(C.byref(cv), hip.u8_table(dev).data_ptr(), B, H, W, C.byref(ov), st),
+                  "fcvsr_bilinear_up4_u8")
+        else:
+            check(L.fcvsr_bilinear_up4(C.byref(cv), B, H, W, C.byref(ov), st), "fcvsr_bilinear_up4")
         fuse_tail = (self.precision != "f32" and n == 64 and Cimg == 1 and self._par["upconv2.weight"].shape[-1] == 1
                      and m.fuse_tail)
         if fuse_tail:
@@ -869,8 +905,12 @@ class Engine:
             wl = self._tap_weights("conv_last0", dt)
             bl = self._par.get("conv_last0.bias")
             u1v = view(u1)
-            check(L.fcvsr_tail_fused(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B,
-                                     2 * H, 2 * W, C.byref(ov), st), "fcvsr_tail_fused")
+            if quant is None:
+                check(L.fcvsr_tail_fused(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B,
+                                         2 * H, 2 * W, C.byref(ov), st), "fcvsr_tail_fused")
+            else:
+                check(L.fcvsr_tail_fused_u8(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B,
+                                            2 * H, 2 * W, C.byref(ov), C.byref(qv), quant, st), "fcvsr_tail_fused_u8")
         else:
             u2 = self._new(dev, B, 4 * H, 4 * W, n, dtype=self._adt())
             self._conv("upconv2", [u1], u2, act=ACT_PRELU, slope_t=a_t, ps=True)
@@ -878,10 +918,16 @@ class Engine:
                 # 3x3 up-convs (full / RGB models): conv_last0 as a memory-bound "taps are MFMA columns" pass over u2
                 wl = self._last_weights("conv_last0", self._adt(), Cimg)
                 u2v = view(u2)
-                check(L.fcvsr_conv_last(C.byref(u2v), wl.data_ptr(), ptr(self._par.get("conv_last0.bias")), B, 4 * H, 4 * W, Cimg,
-                                        C.byref(ov), st), "fcvsr_conv_last")
+                if quant is None:
+                    check(L.fcvsr_conv_last(C.byref(u2v), wl.data_ptr(), ptr(self._par.get("conv_last0.bias")), B, 4 * H, 4 * W,
+                                            Cimg, C.byref(ov), st), "fcvsr_conv_last")
+                else:
+                    check(L.fcvsr_conv_last_u8(C.byref(u2v), wl.data_ptr(), ptr(self._par.get("conv_last0.bias")), B, 4 * H,
+                                               4 * W, Cimg, C.byref(ov), C.byref(qv), quant, st), "fcvsr_conv_last_u8")
             else:
                 self._conv("conv_last0", [u2], out_v, res=[out_v])
+                if quant is not None:
+                    check(L.fcvsr_quantise_u8(res.data_ptr(), res.numel(), quant, out.data_ptr(), st), "fcvsr_quantise_u8")
         if self.taps is not None:
             self.taps["out"] = out.clone()
         return out

@@ -6,6 +6,9 @@ multiple of 4 the way the reference pads 270 -> 272 (zero rows appended at the b
 of windows, crop the padding off the SR frame (:81-86), clamp to [0,1], scale by 255 and TRUNCATE to uint8 (:88-89;
 mmedit's tensor2img rounds instead - `quantise="round"`).  Frames are independent, so windows are batched and, across
 GPUs, sharded by `fcvsr_amd.harness.sharding`.
+
+uint8 LR frames (decoded 8-bit video) take the model's uint8 path (`super_resolve_u8`): the window is read as bytes by the first
+kernels and the last kernel writes the quantised frames, with the same results as the float frames `lr.float() / 255`.
 """
 from __future__ import annotations
 
@@ -28,22 +31,30 @@ def pad_to_multiple(frames: torch.Tensor, mult: int = 4) -> torch.Tensor:
     return torch.nn.functional.pad(frames, (0, pw, 0, ph))
 
 
+def _lr_frames(lr: torch.Tensor, dev) -> torch.Tensor:
+    """The padded LR sequence on the device: uint8 frames stay uint8 (the model's uint8 path), anything else becomes f32."""
+    return pad_to_multiple(lr if lr.dtype == torch.uint8 else lr.float(), 4).to(dev)
+
+
 @torch.no_grad()
 def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                            centres: Optional[Iterable[int]] = None, quantise: str = "truncate") -> np.ndarray:
-    """lr: (N,C,H,W) float in [0,1] (host or device).  Returns uint8 (len(centres),C,4H,4W) SR frames."""
+    """lr: (N,C,H,W) float in [0,1], or uint8 (host or device).  Returns uint8 (len(centres),C,4H,4W) SR frames."""
     N, C, H, W = lr.shape
     dev = next(model.parameters()).device
-    x = pad_to_multiple(lr.float(), 4).to(dev)
+    x = _lr_frames(lr, dev)
     centres = list(range(N)) if centres is None else list(centres)
     out: List[np.ndarray] = []
     for s in range(0, len(centres), batch):
         idx = [window_indices(i, num_frames, N, padding) for i in centres[s:s + batch]]
         win = torch.stack([x[j] for j in idx], 0)                 # (b, 7, C, Hp, Wp)
-        sr = model(win)[:, :, :4 * H, :4 * W]
-        sr = sr.clamp(0, 1) * 255.0
-        sr = sr.round() if quantise == "round" else sr            # uint8 cast truncates
-        out.append(sr.to(torch.uint8).cpu().numpy())
+        if win.dtype == torch.uint8:                              # quantised by the model's last kernel
+            sr = model.super_resolve_u8(win, quantise)[:, :, :4 * H, :4 * W]
+        else:
+            sr = model(win)[:, :, :4 * H, :4 * W]
+            sr = sr.clamp(0, 1) * 255.0
+            sr = (sr.round() if quantise == "round" else sr).to(torch.uint8)     # uint8 cast truncates
+        out.append(sr.cpu().numpy())
     return np.concatenate(out, 0)
 
 
@@ -63,9 +74,10 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
-    lr: (N,C,H,W) float in [0,1]; hr: uint8 (N,C,4H,4W) (host or device).  Windows, padding, crop and quantisation are those of
-    `super_resolve_sequence`; each batch is scored straight from the model output (cropped by view, quantised in the metric
-    kernel) by `device_metrics.frame_metrics`.  Without `return_frames` no SR frame leaves the device."""
+    lr: (N,C,H,W) float in [0,1], or uint8; hr: uint8 (N,C,4H,4W) (host or device).  Windows, padding, crop and quantisation are
+    those of `super_resolve_sequence`; each batch is scored straight from the model output (cropped by view, quantised in the
+    metric kernel - or, for uint8 lr, in the model's last kernel) by `device_metrics.frame_metrics`.  Without `return_frames` no
+    SR frame leaves the device."""
     from .device_metrics import frame_metrics
     N, C, H, W = lr.shape
     if tuple(hr.shape) != (N, C, 4 * H, 4 * W):
@@ -75,11 +87,19 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     if quantise not in ("truncate", "round"):
         raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
     dev = next(model.parameters()).device
-    x = pad_to_multiple(lr.float(), 4).to(dev)
+    x = _lr_frames(lr, dev)
     p_dev, s_dev, frames = [], [], []                             # per-batch device results, fetched once at the end
     for s in range(0, N, batch):
         idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
         win = torch.stack([x[j] for j in idx], 0)                 # (b, 7, C, Hp, Wp)
+        if win.dtype == torch.uint8:
+            sr8 = model.super_resolve_u8(win, quantise)[:, :, :4 * H, :4 * W]
+            p, q = frame_metrics(sr8, hr[s:s + len(idx)].to(dev), crop_border=crop_border, quantise=None, convert_to=convert_to)
+            p_dev.append(p)
+            s_dev.append(q)
+            if return_frames:
+                frames.append(sr8.cpu().numpy())
+            continue
         sr = model(win)[:, :, :4 * H, :4 * W]
         p, q = frame_metrics(sr, hr[s:s + len(idx)].to(dev), crop_border=crop_border, quantise=quantise, convert_to=convert_to)
         p_dev.append(p)
@@ -119,7 +139,9 @@ class StreamedSuperResolver:
       round-2 version re-uploaded all 7, 1.6 MB per window instead of 0.23 MB); the quantised SR frames come back into a
       preallocated pinned uint8 buffer.  Only the ring and two batches are resident in HBM;
     * the last, partial batch is padded to the full batch size so that every call has the same shape (one hipGraph / one
-      set of cached buffers in the engine), padded outputs are dropped.
+      set of cached buffers in the engine), padded outputs are dropped;
+    * uint8 sequences keep the staging buffers and the ring in uint8 (a quarter of the upload bytes) and take the model's
+      uint8 path: the quantised frames come from the last kernel, with no torch passes before the copy to the host.
     `stats` (after run): frames uploaded, H2D / D2H bytes.
     """
 
@@ -135,7 +157,7 @@ class StreamedSuperResolver:
 
     @torch.no_grad()
     def run(self, sequences, rank: int = 0, world: int = 1):
-        """sequences: list of (N_s, C, H, W) float tensors in [0,1] (host; all of one frame size).
+        """sequences: list of (N_s, C, H, W) float tensors in [0,1], or uint8 tensors (host; all of one frame size and dtype).
         Returns {seq: (first_centre, uint8 array (n, C, 4H, 4W))} for the frames this rank owns."""
         from .sharding import shard_sequences
         seq_lens = [int(s.shape[0]) for s in sequences]
@@ -143,9 +165,13 @@ class StreamedSuperResolver:
         if not work:
             return {}
         C, H, W = sequences[0].shape[1:]
+        u8 = sequences[0].dtype == torch.uint8
         for s in sequences:
             if tuple(s.shape[1:]) != (C, H, W):
                 raise ValueError("all sequences of one run must share the frame size")
+            if (s.dtype == torch.uint8) != u8:
+                raise ValueError("all sequences of one run must be uint8, or all float")
+        fdt = torch.uint8 if u8 else torch.float32
         ph, pw = (-H) % 4, (-W) % 4
         Hp, Wp = H + ph, W + pw
         B, T = self.batch, self.num_frames
@@ -165,11 +191,11 @@ class StreamedSuperResolver:
         ring_n = 2 * max(len(a) + len(b) for a, b in zip(need, need[1:] + [[]])) + max_new      # > two consecutive batches' frames
         # buffers (pinned staging, device ring, pinned output) are kept across runs of the same geometry: page-locking a few
         # hundred MB costs more than streaming a sequence
-        key = (ring_n, max_new, len(work), C, H, W, B, T, str(self.device))
+        key = (ring_n, max_new, len(work), C, H, W, B, T, str(self.device), fdt)
         if getattr(self, "_buf_key", None) != key:
             self._bufs = dict(
-                ring=torch.zeros((ring_n, C, Hp, Wp), dtype=torch.float32, device=self.device),   # zero padding rows / columns stay zero
-                stage=[torch.zeros((max_new, C, Hp, Wp), dtype=torch.float32, **pin) for _ in range(2)],
+                ring=torch.zeros((ring_n, C, Hp, Wp), dtype=fdt, device=self.device),   # zero padding rows / columns stay zero
+                stage=[torch.zeros((max_new, C, Hp, Wp), dtype=fdt, **pin) for _ in range(2)],
                 slot_stage=[torch.zeros((max_new,), dtype=torch.int64, **pin) for _ in range(2)],
                 gidx_stage=[torch.zeros((B * T,), dtype=torch.int64, **pin) for _ in range(2)],
                 gidx_dev=[torch.zeros((B * T,), dtype=torch.int64, device=self.device) for _ in range(2)],
@@ -234,15 +260,19 @@ class StreamedSuperResolver:
                 if on_gpu and bi >= 1:
                     ready[(bi + 1) & 1].synchronize()                     # staging buffers of batch bi-1 have been consumed
                 fill(bi + 1)                                              # host work + upload overlap the model call below
-            sr = self.model(win)[:, :, :4 * H, :4 * W]
-            sr = sr.clamp(0, 1) * 255.0
-            sr = sr.round() if self.quantise == "round" else sr
             n = len(items)
-            out_host[pos:pos + n].copy_(sr[:n].to(torch.uint8), non_blocking=on_gpu)
+            if u8:                                                    # quantised by the model's last kernel
+                sr = self.model.super_resolve_u8(win, self.quantise)[:, :, :4 * H, :4 * W]
+                out_host[pos:pos + n].copy_(sr[:n], non_blocking=on_gpu)
+            else:
+                sr = self.model(win)[:, :, :4 * H, :4 * W]
+                sr = sr.clamp(0, 1) * 255.0
+                sr = sr.round() if self.quantise == "round" else sr
+                out_host[pos:pos + n].copy_(sr[:n].to(torch.uint8), non_blocking=on_gpu)
             pos += n
         if on_gpu:
             torch.cuda.synchronize(self.device)
-        self.stats = {"frames_uploaded": up_frames, "windows": len(work), "h2d_bytes": up_frames * C * Hp * Wp * 4,
+        self.stats = {"frames_uploaded": up_frames, "windows": len(work), "h2d_bytes": up_frames * C * Hp * Wp * ring.element_size(),
                       "d2h_bytes": len(work) * C * 16 * H * W, "ring_slots": ring_n}
         res, arr, k = {}, out_host.numpy(), 0
         for (s, a, b) in shard_sequences(seq_lens, rank, world):

@@ -1,0 +1,141 @@
+"""Planar 8-bit YUV 4:2:0 (I420) sequences: reader, writer, the reference's file naming, and 4x super-resolution from file to
+file (the test lists of reference CVSR_train/test_LD_freqCVSR_S_22.py:126-150 are raw sequences named ``Name_WxH_NF.yuv``).
+
+Frame layout: Y (H x W), then U and V (H/2 x W/2 each), one byte per sample, frames back to back.  Y is super-resolved by the
+model's uint8 path (windows of 7 frames, the reference's edge-replicate ``generate_input_index`` by default); U and V are
+up-sampled 4x by the bicubic chroma kernel (``hip.chroma_up4``).  10-bit sequences are not supported.
+"""
+from __future__ import annotations
+
+import os
+import re
+import time
+from typing import NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .. import hip
+from .infer import pad_to_multiple
+from .windows import window_indices
+
+
+class YuvName(NamedTuple):
+    name: str               # everything before the _WxH token (e.g. "BasketballDrive_fps50")
+    width: int
+    height: int
+    frames: Optional[int]   # the _NF token, None when the name carries none
+
+
+_SIZE = re.compile(r"_(\d+)x(\d+)(?=_|\.|$)")
+_FRAMES = re.compile(r"_(\d+)F(?=_|\.|$)")
+
+
+def parse_yuv_name(path: str) -> YuvName:
+    """``Traffic_640x400_300F.yuv`` -> YuvName("Traffic", 640, 400, 300); ``Kimono1_fps24_480x272_240F.yuv`` ->
+    ("Kimono1_fps24", 480, 272, 240); ``Traffic_2560x1600_30.yuv`` (a frame rate, no frame count) -> (..., None)."""
+    base = os.path.basename(path)
+    stem = base[:-4] if base.lower().endswith(".yuv") else base
+    m = _SIZE.search(stem)
+    if m is None:
+        raise ValueError(f"{base!r}: no _WxH size token (expected Name_WxH_NF.yuv)")
+    f = _FRAMES.search(stem, m.end())
+    return YuvName(stem[:m.start()], int(m.group(1)), int(m.group(2)), int(f.group(1)) if f else None)
+
+
+def _check_size(width: int, height: int):
+    if width <= 0 or height <= 0 or width % 2 or height % 2:
+        raise ValueError(f"4:2:0 frames need an even, positive width and height, got {width}x{height}")
+
+
+def frame_bytes(width: int, height: int) -> int:
+    _check_size(width, height)
+    return width * height * 3 // 2
+
+
+def read_yuv420(path: str, width: int, height: int, frames: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Y (N,H,W), U and V (N,H/2,W/2) uint8 arrays of an I420 file: strided views of one read-only memory map (nothing is
+    copied).  `frames` reads the first N frames only."""
+    fb = frame_bytes(width, height)
+    size = os.path.getsize(path)
+    if size % fb:
+        raise ValueError(f"{path}: {size} bytes is not a whole number of {width}x{height} 4:2:0 frames ({fb} bytes each)")
+    n = size // fb
+    if frames is not None:
+        if frames < 0 or frames > n:
+            raise ValueError(f"{path}: asked for {frames} frames, the file holds {n}")
+        n = frames
+    if n == 0:
+        raise ValueError(f"{path}: no frames")
+    mm = np.memmap(path, dtype=np.uint8, mode="r", shape=(n, fb))
+    ys, cs = width * height, (width // 2) * (height // 2)
+    y = mm[:, :ys].reshape(n, height, width)
+    u = mm[:, ys:ys + cs].reshape(n, height // 2, width // 2)
+    v = mm[:, ys + cs:].reshape(n, height // 2, width // 2)
+    return y, u, v
+
+
+def _write_frames(fh, y: np.ndarray, u: np.ndarray, v: np.ndarray):
+    for i in range(y.shape[0]):
+        fh.write(np.ascontiguousarray(y[i]).tobytes())
+        fh.write(np.ascontiguousarray(u[i]).tobytes())
+        fh.write(np.ascontiguousarray(v[i]).tobytes())
+
+
+def _check_planes(y, u, v):
+    y, u, v = (np.asarray(a) for a in (y, u, v))
+    if any(a.dtype != np.uint8 for a in (y, u, v)):
+        raise ValueError("planes must be uint8 (8-bit 4:2:0)")
+    if y.ndim == 2:
+        y, u, v = y[None], u[None], v[None]
+    if y.ndim != 3 or u.shape != v.shape or u.ndim != 3:
+        raise ValueError(f"expected Y (N,H,W), U and V (N,H/2,W/2), got {y.shape}, {u.shape}, {v.shape}")
+    n, h, w = y.shape
+    _check_size(w, h)
+    if u.shape != (n, h // 2, w // 2):
+        raise ValueError(f"chroma planes must be (N,H/2,W/2) = {(n, h // 2, w // 2)}, got {u.shape}")
+    return y, u, v
+
+
+def write_yuv420(path: str, y: np.ndarray, u: np.ndarray, v: np.ndarray) -> None:
+    """Write Y (N,H,W), U and V (N,H/2,W/2) uint8 planes (or single frames (H,W), (H/2,W/2)) as an I420 file."""
+    y, u, v = _check_planes(y, u, v)
+    with open(path, "wb") as fh:
+        _write_frames(fh, y, u, v)
+
+
+@torch.no_grad()
+def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
+                         quantise: str = "truncate", num_frames: int = 7) -> dict:
+    """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
+
+    Y: the frames go to the device once as uint8, windows of `num_frames` frames (`padding`, as `super_resolve_sequence`) run
+    through ``model.super_resolve_u8`` in batches of `batch`, rows / columns padded to a multiple of 4 as the reference pads
+    270 -> 272 and cropped off again.  U, V: ``hip.chroma_up4`` (bicubic) on both planes of a batch in one launch.  Frames are
+    written in order as each batch completes.  Returns stats: frames, seconds, fps, bytes read and written."""
+    if getattr(model, "_img_ch", None) != 1:
+        raise ValueError(f"super_resolve_yuv420 needs a one-channel (Y) model, got C={getattr(model, '_img_ch', None)}")
+    if quantise not in hip.QUANTISE:
+        raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    y, u, v = read_yuv420(src, width, height)
+    N, H, W = y.shape
+    dev = next(model.parameters()).device
+    t0 = time.perf_counter()
+    x = pad_to_multiple(torch.from_numpy(np.ascontiguousarray(y)).to(dev)[:, None], 4)     # (N,1,Hp,Wp) uint8, zero padded
+    written = 0
+    with open(dst, "wb") as fh:
+        for s in range(0, N, batch):
+            e = min(N, s + batch)
+            idx = [window_indices(i, num_frames, N, padding) for i in range(s, e)]
+            win = torch.stack([x[j] for j in idx], 0)                                     # (b, 7, 1, Hp, Wp)
+            ysr = model.super_resolve_u8(win, quantise)[:, 0, :4 * H, :4 * W]
+            uv = torch.from_numpy(np.concatenate([u[s:e], v[s:e]], 0)).to(dev)            # (2b, H/2, W/2)
+            uvsr = hip.chroma_up4(uv)
+            ysr, uvsr = ysr.cpu().numpy(), uvsr.cpu().numpy()
+            _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
+            written += ysr.nbytes + uvsr.nbytes
+    dt = time.perf_counter() - t0
+    return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"), "bytes_read": N * frame_bytes(W, H),
+            "bytes_written": written, "out_size": (4 * W, 4 * H)}

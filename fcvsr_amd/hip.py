@@ -15,9 +15,9 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libfcvsr_hip.so")
 
-F32, BF16, F16 = 0, 1, 2
+F32, BF16, F16, U8 = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_PRELU = 0, 1, 2, 3
-_DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
+_DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.uint8: U8}
 
 
 class View(C.Structure):
@@ -155,6 +155,13 @@ SIGNATURES = {
     "fcvsr_frame_metrics_scratch_bytes": [_I] * 6,
     "fcvsr_frame_metrics": [_VP, C.POINTER(C.c_int64), _I, _VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I,
                             C.POINTER(C.c_double), _VP, _VP, C.c_longlong, _VP],
+    "fcvsr_feat_extract_u8": [_PV, _VP, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _VP],
+    "fcvsr_bilinear_up4_u8": [_PV, _VP, _I, _I, _I, _PV, _VP],
+    "fcvsr_tail_fused_u8": [_PV, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _PV, _PV, _I, _VP],
+    "fcvsr_conv_last_u8": [_PV, _VP, _VP, _I, _I, _I, _I, _PV, _PV, _I, _VP],
+    "fcvsr_u8_to_f32": [_VP, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_quantise_u8": [_VP, C.c_longlong, _I, _VP, _VP],
+    "fcvsr_chroma_up4": [_VP, _VP, _I, _I, _I, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
@@ -367,4 +374,41 @@ def frame_metric_sums(sr: torch.Tensor, hr: torch.Tensor, quantise: int, crop_bo
     win = (C.c_double * 11)(*[float(v) for v in window])
     check(lib().fcvsr_frame_metrics(sr.data_ptr(), s_st, quantise, hr.data_ptr(), h_st, N, Cc, H, W, crop_border, to_y, win,
                                     out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, stream_ptr()), "fcvsr_frame_metrics")
+    return out
+
+
+QUANTISE = {"truncate": QUANT_TRUNCATE, "round": QUANT_ROUND}
+_U8_TABLES = {}
+
+
+def u8_table(device) -> torch.Tensor:
+    """The 256-entry f32 table of the uint8 entry points on `device`: entry k is the f32 that ``uint8 -> .float() / 255`` gives on
+    the host, so a kernel fed uint8 frames sees the floats of a caller that converts its frames on the host.  Built once per device
+    (create it outside stream fan-out and graph capture: Engine.forward_u8's first pass does)."""
+    key = str(torch.device(device))
+    t = _U8_TABLES.get(key)
+    if t is None:
+        t = (torch.arange(256, dtype=torch.uint8).float() / 255).to(device)
+        torch.cuda.synchronize(device)          # readers on any stream find it complete
+        _U8_TABLES[key] = t
+    return t
+
+
+def chroma_up4(planes: torch.Tensor) -> torch.Tensor:
+    """fcvsr_chroma_up4: (P,h,w) uint8 planes on the HIP device -> (P,4h,4w) uint8, one launch.  Defined as
+    ``F.interpolate(p.float() / 255, scale_factor=4, mode="bicubic", align_corners=False)``, clamp(0, 1), * 255, rounded half to
+    even (within one code value of that torch expression: the kernel's f32 sums are not torch's)."""
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or planes.dim() != 3:
+        raise ValueError(f"expected uint8 (P,h,w) planes, got {getattr(planes, 'dtype', type(planes))} "
+                         f"{tuple(getattr(planes, 'shape', ()))}")
+    if not planes.is_cuda:
+        raise RuntimeError("chroma_up4 runs on the HIP device only (there is no CPU fallback)")
+    P, h, w = planes.shape
+    src = planes.contiguous()
+    out = torch.empty((P, 4 * h, 4 * w), dtype=torch.uint8, device=planes.device)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(planes.device):
+        check(lib().fcvsr_chroma_up4(src.data_ptr(), u8_table(planes.device).data_ptr(), P, h, w, out.data_ptr(), stream_ptr()),
+              "fcvsr_chroma_up4")
     return out

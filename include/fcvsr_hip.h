@@ -29,6 +29,7 @@ extern "C" {
 
 enum { FCVSR_E_ARG = -1, FCVSR_E_UNSUPPORTED = -2, FCVSR_E_NOGPU = -3 };
 enum { FCVSR_F32 = 0, FCVSR_BF16 = 1, FCVSR_F16 = 2 };
+enum { FCVSR_U8 = 3 };   /* uint8 frames: accepted only by the *_u8 entry points */
 enum { FCVSR_ACT_NONE = 0, FCVSR_ACT_RELU = 1, FCVSR_ACT_LEAKY = 2, FCVSR_ACT_PRELU = 3 };
 
 /* strided (b,y,x,c) window; strides in ELEMENTS of `dtype`; ptr already points at element (0,0,0,0) */
@@ -36,7 +37,7 @@ typedef struct fcvsr_view {
   void*   ptr;
   int64_t sb, sy, sx, sc;
   int32_t c;      /* number of channels in this window */
-  int32_t dtype;  /* FCVSR_F32 | FCVSR_BF16 | FCVSR_F16 */
+  int32_t dtype;  /* FCVSR_F32 | FCVSR_BF16 | FCVSR_F16 (| FCVSR_U8) */
 } fcvsr_view;
 
 /* One 2-D convolution with fused epilogue.  Replaces nn.Conv2d call sites of the path
@@ -446,6 +447,32 @@ int fcvsr_frame_metrics(const void* sr, const int64_t* host_sr_strides, int quan
                         const int64_t* host_hr_strides, int N, int C, int H, int W, int crop_border, int to_y,
                         const double* host_window, double* out, void* scratch, long long scratch_bytes, void* stream);
 
+/* ---- uint8 frame I/O (8-bit decoded frames in, 8-bit SR frames out; contract: Engine.forward_u8 in fcvsr_amd/engine.py) -------
+ * tab: a device table of 256 floats, tab[k] = the f32 of pixel value k (the host builds it with torch as
+ * uint8 -> .float() / 255), so that a uint8 source enters exactly as the f32 frames of a caller converting on the host.
+ * quantise: FCVSR_QUANT_TRUNCATE / _ROUND - an f32 result v is stored as clamp(v, 0, 1) * 255.0f (f32), truncated toward zero /
+ * rounded half to even: the bytes the f32 path's output gives after clamp, * 255, optional round and the cast to uint8. */
+/* feat_extract with a uint8 (B,H,W,7) view x (dtype FCVSR_U8, strides in bytes); every other argument as the f32 entry point. */
+int fcvsr_feat_extract_u8(const fcvsr_view* x, const float* tab, int B, int H, int W, const void* w, const float* bias, int n_blk,
+                          void* const* dst, const int64_t* dst_pix_stride, const int32_t* dst_ch_off, int dst_dtype, void* stream);
+/* bilinear x4 base from a uint8 (B,H,W,c) view into an f32 (B,4H,4W,c) view */
+int fcvsr_bilinear_up4_u8(const fcvsr_view* src, const float* tab, int B, int H, int W, const fcvsr_view* dst, void* stream);
+/* the fused S up-sampler tail with a uint8 result: base (B,2*H2,2*W2,1) f32 holds the bilinear base and is only read; the value
+ * the f32 entry point would store into it is quantised into out (B,2*H2,2*W2,1), dtype FCVSR_U8. */
+int fcvsr_tail_fused_u8(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                        const float* bl, int B, int H2, int W2, const fcvsr_view* base, const fcvsr_view* out, int quantise,
+                        void* stream);
+/* conv_last0 with a uint8 result: base (B,H,W,C) f32 view (the bilinear base, only read), out (B,H,W,C) uint8 view. */
+int fcvsr_conv_last_u8(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C, const fcvsr_view* base,
+                       const fcvsr_view* out, int quantise, void* stream);
+/* n contiguous uint8 values -> f32 through tab (the window of the configurations whose first layer reads f32) */
+int fcvsr_u8_to_f32(const uint8_t* src, const float* tab, long long n, float* dst, void* stream);
+/* n contiguous f32 values -> quantised uint8 (the result of the generic conv_last0 of f32 mode) */
+int fcvsr_quantise_u8(const float* src, long long n, int quantise, uint8_t* dst, void* stream);
+/* chroma up-sampler of the YUV 4:2:0 path: P dense uint8 planes (P,h,w) -> (P,4h,4w), defined as
+ * F.interpolate(p.float() / 255, scale_factor=4, mode="bicubic", align_corners=False), clamp(0, 1), * 255, rounded half to even;
+ * dst 4-byte aligned. */
+int fcvsr_chroma_up4(const uint8_t* src, const float* tab, int P, int h, int w, uint8_t* dst, void* stream);
 #ifdef __cplusplus
 }
 #endif
