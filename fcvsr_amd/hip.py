@@ -50,6 +50,14 @@ class RcbTailArgs(C.Structure):
                 ("W", C.c_int32)]
 
 
+class CropDesc(C.Structure):
+    """fcvsr_crop_desc: one output plane of fcvsr_clip_batch_u8 (``numpy.dtype(CropDesc)`` is its array form)."""
+    _fields_ = [("src", C.c_void_p), ("pitch", C.c_int32), ("top", C.c_int32), ("left", C.c_int32), ("flags", C.c_int32)]
+
+
+CROP_HFLIP, CROP_VFLIP, CROP_TRANSPOSE = 1, 2, 4
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("n_src", C.c_int32), ("src", View * 3), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
@@ -162,6 +170,7 @@ SIGNATURES = {
     "fcvsr_u8_to_f32": [_VP, _VP, C.c_longlong, _VP, _VP],
     "fcvsr_quantise_u8": [_VP, C.c_longlong, _I, _VP, _VP],
     "fcvsr_chroma_up4": [_VP, _VP, _I, _I, _I, _VP, _VP],
+    "fcvsr_clip_batch_u8": [_VP, _VP, _I, _I, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
@@ -411,4 +420,26 @@ def chroma_up4(planes: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(planes.device):
         check(lib().fcvsr_chroma_up4(src.data_ptr(), u8_table(planes.device).data_ptr(), P, h, w, out.data_ptr(), stream_ptr()),
               "fcvsr_chroma_up4")
+    return out
+
+
+def clip_batch(desc: torch.Tensor, s: int, out: torch.Tensor) -> torch.Tensor:
+    """fcvsr_clip_batch_u8: `desc` is a uint8 tensor on the HIP device holding P = numel / sizeof(CropDesc) descriptors (the bytes
+    of a ``numpy.dtype(CropDesc)`` array), `out` a contiguous f32 tensor of P * s * s elements on the same device: plane p becomes
+    the s x s window descriptor p names, flipped / transposed by its flags, pixel k as ``u8_table[k]``.  One launch on the current
+    stream.  The descriptors are device memory nobody checks here: the caller keeps every window inside its plane (and keeps
+    `desc` and the source planes alive until the launch has run)."""
+    for name, t, dt in (("desc", desc, torch.uint8), ("out", out, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+        if not t.is_cuda:
+            raise RuntimeError("clip_batch runs on the HIP device only (there is no CPU fallback)")
+    if desc.device != out.device:
+        raise ValueError(f"desc on {desc.device}, out on {out.device}")
+    P, rem = divmod(desc.numel(), C.sizeof(CropDesc))
+    if rem or P == 0 or out.numel() != P * s * s:
+        raise ValueError(f"{desc.numel()} descriptor bytes / {out.numel()} output elements do not make whole {s} x {s} planes")
+    with torch.cuda.device(out.device):
+        check(lib().fcvsr_clip_batch_u8(desc.data_ptr(), u8_table(out.device).data_ptr(), P, s, out.data_ptr(), stream_ptr()),
+              "fcvsr_clip_batch_u8")
     return out

@@ -5,3 +5,4 @@ from .ops import conv2d                      # noqa: F401
 from .graph import forward_train             # noqa: F401
 from .loss import charbonnier_loss, charbonnier_loss_mmedit   # noqa: F401
 from .step import FlatGradAllReduce, TrainStep                # noqa: F401
+from .data import BatchPlan, DeviceClipSampler, apply_plan_host          # noqa: F401
