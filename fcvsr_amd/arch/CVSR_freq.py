@@ -157,6 +157,9 @@ class _GShiftBase(nn.Module):
     _up_k = 1
     _in_frames = 7
     _img_ch = 1
+    # training passes only: True = no float atomics in the backward, gradients repeat bit for bit (fcvsr_amd.train.graph.forward_train,
+    # `deterministic`).  A plain attribute like `train_precision`: not part of state_dict.
+    train_deterministic = False
 
     def __init__(self, n_features, wiF, AC_Ks, ACNum, Freq_Inv, SCGroupN):
         super().__init__()
@@ -240,7 +243,8 @@ class _GShiftBase(nn.Module):
             from ..train.graph import forward_train
             if x.dim() != 5 or x.shape[1] != self._in_frames or x.shape[2] != self._img_ch:
                 raise ValueError(f"expected (B,{self._in_frames},{self._img_ch},H,W) input, got {tuple(x.shape)}")
-            return forward_train(self.state_dict(keep_vars=True), x, precision=self._train_precision(), packer=self.train_packer())
+            return forward_train(self.state_dict(keep_vars=True), x, precision=self._train_precision(), packer=self.train_packer(),
+                                 deterministic=bool(self.train_deterministic))
         return self._get_engine().forward(x)
 
     def super_resolve_u8(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:

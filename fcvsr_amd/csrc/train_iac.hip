@@ -4,8 +4,11 @@
 // as two launches on NHWC f32 tensors (the forward is fcvsr_warp / fcvsr_sac_v / fcvsr_sac_h, which leave s and v in memory):
 //   fcvsr_iac_bwd_sac : g_out -> g_feat_in (+=), g_v, g_K (both passes' contributions, assign or +=)
 //   fcvsr_iac_bwd_warp: g_v -> g_s (vertical pass transposed) -> g_prev (bilinear scatter, float atomics into a zeroed tensor) and g_off
+// The same kernel with the scatter switched off is the source pass of the atomic-free form (train_iac_det.hip): it stores g_s and one
+// destination-cell key per pixel instead, g_off keeps its bits.
 // Under autograd these were ~150 torch kernels per iteration and direction (gathers, strided multiplies, pads, masks, slices).
 #include "common.h"
+#include "train_iac.h"
 
 namespace fcvsr {
 
@@ -85,9 +88,12 @@ __global__ __launch_bounds__(256) void iac_bwd_sac_kernel(const float* __restric
 
 // thread = (pixel, lane q of 16): channels q + 16 e, e < NE (a wave-instruction of the scatter then adds 16 consecutive floats per
 // pixel).  gv, prev, gprev: dense (B,H,W,C); off: view with 2 channels; goff: dense (B,H,W,2).
-template <int NE>
+// SCATTER = false (source pass of fcvsr_iac_bwd_warp_det): gprev is not touched; g_s goes to gs_out (B,H,W,C) and the pixel's cell
+// (b, y0 + 1, x0 + 1) of the (H+1) x (W+1) grid to key_out, B (H+1) (W+1) for a pixel without an in-range tap; id_out = pixel index.
+template <int NE, bool SCATTER>
 __global__ __launch_bounds__(256) void iac_bwd_warp_kernel(const float* __restrict__ gv, View k1, const float* __restrict__ prev, View off, int B, int H,
-                                                           int W, float* __restrict__ gprev, float* __restrict__ goff) {
+                                                           int W, float* __restrict__ gprev, float* __restrict__ goff, float* __restrict__ gs_out,
+                                                           unsigned* __restrict__ key_out, unsigned* __restrict__ id_out) {
   constexpr int C = 16 * NE;
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long npix = (long long)B * H * W;
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(256) void iac_bwd_warp_kernel(const float* __restri
       for (int e = 0; e < NE; ++e) {
         const float pv = in ? prev[o + q + 16 * e] : 0.f;
         p[dy][dx][e] = pv;
-        if (in && live) atomicAdd(gprev + o + q + 16 * e, w * gs[e]);
+        if (SCATTER && in && live) atomicAdd(gprev + o + q + 16 * e, w * gs[e]);
       }
     }
 #pragma unroll
@@ -150,22 +156,42 @@ __global__ __launch_bounds__(256) void iac_bwd_warp_kernel(const float* __restri
   dsx += __shfl_xor(dsx, 1); dsx += __shfl_xor(dsx, 2); dsx += __shfl_xor(dsx, 4); dsx += __shfl_xor(dsx, 8);
   dsy += __shfl_xor(dsy, 1); dsy += __shfl_xor(dsy, 2); dsy += __shfl_xor(dsy, 4); dsy += __shfl_xor(dsy, 8);
   if (q == 0 && live) *reinterpret_cast<float2*>(goff + pixg * 2) = make_float2(dsx, dsy);
+  if (!SCATTER && live) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e) gs_out[pixg * C + q + 16 * e] = gs[e];
+    if (q == 0) {
+      const bool hit = x0 >= -1 && x0 < W && y0 >= -1 && y0 < H;          // at least one of the four taps is inside the image
+      key_out[pixg] = hit ? (unsigned)((b * (H + 1) + y0 + 1) * (W + 1) + x0 + 1) : (unsigned)(B * (H + 1) * (W + 1));
+      id_out[pixg] = (unsigned)pixg;
+    }
+  }
+}
+
+bool iac_k1_ok(const fcvsr_view* v, int C) {
+  return v && v->ptr && v->dtype == FCVSR_F32 && v->sc == 1 && v->c == 3 * C && v->sx % 4 == 0 && v->sy % 4 == 0 && v->sb % 4 == 0 &&
+         ((uintptr_t)v->ptr % 16) == 0;
+}
+
+void iac_bwd_warp_source_launch(const float* gv, const fcvsr_view& k1, const float* prev, const fcvsr_view& off, int B, int H, int W, int C,
+                                float* goff, float* gs_out, unsigned* key_out, unsigned* id_out, hipStream_t stream) {
+  const long long total = (long long)B * H * W * 16;
+  if (C == 64)
+    hipLaunchKernelGGL((iac_bwd_warp_kernel<4, false>), dim3(cdiv(total, 256)), dim3(256), 0, stream, gv, to_view(k1), prev, to_view(off), B, H, W,
+                       (float*)nullptr, goff, gs_out, key_out, id_out);
+  else
+    hipLaunchKernelGGL((iac_bwd_warp_kernel<2, false>), dim3(cdiv(total, 256)), dim3(256), 0, stream, gv, to_view(k1), prev, to_view(off), B, H, W,
+                       (float*)nullptr, goff, gs_out, key_out, id_out);
 }
 
 }  // namespace fcvsr
 
 using namespace fcvsr;
 
-static bool k_ok(const fcvsr_view* v, int C) {
-  return v && v->ptr && v->dtype == FCVSR_F32 && v->sc == 1 && v->c == 3 * C && v->sx % 4 == 0 && v->sy % 4 == 0 && v->sb % 4 == 0 &&
-         ((uintptr_t)v->ptr % 16) == 0;
-}
-
 extern "C" int fcvsr_iac_bwd_sac(const float* gy, const float* yout, const float* v, const float* s, const fcvsr_view* k1, float slope, int B,
                                  int H, int W, int C, float* gfin, int fin_accumulate, float* gv, const fcvsr_view* gk, int k_accumulate,
                                  void* stream) {
   FCVSR_CHECK_ARG(gy && yout && v && s && gfin && gv, "null pointer");
-  FCVSR_CHECK_ARG(C % 4 == 0 && k_ok(k1, C) && k_ok(gk, C), "k1 / gk: f32 views with 3*C contiguous channels, 16-byte aligned");
+  FCVSR_CHECK_ARG(C % 4 == 0 && iac_k1_ok(k1, C) && iac_k1_ok(gk, C), "k1 / gk: f32 views with 3*C contiguous channels, 16-byte aligned");
   const long long total = (long long)B * H * W * (C / 4);
   hipLaunchKernelGGL(iac_bwd_sac_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, gy, yout, v, s, to_view(*k1), slope, B, H, W, C,
                      gfin, fin_accumulate, gv, to_view(*gk), k_accumulate);
@@ -176,15 +202,15 @@ extern "C" int fcvsr_iac_bwd_sac(const float* gy, const float* yout, const float
 extern "C" int fcvsr_iac_bwd_warp(const float* gv, const fcvsr_view* k1, const float* prev, const fcvsr_view* off, int B, int H, int W, int C,
                                   float* gprev_zeroed, float* goff, void* stream) {
   FCVSR_CHECK_ARG(gv && prev && gprev_zeroed && goff, "null pointer");
-  FCVSR_CHECK_ARG((C == 32 || C == 64) && k_ok(k1, C), "C in {32, 64}; k1: f32 view with 3*C contiguous channels");
+  FCVSR_CHECK_ARG((C == 32 || C == 64) && iac_k1_ok(k1, C), "C in {32, 64}; k1: f32 view with 3*C contiguous channels");
   FCVSR_CHECK_ARG(off && off->ptr && off->c >= 2 && off->dtype == FCVSR_F32, "off needs 2 f32 channels");
   const long long total = (long long)B * H * W * 16;
   if (C == 64)
-    hipLaunchKernelGGL(iac_bwd_warp_kernel<4>, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, gv, to_view(*k1), prev, to_view(*off), B, H, W,
-                       gprev_zeroed, goff);
+    hipLaunchKernelGGL((iac_bwd_warp_kernel<4, true>), dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, gv, to_view(*k1), prev, to_view(*off),
+                       B, H, W, gprev_zeroed, goff, (float*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr);
   else
-    hipLaunchKernelGGL(iac_bwd_warp_kernel<2>, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, gv, to_view(*k1), prev, to_view(*off), B, H, W,
-                       gprev_zeroed, goff);
+    hipLaunchKernelGGL((iac_bwd_warp_kernel<2, true>), dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, gv, to_view(*k1), prev, to_view(*off),
+                       B, H, W, gprev_zeroed, goff, (float*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

@@ -142,6 +142,8 @@ SIGNATURES = {
     "fcvsr_colsum": [_VP, C.c_longlong, _I, _VP, _VP, C.c_longlong, _I, _VP],
     "fcvsr_iac_bwd_sac": [_VP, _VP, _VP, _VP, _PV, _F, _I, _I, _I, _I, _VP, _I, _VP, _PV, _I, _VP],
     "fcvsr_iac_bwd_warp": [_VP, _PV, _VP, _PV, _I, _I, _I, _I, _VP, _VP, _VP],
+    "fcvsr_iac_bwd_warp_det_workspace": [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    "fcvsr_iac_bwd_warp_det": [_VP, _PV, _VP, _PV, _I, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP],
     "fcvsr_prelu_fwd": [_VP, _VP, _VP, C.c_longlong, _VP],
     "fcvsr_prelu_bwd": [_VP, _VP, _VP, _VP, _VP, _VP, C.c_longlong, _VP],
     "fcvsr_wgrad_cout1_scratch_elems": [_I, _I, _I],

@@ -110,10 +110,13 @@ class _IacFn(torch.autograd.Function):
     LeakyReLU(SAC_h(SAC_v(flow_warp(feat, off_i), K1_i), K1_i) + feat_in) per direction, the two directions sharing the predicted
     kernels K.  Forward: fcvsr_warp / fcvsr_sac_v / fcvsr_sac_h (3 launches per iteration and direction); backward: two launches per
     iteration and direction (fcvsr_iac_bwd_sac, fcvsr_iac_bwd_warp) + one fill.  inputs: feat_f, feat_b (B,C,H,W), K (B,A*6C,H,W),
-    then the A forward and the A backward offset fields (B,2,H,W)."""
+    then the A forward and the A backward offset fields (B,2,H,W).
+    deterministic: the warp's backward is fcvsr_iac_bwd_warp_det (no float atomics, fixed summation order; source pass, sort and
+    gather instead of fill and scatter) with one workspace tensor per backward call: all iterations of both directions run in order on
+    one stream and share it."""
 
     @staticmethod
-    def forward(ctx, feat_f, feat_b, K, A, slope, *offs):
+    def forward(ctx, feat_f, feat_b, K, A, slope, deterministic, *offs):
         import ctypes as C_
         L = hip.lib()
         st = hip.stream_ptr()
@@ -138,7 +141,7 @@ class _IacFn(torch.autograd.Function):
                 prev = y
             outs.append(prev.permute(0, 3, 1, 2))
         ctx.save_for_backward(Kv, *offv, *saved)
-        ctx.A, ctx.slope, ctx.Cn = A, slope, Cn
+        ctx.A, ctx.slope, ctx.Cn, ctx.deterministic = A, slope, Cn, deterministic
         return outs[0], outs[1]
 
     @staticmethod
@@ -153,6 +156,10 @@ class _IacFn(torch.autograd.Function):
         B, H, W, KC = Kv.shape
         gK = torch.zeros_like(Kv)                                           # the never-read F2 halves keep a zero gradient
         g_feats, g_offs = [], [None] * (2 * A)
+        if ctx.deterministic:
+            nbytes = C_.c_size_t(0)
+            hip.check(L.fcvsr_iac_bwd_warp_det_workspace(B, H, W, Cn, C_.byref(nbytes)), "fcvsr_iac_bwd_warp_det_workspace")
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=Kv.device)
         for d, g_out in enumerate((g_f, g_b)):
             g = _nhwc(g_out.float())
             gfin = torch.empty_like(g)
@@ -163,23 +170,29 @@ class _IacFn(torch.autograd.Function):
                 gv = torch.empty_like(g)
                 hip.check(L.fcvsr_iac_bwd_sac(g.data_ptr(), y.data_ptr(), v.data_ptr(), s.data_ptr(), C_.byref(k1), slope, B, H, W, Cn,
                                               gfin.data_ptr(), int(i != A - 1), gv.data_ptr(), C_.byref(gk1), int(d == 1), st), "fcvsr_iac_bwd_sac")
-                gprev = torch.zeros_like(g)
                 goff = torch.empty((B, H, W, 2), dtype=torch.float32, device=g.device)
                 ov = hip.view(offv[d * A + i])
-                hip.check(L.fcvsr_iac_bwd_warp(gv.data_ptr(), C_.byref(k1), prev.data_ptr(), C_.byref(ov), B, H, W, Cn, gprev.data_ptr(),
-                                               goff.data_ptr(), st), "fcvsr_iac_bwd_warp")
+                if ctx.deterministic:
+                    gprev = torch.empty_like(g)                             # written completely by the gather
+                    hip.check(L.fcvsr_iac_bwd_warp_det(gv.data_ptr(), C_.byref(k1), prev.data_ptr(), C_.byref(ov), B, H, W, Cn, gprev.data_ptr(),
+                                                       goff.data_ptr(), ws.data_ptr(), ws.numel(), st), "fcvsr_iac_bwd_warp_det")
+                else:
+                    gprev = torch.zeros_like(g)
+                    hip.check(L.fcvsr_iac_bwd_warp(gv.data_ptr(), C_.byref(k1), prev.data_ptr(), C_.byref(ov), B, H, W, Cn, gprev.data_ptr(),
+                                                   goff.data_ptr(), st), "fcvsr_iac_bwd_warp")
                 g_offs[d * A + i] = goff.permute(0, 3, 1, 2)
                 g = gprev
             g_feats.append((gfin + g).permute(0, 3, 1, 2))                 # prev of iteration 0 is feat_in itself
-        return (g_feats[0], g_feats[1], gK.permute(0, 3, 1, 2), None, None, *g_offs)
+        return (g_feats[0], g_feats[1], gK.permute(0, 3, 1, 2), None, None, None, *g_offs)
 
 
-def iac_both(feat_f: torch.Tensor, feat_b: torch.Tensor, K: torch.Tensor, offs_f, offs_b, slope: float = 0.1):
-    """Both alignment directions of IAC (A = len(offs_f) iterations) with the kernel predictor output K shared; C in {32, 64}."""
+def iac_both(feat_f: torch.Tensor, feat_b: torch.Tensor, K: torch.Tensor, offs_f, offs_b, slope: float = 0.1, deterministic: bool = False):
+    """Both alignment directions of IAC (A = len(offs_f) iterations) with the kernel predictor output K shared; C in {32, 64}.
+    deterministic=True: the backward uses no float atomics - two backward passes of the same inputs give the same bits."""
     if not feat_f.is_cuda:
         raise RuntimeError("fcvsr_amd.train.blocks needs device tensors (the HIP path has no CPU fallback)")
     A = len(offs_f)
-    return _IacFn.apply(feat_f, feat_b, K, A, float(slope), *offs_f, *offs_b)
+    return _IacFn.apply(feat_f, feat_b, K, A, float(slope), bool(deterministic), *offs_f, *offs_b)
 
 
 class _PReluFn(torch.autograd.Function):

@@ -32,9 +32,11 @@ Tensor = torch.Tensor
 
 
 class _Ctx:
-    def __init__(self, p: Dict[str, Tensor], precision: str, fused_blocks: bool = True, packer: Optional[WeightPacker] = None):
+    def __init__(self, p: Dict[str, Tensor], precision: str, fused_blocks: bool = True, packer: Optional[WeightPacker] = None,
+                 deterministic: bool = False):
         self.p, self.precision, self.packer = p, precision, packer
         self.fused_blocks = fused_blocks                # False: every non-convolution operator as torch ops (the test reference)
+        self.deterministic = deterministic              # True: no float atomics in the backward (blocks.iac_both), torch routes refused
 
     def conv(self, key: str, x: Tensor, stride: int = 1, act=None, slope: float = 0.0) -> Tensor:
         """nn.Conv2d + optional LeakyReLU / ReLU evaluated in the HIP kernel's epilogue (one launch)."""
@@ -186,8 +188,12 @@ def _mgaa(c: _Ctx, key: str, x: Tensor, A: int) -> Tensor:
         offs[1].append(fld[B:])
     K = c.conv(key + ".F.1", c.conv(key + ".F.0", c.conv(key + ".conv_KP", x2)))
     if c.fused_blocks and d in (32, 64):
-        a_f, a_b = iac_both(x1, x3, K, offs[0], offs[1], 0.1)
+        a_f, a_b = iac_both(x1, x3, K, offs[0], offs[1], 0.1, c.deterministic)
         return c.conv(key + ".conv3", torch.cat([a_f, a_b], 1)) + x2
+    if c.deterministic:
+        raise ValueError(f"deterministic=True needs the HIP alignment block (fused_blocks=True and a feature width of 32 or 64, got "
+                         f"fused_blocks={c.fused_blocks}, width {d}): the torch route's gather and replicate padding scatter-add in their "
+                         "backward in no fixed order")
     al = []
     for feat_in, ofs in ((x1, offs[0]), (x3, offs[1])):
         feat = feat_in
@@ -268,6 +274,10 @@ def _block_rcb(c: _Ctx, key: str, xs: List[Tensor]) -> List[Tensor]:
     if c.fused_blocks and all(t.shape[2] % 2 == 0 and t.shape[3] % 2 == 0 for t in xs[:2]) and xs[0].shape[1] % 4 == 0:
         # (for even sizes the x0.5 bilinear down-sampling is the 2x2 mean; the doubled R0 / R2 of :771-776 are r_scale = 2)
         return [xscale(xs[0], R[0], 2.0, None, u1), xscale(xs[1], R[1], 1.0, d0, u2), xscale(xs[2], R[2], 2.0, d1, None)]
+    if c.deterministic:
+        raise ValueError("deterministic=True needs the HIP cross-scale sum (fused_blocks=True, even sizes on the first two pyramid levels, "
+                         f"channels a multiple of 4; got fused_blocks={c.fused_blocks}, levels {[tuple(t.shape[1:]) for t in xs[:2]]}): the "
+                         "backward of F.interpolate's bilinear resampling adds in no fixed order")
     dn = [F.interpolate(t, scale_factor=0.5, mode="bilinear", align_corners=False) for t in (d0, d1)]
     up = [F.interpolate(t, scale_factor=2.0, mode="bilinear", align_corners=False) for t in (u1, u2)]
     return [xs[0] + R[0] + R[0] + up[0], xs[1] + R[1] + dn[0] + up[1], xs[2] + R[2] + dn[1] + R[2]]
@@ -285,10 +295,14 @@ def _scnet(c: _Ctx, key: str, xs: List[Tensor], G: int) -> List[Tensor]:
 
 
 def forward_train(p: Dict[str, Tensor], x: Tensor, *, precision: str = "f32", fused_blocks: bool = True,
-                  packer: Optional[WeightPacker] = None) -> Tensor:
+                  packer: Optional[WeightPacker] = None, deterministic: bool = False) -> Tensor:
     """x: (B,7,C,H,W) device tensor in [0,1] -> (B,C,4H,4W), differentiable w.r.t. every live parameter in `p`.
     `packer`: the WeightPacker of this parameter set at this precision (one per model and train precision, kept across passes: it
-    replays the 16-bit weight packings of a pass as one launch).  None: every convolution packs its weight per call."""
+    replays the 16-bit weight packings of a pass as one launch).  None: every convolution packs its weight per call.
+    `deterministic`: the backward of the alignment warp sums in a fixed order (fcvsr_iac_bwd_warp_det) instead of with float atomics, so
+    the gradients of two passes over the same input agree bit for bit.  The routes that leave the HIP blocks for torch operators with
+    an order-dependent backward raise ValueError in this mode, where they branch off (`_mgaa`, `_block_rcb`): fused_blocks=False, a
+    feature width outside {32, 64}, odd sizes on the first two pyramid levels."""
     if not x.is_cuda:
         raise RuntimeError("fcvsr_amd.train needs device tensors (the HIP path has no CPU fallback)")
     n = p["conv_last0.weight"].shape[1]
@@ -300,7 +314,7 @@ def forward_train(p: Dict[str, Tensor], x: Tensor, *, precision: str = "f32", fu
         raise ValueError("H and W must be multiples of 4 (3-level pyramid, reference BlockRCB :766-777)")
     if packer is not None:
         packer.begin_pass()
-    c = _Ctx(p, precision, fused_blocks, packer)
+    c = _Ctx(p, precision, fused_blocks, packer, deterministic)
     x7 = x.reshape(B, T * C, H, W).float()
     if precision == "f32" or (T * C) % 64 == 0:
         feat = conv2d(x7, p["feat_extract.0.weight"], p["feat_extract.0.bias"], 1, "f32", packer=packer)

@@ -82,11 +82,19 @@ class TrainStep:
 
     def __init__(self, model: torch.nn.Module, *, lr: float = 1e-4, weight_decay: float = 1e-5,
                  loss_fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor] = charbonnier_loss, reduce_op: str = "sum",
-                 optimizer: Optional[torch.optim.Optimizer] = None, group=None, use_graph: bool = False):
+                 optimizer: Optional[torch.optim.Optimizer] = None, group=None, use_graph: bool = False,
+                 deterministic: Optional[bool] = None):
         """use_graph: capture forward + loss + backward of the first batch shape in a hipGraph and replay it (the step is ~4 k
         small launches; replaying removes their host cost).  Gradients then live in static buffers; the all-reduce and the
-        optimizer step stay eager.  Batches must keep the captured shape (a different shape is captured anew)."""
+        optimizer step stay eager.  Batches must keep the captured shape (a different shape is captured anew).
+        deterministic: True / False sets `model.train_deterministic` (True: the backward uses no float atomics, so a step from the same
+        weights and batch gives the same gradients, loss and updated weights bit for bit, eager or replayed); None leaves it alone."""
         self.model = model
+        if deterministic is not None:
+            if not hasattr(model, "train_deterministic"):
+                raise ValueError("deterministic needs a model with a `train_deterministic` attribute (the drop-in modules of "
+                                 "fcvsr_amd.arch): on any other module the flag would change nothing")
+            model.train_deterministic = bool(deterministic)
         self.use_graph = use_graph
         self._graphs = {}
         named = trainable_parameters(model)
@@ -123,7 +131,8 @@ class TrainStep:
         return float(loss.detach())
 
     def _graphed(self, lr_frames: torch.Tensor, hr: torch.Tensor) -> torch.Tensor:
-        key = (tuple(lr_frames.shape), tuple(hr.shape), str(lr_frames.device))
+        # (the captured graph has the kernel choice of the deterministic mode baked in)
+        key = (tuple(lr_frames.shape), tuple(hr.shape), str(lr_frames.device), bool(getattr(self.model, "train_deterministic", False)))
         ent = self._graphs.get(key)
         if ent is None:
             sx, sh = lr_frames.clone(), hr.clone()
@@ -186,7 +195,7 @@ def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torc
         lr: float = 1e-4, weight_decay: float = 1e-5, milestones: Sequence[int] = (2000, 8000, 12000, 20000), gamma: float = 0.5,
         val_itv: int = 1, ckpt_dir: Optional[str] = None, warm_start_epoch: int = 0, log: Callable[[str], None] = print,
         val_sequences: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None,
-        on_validate: Optional[Callable[[int, float, float], None]] = None) -> List[float]:
+        on_validate: Optional[Callable[[int, float, float], None]] = None, deterministic: Optional[bool] = None) -> List[float]:
     """Epoch loop of the reference (train_LD_freqCVSR_S_22.py:239-266): MultiStepLR stepped at the START of every epoch,
     Charbonnier-sum loss, Adam, `epoch-%d.pth` state_dict checkpoints every `val_itv` epochs (rank 0).
     `batches(epoch)` yields {'lr_imgs': (b,C,7,h,w), 'hr_imgs': (b,C,f',4h,4w)} like the reference DataLoader.
@@ -195,8 +204,10 @@ def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torc
     on rank 0 (the reference's eval_seq, :263-280): the average over the sequences of each one's mean per-frame PSNR / SSIM
     (`harness.infer.evaluate_sequence` with its defaults: crop border 4, truncating quantisation) is logged as
     `PSNR:%f, SSIM: %f` and passed to `on_validate(epoch, psnr, ssim)` (epoch counted from 1).  It runs under no_grad:
-    parameters, gradients and optimizer state are not touched."""
-    step = TrainStep(model, lr=lr, weight_decay=weight_decay)
+    parameters, gradients and optimizer state are not touched.
+
+    deterministic: passed to `TrainStep` (True: bit-repeatable steps; None leaves `model.train_deterministic` as it is)."""
+    step = TrainStep(model, lr=lr, weight_decay=weight_decay, deterministic=deterministic)
     sched = torch.optim.lr_scheduler.MultiStepLR(step.optimizer, milestones=list(milestones), gamma=gamma)
     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
     model.train()

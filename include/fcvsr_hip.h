@@ -19,6 +19,7 @@
 #ifndef FCVSR_HIP_H
 #define FCVSR_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -183,6 +184,16 @@ int fcvsr_iac_bwd_sac(const float* gy, const float* yout, const float* v, const 
                       int W, int C, float* gfin, int fin_accumulate, float* gv, const fcvsr_view* gk, int k_accumulate, void* stream);
 int fcvsr_iac_bwd_warp(const float* gv, const fcvsr_view* k1, const float* prev, const fcvsr_view* off, int B, int H, int W, int C,
                        float* gprev_zeroed, float* goff, void* stream);
+/* fcvsr_iac_bwd_warp without float atomics (flow_warp backward, CVSR_freq.py:1188-1227 inside :1230-1250): same gs, same goff bits, and
+ * gprev summed by a gather in a fixed order - two calls on the same inputs give the same bits; against the scatter form only the order
+ * of the additions differs.  Three steps on `stream`: the source pass (gs, goff, one destination-cell key per pixel), a stable radix
+ * sort of (key, pixel) pairs, the gather.  gprev is written completely (zeros where no source lands) and need not be zeroed.
+ * workspace: device memory, 16-byte aligned, at least the byte count the _workspace query returns for the same B, H, W, C; it holds gs,
+ * the keys and pixel ids (both sort buffers), the cell index and the sort's scratch, and may be reused by the next call on the stream.
+ * C in {32, 64}; B (H+1) (W+1) < 2^31.  A null, misaligned or too small workspace is FCVSR_E_ARG and nothing is launched. */
+int fcvsr_iac_bwd_warp_det_workspace(int B, int H, int W, int C, size_t* bytes);
+int fcvsr_iac_bwd_warp_det(const float* gv, const fcvsr_view* k1, const float* prev, const fcvsr_view* off, int B, int H, int W, int C,
+                           float* gprev, float* goff, void* workspace, size_t workspace_bytes, void* stream);
 /* fcvsr_conv2d_wgrad_mfma summed over 1..3 problems that share the weight (the pyramid levels of a BlockRCB layer): one launch per
  * problem into consecutive slab ranges of one scratch buffer and ONE ordered reduction (no per-level gradient tensors). */
 long long fcvsr_conv2d_wgrad_mfma_groups_scratch_elems(const int* B, const int* H, const int* W, int n_groups, int cin, int cout, int kh,
