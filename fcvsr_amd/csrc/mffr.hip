@@ -173,6 +173,104 @@ __global__ __launch_bounds__(kRedThreads) void divenh_apply_next_v4_kernel(DivEn
   }
 }
 
+// The chain without the round trip of s_f, s_o (fcvsr_divenh_stage): the running sums after band i are a pointwise function of
+// bands 0..i and of the per-(clip, channel) gates of those bands, so the stage for band i recomputes them in registers from the
+// NB = i - j0 + 1 bands it reads (CK: starting from a stored checkpoint of the sums after band j0-1) - the arithmetic, the
+// partition and the summation order are those of divenh_apply_next_v4_kernel, so the partial sums have the same bits.  Nothing
+// but the partials is written unless out_s_f / out_s_o ask for it.  The NB + CK*2 + NEXT loads of a pixel quad are independent
+// and issued as one batch.
+template <int NB, bool CK, bool NEXT>
+__global__ __launch_bounds__(kRedThreads) void divenh_stage_kernel(fcvsr_divenh_stage_args e, float* partial) {
+  __shared__ float4 sm[2][kRedThreads];
+  const int C = e.C, Cq = C >> 2, B = e.B;
+  const long long npix = (long long)e.H * e.W;
+  const int b = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
+  const int R = kRedThreads / Cq;
+  const int sub = threadIdx.x / Cq, cq = threadIdx.x % Cq;
+  float4 a1 = make_float4(0.f, 0.f, 0.f, 0.f), a2 = a1;
+  if (sub < R) {
+    const int c = cq * 4;
+    float aa[NB][4], bb[NB][4], g1v[NB][4], g2v[NB][4], mean[4] = {0.f, 0.f, 0.f, 0.f}, an[4] = {0.f, 0.f, 0.f, 0.f},
+          bn[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        aa[j][k] = 0.2f * e.a[j][c + k];
+        bb[j][k] = e.b[j][c + k];
+        g1v[j][k] = e.g1[j][b * C + c + k];
+        g2v[j][k] = (CK || j > 0) ? e.g2[j][b * C + c + k] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!CK) mean[k] = e.mean_f_sum[b * C + c + k] * e.inv_hw;
+      if (NEXT) { an[k] = 0.2f * e.a_next[c + k]; bn[k] = e.b_next[c + k]; }
+    }
+    const long long p0 = (long long)blk * kRedPix;
+    const long long p1 = (p0 + kRedPix < npix) ? p0 + kRedPix : npix;
+    for (long long p = p0 + sub; p < p1; p += R) {
+      const long long i = ((long long)b * npix + p) * C + c;
+      float4 f4[NB], sf4 = make_float4(0.f, 0.f, 0.f, 0.f), so4 = sf4, fn4 = sf4;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) f4[j] = *reinterpret_cast<const float4*>(e.f[j] + i);
+      if (CK) { sf4 = *reinterpret_cast<const float4*>(e.ck_s_f + i); so4 = *reinterpret_cast<const float4*>(e.ck_s_o + i); }
+      if (NEXT) fn4 = *reinterpret_cast<const float4*>(e.f_next + i);
+      float sf[4] = {sf4.x, sf4.y, sf4.z, sf4.w}, so[4] = {so4.x, so4.y, so4.z, so4.w};
+      const float fn[4] = {fn4.x, fn4.y, fn4.z, fn4.w};
+      float o1[4], o2[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const float fv = k == 0 ? f4[j].x : k == 1 ? f4[j].y : k == 2 ? f4[j].z : f4[j].w;
+          if (!CK && j == 0) {                              // the first band: exactly DivEnhExprF::eval / DivEnhApplyNextF
+            const float t = fv - mean[k];
+            const float e1 = aa[j][k] * t * fv + bb[j][k] * fv;
+            const float o = e1 * g1v[j][k];
+            sf[k] = fv;
+            so[k] = o;
+          } else {
+            const float t = fv - sf[k] + 0.2f * so[k];
+            const float e1 = aa[j][k] * t * fv + bb[j][k] * fv;
+            const float e2 = aa[j][k] * so[k] * fv + bb[j][k] * fv;
+            float o = e1 * g1v[j][k];
+            o += e2 * g2v[j][k];
+            sf[k] = sf[k] + fv;
+            so[k] = so[k] + o;
+          }
+        }
+        if (NEXT) {
+          const float t = fn[k] - sf[k] + 0.2f * so[k];
+          o1[k] = an[k] * t * fn[k] + bn[k] * fn[k];
+          o2[k] = an[k] * so[k] * fn[k] + bn[k] * fn[k];
+        } else {
+          o1[k] = so[k];
+          o2[k] = 0.f;
+        }
+      }
+      if (e.out_s_f) *reinterpret_cast<float4*>(e.out_s_f + i) = make_float4(sf[0], sf[1], sf[2], sf[3]);
+      if (e.out_s_o) *reinterpret_cast<float4*>(e.out_s_o + i) = make_float4(so[0], so[1], so[2], so[3]);
+      a1.x += o1[0]; a1.y += o1[1]; a1.z += o1[2]; a1.w += o1[3];
+      a2.x += o2[0]; a2.y += o2[1]; a2.z += o2[2]; a2.w += o2[3];
+    }
+  }
+  sm[0][threadIdx.x] = a1;
+  sm[1][threadIdx.x] = a2;
+  __syncthreads();
+  if (threadIdx.x < Cq) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int r = 0; r < R; ++r) {
+        const float4 v = sm[k][r * Cq + threadIdx.x];
+        t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+      }
+      *reinterpret_cast<float4*>(partial + (((long long)k * B + b) * nblk + blk) * C + threadIdx.x * 4) = t;
+    }
+  }
+}
+
 template <int XD>
 __device__ __forceinline__ float4 ld_x4(const void* base, long long quad) {
   if (XD == FCVSR_F32) return reinterpret_cast<const float4*>(base)[quad];
@@ -258,6 +356,47 @@ extern "C" int fcvsr_divenh_apply_next(int first, const float* f, float* s_f, fl
   else hipLaunchKernelGGL((reduce_stage1<2, DivEnhApplyNextF>), dim3(nblk, B), dim3(kRedThreads), 0, st, ex, B, HW, C, scratch);
   FCVSR_LAUNCH_CHECK();
   hipLaunchKernelGGL(reduce_stage2, dim3(2 * B), dim3(kRedThreads), 0, st, (const float*)scratch, 2 * B, nblk, C, sums);
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fcvsr_divenh_stage(const fcvsr_divenh_stage_args* a, void* stream) {
+  FCVSR_CHECK_ARG(a && a->sums && a->scratch, "null pointer");
+  FCVSR_CHECK_ARG(a->n_bands >= 1 && a->n_bands <= 4, "1..4 replayed bands");
+  FCVSR_CHECK_ARG(a->B > 0 && a->H > 0 && a->W > 0 && a->C > 0 && a->C <= 256, "bad sizes");
+  FCVSR_CHECK_ARG(a->C % 4 == 0 && kRedThreads % (a->C / 4) == 0, "C % 4 == 0 and 256 % (C/4) == 0 required");
+  const bool ck = a->ck_s_f != nullptr, next = a->f_next != nullptr;
+  FCVSR_CHECK_ARG(ck == (a->ck_s_o != nullptr), "checkpoint: both running sums or none");
+  FCVSR_CHECK_ARG(ck || a->mean_f_sum, "the first band needs the sums of f");
+  FCVSR_CHECK_ARG(next == (a->a_next != nullptr) && next == (a->b_next != nullptr), "next band: all or none");
+  auto al16 = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
+  for (int j = 0; j < a->n_bands; ++j) {
+    FCVSR_CHECK_ARG(a->f[j] && a->a[j] && a->b[j] && a->g1[j] && (a->g2[j] || (!ck && j == 0)), "band: null pointer");
+    FCVSR_CHECK_ARG(al16(a->f[j]), "bands must be 16-byte aligned");
+  }
+  FCVSR_CHECK_ARG(al16(a->ck_s_f) && al16(a->ck_s_o) && al16(a->f_next) && al16(a->out_s_f) && al16(a->out_s_o) && al16(a->scratch),
+                  "tensors must be 16-byte aligned");
+  const long long HW = (long long)a->H * a->W;
+  const int nblk = red_blocks(HW);
+  FCVSR_CHECK_ARG(a->scratch_elems >= 2ll * a->B * nblk * a->C, "scratch too small");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(nblk, a->B), block(kRedThreads);
+#define FCVSR_DS(NB, CK, NX) hipLaunchKernelGGL((divenh_stage_kernel<NB, CK, NX>), grid, block, 0, st, *a, a->scratch)
+#define FCVSR_DS_NB(NB)                                                                   \
+  do {                                                                                    \
+    if (ck) { if (next) FCVSR_DS(NB, true, true); else FCVSR_DS(NB, true, false); }       \
+    else { if (next) FCVSR_DS(NB, false, true); else FCVSR_DS(NB, false, false); }        \
+  } while (0)
+  switch (a->n_bands) {
+    case 1: FCVSR_DS_NB(1); break;
+    case 2: FCVSR_DS_NB(2); break;
+    case 3: FCVSR_DS_NB(3); break;
+    default: FCVSR_DS_NB(4); break;
+  }
+#undef FCVSR_DS_NB
+#undef FCVSR_DS
+  FCVSR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(reduce_stage2, dim3(2 * a->B), dim3(kRedThreads), 0, st, (const float*)a->scratch, 2 * a->B, nblk, a->C, a->sums);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

@@ -2,6 +2,7 @@
 // base skip F.interpolate(shortcut[:, T//2], scale_factor=4, mode='bilinear') (align_corners=False).
 #include "common.h"
 #include "mfma_util.h"
+#include "bilinear.h"
 
 namespace fcvsr {
 
@@ -47,7 +48,6 @@ __global__ void pixel_shuffle16_kernel(const float* src, View dst, int B, int H,
       make_uint4(lo.x, lo.y, hi.x, hi.y);
 }
 
-// U8: src holds uint8 frames, pixel k read as tab[k] (u8.h) - the same arithmetic on the same f32 values as the f32 source
 template <bool U8>
 __device__ __forceinline__ void bilinear_up4_px(View src, const float* tab, int B, int H, int W, View dst) {
   const int Ho = 4 * H, Wo = 4 * W;
@@ -59,22 +59,7 @@ __device__ __forceinline__ void bilinear_up4_px(View src, const float* tab, int 
   const int oy = (int)((t / Wo) % Ho);
   const int c = (int)((t / ((long long)Wo * Ho)) % dst.c);
   const int b = (int)(t / ((long long)Wo * Ho * dst.c));
-  float sy = 0.25f * ((float)oy + 0.5f) - 0.5f; sy = sy < 0.f ? 0.f : sy;
-  float sx = 0.25f * ((float)ox + 0.5f) - 0.5f; sx = sx < 0.f ? 0.f : sx;
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float ly = sy - (float)y0, lx = sx - (float)x0;
-  const long long o00 = (long long)y0 * src.sy + (long long)x0 * src.sx, o01 = (long long)y0 * src.sy + (long long)x1 * src.sx;
-  const long long o10 = (long long)y1 * src.sy + (long long)x0 * src.sx, o11 = (long long)y1 * src.sy + (long long)x1 * src.sx;
-  float v00, v01, v10, v11;
-  if constexpr (U8) {
-    const uint8_t* sp = reinterpret_cast<const uint8_t*>(src.p) + (long long)b * src.sb + (long long)c * src.sc;
-    v00 = tab[sp[o00]]; v01 = tab[sp[o01]]; v10 = tab[sp[o10]]; v11 = tab[sp[o11]];
-  } else {
-    const float* sp = src.p + (long long)b * src.sb + (long long)c * src.sc;
-    v00 = sp[o00]; v01 = sp[o01]; v10 = sp[o10]; v11 = sp[o11];
-  }
-  const float v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+  const float v = bilinear_up4_at<U8>(src, tab, H, W, b, c, oy, ox);
   dst.p[(long long)b * dst.sb + (long long)oy * dst.sy + (long long)ox * dst.sx + (long long)c * dst.sc] = v;
 }
 

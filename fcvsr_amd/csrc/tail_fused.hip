@@ -10,20 +10,27 @@
 //      the 340 halo pixels - 44 small MFMAs instead of 576 multiply-adds per output pixel on the vector ALU.
 //   3. out[y][x] += bias + sum_tap P[y+dy][x+dx][tap]   (out holds the bilinear x4 base skip).
 // HBM traffic per output pixel: 14 bytes of u1 (with halo) + 8 bytes of out, instead of 128 written + ~170 read.
+// BASE != 0 (fcvsr_tail_fused_base, _base_u8): the base skip is not read from `out` but evaluated for the thread's pixel from the
+// centre LR frame (bilinear.h: four cached loads from a 230 KB frame; BASE == 2: a uint8 frame read through the table of u8.h), so
+// the result is write-only and no kernel has to pre-fill an f32 base.
 // Q != 0 (fcvsr_tail_fused_u8): `out` is only read (the f32 base) and the sum goes, quantised (u8.h), to the uint8 frame out8.
 #include "common.h"
 #include "mfma_util.h"
+#include "bilinear.h"
 #include "u8.h"
+#include <type_traits>
 
 namespace fcvsr {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
-constexpr int kTfTH = 8, kTfTW = 32;                       // output tile
+constexpr int kTfTH = 8, kTfTW = 32;                       // output tile: one thread per output pixel
 constexpr int kTfHH = kTfTH + 2, kTfHW = kTfTW + 2;        // halo of the 3x3 convolution (output resolution)
 constexpr int kTfNHP = kTfHH * kTfHW;                      // 340
 constexpr int kTfUH = kTfTH / 2 + 2, kTfUW = kTfTW / 2 + 2;   // 6 x 18 pixels of u1
 constexpr int kTfNU = kTfUH * kTfUW;                       // 108
+constexpr int kTfNF = (kTfNU + 31) / 32;                   // 32-pixel fragments of GEMM 1 (the last one holds 12 pixels)
+static_assert(kTfTH * kTfTW == 256, "one thread per output pixel");
 constexpr int kTfRow = 64 + 8;                             // halfwords per halo pixel in LDS (padded: conflict-free fragments)
 constexpr int kTfPRow = 9;                                 // floats per pixel of the tap table (odd stride)
 constexpr int kTfNPT = (kTfNHP + 15) / 16;                 // 22 pixel tiles of GEMM 2
@@ -37,6 +44,8 @@ struct TailArgs {
   const float* bl;         // conv_last0 bias (1 value, may be null)
   View out;                // (B, 2*H2, 2*W2, 1) f32, read-modify-write (Q != 0: read only)
   View out8;               // Q != 0: (B, 2*H2, 2*W2, 1) uint8 destination
+  View centre;             // BASE: (B, H2/2, W2/2, 1) centre LR frame (source of the bilinear x4 base skip), f32 or (BASE == 2) uint8
+  const float* tab;        // BASE == 2: the 256-float table of the uint8 entry points
   int B, H2, W2, tiles_x, tiles_y;
   int ntiles;              // B * tiles_x * tiles_y, split into contiguous runs over the launched workgroups
 };
@@ -49,7 +58,7 @@ __device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
 }
 
-template <bool BF16, int Q = 0>
+template <bool BF16, int Q = 0, int BASE = 0>
 __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
   // 48 KiB: the tap table P of step 2 overwrites the u2 tile it was computed from (3 workgroups per CU)
   __shared__ __align__(16) uint16_t u2_s[kTfNHP * kTfRow];
@@ -80,10 +89,27 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
     b2_s[tid0] = a.b2 ? a.b2[tid0] : 0.f;
   }
   const float slope = a.slope[0];
+  // PReLU(x) = max(x, slope*x) whenever 0 <= slope <= 1 (one multiply and one max per value; x >= 0: slope*x <= x, x < 0:
+  // slope*x >= x, and slope*x is the product the generic form rounds).  Wave-uniform; any other slope takes the generic form.
+  const bool slope01 = slope >= 0.f && slope <= 1.f;
   const float blast = a.bl ? a.bl[0] : 0.f;
   const int per_img = a.tiles_x * a.tiles_y;
   const int HH = 2 * a.H2, WW = 2 * a.W2;
   __syncthreads();
+  // where lane r of fragment nt stores its u1 pixel's sub-pixel `wave` inside the 10 x 34 halo (halfwords; -1: a dead slot or a
+  // position outside the halo): the same for every tile
+  int u2_off[kTfNF];
+#pragma unroll
+  for (int nt = 0; nt < kTfNF; ++nt) {
+    const int p = nt * 32 + (threadIdx.x & 31);
+    const int uy = p / kTfUW, ux = p - uy * kTfUW;
+    const int hr = 2 * uy + (int)(threadIdx.x >> 7) - 1, hc = 2 * ux + (int)((threadIdx.x >> 6) & 1) - 1;
+    const bool keep = p < kTfNU && hr >= 0 && hr < kTfHH && hc >= 0 && hc < kTfHW;
+    u2_off[nt] = keep ? (hr * kTfHW + hc) * kTfRow + 4 * (int)((threadIdx.x >> 5) & 1) : -1;
+  }
+  // the slope is the same for every tile: the whole tile loop exists once per PReLU form
+  auto run_tiles = [&](auto s01_c) {
+  constexpr bool S01 = decltype(s01_c)::value;
 #pragma unroll 1
   for (int t = t_begin; t < t_end; ++t) {
   // lane-derived offsets are recomputed per tile: hoisted out of the loop they cost registers the tile body has no room for
@@ -93,19 +119,23 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
   const int b = t / per_img;
   const int t2 = t - b * per_img;
   const int Y0 = (t2 / a.tiles_x) * kTfTH, X0 = (t2 % a.tiles_x) * kTfTW;
-  // this thread's output pixel: its current value (the base skip) is requested now and consumed at the very end
+  // this thread's output pixel.  BASE == 0: its current value (the base skip) is requested now and consumed at the very end;
+  // the f32 tensor `out` exists only where it is read (BASE == 0) or written (Q == 0)
   const int oy = Y0 + (tid >> 5), ox = X0 + (tid & 31);
   const bool olive = oy < HH && ox < WW;
-  float* op = a.out.p + (long long)b * a.out.sb + (long long)(olive ? oy : 0) * a.out.sy + (long long)(olive ? ox : 0) * a.out.sx;
-  const float base = *op;
+  float* op = nullptr;
+  if constexpr (BASE == 0 || Q == 0)
+    op = a.out.p + (long long)b * a.out.sb + (long long)(olive ? oy : 0) * a.out.sy + (long long)(olive ? ox : 0) * a.out.sx;
+  float base = 0.f;
+  if constexpr (BASE == 0) base = *op;
 
   // ---- GEMM 1: u2 = PReLU(W2 . u1 + b2), wave = sub-pixel -----------------------------------------------------------------
   {
     const int r = lane & 31, h = lane >> 5;
     const uint16_t* ub = reinterpret_cast<const uint16_t*>(a.u1.p) + (long long)b * a.u1.sb + h * 8;
-    uint4 kf[4][4];
+    uint4 kf[kTfNF][4];
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
+    for (int nt = 0; nt < kTfNF; ++nt) {
       int p = nt * 32 + r;
       p = p < kTfNU ? p : kTfNU - 1;
       const int uy = p / kTfUW, ux = p - uy * kTfUW;
@@ -124,32 +154,53 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
       for (int g = 0; g < 4; ++g)
         bq[g] = *reinterpret_cast<const float4*>(b2_s + wave * 64 + q * 32 + 8 * g + 4 * h);
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
+      for (int nt = 0; nt < kTfNF; ++nt) {
         f32x16_t acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) acc = mfma<BF16>(wf[q][kk], kf[nt][kk], acc);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int c = q * 32 + 8 * g;                      // acc[4g..4g+3] = channels c + 4h .. c + 4h + 3 of sub-pixel `wave`
+          // the bias is added last (products first, as the stand-alone layer stores them): as the MFMA's C operand it would be
+          // rounded into every partial sum and change the f32 result
+          float4 v = make_float4(acc[4 * g] + bq[g].x, acc[4 * g + 1] + bq[g].y, acc[4 * g + 2] + bq[g].z, acc[4 * g + 3] + bq[g].w);
+          if constexpr (S01) {
+            v.x = fmaxf(v.x, slope * v.x); v.y = fmaxf(v.y, slope * v.y);
+            v.z = fmaxf(v.z, slope * v.z); v.w = fmaxf(v.w, slope * v.w);
+          } else {
+            // PReLU as max(x,0) + slope*min(x,0): the same values as the select form
+            v.x = fmaf(slope, fminf(v.x, 0.f), fmaxf(v.x, 0.f)); v.y = fmaf(slope, fminf(v.y, 0.f), fmaxf(v.y, 0.f));
+            v.z = fmaf(slope, fminf(v.z, 0.f), fmaxf(v.z, 0.f)); v.w = fmaf(slope, fminf(v.w, 0.f), fmaxf(v.w, 0.f));
+          }
+          if (u2_off[nt] >= 0) *reinterpret_cast<uint2*>(u2_s + u2_off[nt] + c) = cvt4<BF16>(v);
+        }
+      }
+    }
+    // zero padding of conv_last0, only in tiles whose 10 x 34 halo leaves the image (7 % of them at 720 x 1280; a uniform
+    // branch): every lane overwrites the positions outside the image that it has just stored (same lane, same addresses: in order)
+    if (Y0 < 1 || Y0 + kTfTH + 1 > HH || X0 < 1 || X0 + kTfTW + 1 > WW) {
+#pragma unroll 1
+      for (int nt = 0; nt < kTfNF; ++nt) {
         const int p = nt * 32 + r;
         const int uy = p / kTfUW, ux = p - uy * kTfUW;
-        const int hr = 2 * uy + sy - 1, hc = 2 * ux + sx - 1;   // position inside the 10 x 34 halo
+        const int hr = 2 * uy + sy - 1, hc = 2 * ux + sx - 1;
         const int Y = Y0 - 1 + hr, X = X0 - 1 + hc;
         const bool keep = p < kTfNU && hr >= 0 && hr < kTfHH && hc >= 0 && hc < kTfHW;
         const bool inside = Y >= 0 && Y < HH && X >= 0 && X < WW;
+        if (keep && !inside) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int c = q * 32 + 8 * g + 4 * h;             // acc[4g..4g+3] = channels c..c+3 of sub-pixel `wave`
-          float4 v = make_float4(acc[4 * g] + bq[g].x, acc[4 * g + 1] + bq[g].y, acc[4 * g + 2] + bq[g].z, acc[4 * g + 3] + bq[g].w);
-          // PReLU as max(x,0) + slope*min(x,0): the same values as the select form, in packed-f32 instructions
-          v.x = fmaf(slope, fminf(v.x, 0.f), fmaxf(v.x, 0.f)); v.y = fmaf(slope, fminf(v.y, 0.f), fmaxf(v.y, 0.f));
-          v.z = fmaf(slope, fminf(v.z, 0.f), fmaxf(v.z, 0.f)); v.w = fmaf(slope, fminf(v.w, 0.f), fmaxf(v.w, 0.f));
-          uint2 pk = cvt4<BF16>(v);
-          if (!inside) pk = make_uint2(0u, 0u);              // zero padding of conv_last0
-          if (keep) *reinterpret_cast<uint2*>(u2_s + (hr * kTfHW + hc) * kTfRow + c) = pk;
+          for (int c8 = 0; c8 < 8; ++c8)
+            *reinterpret_cast<uint2*>(u2_s + (hr * kTfHW + hc) * kTfRow + 8 * c8 + 4 * h) = make_uint2(0u, 0u);
         }
       }
     }
   }
+  // the base skip's four source values are requested now (the fragment registers of GEMM 1 are free) and blended at the very end
+  BilinearTaps taps = {};
+  if constexpr (BASE != 0)
+    taps = bilinear_up4_fetch<BASE == 2>(a.centre, a.tab, a.H2 >> 1, a.W2 >> 1, b, 0, olive ? oy : 0, olive ? ox : 0);
   __syncthreads();
 
   // ---- GEMM 2: P[pixel][tap] = u2[pixel][:] . wl[tap][:] ---------------------------------------------------------------------
@@ -184,6 +235,7 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
   {
     const int ty = tid >> 5, tx = tid & 31;
     if (olive) {
+      if constexpr (BASE != 0) base = bilinear_up4_blend(taps);
       float s = base + blast;
 #pragma unroll
       for (int dy = 0; dy < 3; ++dy)
@@ -199,20 +251,25 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
   }
   __syncthreads();                                         // the tap table is read: the next tile's u2 overwrites it
   }
+  };
+  if (slope01) run_tiles(std::true_type{});
+  else run_tiles(std::false_type{});
 }
 
 }  // namespace fcvsr
 
 using namespace fcvsr;
 
-template <int Q>
+template <int Q, int BASE = 0>
 static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl, const float* bl,
-                             int B, int H2, int W2, const fcvsr_view* out, const fcvsr_view* out8, void* stream) {
+                             int B, int H2, int W2, const fcvsr_view* out, const fcvsr_view* out8, void* stream,
+                             const fcvsr_view* centre = nullptr, const float* tab = nullptr) {
+  if (Q != 0 && BASE != 0) out = out8;                     // no f32 tensor at all: `out` is neither read nor written
   FCVSR_CHECK_ARG(u1 && u1->ptr && w2 && slope && wl && out && out->ptr, "null argument");
   FCVSR_CHECK_ARG((u1->dtype == FCVSR_BF16 || u1->dtype == FCVSR_F16) && u1->c == 64 && u1->sc == 1 &&
                       ((uintptr_t)u1->ptr % 16) == 0 && u1->sx % 8 == 0 && u1->sy % 8 == 0 && u1->sb % 8 == 0,
                   "u1: 64 contiguous 16-bit channels, 16-byte aligned");
-  FCVSR_CHECK_ARG(out->dtype == FCVSR_F32 && out->c == 1, "out: one f32 channel");
+  FCVSR_CHECK_ARG((out->dtype == FCVSR_F32 || out == out8) && out->c == 1, "out: one f32 channel");
   FCVSR_CHECK_ARG(((uintptr_t)w2 % 16) == 0 && ((uintptr_t)wl % 16) == 0 && (b2 == nullptr || ((uintptr_t)b2 % 16) == 0),
                   "weights / bias must be 16-byte aligned");
   FCVSR_CHECK_ARG(B > 0 && H2 > 0 && W2 > 0, "bad sizes");
@@ -220,6 +277,15 @@ static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* 
   a.u1 = to_view(*u1); a.w2 = (const uint16_t*)w2; a.b2 = b2; a.slope = slope; a.wl = (const uint16_t*)wl; a.bl = bl;
   a.out = to_view(*out); a.B = B; a.H2 = H2; a.W2 = W2;
   a.out8 = out8 ? to_view(*out8) : a.out;
+  a.centre = a.out;
+  a.tab = tab;
+  if (BASE != 0) {
+    FCVSR_CHECK_ARG(centre && centre->ptr && centre->c == 1 && centre->dtype == (BASE == 2 ? FCVSR_U8 : FCVSR_F32),
+                    "centre: one channel, f32 (uint8 for the _u8 entry point)");
+    FCVSR_CHECK_ARG(BASE != 2 || tab, "uint8 centre frame needs the table");
+    FCVSR_CHECK_ARG(H2 % 2 == 0 && W2 % 2 == 0, "u1 is the x2 level of the centre frame: H2, W2 even");
+    a.centre = to_view(*centre);
+  }
   a.tiles_x = cdiv(2 * W2, kTfTW);
   a.tiles_y = cdiv(2 * H2, kTfTH);
   a.ntiles = B * a.tiles_x * a.tiles_y;
@@ -234,8 +300,8 @@ static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* 
   nwg = nwg < 8 ? 8 : nwg / 8 * 8;
   dim3 grid(nwg < a.ntiles ? nwg : a.ntiles);
   hipStream_t st = (hipStream_t)stream;
-  if (u1->dtype == FCVSR_BF16) hipLaunchKernelGGL((tail_fused_kernel<true, Q>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((tail_fused_kernel<false, Q>), grid, dim3(256), 0, st, a);
+  if (u1->dtype == FCVSR_BF16) hipLaunchKernelGGL((tail_fused_kernel<true, Q, BASE>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((tail_fused_kernel<false, Q, BASE>), grid, dim3(256), 0, st, a);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }
@@ -243,6 +309,22 @@ static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* 
 extern "C" int fcvsr_tail_fused(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
                                 const float* bl, int B, int H2, int W2, const fcvsr_view* out, void* stream) {
   return tail_fused_launch<0>(u1, w2, b2, slope, wl, bl, B, H2, W2, out, nullptr, stream);
+}
+
+extern "C" int fcvsr_tail_fused_base(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                                     const float* bl, const fcvsr_view* centre, int B, int H2, int W2, const fcvsr_view* out,
+                                     void* stream) {
+  return tail_fused_launch<0, 1>(u1, w2, b2, slope, wl, bl, B, H2, W2, out, nullptr, stream, centre);
+}
+
+extern "C" int fcvsr_tail_fused_base_u8(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                                        const float* bl, const fcvsr_view* centre, const float* tab, int B, int H2, int W2,
+                                        const fcvsr_view* out, int quantise, void* stream) {
+  FCVSR_CHECK_ARG(out && out->ptr && out->dtype == FCVSR_U8 && out->c == 1, "out: one uint8 channel");
+  FCVSR_CHECK_ARG(quantise == FCVSR_QUANT_TRUNCATE || quantise == FCVSR_QUANT_ROUND, "quantise: FCVSR_QUANT_TRUNCATE or _ROUND");
+  if (quantise == FCVSR_QUANT_TRUNCATE)
+    return tail_fused_launch<FCVSR_QUANT_TRUNCATE, 2>(u1, w2, b2, slope, wl, bl, B, H2, W2, nullptr, out, stream, centre, tab);
+  return tail_fused_launch<FCVSR_QUANT_ROUND, 2>(u1, w2, b2, slope, wl, bl, B, H2, W2, nullptr, out, stream, centre, tab);
 }
 
 extern "C" int fcvsr_tail_fused_u8(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,

@@ -495,27 +495,57 @@ class Engine:
         check(L.fcvsr_irfft2_bands(spec.data_ptr(), 2 * n, 0, n, B, H, W, n, masks.data_ptr(), Q, work.data_ptr(), bvs, st),
               "fcvsr_irfft2_bands")
         freq = [bands[Q - 1 - i] for i in range(Q)]               # 'l2h' => reversed band list (:2204-2205)
-        s_f = self._new(dev, B, H, W, n)
         s_o = self._new(dev, B, H, W, n)
         nblk = (H * W + 255) // 256
         scratch = self._new(dev, 2 * B * nblk * n)
         sums = self._new(dev, 2, B, n)
         inv_hw = 1.0 / (H * W)
         mean_sum = self._channel_sum(freq[0])
-        # reduce(0); then per band: gates from the current sums, apply fused with the reduction the NEXT step needs (the
-        # next band's e1/e2 sums, or the channel sums of s_o for the final CALayer) - s_f, s_o make one round trip per band
         ab = [(par[f"MFFRblock.DivEnh_block.{i}.a"], par[f"MFFRblock.DivEnh_block.{i}.b"]) for i in range(Q)]
-        check(L.fcvsr_divenh(0, 1, freq[0].data_ptr(), s_f.data_ptr(), s_o.data_ptr(), ab[0][0].data_ptr(),
-                             ab[0][1].data_ptr(), mean_sum.data_ptr(), inv_hw, None, None, sums.data_ptr(),
+        # fcvsr_divenh_stage: the running sums are replayed in registers from the bands (16-byte accesses: n % 4 == 0
+        # and 16-byte-aligned tensors; anything else takes one band per pass)
+        staged = n % 4 == 0 and 256 % (n // 4) == 0 and all(f.data_ptr() % 16 == 0 for f in freq)
+        # s_f exists only as a checkpoint (Q > 4) or for the one-band-per-pass fallback
+        s_f = self._new(dev, B, H, W, n) if (Q > 4 or not staged) else None
+        # (reduce mode of the first band reads neither running sum: where s_f does not exist s_o stands in for the non-NULL check)
+        check(L.fcvsr_divenh(0, 1, freq[0].data_ptr(), (s_f if s_f is not None else s_o).data_ptr(), s_o.data_ptr(),
+                             ab[0][0].data_ptr(), ab[0][1].data_ptr(), mean_sum.data_ptr(), inv_hw, None, None, sums.data_ptr(),
                              scratch.data_ptr(), scratch.numel(), B, H, W, n, st), "fcvsr_divenh(reduce)")
+        gates = []                                                # (g1, g2) of every band: the replay needs the earlier ones
+        j0 = 0                                                    # first band the stages replay (bands < j0: the checkpoint)
         for i in range(Q):
             pre = f"MFFRblock.DivEnh_block.{i}"
             a, b = ab[i]
             first = 1 if i == 0 else 0
             g1 = self._ca_gate(sums[0], inv_hw, pre + ".ca", B, n)
             g2 = self._ca_gate(sums[1], inv_hw, pre + ".ca", B, n) if i > 0 else None
+            gates.append((g1, g2))
             sums = self._new(dev, 2, B, n)                        # the gates above were computed from the previous buffer
             nxt = i + 1 < Q
+            if staged:
+                # per stage: read bands j0..i (+ the checkpoint, + band i+1), write only the partial sums; the last band stores
+                # s_o, and every fourth band of a longer chain stores s_f, s_o as the checkpoint the next four replay from
+                sa = hip.DivEnhStageArgs()
+                if j0 > 0:
+                    sa.ck_s_f, sa.ck_s_o = s_f.data_ptr(), s_o.data_ptr()
+                for k, j in enumerate(range(j0, i + 1)):
+                    sa.f[k], sa.a[k], sa.b[k] = freq[j].data_ptr(), ab[j][0].data_ptr(), ab[j][1].data_ptr()
+                    sa.g1[k], sa.g2[k] = gates[j][0].data_ptr(), ptr(gates[j][1])
+                sa.mean_f_sum = mean_sum.data_ptr()
+                if nxt:
+                    sa.f_next, sa.a_next, sa.b_next = freq[i + 1].data_ptr(), ab[i + 1][0].data_ptr(), ab[i + 1][1].data_ptr()
+                ckpt = nxt and i - j0 == 3
+                if ckpt:
+                    sa.out_s_f = s_f.data_ptr()
+                if ckpt or not nxt:
+                    sa.out_s_o = s_o.data_ptr()
+                sa.sums, sa.scratch, sa.scratch_elems = sums.data_ptr(), scratch.data_ptr(), scratch.numel()
+                sa.inv_hw, sa.n_bands, sa.B, sa.H, sa.W, sa.C = inv_hw, i - j0 + 1, B, H, W, n
+                check(L.fcvsr_divenh_stage(C.byref(sa), st), "fcvsr_divenh_stage")
+                if ckpt:
+                    j0 = i + 1
+                continue
+            # one band per pass: s_f, s_o make one round trip per band (apply fused with the reduction the NEXT step needs)
             check(L.fcvsr_divenh_apply_next(first, freq[i].data_ptr(), s_f.data_ptr(), s_o.data_ptr(), a.data_ptr(),
                                             b.data_ptr(), mean_sum.data_ptr(), inv_hw, g1.data_ptr(), ptr(g2),
                                             freq[i + 1].data_ptr() if nxt else None,
@@ -885,19 +915,23 @@ class Engine:
         self._conv("upconv1", [fz], u1, act=ACT_PRELU, slope_t=a_t, ps=True)
         if out is None:                                           # NCHW boundary tensor
             out = self._new(dev, B, Cimg, 4 * H, 4 * W, dtype=torch.float32 if quant is None else torch.uint8)
-        # uint8 result: the f32 base and, where the last layer has no uint8 variant, the f32 result live in a scratch
-        res = out if quant is None else self._new(dev, B, Cimg, 4 * H, 4 * W)
+        fuse_tail = (self.precision != "f32" and n == 64 and Cimg == 1 and self._par["upconv2.weight"].shape[-1] == 1
+                     and m.fuse_tail)
+        # the fused tail evaluates the base skip itself from the centre frame (f32 frames -> f32 result, uint8 -> uint8): no base
+        # pass, and the uint8 result needs no f32 scratch
+        base_in_tail = fuse_tail and (x.dtype == torch.uint8) == (quant is not None)
+        # uint8 result otherwise: the f32 base and, where the last layer has no uint8 variant, the f32 result live in a scratch
+        res = out if (quant is None or base_in_tail) else self._new(dev, B, Cimg, 4 * H, 4 * W)
         out_v = res.permute(0, 2, 3, 1)
         centre = x[:, T // 2].permute(0, 2, 3, 1)                 # (B,H,W,Cimg) view of the centre LR frame
         cv, ov = view(centre), view(out_v)
         qv = view(out.permute(0, 2, 3, 1)) if quant is not None else None
-        if x.dtype == torch.uint8:
-            check(L.fcvsr_bilinear_up4_u8(C.byref(cv), hip.u8_table(dev).data_ptr(), B, H, W, C.byref(ov), st),
-                  "fcvsr_bilinear_up4_u8")
-        else:
-            check(L.fcvsr_bilinear_up4(C.byref(cv), B, H, W, C.byref(ov), st), "fcvsr_bilinear_up4")
-        fuse_tail = (self.precision != "f32" and n == 64 and Cimg == 1 and self._par["upconv2.weight"].shape[-1] == 1
-                     and m.fuse_tail)
+        if not base_in_tail:
+            if x.dtype == torch.uint8:
+                check(L.fcvsr_bilinear_up4_u8(C.byref(cv), hip.u8_table(dev).data_ptr(), B, H, W, C.byref(ov), st),
+                      "fcvsr_bilinear_up4_u8")
+            else:
+                check(L.fcvsr_bilinear_up4(C.byref(cv), B, H, W, C.byref(ov), st), "fcvsr_bilinear_up4")
         if fuse_tail:
             # upconv2 (1x1) + PixelShuffle + PReLU + conv_last0 in one kernel: the 64-channel tensor at 4H x 4W is never stored
             dt = self._adt()
@@ -905,7 +939,14 @@ class Engine:
             wl = self._tap_weights("conv_last0", dt)
             bl = self._par.get("conv_last0.bias")
             u1v = view(u1)
-            if quant is None:
+            if base_in_tail and quant is None:
+                check(L.fcvsr_tail_fused_base(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl),
+                                              C.byref(cv), B, 2 * H, 2 * W, C.byref(ov), st), "fcvsr_tail_fused_base")
+            elif base_in_tail:
+                check(L.fcvsr_tail_fused_base_u8(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl),
+                                                 C.byref(cv), hip.u8_table(dev).data_ptr(), B, 2 * H, 2 * W, C.byref(qv), quant,
+                                                 st), "fcvsr_tail_fused_base_u8")
+            elif quant is None:
                 check(L.fcvsr_tail_fused(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B,
                                          2 * H, 2 * W, C.byref(ov), st), "fcvsr_tail_fused")
             else:

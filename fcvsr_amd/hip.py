@@ -50,6 +50,16 @@ class RcbTailArgs(C.Structure):
                 ("W", C.c_int32)]
 
 
+class DivEnhStageArgs(C.Structure):
+    """fcvsr_divenh_stage_args: one stage of the DivEnh chain (bands j0..i replayed in registers, see include/fcvsr_hip.h)."""
+    _fields_ = [("ck_s_f", C.c_void_p), ("ck_s_o", C.c_void_p), ("f", C.c_void_p * 4), ("a", C.c_void_p * 4),
+                ("b", C.c_void_p * 4), ("g1", C.c_void_p * 4), ("g2", C.c_void_p * 4), ("mean_f_sum", C.c_void_p),
+                ("f_next", C.c_void_p), ("a_next", C.c_void_p), ("b_next", C.c_void_p), ("out_s_f", C.c_void_p),
+                ("out_s_o", C.c_void_p), ("sums", C.c_void_p), ("scratch", C.c_void_p), ("scratch_elems", C.c_int64),
+                ("inv_hw", C.c_float), ("n_bands", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("C", C.c_int32)]
+
+
 class CropDesc(C.Structure):
     """fcvsr_crop_desc: one output plane of fcvsr_clip_batch_u8 (``numpy.dtype(CropDesc)`` is its array form)."""
     _fields_ = [("src", C.c_void_p), ("pitch", C.c_int32), ("top", C.c_int32), ("left", C.c_int32), ("flags", C.c_int32)]
@@ -118,6 +128,7 @@ SIGNATURES = {
     "fcvsr_iac_step2_fused": [_PV, _PV, _PV, _VP, _VP, _PV, _F, _I, _I, _I, _PV, _VP],
     "fcvsr_divenh": [_I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, _I, _VP],
     "fcvsr_divenh_apply_next": [_I, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I, _I, _I, _I, _VP],
+    "fcvsr_divenh_stage": [C.POINTER(DivEnhStageArgs), _VP],
     "fcvsr_scale_add": [_VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, _VP],
     "fcvsr_gc_context": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _I64, _VP],
     "fcvsr_gc_finish": [_VP, _I, _VP, _VP, _I, _I, _VP, _VP],
@@ -133,6 +144,7 @@ SIGNATURES = {
     "fcvsr_pixel_shuffle16": [_VP, _PV, _I, _I, _I, _I, _VP],
     "fcvsr_bilinear_up4": [_PV, _I, _I, _I, _PV, _VP],
     "fcvsr_tail_fused": [_PV, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _PV, _VP],
+    "fcvsr_tail_fused_base": [_PV, _VP, _VP, _VP, _VP, _VP, _PV, _I, _I, _I, _PV, _VP],
     "fcvsr_conv_last": [_PV, _VP, _VP, _I, _I, _I, _I, _PV, _VP],
     "fcvsr_pack_weight_mfma": [_VP, _I, _I, _I, _I, _VP, _I, _I, _I, _I, _VP],
     "fcvsr_pack_weights_multi_block_elems": [],
@@ -168,6 +180,7 @@ SIGNATURES = {
     "fcvsr_feat_extract_u8": [_PV, _VP, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _VP],
     "fcvsr_bilinear_up4_u8": [_PV, _VP, _I, _I, _I, _PV, _VP],
     "fcvsr_tail_fused_u8": [_PV, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _PV, _PV, _I, _VP],
+    "fcvsr_tail_fused_base_u8": [_PV, _VP, _VP, _VP, _VP, _VP, _PV, _VP, _I, _I, _I, _PV, _I, _VP],
     "fcvsr_conv_last_u8": [_PV, _VP, _VP, _I, _I, _I, _I, _PV, _PV, _I, _VP],
     "fcvsr_u8_to_f32": [_VP, _VP, C.c_longlong, _VP, _VP],
     "fcvsr_quantise_u8": [_VP, C.c_longlong, _I, _VP, _VP],

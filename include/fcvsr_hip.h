@@ -316,6 +316,38 @@ int fcvsr_divenh_apply_next(int first, const float* f, float* s_f, float* s_o, c
                             const float* mean_f_sum, float inv_hw, const float* g1, const float* g2,
                             const float* f_next, const float* a_next, const float* b_next, float* sums,
                             float* scratch, int64_t scratch_elems, int B, int H, int W, int C, void* stream);
+/* One stage of the DivEnh chain without the round trip of the running sums: s_f, s_o are a pointwise recurrence over the
+ * bands (s_f_j = s_f_{j-1} + f_j, s_o_j = s_o_{j-1} + e1_j*g1_j + e2_j*g2_j), so the stage for band i replays bands j0..i in
+ * registers from the bands themselves (n_bands = i - j0 + 1 <= 4, with the arithmetic of fcvsr_divenh_apply_next) and then
+ * accumulates the reduction the next step needs, in fcvsr_divenh_apply_next's partition and order: sums[2][B][C] has the bits
+ * the chain of fcvsr_divenh_apply_next calls gives.
+ *   ck_s_f, ck_s_o: the running sums after band j0-1 (both NULL: j0 == 0, band f[0] is the first band and g2[0] is not read);
+ *   f[k], a[k], b[k], g1[k], g2[k]: band j0+k, its parameters [C] and its gates [B][C];
+ *   f_next, a_next, b_next: band i+1 (sums = its e1, e2 sums), or all NULL (sums[0] = channel sums of s_o_i, sums[1] = 0);
+ *   out_s_f, out_s_o: where s_f_i / s_o_i are stored, each may be NULL (nothing but the partial sums is written then).
+ * C % 4 == 0, 256 % (C/4) == 0, every tensor dense NHWC (B,H,W,C) f32 and 16-byte aligned; scratch >= 2*B*ceil(H*W/256)*C
+ * floats.  Other shapes: FCVSR_E_ARG (callers use fcvsr_divenh_apply_next there). */
+typedef struct {
+  const float* ck_s_f;
+  const float* ck_s_o;
+  const float* f[4];
+  const float* a[4];
+  const float* b[4];
+  const float* g1[4];
+  const float* g2[4];
+  const float* mean_f_sum;  /* [B][C] sums of the first band (read when j0 == 0) */
+  const float* f_next;
+  const float* a_next;
+  const float* b_next;
+  float*       out_s_f;
+  float*       out_s_o;
+  float*       sums;
+  float*       scratch;
+  int64_t      scratch_elems;
+  float        inv_hw;
+  int32_t      n_bands, B, H, W, C;
+} fcvsr_divenh_stage_args;
+int fcvsr_divenh_stage(const fcvsr_divenh_stage_args* a, void* stream);
 /* out = z*gate[b][c] + x   (final CALayer of MFFR, :2229-2230); x read as x_dtype, out stored as out_dtype */
 int fcvsr_scale_add(const float* z, const float* gate, const void* x, int x_dtype, void* out, int out_dtype, int B, int H,
                     int W, int C, void* stream);
@@ -434,6 +466,10 @@ int fcvsr_bilinear_up4(const fcvsr_view* src, int B, int H, int W, const fcvsr_v
  * holds the bilinear base skip).  The (B,2*H2,2*W2,64) intermediate is never stored. */
 int fcvsr_tail_fused(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
                      const float* bl, int B, int H2, int W2, const fcvsr_view* out, void* stream);
+/* The same with the bilinear x4 base skip (:2644) evaluated inside the kernel from the centre LR frame, centre (B,H2/2,W2/2,1)
+ * f32 (any strides), H2 and W2 even: out is only written, with the bits of fcvsr_bilinear_up4 followed by fcvsr_tail_fused. */
+int fcvsr_tail_fused_base(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                          const float* bl, const fcvsr_view* centre, int B, int H2, int W2, const fcvsr_view* out, void* stream);
 /* conv_last0 alone (:2607 / :2683; the RGB twins' 3-channel variant): out += bias + conv3x3(u), u (B,H,W,64) dense 16-bit at the
  * OUTPUT resolution, out a (B,H,W,C) f32 view (any strides: the NCHW result), C = 1..3.  w: [16 (C = 1) or 32][64] in u's dtype,
  * row tap*C + c (tap = ky*3 + kx), zero rows past 9C.  Used where fcvsr_tail_fused does not apply (3x3 up-convs). */
@@ -473,6 +509,11 @@ int fcvsr_bilinear_up4_u8(const fcvsr_view* src, const float* tab, int B, int H,
 int fcvsr_tail_fused_u8(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
                         const float* bl, int B, int H2, int W2, const fcvsr_view* base, const fcvsr_view* out, int quantise,
                         void* stream);
+/* uint8 frames in, uint8 result, no f32 base at all: centre (B,H2/2,W2/2,1) uint8 is the centre LR frame, read through tab; out
+ * gets the bytes of fcvsr_bilinear_up4_u8 followed by fcvsr_tail_fused_u8. */
+int fcvsr_tail_fused_base_u8(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                             const float* bl, const fcvsr_view* centre, const float* tab, int B, int H2, int W2,
+                             const fcvsr_view* out, int quantise, void* stream);
 /* conv_last0 with a uint8 result: base (B,H,W,C) f32 view (the bilinear base, only read), out (B,H,W,C) uint8 view. */
 int fcvsr_conv_last_u8(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C, const fcvsr_view* base,
                        const fcvsr_view* out, int quantise, void* stream);
