@@ -24,48 +24,13 @@
 // issues v_mfma_f32_16x16x32 over 32 channels where these kernels chain two 32x32x16 over 16 each, and on gfx950 the two give the
 // same bits (measured on random data, every case of those tests), so these kernels keep the 32x32x16 shape.
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 #include "mfma_util.h"
+#include "conv_plan.h"
 #include "conv_res.h"
 
 namespace fcvsr {
-
-// tile rows (one per wave: 4-row tiles leave room for more co-resident workgroups in different phases; 8-row tiles measured
-// 0.85-1.0x), tile cols, channel chunk, padded LDS row (halfwords)
-constexpr int kTH = 4, kTW = 32, kCK = 64, kLD = kCK + 8;
-
-struct MGroup {
-  View src[3];
-  View res[2];
-  View dst;
-  float* gc_partial;   // [B][tiles_per_image*4][cout+2] (nullptr = off)
-  int B, H, W;         // spatial size (stride-1 "same" conv: output size == input size)
-  int tiles_x, tiles_y;
-  int tile_begin;      // first flattened tile id of this group
-};
-
-struct MfmaArgs {
-  int n_groups;
-  MGroup g[3];
-  int n_src, n_res;
-  int seg_c[3];        // channels per source segment
-  int cin_total, cin16, cin_pad, cout, cout_pad, n_nblk;
-  const uint16_t* w;   // [taps][cout_pad][cin_pad]
-  const float* bias;
-  int act;
-  float slope;
-  const float* slope_ptr;
-  float rs[2];
-  int ps;
-  int flat;            // 1x1: treat pixels as a flat list of B*H*W
-  int src16, dst16;    // sources / destination stored in the MFMA dtype (16-bit) instead of f32
-  int dstbf;           // the 16-bit destination format is bf16 (generic kernel: may differ from the MFMA dtype)
-  int res16;           // residual inputs stored in the MFMA dtype (lean 3x3 kernel only: 16-bit trunk)
-  int gc16;            // lean 3x3 kernel with ContextBlock fusion: the 4-couts-per-lane epilogue stores the MFMA dtype (8 bytes)
-  const float* gc_wmask;   // ContextBlock fusion: per-wave online-softmax partials of the output (cout <= 64, 3x3)
-  int planar;          // single f32 source with arbitrary channel stride (the NCHW frames of feat_extract), cin <= 64
-  int sub2;            // stride-2 convolution: evaluate at full resolution, keep the even output pixels only
-};
 
 struct EpiCtx {
   int act, n_res, ps, flat, H, W, b, dst16, dstbf, sub2, cq4;   // dstbf: 16-bit destination is bf16 (may differ from the MFMA dtype)   // cq4 = cout/4 (pixel-shuffle: couts are ordered sub-pixel-major)
@@ -1372,104 +1337,112 @@ __global__ __launch_bounds__(256, 2) void conv1ps_res_kernel(MfmaArgs a, int nro
 template <bool BF16>
 static hipError_t launch_conv1ps_res(const MfmaArgs& a, int nrows, hipStream_t st) {
   int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static DevOnce attr;
+  const hipError_t e = once_per_device(attr, [&] {
+    return hipFuncSetAttribute((const void*)conv1ps_res_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv1ps_res_lds(256));
+  }, &dev);
   if (e != hipSuccess) return e;
   const int cus = device_cu_count(dev);
   int grid = (nrows + 3) / 4;
   const int cap = 2 * (cus > 0 ? cus : 256);
   if (grid > cap) grid = cap;
-  static DevOnce attr;
-  e = once_per_device(attr, [&] {
-    return hipFuncSetAttribute((const void*)conv1ps_res_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv1ps_res_lds(256));
-  });
-  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((conv1ps_res_kernel<BF16>), dim3(grid), dim3(256), conv1ps_res_lds(a.cout), st, a, nrows);
   return hipGetLastError();
 }
 
-template <bool BF16, bool SRC16, bool DST16>
-static hipError_t launch_lean_s2(const MfmaArgs& a, int total_tiles, hipStream_t st) {
-  const size_t lds = ((size_t)5 * 2 * 33 * kLD + (size_t)64 * kLD) * sizeof(uint16_t);     // > the 18,432-byte transpose area
-  hipLaunchKernelGGL((conv3s2_lean_kernel<BF16, SRC16, DST16>), dim3(total_tiles * a.n_nblk), dim3(256), lds, st, a);
+// Dynamic LDS of a tile kernel: the staged input tile of `pixels` and NT weight rows (kLD halfwords each), or the epilogue's
+// transpose area of `epi_rows` rows of floats (the ContextBlock partials are 4 of 132) where that is larger
+constexpr size_t tile_lds(int pixels, int nt, int epi_rows) {
+  const size_t lds = (size_t)(pixels + nt) * kLD * sizeof(uint16_t), epi = (size_t)epi_rows * ((nt >= 64 ? 64 : 32) + 4) * sizeof(float);
+  return lds < epi ? epi : lds;
+}
+
+// one workgroup per pixel tile and cout block; `attr` (one per kernel instantiation that needs it) raises the dynamic-LDS limit once
+template <class K>
+static hipError_t launch_tiles(K kernel, DevOnce* attr, size_t lds, const MfmaArgs& a, int total_tiles, hipStream_t st) {
+  if (attr) {
+    const hipError_t e = once_per_device(*attr, [&] { return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(total_tiles * a.n_nblk), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
-template <bool BF16>
-static hipError_t dispatch_lean_s2(const MfmaArgs& a, int total_tiles, hipStream_t st) {
-  if (a.src16) return a.dst16 ? launch_lean_s2<BF16, true, true>(a, total_tiles, st) : launch_lean_s2<BF16, true, false>(a, total_tiles, st);
-  return a.dst16 ? launch_lean_s2<BF16, false, true>(a, total_tiles, st) : launch_lean_s2<BF16, false, false>(a, total_tiles, st);
+template <bool BF16, bool SRC16, bool DST16>
+static hipError_t launch_lean_s2(const MfmaArgs& a, int total_tiles, hipStream_t st) {      // 5 x 2 x 33 polyphase halo pixels: > the 18,432-byte transpose area
+  return launch_tiles(conv3s2_lean_kernel<BF16, SRC16, DST16>, nullptr, tile_lds(5 * 2 * 33, 64, 0), a, total_tiles, st);
 }
-
 template <bool BF16, int NT, bool SRC16, bool DST16, bool PS>
 static hipError_t launch_lean1(const MfmaArgs& a, int total_tiles, hipStream_t st) {
-  size_t lds = ((size_t)128 * kLD + (size_t)NT * kLD) * sizeof(uint16_t);
-  const size_t epi = 4ull * 32 * ((NT >= 64 ? 64 : 32) + 4) * sizeof(float);
-  if (lds < epi) lds = epi;
-  hipLaunchKernelGGL((conv1_lean_kernel<BF16, NT, SRC16, DST16, PS>), dim3(total_tiles * a.n_nblk), dim3(256), lds, st, a);
-  return hipGetLastError();
+  return launch_tiles(conv1_lean_kernel<BF16, NT, SRC16, DST16, PS>, nullptr, tile_lds(128, NT, 4 * 32), a, total_tiles, st);
 }
-
-template <bool BF16>
-static hipError_t dispatch_lean1(const MfmaArgs& a, int nt, int total_tiles, hipStream_t st) {
-#define FCVSR_L1(NTV, PSV)                                                                                      \
-  (a.src16 ? (a.dst16 ? launch_lean1<BF16, NTV, true, true, PSV>(a, total_tiles, st)                              \
-                      : launch_lean1<BF16, NTV, true, false, PSV>(a, total_tiles, st))                            \
-           : (a.dst16 ? launch_lean1<BF16, NTV, false, true, PSV>(a, total_tiles, st)                             \
-                      : launch_lean1<BF16, NTV, false, false, PSV>(a, total_tiles, st)))
-  if (a.ps) return nt == 64 ? FCVSR_L1(64, true) : FCVSR_L1(32, true);
-  return nt == 64 ? FCVSR_L1(64, false) : FCVSR_L1(32, false);
-#undef FCVSR_L1
-}
-
 template <bool BF16, int NT, bool SRC16, bool DST16>
 static hipError_t launch_lean(const MfmaArgs& a, int total_tiles, hipStream_t st) {
-  size_t lds = ((size_t)6 * (kTW + 2) * kLD + (size_t)NT * kLD) * sizeof(uint16_t);
-  const size_t epi = (4ull * 32 + 4) * ((NT >= 64 ? 64 : 32) + 4) * sizeof(float);
-  if (lds < epi) lds = epi;
   static DevOnce attr;
-  hipError_t e = once_per_device(attr, [&] {
-    return hipFuncSetAttribute((const void*)conv3_lean_kernel<BF16, NT, SRC16, DST16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((conv3_lean_kernel<BF16, NT, SRC16, DST16>), dim3(total_tiles * a.n_nblk), dim3(256), lds, st, a);
-  return hipGetLastError();
+  return launch_tiles(conv3_lean_kernel<BF16, NT, SRC16, DST16>, &attr, tile_lds(6 * (kTW + 2), NT, 4 * 32 + 4), a, total_tiles, st);
 }
-
-template <bool BF16>
-static hipError_t dispatch_lean(const MfmaArgs& a, int nt, int total_tiles, hipStream_t st) {
-#define FCVSR_LEAN(NTV)                                                                                       \
-  (a.src16 ? (a.dst16 ? launch_lean<BF16, NTV, true, true>(a, total_tiles, st)                                  \
-                      : launch_lean<BF16, NTV, true, false>(a, total_tiles, st))                                \
-           : (a.dst16 ? launch_lean<BF16, NTV, false, true>(a, total_tiles, st)                                 \
-                      : launch_lean<BF16, NTV, false, false>(a, total_tiles, st)))
-  if (nt == 64) return FCVSR_LEAN(64);     // (the 128-cout tile measured 0.65x and spilled: no longer built)
-  return FCVSR_LEAN(32);
-#undef FCVSR_LEAN
-}
-
 template <bool BF16, int NT, int KS>
 static hipError_t launch_mfma(const MfmaArgs& a, int total_tiles, hipStream_t st) {
-  constexpr int PAD = KS / 2;
-  size_t lds = ((size_t)(kTH + 2 * PAD) * (kTW + 2 * PAD) * kLD + (size_t)NT * kLD) * sizeof(uint16_t);
-  const size_t epi = (4ull * 32 + 4) * ((NT >= 64 ? 64 : 32) + 4) * sizeof(float);   // epilogue transpose + GC partial areas
-  if (lds < epi) lds = epi;
   static DevOnce attr;
-  hipError_t e = once_per_device(attr, [&] {
-    return hipFuncSetAttribute((const void*)conv_mfma_kernel<BF16, NT, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((conv_mfma_kernel<BF16, NT, KS>), dim3(total_tiles * a.n_nblk), dim3(256), lds, st, a);
-  return hipGetLastError();
+  return launch_tiles(conv_mfma_kernel<BF16, NT, KS>, &attr, tile_lds((kTH + 2 * (KS / 2)) * (kTW + 2 * (KS / 2)), NT, 4 * 32 + 4), a, total_tiles, st);
 }
 
-template <bool BF16>
-static hipError_t dispatch(const MfmaArgs& a, int nt, int ks, int total_tiles, hipStream_t st) {
-  if (ks == 3) {
-    if (nt == 64) return launch_mfma<BF16, 64, 3>(a, total_tiles, st);
-    return launch_mfma<BF16, 32, 3>(a, total_tiles, st);
+// f(c0, c1, ...) with every runtime bool turned into a std::true_type / std::false_type argument: a generic lambda that names
+// a kernel's bool template arguments by them is instantiated once per combination
+template <class F> static hipError_t with_bools(F f) { return f(); }
+template <class F, class... Rest>
+static hipError_t with_bools(F f, bool b, Rest... rest) {
+  return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+           : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+// the resident-weight 3x3 kernel's argument block: its own 8 x 32 tiling of the same groups
+static ResArgs to_res_args(const MfmaArgs& a, const void* zeros) {
+  ResArgs wa;
+  wa.n_groups = a.n_groups; wa.total_tiles = 0;
+  for (int g = 0; g < 3; ++g) {
+    const MGroup& G = a.g[g < a.n_groups ? g : 0];
+    ResGroup& Wg = wa.g[g];
+    Wg.src = G.src[0]; Wg.res[0] = G.res[0]; Wg.res[1] = G.res[1]; Wg.dst = G.dst; Wg.gc_partial = nullptr; Wg.B = G.B; Wg.H = G.H; Wg.W = G.W;
+    Wg.tiles_x = cdiv(G.W, 32); Wg.tiles_y = cdiv(G.H, 8); Wg.tile_begin = wa.total_tiles;
+    if (g < a.n_groups) wa.total_tiles += G.B * Wg.tiles_x * Wg.tiles_y;
   }
-  if (nt == 64) return launch_mfma<BF16, 64, 1>(a, total_tiles, st);
-  return launch_mfma<BF16, 32, 1>(a, total_tiles, st);
+  wa.cin = a.cin_total; wa.cout = a.cout; wa.cout_pad = a.cout_pad; wa.cin_pad = a.cin_pad;
+  wa.w = a.w; wa.bias = a.bias; wa.act = a.act; wa.slope = a.slope; wa.slope_ptr = a.slope_ptr;
+  wa.rs[0] = a.rs[0]; wa.rs[1] = a.rs[1]; wa.n_res = a.n_res; wa.res16 = a.res16; wa.ps = a.ps; wa.zeros = zeros;
+  return wa;
+}
+
+// the one place a plan becomes a launch: each case instantiates its kernel for every value of the template arguments it names
+static hipError_t launch_plan(const ConvPlan& p, hipStream_t st) {
+  const MfmaArgs& a = p.args;
+  const int tiles = p.total_tiles;
+  const bool nt64 = p.nt == 64;        // (a 128-cout tile of the lean 3x3 kernel measured 0.65x and spilled: not built)
+  switch (p.path) {
+    case kGeneric:
+      return with_bools([&](auto bf) {
+        if (a.flat) return nt64 ? launch_mfma<bf(), 64, 1>(a, tiles, st) : launch_mfma<bf(), 32, 1>(a, tiles, st);
+        return nt64 ? launch_mfma<bf(), 64, 3>(a, tiles, st) : launch_mfma<bf(), 32, 3>(a, tiles, st);
+      }, p.bf16);
+    case kLean3:
+      return with_bools([&](auto bf, auto s16, auto d16) {
+        return nt64 ? launch_lean<bf(), 64, s16(), d16()>(a, tiles, st) : launch_lean<bf(), 32, s16(), d16()>(a, tiles, st);
+      }, p.bf16, a.src16 != 0, a.dst16 != 0);
+    case kLean3S2:
+      return with_bools([&](auto bf, auto s16, auto d16) { return launch_lean_s2<bf(), s16(), d16()>(a, tiles, st); }, p.bf16, a.src16 != 0, a.dst16 != 0);
+    case kLean1:
+      return with_bools([&](auto bf, auto s16, auto d16, auto ps) {
+        return nt64 ? launch_lean1<bf(), 64, s16(), d16(), ps()>(a, tiles, st) : launch_lean1<bf(), 32, s16(), d16(), ps()>(a, tiles, st);
+      }, p.bf16, a.src16 != 0, a.dst16 != 0, a.ps != 0);
+    case kRes1PS:      // rows of 32 pixels
+      return with_bools([&](auto bf) { return launch_conv1ps_res<bf()>(a, cdiv((long long)a.g[0].B * a.g[0].H * a.g[0].W, 32), st); }, p.bf16);
+    case kRes3: {
+      const void* zeros = nullptr;
+      const hipError_t e = conv3_res_zero_page(st, &zeros);
+      return e != hipSuccess ? e : launch_conv3_res(to_res_args(a, zeros), p.bf16, a.dst16 != 0, st);
+    }
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace fcvsr
@@ -1479,314 +1452,23 @@ using namespace fcvsr;
 // name of the kernel the last fcvsr_conv2d_mfma call of this thread launched (bench.py groups its per-launch timings by it)
 static thread_local char g_last_kernel[96] = "";
 extern "C" const char* fcvsr_last_conv_kernel(void) { return g_last_kernel; }
-#define FCVSR_NOTE_KERNEL(...) snprintf(g_last_kernel, sizeof(g_last_kernel), __VA_ARGS__)
-static const char* tf(int v) { return v ? "true" : "false"; }
 
-// channel-contiguous res/dst views are accessed 16 bytes at a time
-static bool vec_view_ok(const fcvsr_view& v) {
-  const int g = v.dtype == FCVSR_F32 ? 4 : 8;   // 16-byte granules for f32 quads, 8-byte for 16-bit quads (keep 16 for safety)
-  return v.sc != 1 || v.c < 4 || (v.sx % 4 == 0 && v.sy % 4 == 0 && v.sb % 4 == 0 && ((uintptr_t)v.ptr % (g == 4 ? 16 : 8)) == 0);
+// The seam tests and benchmarks select a path through, read here and nowhere else.  FCVSR_MFMA_LEAN: 0 = no lean kernel, anything else
+// or unset = allowed.  FCVSR_MFMA_RES: 0 = no resident-weight kernel, another number = whenever eligible, unset = by size.
+static ConvPolicy policy_from_env() {
+  const char* lean = getenv("FCVSR_MFMA_LEAN");
+  const char* res = getenv("FCVSR_MFMA_RES");
+  return ConvPolicy{lean ? (atoi(lean) != 0 ? 1 : 0) : 1, res ? (atoi(res) != 0 ? 1 : 0) : 2};
 }
-
-// sources: f32 (converted while staging, 4 channels = 16 bytes per lane) or already in the MFMA dtype (8 channels per lane)
-static bool src_ok(const fcvsr_view& v, int mma_dtype) {
-  if (!v.ptr || v.sc != 1 || ((uintptr_t)v.ptr % 16) != 0) return false;
-  const int g = v.dtype == FCVSR_F32 ? 4 : 8;
-  if (v.dtype != FCVSR_F32 && v.dtype != mma_dtype) return false;
-  return v.c % g == 0 && v.sx % g == 0 && v.sy % g == 0 && v.sb % g == 0;
-}
-
-// the resident-weight kernel pays once a launch has this many workgroup-tiles (tiles x cout blocks): below it, the lean kernel
-static constexpr int kResMinTiles = 768;
 
 extern "C" int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int mma_dtype, void* stream) {
-  FCVSR_CHECK_ARG(descs != nullptr && n_groups >= 1 && n_groups <= 3, "1..3 problem groups");
-  FCVSR_CHECK_ARG(mma_dtype == FCVSR_BF16 || mma_dtype == FCVSR_F16, "mma_dtype must be BF16 or F16");
-  const fcvsr_conv_desc& d0 = descs[0];
-  FCVSR_CHECK_ARG(d0.kh == d0.kw && (d0.kh == 1 || d0.kh == 3) && d0.pad == d0.kh / 2 &&
-                      (d0.stride == 1 || (d0.stride == 2 && d0.kh == 3 && !d0.pixel_shuffle)),
-                  "MFMA path: 1x1 or 3x3 stride 1, or 3x3 stride 2, same padding");
-  FCVSR_CHECK_ARG(d0.n_src >= 1 && d0.n_src <= 3 && d0.n_res >= 0 && d0.n_res <= 2 && d0.cout > 0, "bad descriptor");
-  FCVSR_CHECK_ARG(d0.weight != nullptr && d0.cout_pad % 128 == 0 && d0.cout_pad >= d0.cout, "weight must be MFMA-packed");
-  FCVSR_CHECK_ARG(!(d0.act == FCVSR_ACT_PRELU) || d0.slope_ptr != nullptr, "PReLU needs slope_ptr");
-  FCVSR_CHECK_ARG(!d0.pixel_shuffle || d0.cout % 16 == 0, "pixel_shuffle needs cout%16==0 (sub-pixel-major packing)");
-  MfmaArgs a;
-  a.src16 = d0.src[0].dtype != FCVSR_F32;
-  a.res16 = (d0.n_res > 0 && d0.res[0].dtype != FCVSR_F32) ? 1 : 0;
-  a.sub2 = d0.stride == 2;
-  a.planar = (d0.n_src == 1 && d0.src[0].sc != 1) ? 1 : 0;
-  FCVSR_CHECK_ARG(!a.planar || (d0.src[0].dtype == FCVSR_F32 && d0.src[0].c <= 32 && d0.kh == 3),
-                  "planar (channel-strided) source: one f32 source with <= 32 channels, 3x3");
-  a.dst16 = d0.dst.dtype != FCVSR_F32;
-  a.gc16 = 0;
-  a.dstbf = d0.dst.dtype == FCVSR_BF16;
-  const bool dst_native = d0.dst.dtype == FCVSR_F32 || d0.dst.dtype == mma_dtype;   // lean kernels store f32 / MFMA dtype only
-  a.n_groups = n_groups;
-  a.n_src = d0.n_src;
-  a.n_res = d0.n_res;
-  int cin = 0;
-  for (int s = 0; s < 3; ++s) {
-    a.seg_c[s] = s < d0.n_src ? d0.src[s].c : (1 << 30);
-    if (s < d0.n_src) cin += d0.src[s].c;
-  }
-  a.cin_total = cin;
-  a.cin16 = (cin + 15) / 16 * 16;
-  a.cin_pad = (cin + 63) / 64 * 64;   // packer pads cin to a multiple of 64 (16-byte weight loads stay in bounds)
-  a.cout = d0.cout;
-  a.cout_pad = d0.cout_pad;
-  // N tile: measured faster with <= 64 couts per workgroup (register pressure of 128-cout accumulators costs more than
-  // re-staging the input tile for the second N-block)
-  const int nt = d0.cout > 32 ? 64 : 32;
-  a.n_nblk = (d0.cout + nt - 1) / nt;
-  a.w = (const uint16_t*)d0.weight;
-  a.bias = d0.bias;
-  a.act = d0.act;
-  a.slope = d0.slope;
-  a.slope_ptr = d0.slope_ptr;
-  a.rs[0] = d0.res_scale[0];
-  a.rs[1] = d0.res_scale[1];
-  a.ps = d0.pixel_shuffle;
-  a.flat = d0.kh == 1 ? 1 : 0;
-  a.gc_wmask = d0.gc_wmask;
-  FCVSR_CHECK_ARG(d0.gc_wmask == nullptr || (d0.kh == 3 && d0.stride == 1 && d0.cout <= 64 && !d0.pixel_shuffle &&
-                                             ((uintptr_t)d0.gc_wmask % 16) == 0),
-                  "ContextBlock fusion: 3x3 stride-1 layer with cout <= 64");
-  int tiles = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    const fcvsr_conv_desc& d = descs[g];
-    FCVSR_CHECK_ARG(d.kh == d0.kh && d.kw == d0.kw && d.stride == d0.stride && d.n_src == d0.n_src && d.n_res == d0.n_res &&
-                        d.cout == d0.cout && d.weight == d0.weight && d.bias == d0.bias && d.act == d0.act &&
-                        d.pixel_shuffle == d0.pixel_shuffle,
-                    "groups must share weights and epilogue");
-    FCVSR_CHECK_ARG(d.B > 0 && d.H > 0 && d.W > 0, "empty problem");
-    MGroup& G = a.g[g];
-    for (int s = 0; s < d.n_src; ++s) {
-      FCVSR_CHECK_ARG((a.planar ? (d.src[s].ptr != nullptr && d.src[s].sc != 1) : src_ok(d.src[s], mma_dtype)) &&
-                          d.src[s].c == d0.src[s].c && d.src[s].dtype == d0.src[0].dtype,
-                      "src: f32 or MFMA dtype (all alike), channel-contiguous, 16-byte aligned, c%4==0 (f32) / c%8==0 (16-bit)");
-      G.src[s] = to_view(d.src[s]);
-      if (a.flat)
-        FCVSR_CHECK_ARG(d.src[s].sy == d.src[s].sx * d.W && d.src[s].sb == d.src[s].sy * d.H, "1x1 needs uniformly strided pixels");
-    }
-    for (int q = 0; q < d.n_res; ++q) {
-      FCVSR_CHECK_ARG(d.res[q].ptr && (d.res[q].dtype == FCVSR_F32 || d.res[q].dtype == mma_dtype) &&
-                          d.res[q].dtype == d0.res[0].dtype && vec_view_ok(d.res[q]),
-                      "res must be f32 or the MFMA dtype (all alike), vector-aligned");
-      G.res[q] = to_view(d.res[q]);
-      if (a.flat)
-        FCVSR_CHECK_ARG(d.res[q].sy == d.res[q].sx * d.W && d.res[q].sb == d.res[q].sy * d.H, "1x1 needs uniformly strided res");
-    }
-    FCVSR_CHECK_ARG(d.dst.ptr && (d.dst.dtype == FCVSR_F32 || d.dst.dtype == FCVSR_BF16 || d.dst.dtype == FCVSR_F16) &&
-                        d.dst.dtype == d0.dst.dtype && vec_view_ok(d.dst), "dst must be f32 / bf16 / f16, vector-aligned");
-    FCVSR_CHECK_ARG(d.bias == nullptr || ((uintptr_t)d.bias % 16) == 0, "bias must be 16-byte aligned");
-    G.dst = to_view(d.dst);
-    if (a.flat && !d.pixel_shuffle)
-      FCVSR_CHECK_ARG(d.dst.sy == d.dst.sx * d.W && d.dst.sb == d.dst.sy * d.H, "1x1 needs uniformly strided dst");
-    G.gc_partial = d.gc_partial;
-    FCVSR_CHECK_ARG((d.gc_wmask == nullptr) == (d.gc_partial == nullptr) && d.gc_wmask == d0.gc_wmask, "gc fields: all groups alike");
-    G.B = d.B; G.H = d.H; G.W = d.W;
-    G.tile_begin = tiles;
-    if (a.flat) {
-      G.tiles_x = 1; G.tiles_y = 1;
-      tiles += cdiv((long long)d.B * d.H * d.W, kTH * kTW);
-    } else {
-      G.tiles_x = cdiv(d.W, kTW);
-      G.tiles_y = cdiv(d.H, kTH);
-      tiles += d.B * G.tiles_x * G.tiles_y;
-    }
-  }
-  for (int g = n_groups; g < 3; ++g) a.g[g] = a.g[0];
-  hipStream_t st = (hipStream_t)stream;
-  // lean fast path: 3x3 stride 1, one dense source, cin multiple of 64, plain channel-contiguous destination and residuals
-  bool lean = dst_native && d0.kh == 3 && d0.stride == 1 && d0.n_src == 1 && !a.planar && !a.ps && (cin % 64 == 0) &&
-              (!a.dst16 || d0.cout % 8 == 0) && (d0.gc_wmask == nullptr || d0.cout % 4 == 0);
-  for (int g = 0; g < n_groups && lean; ++g) {
-    const fcvsr_conv_desc& d = descs[g];
-    long long ext = (long long)d.B * d.H * d.W * (long long)(d.src[0].sx > d.dst.sx ? d.src[0].sx : d.dst.sx);
-    if (d.dst.sc != 1) ext = (long long)d.B * d.dst.sb;                 // strided (e.g. NCHW) destination
-    lean = lean && (!a.dst16 || d.dst.sc == 1) && ext < (1ll << 29);
-    for (int q = 0; q < d.n_res; ++q)
-      lean = lean && (d.res[q].dtype == FCVSR_F32 || d.res[q].sc == 1) && (!a.dst16 || d.res[q].sc == 1);
-  }
-  if (d0.gc_wmask != nullptr && a.dst16) {
-    // ContextBlock partials come out of the 4-couts-per-lane epilogue: run that variant and let it store 16-bit values
-    bool ok16 = lean && dst_native && d0.n_res == 0 && d0.cout % 4 == 0;
-    for (int g = 0; g < n_groups; ++g) ok16 = ok16 && descs[g].dst.sc == 1;
-    FCVSR_CHECK_ARG(ok16, "ContextBlock fusion with a 16-bit destination needs the lean 3x3 path, no residuals");
-    a.gc16 = 1;
-    a.dst16 = 0;
-  }
-  FCVSR_CHECK_ARG(!a.res16 || lean, "16-bit residuals are only supported by the lean 3x3 path");
-  {
-    const char* e = getenv("FCVSR_MFMA_LEAN");
-    if (e && atoi(e) == 0) lean = false;
-  }
-  // lean 1x1 (flat) path: every source a multiple of 64 channels, channel-contiguous destination, f32 residuals;
-  // pixel shuffle only without residuals
-  bool lean1 = dst_native && d0.kh == 1 && (d0.cout % 8 == 0) && !a.planar;
-  for (int s2 = 0; s2 < d0.n_src && lean1; ++s2) lean1 = lean1 && (d0.src[s2].c % 64 == 0);
-  lean1 = lean1 && (!a.ps || (d0.n_res == 0 && (d0.cout / 4) % 8 == 0));
-  for (int g = 0; g < n_groups && lean1; ++g) {
-    const fcvsr_conv_desc& d = descs[g];
-    long long maxsx = d.dst.sx;
-    for (int s2 = 0; s2 < d.n_src; ++s2) maxsx = d.src[s2].sx > maxsx ? d.src[s2].sx : maxsx;
-    lean1 = lean1 && d.dst.sc == 1 && (long long)d.B * d.H * d.W * maxsx * 4 < (1ll << 31);
-    for (int q = 0; q < d.n_res; ++q)
-      lean1 = lean1 && d.res[q].sc == 1 && d.res[q].dtype == FCVSR_F32 && (long long)d.B * d.H * d.W * d.res[q].sx < (1ll << 31);
-  }
-  {
-    const char* e2 = getenv("FCVSR_MFMA_LEAN");
-    if (e2 && atoi(e2) == 0) lean1 = false;
-  }
-  hipError_t e;
-  // pixel-shuffle 1x1 up-convolution 64 -> cout (<= 256) with resident weights: one 16-bit source, 16-bit destination.
-  // FCVSR_MFMA_RES=0 leaves it to the lean 1x1 kernel (the tests' reference for it).
-  bool res1 = lean1 && a.ps && a.src16 && a.dst16 && n_groups == 1 && cin == 64 && d0.cout % 32 == 0 && d0.cout <= 256 &&
-              d0.dst.sx % 8 == 0 && d0.dst.sy % 8 == 0 && d0.dst.sb % 8 == 0 && ((uintptr_t)d0.dst.ptr % 16) == 0;
-  {
-    const char* e4 = getenv("FCVSR_MFMA_RES");
-    if (e4 && atoi(e4) == 0) res1 = false;
-  }
-  if (res1) {
-    FCVSR_NOTE_KERNEL("conv1ps_res_kernel<%s>", tf(mma_dtype == FCVSR_BF16));
-    const int nrows = (int)cdiv((long long)d0.B * d0.H * d0.W, 32);
-    e = (mma_dtype == FCVSR_BF16) ? launch_conv1ps_res<true>(a, nrows, st) : launch_conv1ps_res<false>(a, nrows, st);
-    if (e != hipSuccess) {
-      set_error("fcvsr_conv2d_mfma: launch failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    return 0;
-  }
-  // lean stride-2 3x3 path: one dense source of a multiple of 64 channels, cout a multiple of 64, channel-contiguous
-  // destination, no residuals.  Tiles are 2 x 32 pixels of the OUTPUT.
-  bool s2 = dst_native && d0.kh == 3 && d0.stride == 2 && d0.n_src == 1 && !a.planar && (cin % 64 == 0) && d0.cout % 64 == 0 &&
-            d0.n_res == 0 && d0.gc_wmask == nullptr;
-  for (int g = 0; g < n_groups && s2; ++g) {
-    const fcvsr_conv_desc& d = descs[g];
-    const int dg = a.dst16 ? 8 : 4;
-    s2 = s2 && d.dst.sc == 1 && d.dst.sx % dg == 0 && d.dst.sy % dg == 0 && d.dst.sb % dg == 0 && ((uintptr_t)d.dst.ptr % 16) == 0 &&
-         (long long)d.B * d.H * d.W * d.src[0].sx < (1ll << 29);
-  }
-  {
-    const char* e5 = getenv("FCVSR_MFMA_LEAN");
-    if (e5 && atoi(e5) == 0) s2 = false;
-  }
-  if (s2) {
-    MfmaArgs a2 = a;
-    a2.n_nblk = d0.cout / 64;
-    int t2 = 0;
-    for (int g = 0; g < n_groups; ++g) {
-      MGroup& G = a2.g[g];
-      G.tiles_x = cdiv((G.W + 1) / 2, kTW);
-      G.tiles_y = cdiv((G.H + 1) / 2, 2);
-      G.tile_begin = t2;
-      t2 += G.B * G.tiles_x * G.tiles_y;
-    }
-    for (int g = n_groups; g < 3; ++g) a2.g[g] = a2.g[0];
-    FCVSR_NOTE_KERNEL("conv3s2_lean_kernel<%s, %s, %s>", tf(mma_dtype == FCVSR_BF16), tf(a.src16), tf(a.dst16));
-    e = (mma_dtype == FCVSR_BF16) ? dispatch_lean_s2<true>(a2, t2, st) : dispatch_lean_s2<false>(a2, t2, st);
-    if (e != hipSuccess) {
-      set_error("fcvsr_conv2d_mfma: launch failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    return 0;
-  }
-  if (lean1) {
-    FCVSR_NOTE_KERNEL("conv1_lean_kernel<%s, %d, %s, %s, %s>", tf(mma_dtype == FCVSR_BF16), nt, tf(a.src16), tf(a.dst16), tf(a.ps));
-    e = (mma_dtype == FCVSR_BF16) ? dispatch_lean1<true>(a, nt, tiles, st) : dispatch_lean1<false>(a, nt, tiles, st);
-    if (e != hipSuccess) {
-      set_error("fcvsr_conv2d_mfma: launch failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    return 0;
-  }
-  // LDS-resident-weight persistent kernel (conv_res.hip): one dense 16-bit source of 64 or 128 channels, cout a multiple of
-  // 64, channel-contiguous 16-byte-aligned destination and residuals, no ContextBlock fusion.  It pays once every workgroup
-  // amortises its 72 KiB weight copy over a few 8 x 32 tiles; small launches stay on the lean kernel.
-  // Pixel-shuffled layers (the 3x3 up-convs of the full / RGB models, 64 -> 256) qualify too: with sub-pixel-major rows a
-  // 64-cout block is one sub-pixel, so PixelShuffle is only a different destination pixel (no residuals, 16-bit destination).
-  const bool res_ps = a.ps && dst_native && d0.kh == 3 && d0.stride == 1 && d0.n_src == 1 && !a.planar && cin == 64 &&
-                      d0.cout % 256 == 0 && d0.n_res == 0 && a.dst16 && a.src16 && d0.gc_wmask == nullptr;
-  bool res = (lean || res_ps) && a.src16 && conv3_res_supports(cin, d0.cout) && d0.gc_wmask == nullptr && d0.cout == d0.cout / 64 * 64;
-  int rtiles = 0;
-  for (int g = 0; g < n_groups && res; ++g) {
-    const fcvsr_conv_desc& d = descs[g];
-    const int dg = a.dst16 ? 8 : 4;
-    res = res && d.dst.sc == 1 && d.dst.sx % dg == 0 && d.dst.sy % dg == 0 && d.dst.sb % dg == 0 && ((uintptr_t)d.dst.ptr % 16) == 0;
-    res = res && d.src[0].sx % 8 == 0 && d.src[0].sy % 8 == 0 && d.src[0].sb % 8 == 0;
-    for (int q = 0; q < d.n_res; ++q) {
-      const int rg = d.res[q].dtype == FCVSR_F32 ? 4 : 8;
-      res = res && d.res[q].sc == 1 && d.res[q].sx % rg == 0 && d.res[q].sy % rg == 0 && d.res[q].sb % rg == 0 &&
-            ((uintptr_t)d.res[q].ptr % 16) == 0;
-    }
-    rtiles += conv3_res_tiles(d.B, d.H, d.W);
-    // (destination element offsets are formed in 32-bit arithmetic and widened before the byte scaling: < 2^30 elements keeps
-    // every intermediate positive; 16 clips of 720 x 1280 x 64 are 0.94 * 2^30)
-    if (res_ps) res = res && d.dst.c == d0.cout / 4 && (long long)d.B * d.dst.sb < (1ll << 30) && (long long)d.B * d.src[0].sb < (1ll << 29) &&
-                      d.src[0].sc == 1 && ((uintptr_t)d.src[0].ptr % 16) == 0;
-  }
-  {
-    // FCVSR_MFMA_RES: 0 never, 1 always (when eligible), unset: by size (kResMinTiles workgroup-tiles)
-    const char* e3 = getenv("FCVSR_MFMA_RES");
-    const int res_mode = e3 ? (atoi(e3) ? 1 : 0) : 2;
-    if (res_mode == 0 || (res_mode == 2 && rtiles * (cin == 64 ? d0.cout / 64 : d0.cout / 32) < kResMinTiles)) res = false;
-  }
-  if (res) {
-    // 256 zero bytes per DEVICE (the source of halo pixels outside the image), created on first use.  hipMalloc / hipMemset are
-    // not capturable: the engine runs every configuration eagerly before it captures a hipGraph, so this never happens inside
-    // a capture; a capture that does reach it fails loudly here rather than reading another device's page.
-    static void* zeros_dev[64] = {nullptr};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("fcvsr_conv2d_mfma: bad device index"); return FCVSR_E_ARG; }
-    if (!zeros_dev[dev]) {
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-        set_error("fcvsr_conv2d_mfma: first use on this device inside a stream capture (run the layer once eagerly first)");
-        return FCVSR_E_ARG;
-      }
-      void* z = nullptr;
-      hipError_t ez = hipMalloc(&z, 256);
-      if (ez == hipSuccess) ez = hipMemset(z, 0, 256);
-      if (ez != hipSuccess) {
-        set_error("fcvsr_conv2d_mfma: zero page allocation failed: %s", hipGetErrorString(ez));
-        return (int)ez;
-      }
-      zeros_dev[dev] = z;
-    }
-    void* zeros = zeros_dev[dev];
-    ResArgs wa;
-    wa.n_groups = n_groups;
-    int wtiles = 0;
-    for (int g = 0; g < 3; ++g) {
-      const MGroup& G = a.g[g < n_groups ? g : 0];
-      ResGroup& Wg = wa.g[g];
-      Wg.src = G.src[0]; Wg.res[0] = G.res[0]; Wg.res[1] = G.res[1]; Wg.dst = G.dst; Wg.gc_partial = nullptr;
-      Wg.B = G.B; Wg.H = G.H; Wg.W = G.W;
-      Wg.tiles_x = cdiv(G.W, 32);
-      Wg.tiles_y = cdiv(G.H, 8);
-      Wg.tile_begin = wtiles;
-      if (g < n_groups) wtiles += G.B * Wg.tiles_x * Wg.tiles_y;
-    }
-    wa.total_tiles = wtiles;
-    wa.cin = cin; wa.cout = d0.cout; wa.cout_pad = d0.cout_pad; wa.cin_pad = a.cin_pad;
-    wa.w = a.w; wa.bias = a.bias; wa.act = a.act; wa.slope = a.slope; wa.slope_ptr = a.slope_ptr;
-    wa.rs[0] = a.rs[0]; wa.rs[1] = a.rs[1]; wa.n_res = a.n_res; wa.res16 = a.res16; wa.ps = a.ps; wa.zeros = zeros;
-    FCVSR_NOTE_KERNEL("conv3_res_kernel<%s, %d, %d, %d>", tf(mma_dtype == FCVSR_BF16), !a.dst16 ? 0 : (a.n_res == 0 ? 2 : 1), cin / 64,
-                      a.act == FCVSR_ACT_NONE ? 2 : ((a.act == FCVSR_ACT_RELU || (a.act == FCVSR_ACT_LEAKY && a.slope >= 0.f && a.slope <= 1.f)) ? 1 : 0));
-    e = launch_conv3_res(wa, mma_dtype == FCVSR_BF16, a.dst16 != 0, st);
-    if (e != hipSuccess) {
-      set_error("fcvsr_conv2d_mfma: resident-weight launch failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    return 0;
-  }
-  if (lean) FCVSR_NOTE_KERNEL("conv3_lean_kernel<%s, %d, %s, %s>%s", tf(mma_dtype == FCVSR_BF16), nt, tf(a.src16), tf(a.dst16), a.gc_wmask ? " +gc" : "");
-  else FCVSR_NOTE_KERNEL("conv_mfma_kernel<%s, %d, %d>", tf(mma_dtype == FCVSR_BF16), nt, d0.kh);
-  if (lean) e = (mma_dtype == FCVSR_BF16) ? dispatch_lean<true>(a, nt, tiles, st) : dispatch_lean<false>(a, nt, tiles, st);
-  else e = (mma_dtype == FCVSR_BF16) ? dispatch<true>(a, nt, d0.kh, tiles, st) : dispatch<false>(a, nt, d0.kh, tiles, st);
-  if (e != hipSuccess) {
-    set_error("fcvsr_conv2d_mfma: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  ConvPlan plan;
+  const int rc = plan_conv2d_mfma(descs, n_groups, mma_dtype, policy_from_env(), &plan);
+  if (rc != 0) return rc;
+  format_kernel_name(plan, g_last_kernel, sizeof(g_last_kernel));
+  const hipError_t e = launch_plan(plan, (hipStream_t)stream);
+  if (e == hipSuccess) return 0;
+  if (e == hipErrorStreamCaptureUnsupported) set_error("fcvsr_conv2d_mfma: first use on this device inside a stream capture (run the layer once eagerly first)");
+  else set_error("fcvsr_conv2d_mfma: %s failed: %s", plan.path == kRes3 ? "resident-weight launch" : "launch", hipGetErrorString(e));
+  return (int)e;
 }

@@ -31,6 +31,15 @@ struct ResArgs {
 // returns hipSuccess, or hipErrorInvalidValue when the shape is not one the kernel is built for
 hipError_t launch_conv3_res(const ResArgs& a, bool bf16, bool dst16, hipStream_t st);
 bool conv3_res_supports(int cin, int cout);
+// the instantiation conv3_res_kernel<BF16, mode, nch, nsu> that serves a problem (the launch and the reported kernel name use it).
+// mode: 0 f32 destination, 1 16-bit destination with residuals, 2 16-bit without; nch: 64-channel input chunks; nsu: how much
+// the host knows about the activation's negative slope ns: 2 none (identity), 1 0 <= ns <= 1 (act(x) = max(x, ns * x)), 0 neither
+// (PReLU: the slope is in device memory)
+struct ResVariant { int mode, nch, nsu; };
+ResVariant conv3_res_variant(int cin, int n_res, int act, float slope, bool dst16);
+// *zeros: this device's 256 zero bytes (ResArgs::zeros), created on first use; hipErrorStreamCaptureUnsupported when that first
+// use is inside a stream capture
+hipError_t conv3_res_zero_page(hipStream_t st, const void** zeros);
 // 8 x 32 tiles of one problem
 inline int conv3_res_tiles(int B, int H, int W) { return B * ((H + 7) / 8) * ((W + 31) / 32); }
 

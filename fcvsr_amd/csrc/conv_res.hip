@@ -479,30 +479,45 @@ static hipError_t launch_res(const ResArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <bool BF16, int NCH>
-static hipError_t launch_res_mode(const ResArgs& a, bool dst16, hipStream_t st) {
+ResVariant conv3_res_variant(int cin, int n_res, int act, float slope, bool dst16) {
   // act(x) = max(x, ns * x) needs 0 <= ns <= 1: known on the host for every activation but PReLU (slope in device memory)
-  const bool nsu = a.act == FCVSR_ACT_NONE || a.act == FCVSR_ACT_RELU || (a.act == FCVSR_ACT_LEAKY && a.slope >= 0.f && a.slope <= 1.f);
-  const int mode = !dst16 ? 0 : (a.n_res == 0 ? 2 : 1);
-  if (a.act == FCVSR_ACT_NONE) {
-    if (mode == 0) return launch_res<BF16, 0, NCH, 2>(a, st);
-    if (mode == 1) return launch_res<BF16, 1, NCH, 2>(a, st);
-    return launch_res<BF16, 2, NCH, 2>(a, st);
-  }
-  if (nsu) {
-    if (mode == 0) return launch_res<BF16, 0, NCH, 1>(a, st);
-    if (mode == 1) return launch_res<BF16, 1, NCH, 1>(a, st);
-    return launch_res<BF16, 2, NCH, 1>(a, st);
-  }
-  if (mode == 0) return launch_res<BF16, 0, NCH, 0>(a, st);
-  if (mode == 1) return launch_res<BF16, 1, NCH, 0>(a, st);
-  return launch_res<BF16, 2, NCH, 0>(a, st);
+  const bool ns01 = act == FCVSR_ACT_RELU || (act == FCVSR_ACT_LEAKY && slope >= 0.f && slope <= 1.f);
+  return ResVariant{!dst16 ? 0 : (n_res == 0 ? 2 : 1), cin / 64, act == FCVSR_ACT_NONE ? 2 : (ns01 ? 1 : 0)};
+}
+
+template <bool BF16, int NCH, int NSU>
+static hipError_t launch_res_mode(const ResArgs& a, int mode, hipStream_t st) {
+  return mode == 0 ? launch_res<BF16, 0, NCH, NSU>(a, st) : mode == 1 ? launch_res<BF16, 1, NCH, NSU>(a, st) : launch_res<BF16, 2, NCH, NSU>(a, st);
+}
+
+template <bool BF16, int NCH>
+static hipError_t launch_res_nsu(const ResArgs& a, const ResVariant& v, hipStream_t st) {
+  return v.nsu == 2   ? launch_res_mode<BF16, NCH, 2>(a, v.mode, st)
+         : v.nsu == 1 ? launch_res_mode<BF16, NCH, 1>(a, v.mode, st) : launch_res_mode<BF16, NCH, 0>(a, v.mode, st);
 }
 
 hipError_t launch_conv3_res(const ResArgs& a, bool bf16, bool dst16, hipStream_t st) {
   if (!conv3_res_supports(a.cin, a.cout)) return hipErrorInvalidValue;
-  if (a.cin == 64) return bf16 ? launch_res_mode<true, 1>(a, dst16, st) : launch_res_mode<false, 1>(a, dst16, st);
-  return bf16 ? launch_res_mode<true, 2>(a, dst16, st) : launch_res_mode<false, 2>(a, dst16, st);
+  const ResVariant v = conv3_res_variant(a.cin, a.n_res, a.act, a.slope, dst16);
+  if (v.nch == 1) return bf16 ? launch_res_nsu<true, 1>(a, v, st) : launch_res_nsu<false, 1>(a, v, st);
+  return bf16 ? launch_res_nsu<true, 2>(a, v, st) : launch_res_nsu<false, 2>(a, v, st);
+}
+
+// 256 zero bytes per DEVICE (the source of halo pixels outside the image), created on first use.  hipMalloc / hipMemset are not
+// capturable: the engine runs every configuration eagerly before it captures a hipGraph, so this never happens inside a
+// capture; a capture that does reach it is refused rather than handed another device's page.
+hipError_t conv3_res_zero_page(hipStream_t st, const void** zeros) {
+  static void* page[64] = {nullptr};
+  static DevOnce made;
+  int dev = 0;
+  const hipError_t e = once_per_device(made, [&] {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return hipErrorStreamCaptureUnsupported;
+    const hipError_t ez = hipMalloc(&page[dev], 256);
+    return ez != hipSuccess ? ez : hipMemset(page[dev], 0, 256);
+  }, &dev);
+  if (e == hipSuccess) *zeros = page[dev];
+  return e;
 }
 
 }  // namespace fcvsr

@@ -109,6 +109,7 @@ SIGNATURES = {
     "fcvsr_conv2d_f32mfma": [C.POINTER(ConvDesc), _VP],
     "fcvsr_conv2d_f32mfma_eligible": [C.POINTER(ConvDesc)],
     "fcvsr_conv2d_mfma": [C.POINTER(ConvDesc), _I, _I, _VP],
+    "fcvsr_conv2d_mfma_plan": [C.POINTER(ConvDesc), _I, _I, _I, _I, C.c_char_p, _I],
     "fcvsr_rfft2": [_PV, _I, _I, _I, _I, _VP, _I64, _I, _I, _VP],
     "fcvsr_irfft2": [_VP, _I64, _I, _I, _I, _I, _I, _I, _VP, _VP, _PV, _VP],
     "fcvsr_irfft2_bands": [_VP, _I64, _I, _I, _I, _I, _I, _I, _VP, _I, _VP, _PV, _VP],
@@ -321,13 +322,9 @@ def mfma_eligible(ksize: int, stride: int, groups) -> bool:
     return True
 
 
-def conv2d_mfma(groups, wpacked: torch.Tensor, ksize: int, cout: int, mma_dtype: int, *, stride: int = 1,
-                bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: float = 0.0,
-                slope_t: Optional[torch.Tensor] = None, res_scale: Sequence[float] = (), pixel_shuffle: bool = False,
-                gc_wmask: Optional[torch.Tensor] = None, name: str = ""):
-    """groups: 1..3 dicts {srcs: [..], dst: t, res: [..]} sharing weights / epilogue (one launch)."""
-    n = len(groups)
-    descs = (ConvDesc * n)()
+def _mfma_descs(groups, wpacked, ksize, cout, stride, bias, act, slope, slope_t, res_scale, pixel_shuffle, gc_wmask):
+    """The descriptors of a grouped MFMA problem (conv2d_mfma and conv_plan fill them alike) and its algorithmic FLOPs."""
+    descs = (ConvDesc * len(groups))()
     flops = 0.0
     for i, g in enumerate(groups):
         cin = _fill_desc(descs[i], g["srcs"], wpacked, ksize, cout, wpacked.shape[1], g["dst"], bias, stride, act, slope,
@@ -337,6 +334,30 @@ def conv2d_mfma(groups, wpacked: torch.Tensor, ksize: int, cout: int, mma_dtype:
             descs[i].gc_wmask = gc_wmask.data_ptr()
             descs[i].gc_partial = g["gc_partial"].data_ptr()
         flops += 2.0 * descs[i].B * descs[i].H * descs[i].W * cout * cin * ksize * ksize / (stride * stride)
+    return descs, flops
+
+
+def conv_plan(groups, wpacked: torch.Tensor, ksize: int, cout: int, mma_dtype: int, *, lean: int = 1, res: int = 2, stride: int = 1,
+              bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: float = 0.0,
+              slope_t: Optional[torch.Tensor] = None, res_scale: Sequence[float] = (), pixel_shuffle: bool = False,
+              gc_wmask: Optional[torch.Tensor] = None, name: str = "") -> str:
+    """The kernel conv2d_mfma would launch for this problem (the string fcvsr_last_conv_kernel() reports afterwards) under the
+    policy lean (0 | 1, as FCVSR_MFMA_LEAN) and res (0 | 1, or 2 = unset, as FCVSR_MFMA_RES); HipError where it would be rejected.
+    Nothing is launched and the environment is not read; the tensors are looked at for shape, strides and alignment only.  Takes
+    conv2d_mfma's keywords (`name` is unused), so one argument set serves both."""
+    descs, _ = _mfma_descs(groups, wpacked, ksize, cout, stride, bias, act, slope, slope_t, res_scale, pixel_shuffle, gc_wmask)
+    name = C.create_string_buffer(96)
+    check(lib().fcvsr_conv2d_mfma_plan(descs, len(groups), mma_dtype, lean, res, name, len(name)), "fcvsr_conv2d_mfma_plan")
+    return name.value.decode()
+
+
+def conv2d_mfma(groups, wpacked: torch.Tensor, ksize: int, cout: int, mma_dtype: int, *, stride: int = 1,
+                bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: float = 0.0,
+                slope_t: Optional[torch.Tensor] = None, res_scale: Sequence[float] = (), pixel_shuffle: bool = False,
+                gc_wmask: Optional[torch.Tensor] = None, name: str = ""):
+    """groups: 1..3 dicts {srcs: [..], dst: t, res: [..]} sharing weights / epilogue (one launch)."""
+    n = len(groups)
+    descs, flops = _mfma_descs(groups, wpacked, ksize, cout, stride, bias, act, slope, slope_t, res_scale, pixel_shuffle, gc_wmask)
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()

@@ -88,10 +88,30 @@ int fcvsr_conv2d(const fcvsr_conv_desc* d, void* stream);
  * src views may be f32 or already `mma_dtype` (all alike); dst may be f32 or `mma_dtype` (16-bit storage for tensors whose
  * only consumers are further MFMA convolutions: bit-identical results, half the HBM bytes); res views are f32.
  * With pixel_shuffle the weight/bias rows must be ordered sub-pixel-major: row (2*i+j)*(cout/4)+c holds original output
- * channel 4*c+2*i+j, so that one lane's 4 consecutive couts land in one pixel of the shuffled output. */
+ * channel 4*c+2*i+j, so that one lane's 4 consecutive couts land in one pixel of the shuffled output.
+ *
+ * One of six kernels runs: the first path of this list whose conditions hold for every group (DESIGN.md section 4 spells
+ * the conditions out; csrc/conv_plan.hip has one predicate per path).
+ *   1 conv1ps_res_kernel    1x1 pixel-shuffle up-convolution 64 -> cout <= 256, 16-bit source and destination, one group
+ *   2 conv3s2_lean_kernel   3x3 stride 2, one dense source of a multiple of 64 channels, cout % 64 == 0, no residuals
+ *   3 conv1_lean_kernel     1x1, every source a multiple of 64 channels, f32 residuals, channel-contiguous destination
+ *   4 conv3_res_kernel      3x3 stride 1, one dense 16-bit source of 64 / 128 channels, cout % 64 == 0, everything on 16-byte
+ *                           granules, no ContextBlock fusion; launches of at least 768 workgroup-tiles
+ *   5 conv3_lean_kernel     3x3 stride 1, one dense source of a multiple of 64 channels, no pixel shuffle
+ *   6 conv_mfma_kernel      everything else the argument checks admit
+ * 16-bit residuals and ContextBlock fusion into a 16-bit destination are layouts of paths 4 and 5 only: a problem that has one
+ * and would run on path 6 is rejected (FCVSR_E_ARG).
+ * Test and benchmark seam, read once per call: FCVSR_MFMA_LEAN = 0 switches paths 2, 3 and 5 off (and with them path 1 and every
+ * path-4 layer but the pixel-shuffled 64 -> 256 ones), any other value or unset leaves them on; FCVSR_MFMA_RES = 0 switches
+ * paths 1 and 4 off, any other number takes path 4 at every size, unset applies the size rule. */
 int fcvsr_conv2d_mfma(const fcvsr_conv_desc* descs, int n_groups, int mma_dtype, void* stream);
+/* The decision fcvsr_conv2d_mfma would take under the policy (lean: 0 | 1 as FCVSR_MFMA_LEAN, res: 0 | 1, or 2 = unset, as
+ * FCVSR_MFMA_RES), without launching, without a GPU and whatever the environment says: writes the kernel name
+ * fcvsr_last_conv_kernel() would report into kernel_name[cap] and returns 0, or returns the rejection with fcvsr_last_error()
+ * set.  Tensor pointers are looked at for alignment only. */
+int fcvsr_conv2d_mfma_plan(const fcvsr_conv_desc* descs, int n_groups, int mma_dtype, int lean, int res, char* kernel_name, int cap);
 /* Name (template instance) of the kernel the calling thread's last fcvsr_conv2d_mfma call launched, e.g.
- * "conv3_res_kernel<true, true, 1>": measurement aid for bench.py's per-kernel roofline, not part of the data path. */
+ * "conv3_res_kernel<true, 2, 1, 1>": measurement aid for bench.py's per-kernel roofline, not part of the data path. */
 const char* fcvsr_last_conv_kernel(void);
 /* fcvsr_conv2d on the matrix cores with f32 operands (v_mfma_f32_32x32x2_f32: exact f32, bit-equal to an fmaf chain): the
  * arithmetic of the exact-f32 mode for 3x3 / 1x1 stride-1 layers with one dense NHWC f32 source of a multiple of 32 channels,
