@@ -257,6 +257,15 @@ class _GShiftBase(nn.Module):
         capture and ``streams`` apply as in ``forward``."""
         return self._get_engine().forward_u8(x, quantise)
 
+    def super_resolve_u16(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
+        """10-bit frames in, 10-bit SR frames out: x uint16 (B, 7, C, H, W) on a HIP device, 10-bit samples in 16-bit containers
+        (HEVC Main10 / VVC / AV1 material) -> uint16 (B, C, 4H, 4W) with samples in [0, 1023].
+
+        The samples equal those of ``q(clamp(self(x.clamp(max=1023).float() / 1023), 0, 1) * 1023)`` with the division done on the
+        host and q as in ``super_resolve_u8``: full scale is 2^10 - 1, and a sample above 1023 is read as 1023.  Everything else
+        is as in ``super_resolve_u8``."""
+        return self._get_engine().forward_u16(x, quantise)
+
     def _get_engine(self):
         from ..engine import Engine
         if self._engine is None or self._engine._model() is not self:      # (a deepcopy carries the source's engine)
@@ -290,6 +299,10 @@ class GShiftNet_ETC(GShiftNet):
     def super_resolve_u8(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
         raise NotImplementedError("GShiftNet_ETC returns (out_seq, x_up) for a 13-frame input: run its 7-frame windows through "
                                   "a GShiftNet with the same state_dict for uint8 frames")
+
+    def super_resolve_u16(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
+        raise NotImplementedError("GShiftNet_ETC returns (out_seq, x_up) for a 13-frame input: run its 7-frame windows through "
+                                  "a GShiftNet with the same state_dict for 10-bit frames")
 
     def forward(self, x: torch.Tensor):
         if x.dim() != 5 or x.shape[1] != self._in_frames + self._windows - 1 or x.shape[2] != self._img_ch:

@@ -7,7 +7,8 @@
 //   * "taps are output columns": P[pixel][tap*C + c] = sum_k u2[pixel][k] * w[c][k][tap] is a (340 x 64) x (64 x 9C) GEMM on
 //     v_mfma_f32_16x16x32 (2 MFMAs per 16 pixels and 16 columns) instead of 576 C multiply-adds per pixel on the vector ALU;
 //   * out[c][y][x] += bias[c] + sum_tap P[(y+dy, x+dx)][tap*C + c]  - 9 LDS reads per output value.
-// Q != 0 (fcvsr_conv_last_u8): `out` is only read (the f32 base) and the sum goes, quantised (u8.h), to the uint8 frames out8.
+// Q != 0 (fcvsr_conv_last_u8, _u16): `out` is only read (the f32 base) and the sum goes, quantised to PEAK (u8.h), to the integer
+// frames out8 (uint8 for PEAK = 255, uint16 for PEAK = 1023).
 #include "common.h"
 #include "mfma_util.h"
 #include "u8.h"
@@ -25,7 +26,7 @@ struct ClArgs {
   const uint16_t* w;       // [16 * NT][64]: row = tap * C + c (tap = ky*3 + kx), zero rows past 9 C; MFMA dtype
   const float* bias;       // C floats or null
   View out;                // (B, H, W, C) f32 view of the NCHW result, read-modify-write (Q != 0: read only)
-  View out8;               // Q != 0: (B, H, W, C) uint8 destination
+  View out8;               // Q != 0: (B, H, W, C) uint8 / uint16 destination
   int B, H, W, C, tiles_x, tiles_y;
 };
 
@@ -38,7 +39,7 @@ __device__ __forceinline__ f32x4v_t mfma16cl(uint4 a, uint4 b, f32x4v_t c) {
 }
 
 // NT = column tiles of 16 (C = 1: 9 columns -> NT = 1; C = 3: 27 columns -> NT = 2)
-template <bool BF16, int NT, int Q = 0>
+template <bool BF16, int NT, int Q = 0, int PEAK = kPeak8>
 __global__ __launch_bounds__(256, 3) void conv_last_kernel(ClArgs a) {
   constexpr int PROW = 16 * NT + 1;                          // floats per pixel of the tap table (odd stride)
   __shared__ __align__(16) uint16_t u_s[kClNHP * kClRow];    // 48,960 bytes; the tap table overwrites it
@@ -133,8 +134,9 @@ __global__ __launch_bounds__(256, 3) void conv_last_kernel(ClArgs a) {
         if constexpr (Q == 0) {
           op[(long long)c * a.out.sc] = s;
         } else {
-          reinterpret_cast<uint8_t*>(a.out8.p)[(long long)b * a.out8.sb + (long long)oy * a.out8.sy + (long long)ox * a.out8.sx +
-                                               (long long)c * a.out8.sc] = quantise_u8<Q>(s);
+          typedef typename SampleOf<PEAK>::type OT;
+          reinterpret_cast<OT*>(a.out8.p)[(long long)b * a.out8.sb + (long long)oy * a.out8.sy + (long long)ox * a.out8.sx +
+                                          (long long)c * a.out8.sc] = quantise<Q, PEAK, OT>(s);
         }
       }
     }
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(256, 3) void conv_last_kernel(ClArgs a) {
 
 using namespace fcvsr;
 
-template <int Q>
+template <int Q, int PEAK = kPeak8>
 static int conv_last_launch(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C, const fcvsr_view* out,
                             const fcvsr_view* out8, void* stream) {
   FCVSR_CHECK_ARG(u && u->ptr && w && out && out->ptr, "null argument");
@@ -162,11 +164,11 @@ static int conv_last_launch(const fcvsr_view* u, const void* w, const float* bia
   hipStream_t st = (hipStream_t)stream;
   const bool bf = u->dtype == FCVSR_BF16;
   if (C == 1) {
-    if (bf) hipLaunchKernelGGL((conv_last_kernel<true, 1, Q>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_last_kernel<false, 1, Q>), grid, dim3(256), 0, st, a);
+    if (bf) hipLaunchKernelGGL((conv_last_kernel<true, 1, Q, PEAK>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_last_kernel<false, 1, Q, PEAK>), grid, dim3(256), 0, st, a);
   } else {
-    if (bf) hipLaunchKernelGGL((conv_last_kernel<true, 2, Q>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_last_kernel<false, 2, Q>), grid, dim3(256), 0, st, a);
+    if (bf) hipLaunchKernelGGL((conv_last_kernel<true, 2, Q, PEAK>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_last_kernel<false, 2, Q, PEAK>), grid, dim3(256), 0, st, a);
   }
   FCVSR_LAUNCH_CHECK();
   return 0;
@@ -185,4 +187,13 @@ extern "C" int fcvsr_conv_last_u8(const fcvsr_view* u, const void* w, const floa
   FCVSR_CHECK_ARG(quantise == FCVSR_QUANT_TRUNCATE || quantise == FCVSR_QUANT_ROUND, "quantise: FCVSR_QUANT_TRUNCATE or _ROUND");
   if (quantise == FCVSR_QUANT_TRUNCATE) return conv_last_launch<FCVSR_QUANT_TRUNCATE>(u, w, bias, B, H, W, C, base, out, stream);
   return conv_last_launch<FCVSR_QUANT_ROUND>(u, w, bias, B, H, W, C, base, out, stream);
+}
+
+extern "C" int fcvsr_conv_last_u16(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C,
+                                   const fcvsr_view* base, const fcvsr_view* out, int quantise, void* stream) {
+  FCVSR_CHECK_ARG(out && out->ptr && out->dtype == FCVSR_U16 && out->c == C && ((uintptr_t)out->ptr % 2) == 0,
+                  "out: C uint16 channels, 2-byte aligned");
+  FCVSR_CHECK_ARG(quantise == FCVSR_QUANT_TRUNCATE || quantise == FCVSR_QUANT_ROUND, "quantise: FCVSR_QUANT_TRUNCATE or _ROUND");
+  if (quantise == FCVSR_QUANT_TRUNCATE) return conv_last_launch<FCVSR_QUANT_TRUNCATE, kPeak10>(u, w, bias, B, H, W, C, base, out, stream);
+  return conv_last_launch<FCVSR_QUANT_ROUND, kPeak10>(u, w, bias, B, H, W, C, base, out, stream);
 }

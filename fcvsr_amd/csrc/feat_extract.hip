@@ -11,7 +11,9 @@
 //     channel split, :2617-2619), in the storage dtype of the activations.
 // The U8 variant gathers uint8 frames instead (fcvsr_feat_extract_u8): pixel k enters as tab[k] (u8.h), the f32 the f32 variant is
 // fed by a caller that converts on the host, so both variants build the same f16 im2col tile.  The table sits in the LDS of the
-// epilogue tile, which is not written before the tile barrier.
+// epilogue tile, which is not written before the tile barrier.  The U16 variant (fcvsr_feat_extract_u16) gathers 10-bit samples in
+// 16-bit containers through a 1024-float table in the same place (4 KB of the 34 KB epilogue tile: the LDS size does not change);
+// the 1024 values k / 1023 stay distinct in f16.
 #include <type_traits>
 #include "common.h"
 #include "mfma_util.h"
@@ -26,8 +28,8 @@ constexpr int kFeERow = 64 + 4;                    // floats per pixel row of th
 constexpr int kFeMaxBlk = 16;
 
 struct FeatArgs {
-  View x;                   // (B, H, W, Cin) logical view of the planar frames, f32 (uint8 in the U8 variant)
-  const float* tab;         // U8 variant: [256] value of pixel k
+  View x;                   // (B, H, W, Cin) logical view of the planar frames, f32 (uint8 / uint16 in the U8 / U16 variants)
+  const float* tab;         // U8 variant: [256], U16 variant: [1024] value of sample k
   int B, H, W, cin;
   const uint16_t* w;        // [n_blk*64][64] f16: k = tap*cin + c (zero beyond 9*cin)
   const float* bias;        // [n_blk*64] or null
@@ -37,7 +39,7 @@ struct FeatArgs {
   int dch[kFeMaxBlk];
 };
 
-template <bool DSTBF, int CIN, bool U8 = false>
+template <bool DSTBF, int CIN, int SRC = kSrcF32>
 __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
   extern __shared__ __align__(16) unsigned char lds[];
   uint16_t* A_s = reinterpret_cast<uint16_t*>(lds);
@@ -48,8 +50,12 @@ __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
   const long long npix = (long long)a.B * a.H * a.W;
   const long long flat0 = (long long)blockIdx.x * kFePix;
   float* tab_s = reinterpret_cast<float*>(lds + kFePix * kFeLD * 2);
-  if constexpr (U8) {
+  static_assert((kPeak10 + 1) * 4 <= 4 * 32 * kFeERow * 4, "the table must fit into the epilogue tile");
+  if constexpr (SRC == kSrcU8) {
     tab_s[tid] = a.tab[tid];                            // 256 threads, 256 entries
+    __syncthreads();
+  } else if constexpr (SRC == kSrcU16) {
+    reinterpret_cast<float4*>(tab_s)[tid] = reinterpret_cast<const float4*>(a.tab)[tid];   // 256 threads, 1024 entries
     __syncthreads();
   }
 
@@ -65,6 +71,7 @@ __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
     const int b = (int)(pc / ((long long)a.W * a.H));
     const float* xb = a.x.p + (long long)b * a.x.sb;
     const uint8_t* xb8 = reinterpret_cast<const uint8_t*>(a.x.p) + (long long)b * a.x.sb;
+    const uint16_t* xb16 = reinterpret_cast<const uint16_t*>(a.x.p) + (long long)b * a.x.sb;
     const int sy = (int)a.x.sy, sx = (int)a.x.sx, sc = (int)a.x.sc;   // one image spans < 2^31 elements (host check)
     float f[32];
     auto gather = [&](auto koff) {
@@ -79,7 +86,8 @@ __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
         const int iyc = iy < 0 ? 0 : (iy > a.H - 1 ? a.H - 1 : iy), ixc = ix < 0 ? 0 : (ix > a.W - 1 ? a.W - 1 : ix);
         const int off = iyc * sy + ixc * sx + (k < 9 * CIN ? c : 0) * sc;
         float v;
-        if constexpr (U8) v = tab_s[xb8[off]];
+        if constexpr (SRC == kSrcU8) v = tab_s[xb8[off]];
+        else if constexpr (SRC == kSrcU16) v = sample_value<kPeak10>(tab_s, xb16[off]);
         else v = xb[off];
         f[j] = in ? v : 0.f;
       }
@@ -155,7 +163,7 @@ __global__ __launch_bounds__(256, 3) void feat_extract_kernel(FeatArgs a) {
 
 using namespace fcvsr;
 
-template <bool U8>
+template <int SRC>
 static int feat_extract_launch(const fcvsr_view* x, const float* tab, int B, int H, int W, const void* w, const float* bias, int n_blk,
                                void* const* dst, const int64_t* dst_pix_stride, const int32_t* dst_ch_off, int dst_dtype, void* stream) {
   FCVSR_CHECK_ARG((long long)H * x->sy < (1ll << 31) && 7ll * x->sc < (1ll << 31), "image too large for 32-bit offsets");
@@ -176,9 +184,9 @@ static int feat_extract_launch(const fcvsr_view* x, const float* tab, int B, int
   static DevOnce attr;
   {
     hipError_t e = once_per_device(attr, [&] {
-      hipError_t e1 = hipFuncSetAttribute((const void*)feat_extract_kernel<true, 7, U8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipError_t e1 = hipFuncSetAttribute((const void*)feat_extract_kernel<true, 7, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e1 == hipSuccess)
-        e1 = hipFuncSetAttribute((const void*)feat_extract_kernel<false, 7, U8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        e1 = hipFuncSetAttribute((const void*)feat_extract_kernel<false, 7, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       return e1;
     });
     if (e != hipSuccess) {
@@ -189,8 +197,8 @@ static int feat_extract_launch(const fcvsr_view* x, const float* tab, int B, int
   const long long npix = (long long)B * H * W;
   dim3 grid(cdiv(npix, kFePix));
   hipStream_t st = (hipStream_t)stream;
-  if (dst_dtype == FCVSR_BF16) hipLaunchKernelGGL((feat_extract_kernel<true, 7, U8>), grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((feat_extract_kernel<false, 7, U8>), grid, dim3(256), lds, st, a);
+  if (dst_dtype == FCVSR_BF16) hipLaunchKernelGGL((feat_extract_kernel<true, 7, SRC>), grid, dim3(256), lds, st, a);
+  else hipLaunchKernelGGL((feat_extract_kernel<false, 7, SRC>), grid, dim3(256), lds, st, a);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }
@@ -200,7 +208,7 @@ extern "C" int fcvsr_feat_extract(const fcvsr_view* x, int B, int H, int W, cons
                                   void* stream) {
   FCVSR_CHECK_ARG(x && x->ptr && w && dst && dst_pix_stride && dst_ch_off, "null argument");
   FCVSR_CHECK_ARG(x->dtype == FCVSR_F32 && x->c == 7, "x: f32, 7 channels (the Y models' frame stack)");
-  return feat_extract_launch<false>(x, nullptr, B, H, W, w, bias, n_blk, dst, dst_pix_stride, dst_ch_off, dst_dtype, stream);
+  return feat_extract_launch<kSrcF32>(x, nullptr, B, H, W, w, bias, n_blk, dst, dst_pix_stride, dst_ch_off, dst_dtype, stream);
 }
 
 extern "C" int fcvsr_feat_extract_u8(const fcvsr_view* x, const float* tab, int B, int H, int W, const void* w, const float* bias,
@@ -208,5 +216,14 @@ extern "C" int fcvsr_feat_extract_u8(const fcvsr_view* x, const float* tab, int 
                                      int dst_dtype, void* stream) {
   FCVSR_CHECK_ARG(x && x->ptr && tab && w && dst && dst_pix_stride && dst_ch_off, "null argument");
   FCVSR_CHECK_ARG(x->dtype == FCVSR_U8 && x->c == 7, "x: uint8, 7 channels (the Y models' frame stack)");
-  return feat_extract_launch<true>(x, tab, B, H, W, w, bias, n_blk, dst, dst_pix_stride, dst_ch_off, dst_dtype, stream);
+  return feat_extract_launch<kSrcU8>(x, tab, B, H, W, w, bias, n_blk, dst, dst_pix_stride, dst_ch_off, dst_dtype, stream);
+}
+
+extern "C" int fcvsr_feat_extract_u16(const fcvsr_view* x, const float* tab, int B, int H, int W, const void* w, const float* bias,
+                                      int n_blk, void* const* dst, const int64_t* dst_pix_stride, const int32_t* dst_ch_off,
+                                      int dst_dtype, void* stream) {
+  FCVSR_CHECK_ARG(x && x->ptr && tab && w && dst && dst_pix_stride && dst_ch_off, "null argument");
+  FCVSR_CHECK_ARG(x->dtype == FCVSR_U16 && x->c == 7, "x: uint16, 7 channels (the Y models' frame stack)");
+  FCVSR_CHECK_ARG(((uintptr_t)x->ptr % 2) == 0 && ((uintptr_t)tab % 16) == 0, "x 2-byte aligned, table 16-byte aligned");
+  return feat_extract_launch<kSrcU16>(x, tab, B, H, W, w, bias, n_blk, dst, dst_pix_stride, dst_ch_off, dst_dtype, stream);
 }

@@ -10,6 +10,8 @@
 // squared errors cover PSNR-region pixels: a tile owns its 16 x 64 map rectangle, and the last tile of a row / column also the
 // 10 extra rows / columns its halo already holds, so every PSNR pixel is counted exactly once.  A second launch adds each
 // frame's partials in a fixed order (no atomics: bit-reproducible).
+// U16 (fcvsr_frame_metrics_u16): the frames hold 10-bit samples in uint16; f32 SR values are quantised with the 1023 scale and the
+// SSIM constants come from the caller's peak (1023, or HM's 1020); there is no Y conversion.
 #include "common.h"
 
 namespace {
@@ -22,15 +24,18 @@ struct QualityArgs {
   const unsigned char* hr;
   long long h_sn, h_sc, h_sy, h_sx;
   int planes_per_frame, crop, Hc, Wc, Hm, Wm, tiles_x, tiles, quantise, to_y;
+  double peak;                           // U16: the peak of the SSIM constants
   double g[kWin];
   double* part;                          // [plane][tile][2] = {squared-error sum, SSIM-map sum}
 };
 
 // SR value of one sample as the uint8 frame harness/infer.py would produce: clamp(v, 0, 1) * 255.0f (f32 multiply), then
 // truncation toward zero (tensor.to(torch.uint8)) or round-half-to-even (torch.round); uint8 input is used as it is.
+// (U16: uint16 samples, scale 1023.0f)
+template <bool U16>
 __device__ inline double sr_value(const QualityArgs& a, long long off) {
-  if (a.quantise == FCVSR_QUANT_NONE) return (double)((const unsigned char*)a.sr)[off];
-  const float q = fminf(fmaxf(((const float*)a.sr)[off], 0.f), 1.f) * 255.0f;
+  if (a.quantise == FCVSR_QUANT_NONE) return U16 ? (double)((const unsigned short*)a.sr)[off] : (double)((const unsigned char*)a.sr)[off];
+  const float q = fminf(fmaxf(((const float*)a.sr)[off], 0.f), 1.f) * (U16 ? 1023.0f : 255.0f);
   return (double)(a.quantise == FCVSR_QUANT_TRUNCATE ? truncf(q) : rintf(q));
 }
 
@@ -52,6 +57,7 @@ __device__ inline double block_sum(double v, double* sm) {
   return t;
 }
 
+template <bool U16>
 __global__ __launch_bounds__(256) void quality_tile_kernel(QualityArgs a) {
   __shared__ double sx[kLY][kLX], sy[kLY][kLX];    // SR, HR window (zero past the crop edge)
   __shared__ double vs[5][kTY][kLX];               // vertical pass: x, y, x*x, y*y, x*y
@@ -67,11 +73,14 @@ __global__ __launch_bounds__(256) void quality_tile_kernel(QualityArgs a) {
     if (r < ly && q < lx) {
       const long long iy = a.crop + my0 + r, ix = a.crop + mx0 + q;
       const long long so = n * a.s_sn + iy * a.s_sy + ix * a.s_sx, ho = n * a.h_sn + iy * a.h_sy + ix * a.h_sx;
-      if (a.to_y) {
-        xv = y_of(sr_value(a, so), sr_value(a, so + a.s_sc), sr_value(a, so + 2 * a.s_sc));
+      if constexpr (U16) {
+        xv = sr_value<true>(a, so + c * a.s_sc);
+        yv = (double)((const unsigned short*)a.hr)[ho + c * a.h_sc];
+      } else if (a.to_y) {
+        xv = y_of(sr_value<false>(a, so), sr_value<false>(a, so + a.s_sc), sr_value<false>(a, so + 2 * a.s_sc));
         yv = y_of((double)a.hr[ho], (double)a.hr[ho + a.h_sc], (double)a.hr[ho + 2 * a.h_sc]);
       } else {
-        xv = sr_value(a, so + c * a.s_sc);
+        xv = sr_value<false>(a, so + c * a.s_sc);
         yv = (double)a.hr[ho + c * a.h_sc];
       }
     }
@@ -107,7 +116,8 @@ __global__ __launch_bounds__(256) void quality_tile_kernel(QualityArgs a) {
   __syncthreads();
 
   // horizontal pass and the SSIM map of _ssim_plane, summed over this tile's valid map pixels
-  const double k1 = 0.01 * 255, k2 = 0.03 * 255, c1 = k1 * k1, c2 = k2 * k2;
+  const double peak = U16 ? a.peak : 255.0;
+  const double k1 = 0.01 * peak, k2 = 0.03 * peak, c1 = k1 * k1, c2 = k2 * k2;
   const int ro = min(kTY, a.Hm - my0), co = min(kTX, a.Wm - mx0);
   double ssum = 0.0;
   for (int i = threadIdx.x; i < ro * co; i += 256) {
@@ -175,14 +185,19 @@ extern "C" long long fcvsr_frame_metrics_scratch_bytes(int N, int C, int H, int 
   return (long long)N * g.P * g.tiles_x * g.tiles_y * 2 * (long long)sizeof(double);
 }
 
-extern "C" int fcvsr_frame_metrics(const void* sr, const int64_t* host_sr_strides, int quantise, const uint8_t* hr,
-                                   const int64_t* host_hr_strides, int N, int C, int H, int W, int crop_border, int to_y,
-                                   const double* host_window, double* out, void* scratch, long long scratch_bytes, void* stream) {
+template <bool U16>
+static int frame_metrics_launch(const void* sr, const int64_t* host_sr_strides, int quantise, const void* hr, const int64_t* host_hr_strides,
+                         int N, int C, int H, int W, int crop_border, int to_y, const double* host_window, double peak, double* out,
+                         void* scratch, long long scratch_bytes, void* stream) {
   FCVSR_CHECK_ARG(sr && hr && out && scratch, "null device pointer");
   FCVSR_CHECK_ARG(host_sr_strides && host_hr_strides && host_window, "null host pointer");
   FCVSR_CHECK_ARG(N >= 1 && C >= 1 && H >= 1 && W >= 1, "empty frames");
   FCVSR_CHECK_ARG(quantise == FCVSR_QUANT_NONE || quantise == FCVSR_QUANT_TRUNCATE || quantise == FCVSR_QUANT_ROUND, "bad quantise mode");
   FCVSR_CHECK_ARG(to_y == 0 || (to_y == 1 && C == 3), "Y conversion needs 3 channels (RGB)");
+  FCVSR_CHECK_ARG(!(U16 && to_y), "Y conversion is not defined for 10-bit frames");
+  FCVSR_CHECK_ARG(!U16 || (peak > 0.0 && peak <= 65535.0), "peak: positive");
+  FCVSR_CHECK_ARG(!U16 || (((uintptr_t)hr % 2) == 0 && (quantise != FCVSR_QUANT_NONE || ((uintptr_t)sr % 2) == 0)),
+                  "uint16 frames must be 2-byte aligned");
   FCVSR_CHECK_ARG(crop_border >= 0, "negative crop_border");
   const Geometry g = geometry(C, H, W, crop_border, to_y);
   FCVSR_CHECK_ARG(g.Hm >= 1 && g.Wm >= 1, "frame too small for crop_border + the 11x11 SSIM window");
@@ -192,7 +207,7 @@ extern "C" int fcvsr_frame_metrics(const void* sr, const int64_t* host_sr_stride
   QualityArgs a;
   a.sr = sr;
   a.s_sn = host_sr_strides[0]; a.s_sc = host_sr_strides[1]; a.s_sy = host_sr_strides[2]; a.s_sx = host_sr_strides[3];
-  a.hr = hr;
+  a.hr = (const unsigned char*)hr;
   a.h_sn = host_hr_strides[0]; a.h_sc = host_hr_strides[1]; a.h_sy = host_hr_strides[2]; a.h_sx = host_hr_strides[3];
   a.planes_per_frame = g.P;
   a.crop = crop_border;
@@ -201,11 +216,27 @@ extern "C" int fcvsr_frame_metrics(const void* sr, const int64_t* host_sr_stride
   a.tiles = g.tiles_x * g.tiles_y;
   a.quantise = quantise;
   a.to_y = to_y;
+  a.peak = peak;
   for (int k = 0; k < kWin; ++k) a.g[k] = host_window[k];
   a.part = (double*)scratch;
-  hipLaunchKernelGGL(quality_tile_kernel, dim3((unsigned)a.tiles, (unsigned)(N * g.P)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(quality_tile_kernel<U16>, dim3((unsigned)a.tiles, (unsigned)(N * g.P)), dim3(256), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(quality_finish_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, (const double*)scratch,
                      (long long)g.P * a.tiles, out);
   FCVSR_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fcvsr_frame_metrics(const void* sr, const int64_t* host_sr_strides, int quantise, const uint8_t* hr,
+                                   const int64_t* host_hr_strides, int N, int C, int H, int W, int crop_border, int to_y,
+                                   const double* host_window, double* out, void* scratch, long long scratch_bytes, void* stream) {
+  return frame_metrics_launch<false>(sr, host_sr_strides, quantise, hr, host_hr_strides, N, C, H, W, crop_border, to_y, host_window,
+                                     255.0, out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int fcvsr_frame_metrics_u16(const void* sr, const int64_t* host_sr_strides, int quantise, const uint16_t* hr,
+                                       const int64_t* host_hr_strides, int N, int C, int H, int W, int crop_border, int to_y,
+                                       const double* host_window, double peak, double* out, void* scratch, long long scratch_bytes,
+                                       void* stream) {
+  return frame_metrics_launch<true>(sr, host_sr_strides, quantise, hr, host_hr_strides, N, C, H, W, crop_border, to_y, host_window,
+                                    peak, out, scratch, scratch_bytes, stream);
 }

@@ -48,7 +48,7 @@ __global__ void pixel_shuffle16_kernel(const float* src, View dst, int B, int H,
       make_uint4(lo.x, lo.y, hi.x, hi.y);
 }
 
-template <bool U8>
+template <int SRC>
 __device__ __forceinline__ void bilinear_up4_px(View src, const float* tab, int B, int H, int W, View dst) {
   const int Ho = 4 * H, Wo = 4 * W;
   const long long total = (long long)B * Ho * Wo * dst.c;
@@ -59,14 +59,18 @@ __device__ __forceinline__ void bilinear_up4_px(View src, const float* tab, int 
   const int oy = (int)((t / Wo) % Ho);
   const int c = (int)((t / ((long long)Wo * Ho)) % dst.c);
   const int b = (int)(t / ((long long)Wo * Ho * dst.c));
-  const float v = bilinear_up4_at<U8>(src, tab, H, W, b, c, oy, ox);
+  const float v = bilinear_up4_at<SRC>(src, tab, H, W, b, c, oy, ox);
   dst.p[(long long)b * dst.sb + (long long)oy * dst.sy + (long long)ox * dst.sx + (long long)c * dst.sc] = v;
 }
 
-__global__ void bilinear_up4_kernel(View src, int B, int H, int W, View dst) { bilinear_up4_px<false>(src, nullptr, B, H, W, dst); }
+__global__ void bilinear_up4_kernel(View src, int B, int H, int W, View dst) { bilinear_up4_px<kSrcF32>(src, nullptr, B, H, W, dst); }
 
 __global__ void bilinear_up4_u8_kernel(View src, const float* tab, int B, int H, int W, View dst) {
-  bilinear_up4_px<true>(src, tab, B, H, W, dst);
+  bilinear_up4_px<kSrcU8>(src, tab, B, H, W, dst);
+}
+
+__global__ void bilinear_up4_u16_kernel(View src, const float* tab, int B, int H, int W, View dst) {
+  bilinear_up4_px<kSrcU16>(src, tab, B, H, W, dst);
 }
 
 }  // namespace fcvsr
@@ -114,6 +118,18 @@ extern "C" int fcvsr_bilinear_up4_u8(const fcvsr_view* src, const float* tab, in
   FCVSR_CHECK_ARG(B > 0 && H > 0 && W > 0 && src->c == dst->c && dst->c > 0, "bad sizes");
   const long long total = (long long)B * 16 * H * W * dst->c;
   hipLaunchKernelGGL(bilinear_up4_u8_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, to_view(*src), tab, B, H,
+                     W, to_view(*dst));
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fcvsr_bilinear_up4_u16(const fcvsr_view* src, const float* tab, int B, int H, int W, const fcvsr_view* dst, void* stream) {
+  FCVSR_CHECK_ARG(src && dst && src->ptr && dst->ptr && tab, "null pointer");
+  FCVSR_CHECK_ARG(src->dtype == FCVSR_U16 && dst->dtype == FCVSR_F32, "uint16 source, f32 destination");
+  FCVSR_CHECK_ARG(((uintptr_t)src->ptr % 2) == 0, "src: 2-byte aligned");
+  FCVSR_CHECK_ARG(B > 0 && H > 0 && W > 0 && src->c == dst->c && dst->c > 0, "bad sizes");
+  const long long total = (long long)B * 16 * H * W * dst->c;
+  hipLaunchKernelGGL(bilinear_up4_u16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, to_view(*src), tab, B, H,
                      W, to_view(*dst));
   FCVSR_LAUNCH_CHECK();
   return 0;

@@ -11,9 +11,10 @@
 //   3. out[y][x] += bias + sum_tap P[y+dy][x+dx][tap]   (out holds the bilinear x4 base skip).
 // HBM traffic per output pixel: 14 bytes of u1 (with halo) + 8 bytes of out, instead of 128 written + ~170 read.
 // BASE != 0 (fcvsr_tail_fused_base, _base_u8): the base skip is not read from `out` but evaluated for the thread's pixel from the
-// centre LR frame (bilinear.h: four cached loads from a 230 KB frame; BASE == 2: a uint8 frame read through the table of u8.h), so
-// the result is write-only and no kernel has to pre-fill an f32 base.
-// Q != 0 (fcvsr_tail_fused_u8): `out` is only read (the f32 base) and the sum goes, quantised (u8.h), to the uint8 frame out8.
+// centre LR frame (bilinear.h: four cached loads from a 230 KB frame; BASE == 2: a uint8 frame, BASE == 3: a frame of 10-bit samples
+// in uint16, both read through the table of u8.h), so the result is write-only and no kernel has to pre-fill an f32 base.
+// Q != 0 (fcvsr_tail_fused_u8, _u16): `out` is only read (the f32 base) and the sum goes, quantised to PEAK (u8.h), to the integer
+// frame out8 (uint8 for PEAK = 255, uint16 for PEAK = 1023).
 #include "common.h"
 #include "mfma_util.h"
 #include "bilinear.h"
@@ -43,9 +44,10 @@ struct TailArgs {
   const uint16_t* wl;      // [16][64] conv_last0: row = tap (ky*3+kx), rows 9..15 zero
   const float* bl;         // conv_last0 bias (1 value, may be null)
   View out;                // (B, 2*H2, 2*W2, 1) f32, read-modify-write (Q != 0: read only)
-  View out8;               // Q != 0: (B, 2*H2, 2*W2, 1) uint8 destination
-  View centre;             // BASE: (B, H2/2, W2/2, 1) centre LR frame (source of the bilinear x4 base skip), f32 or (BASE == 2) uint8
-  const float* tab;        // BASE == 2: the 256-float table of the uint8 entry points
+  View out8;               // Q != 0: (B, 2*H2, 2*W2, 1) uint8 / uint16 destination
+  View centre;             // BASE: (B, H2/2, W2/2, 1) centre LR frame (source of the bilinear x4 base skip): f32, uint8 (BASE == 2) or
+                           // uint16 (BASE == 3)
+  const float* tab;        // BASE >= 2: the table of the integer entry points (256 or 1024 floats)
   int B, H2, W2, tiles_x, tiles_y;
   int ntiles;              // B * tiles_x * tiles_y, split into contiguous runs over the launched workgroups
 };
@@ -58,8 +60,9 @@ __device__ __forceinline__ f32x4_t mfma16(uint4 a, uint4 b, f32x4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
 }
 
-template <bool BF16, int Q = 0, int BASE = 0>
+template <bool BF16, int Q = 0, int BASE = 0, int PEAK = kPeak8>
 __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
+  static_assert(BASE >= 0 && BASE <= 3, "BASE - 1 is the centre frame's format (kSrcF32, kSrcU8, kSrcU16)");
   // 48 KiB: the tap table P of step 2 overwrites the u2 tile it was computed from (3 workgroups per CU)
   __shared__ __align__(16) uint16_t u2_s[kTfNHP * kTfRow];
   float* p_s = reinterpret_cast<float*>(u2_s);
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
   // the base skip's four source values are requested now (the fragment registers of GEMM 1 are free) and blended at the very end
   BilinearTaps taps = {};
   if constexpr (BASE != 0)
-    taps = bilinear_up4_fetch<BASE == 2>(a.centre, a.tab, a.H2 >> 1, a.W2 >> 1, b, 0, olive ? oy : 0, olive ? ox : 0);
+    taps = bilinear_up4_fetch<BASE - 1>(a.centre, a.tab, a.H2 >> 1, a.W2 >> 1, b, 0, olive ? oy : 0, olive ? ox : 0);
   __syncthreads();
 
   // ---- GEMM 2: P[pixel][tap] = u2[pixel][:] . wl[tap][:] ---------------------------------------------------------------------
@@ -244,8 +247,9 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
       if constexpr (Q == 0) {
         *op = s;
       } else {
-        reinterpret_cast<uint8_t*>(a.out8.p)[(long long)b * a.out8.sb + (long long)oy * a.out8.sy + (long long)ox * a.out8.sx] =
-            quantise_u8<Q>(s);
+        typedef typename SampleOf<PEAK>::type OT;
+        reinterpret_cast<OT*>(a.out8.p)[(long long)b * a.out8.sb + (long long)oy * a.out8.sy + (long long)ox * a.out8.sx] =
+            quantise<Q, PEAK, OT>(s);
       }
     }
   }
@@ -260,7 +264,7 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
 
 using namespace fcvsr;
 
-template <int Q, int BASE = 0>
+template <int Q, int BASE = 0, int PEAK = kPeak8>
 static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl, const float* bl,
                              int B, int H2, int W2, const fcvsr_view* out, const fcvsr_view* out8, void* stream,
                              const fcvsr_view* centre = nullptr, const float* tab = nullptr) {
@@ -280,9 +284,11 @@ static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* 
   a.centre = a.out;
   a.tab = tab;
   if (BASE != 0) {
-    FCVSR_CHECK_ARG(centre && centre->ptr && centre->c == 1 && centre->dtype == (BASE == 2 ? FCVSR_U8 : FCVSR_F32),
-                    "centre: one channel, f32 (uint8 for the _u8 entry point)");
-    FCVSR_CHECK_ARG(BASE != 2 || tab, "uint8 centre frame needs the table");
+    FCVSR_CHECK_ARG(centre && centre->ptr && centre->c == 1 &&
+                        centre->dtype == (BASE == 3 ? FCVSR_U16 : BASE == 2 ? FCVSR_U8 : FCVSR_F32),
+                    "centre: one channel, f32 (uint8 for the _u8 entry point, uint16 for _u16)");
+    FCVSR_CHECK_ARG(BASE < 2 || tab, "integer centre frame needs the table");
+    FCVSR_CHECK_ARG(BASE != 3 || ((uintptr_t)centre->ptr % 2) == 0, "uint16 centre frame: 2-byte aligned");
     FCVSR_CHECK_ARG(H2 % 2 == 0 && W2 % 2 == 0, "u1 is the x2 level of the centre frame: H2, W2 even");
     a.centre = to_view(*centre);
   }
@@ -300,8 +306,8 @@ static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* 
   nwg = nwg < 8 ? 8 : nwg / 8 * 8;
   dim3 grid(nwg < a.ntiles ? nwg : a.ntiles);
   hipStream_t st = (hipStream_t)stream;
-  if (u1->dtype == FCVSR_BF16) hipLaunchKernelGGL((tail_fused_kernel<true, Q, BASE>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((tail_fused_kernel<false, Q, BASE>), grid, dim3(256), 0, st, a);
+  if (u1->dtype == FCVSR_BF16) hipLaunchKernelGGL((tail_fused_kernel<true, Q, BASE, PEAK>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((tail_fused_kernel<false, Q, BASE, PEAK>), grid, dim3(256), 0, st, a);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }
@@ -335,4 +341,26 @@ extern "C" int fcvsr_tail_fused_u8(const fcvsr_view* u1, const void* w2, const f
   if (quantise == FCVSR_QUANT_TRUNCATE)
     return tail_fused_launch<FCVSR_QUANT_TRUNCATE>(u1, w2, b2, slope, wl, bl, B, H2, W2, base, out, stream);
   return tail_fused_launch<FCVSR_QUANT_ROUND>(u1, w2, b2, slope, wl, bl, B, H2, W2, base, out, stream);
+}
+
+extern "C" int fcvsr_tail_fused_base_u16(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                                         const float* bl, const fcvsr_view* centre, const float* tab, int B, int H2, int W2,
+                                         const fcvsr_view* out, int quantise, void* stream) {
+  FCVSR_CHECK_ARG(out && out->ptr && out->dtype == FCVSR_U16 && out->c == 1 && ((uintptr_t)out->ptr % 2) == 0,
+                  "out: one uint16 channel, 2-byte aligned");
+  FCVSR_CHECK_ARG(quantise == FCVSR_QUANT_TRUNCATE || quantise == FCVSR_QUANT_ROUND, "quantise: FCVSR_QUANT_TRUNCATE or _ROUND");
+  if (quantise == FCVSR_QUANT_TRUNCATE)
+    return tail_fused_launch<FCVSR_QUANT_TRUNCATE, 3, kPeak10>(u1, w2, b2, slope, wl, bl, B, H2, W2, nullptr, out, stream, centre, tab);
+  return tail_fused_launch<FCVSR_QUANT_ROUND, 3, kPeak10>(u1, w2, b2, slope, wl, bl, B, H2, W2, nullptr, out, stream, centre, tab);
+}
+
+extern "C" int fcvsr_tail_fused_u16(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                                    const float* bl, int B, int H2, int W2, const fcvsr_view* base, const fcvsr_view* out, int quantise,
+                                    void* stream) {
+  FCVSR_CHECK_ARG(out && out->ptr && out->dtype == FCVSR_U16 && out->c == 1 && ((uintptr_t)out->ptr % 2) == 0,
+                  "out: one uint16 channel, 2-byte aligned");
+  FCVSR_CHECK_ARG(quantise == FCVSR_QUANT_TRUNCATE || quantise == FCVSR_QUANT_ROUND, "quantise: FCVSR_QUANT_TRUNCATE or _ROUND");
+  if (quantise == FCVSR_QUANT_TRUNCATE)
+    return tail_fused_launch<FCVSR_QUANT_TRUNCATE, 0, kPeak10>(u1, w2, b2, slope, wl, bl, B, H2, W2, base, out, stream);
+  return tail_fused_launch<FCVSR_QUANT_ROUND, 0, kPeak10>(u1, w2, b2, slope, wl, bl, B, H2, W2, base, out, stream);
 }

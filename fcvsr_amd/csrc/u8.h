@@ -1,18 +1,44 @@
-// uint8 frame I/O helpers shared by the *_u8 entry points.
-//   in:  pixel k enters as tab[k], a 256-entry f32 table the host builds with torch (uint8 -> .float() / 255), so a kernel fed
-//        uint8 frames sees exactly the floats the f32 path is fed when the caller converts on the host;
-//   out: the f32 value v the f32 path stores becomes clamp(v, 0, 1) * 255.0f (f32 multiply), truncated toward zero or rounded
-//        half to even - the bytes the harness's torch passes (clamp, * 255, optional round, .to(uint8)) make from it.
+// Integer frame I/O helpers shared by the *_u8 and *_u16 entry points.  A sample format is a storage type and a peak:
+// uint8_t / 255 (8-bit frames) or uint16_t / 1023 (10-bit samples in 16-bit containers).
+//   in:  sample k enters as tab[min(k, PEAK)], a (PEAK + 1)-entry f32 table the host builds with torch (k -> .float() / PEAK), so a
+//        kernel fed integer frames sees exactly the floats the f32 path is fed when the caller converts on the host; the min keeps
+//        a 16-bit container's out-of-range samples inside the table (the float path's x.clamp(max=1023)) and folds away for uint8;
+//   out: the f32 value v the f32 path stores becomes clamp(v, 0, 1) * PEAK (f32 multiply), truncated toward zero or rounded
+//        half to even - the samples the harness's torch passes (clamp, * PEAK, optional round, cast) make from it.
 #pragma once
 #include "common.h"
 
 namespace fcvsr {
 
+constexpr int kPeak8 = 255, kPeak10 = 1023;
+
+// how a kernel's frames are stored: f32, or integer samples read through the table
+enum { kSrcF32 = 0, kSrcU8 = 1, kSrcU16 = 2 };
+
+template <int PEAK> struct SampleOf;
+template <> struct SampleOf<kPeak8> { typedef uint8_t type; };
+template <> struct SampleOf<kPeak10> { typedef uint16_t type; };
+
+template <int SRC> struct SrcFormat;
+template <> struct SrcFormat<kSrcU8> { typedef uint8_t type; static constexpr int peak = kPeak8; };
+template <> struct SrcFormat<kSrcU16> { typedef uint16_t type; static constexpr int peak = kPeak10; };
+
+template <int PEAK, class T>
+__device__ __forceinline__ float sample_value(const float* tab, T k) {
+  const int i = (int)k;
+  return tab[i < PEAK ? i : PEAK];
+}
+
+template <int Q, int PEAK, class T>
+__device__ __forceinline__ T quantise(float v) {
+  static_assert(Q == FCVSR_QUANT_TRUNCATE || Q == FCVSR_QUANT_ROUND, "quantise mode");
+  const float q = fminf(fmaxf(v, 0.f), 1.f) * (float)PEAK;
+  return (T)(Q == FCVSR_QUANT_TRUNCATE ? truncf(q) : rintf(q));
+}
+
 template <int Q>
 __device__ __forceinline__ uint8_t quantise_u8(float v) {
-  static_assert(Q == FCVSR_QUANT_TRUNCATE || Q == FCVSR_QUANT_ROUND, "quantise mode");
-  const float q = fminf(fmaxf(v, 0.f), 1.f) * 255.0f;
-  return (uint8_t)(Q == FCVSR_QUANT_TRUNCATE ? truncf(q) : rintf(q));
+  return quantise<Q, kPeak8, uint8_t>(v);
 }
 
 }  // namespace fcvsr

@@ -55,6 +55,10 @@ def band_masks_half(Q: int, H: int, W: int) -> torch.Tensor:
     return _MASKS[key]
 
 
+# integer frame formats of forward_u8 / forward_u16: the suffix of their entry points and the table their samples are read through
+_INT_IO = {torch.uint8: ("u8", hip.u8_table), torch.uint16: ("u16", hip.u16_table)}
+
+
 class Engine:
     def __init__(self, model):
         self._model = weakref.ref(model)
@@ -737,6 +741,26 @@ class Engine:
         with torch.no_grad():
             return self._forward_checked(x, m, hip.QUANTISE[quantise])
 
+    def forward_u16(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
+        """10-bit frames in, 10-bit SR frames out: x (B,T,C,H,W) uint16 (10-bit samples in 16-bit containers) -> (B,C,4H,4W)
+        uint16, the samples of ``q(clamp(forward(x_f32), 0, 1) * 1023)`` with x_f32 = ``x.clamp(max=1023).float() / 1023`` computed
+        on the host and q as in `forward_u8`.  The divisor is full scale (2^10 - 1); a sample above 1023 is read as 1023.  The same
+        kernels as the uint8 path, instantiated for 2-byte samples and the 1024-entry table of ``hip.u16_table``."""
+        if quantise not in hip.QUANTISE:
+            raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint16:
+            raise ValueError(f"expected a uint16 tensor, got {getattr(x, 'dtype', type(x))}")
+        m = self._model()
+        with torch.no_grad():
+            return self._forward_checked(x, m, hip.QUANTISE[quantise])
+
+    @staticmethod
+    def _copy_of(t, contiguous_only=False):
+        """A copy of t (or t itself if contiguous_only and it is contiguous); uint16 tensors are copied as int16 bits (hip.bits16)."""
+        c = hip.bits16(t)
+        c = c.contiguous() if contiguous_only else c.clone()
+        return c.view(t.dtype)
+
     def _forward_checked(self, x, m, quant=None):
         if x.dim() != 5:
             raise ValueError(f"expected (B,T,C,H,W) input, got {tuple(x.shape)}")
@@ -750,13 +774,14 @@ class Engine:
             raise ValueError("H and W must be multiples of 4 (3-level pyramid, reference BlockRCB :766-777)")
         dev = x.device
         with torch.cuda.device(dev):
-            x = x.contiguous() if quant is not None else x.contiguous().float()
+            x = self._copy_of(x, contiguous_only=True) if quant is not None else x.contiguous().float()
             self._refresh(dev)
             if quant is not None:
-                hip.u8_table(dev)                   # built once, on the caller's stream and outside any capture
+                _INT_IO[x.dtype][1](dev)            # the table: built once, on the caller's stream and outside any capture
             ns = max(1, min(int(getattr(m, "streams", 1)), B))
             flags = (bool(m.trunk16), bool(m.fold_f1), bool(m.fuse_tail), bool(m.fuse_rcb_l0))
-            # the input dtype and the quantise mode are part of every key: a uint8 call never replays an f32 call's graph
+            # the input dtype and the quantise mode are part of every key: a uint8 or uint16 call never replays an f32 call's graph,
+            # nor each other's
             cfg = (tuple(x.shape[1:]), self.precision, str(dev), self._pack_epoch, flags, x.dtype, quant)
             if ns > 1 and cfg not in self._warm:
                 # First pass of a configuration: re-packed weights, band masks and per-kernel attributes are created lazily
@@ -775,7 +800,7 @@ class Engine:
             key = (tuple(x.shape), ns) + cfg[1:]
             ent = self._graphs.get(key)
             if ent is None:
-                sx = x.clone()
+                sx = self._copy_of(x)
                 for _ in range(2):                       # eager warm-up on the capture configuration
                     self._run(sx, m, ns, dev, quant)
                 torch.cuda.synchronize(dev)
@@ -790,9 +815,9 @@ class Engine:
             else:
                 self._graphs.move_to_end(key)
             graph, sx, so = ent
-            sx.copy_(x)
+            hip.bits16(sx).copy_(hip.bits16(x))
             graph.replay()
-            return so.clone()
+            return self._copy_of(so)
 
     def _run(self, x, m, ns, dev, quant=None):
         B, T, Cimg, H, W = x.shape
@@ -803,7 +828,7 @@ class Engine:
         # kernels, so HBM-bound and MFMA-bound phases of different sub-batches overlap and launch tails are filled.
         # Worth +4-5 % at B=16.  (Kernels of several HW queues then share the CUs: see DESIGN.md "Multi-stream replays" for
         # the packed-FP32 / LDS hazard this exposed and how the build avoids it.)
-        out = self._new(dev, B, Cimg, 4 * H, 4 * W, dtype=torch.float32 if quant is None else torch.uint8)
+        out = self._new(dev, B, Cimg, 4 * H, 4 * W, dtype=torch.float32 if quant is None else x.dtype)
         cur = torch.cuda.current_stream(dev)
         while len(self._streams) < ns:
             self._streams.append(torch.cuda.Stream(device=dev))
@@ -819,10 +844,16 @@ class Engine:
         return out
 
     def _forward(self, x, m, B, T, Cimg, H, W, dev, out=None, quant=None):
-        """x: f32 frames, or uint8 frames with quant = hip.QUANT_TRUNCATE / QUANT_ROUND (the result is then uint8)."""
+        """x: f32 frames, or uint8 / uint16 frames with quant = hip.QUANT_TRUNCATE / QUANT_ROUND (the result then has x's dtype)."""
         n = m.n_feats
         L = lib()
         st = stream_ptr()
+        int_in = x.dtype in _INT_IO                              # integer frames: read through the table of their format
+        odt = x.dtype if quant is not None else torch.float32
+        if int_in:
+            sfx, table = _INT_IO[x.dtype]
+            tab = table(dev)
+            entry = lambda name: (getattr(L, f"{name}_{sfx}"), f"{name}_{sfx}")
         a_t = m.lrelu.weight
         # 16-bit activation storage with trunk16 (feat_extract multiplies in f16 - 8-bit pixels stay exact - and stores its
         # output in the mode's activation dtype)
@@ -831,11 +862,13 @@ class Engine:
         adt = self._tdt()
         cin = T * Cimg
         fe_dedicated = adt != torch.float32 and cin == 7 and n == 64
-        if x.dtype == torch.uint8 and not fe_dedicated:
+        if int_in and not fe_dedicated:
             # the generic feat_extract reads f32: the window is converted once (the same floats as a host-side conversion)
             xf = self._new(dev, *x.shape)
-            check(L.fcvsr_u8_to_f32(x.data_ptr(), hip.u8_table(dev).data_ptr(), x.numel(), xf.data_ptr(), st), "fcvsr_u8_to_f32")
+            fn, what = (L.fcvsr_u8_to_f32, "fcvsr_u8_to_f32") if sfx == "u8" else (L.fcvsr_u16_to_f32, "fcvsr_u16_to_f32")
+            check(fn(x.data_ptr(), tab.data_ptr(), x.numel(), xf.data_ptr(), st), what)
             x = xf
+            int_in = False
         xin = x.view(B, T * Cimg, H, W).permute(0, 2, 3, 1)      # (b,y,x,c) strided view of the NCHW frames
         f2 = self._new(dev, B, H, W, n, dtype=adt)
         if fe_dedicated:
@@ -849,10 +882,10 @@ class Engine:
             nb = 7 * n // 64
             P = C.c_void_p * nb
             ptrs = [p13[k, :B].data_ptr() for k in range(3)] + [f2.data_ptr()] + [p13[k, B:].data_ptr() for k in range(3)]
-            if x.dtype == torch.uint8:
-                check(L.fcvsr_feat_extract_u8(C.byref(xv), hip.u8_table(dev).data_ptr(), B, H, W, wf.data_ptr(), ptr(bf), nb,
-                                              P(*ptrs), (C.c_int64 * nb)(*([n] * nb)), (C.c_int32 * nb)(*([0] * nb)),
-                                              self._code(adt), st), "fcvsr_feat_extract_u8")
+            if int_in:
+                fn, what = entry("fcvsr_feat_extract")
+                check(fn(C.byref(xv), tab.data_ptr(), B, H, W, wf.data_ptr(), ptr(bf), nb, P(*ptrs), (C.c_int64 * nb)(*([n] * nb)),
+                         (C.c_int32 * nb)(*([0] * nb)), self._code(adt), st), what)
             else:
                 check(L.fcvsr_feat_extract(C.byref(xv), B, H, W, wf.data_ptr(), ptr(bf), nb, P(*ptrs),
                                            (C.c_int64 * nb)(*([n] * nb)), (C.c_int32 * nb)(*([0] * nb)), self._code(adt), st),
@@ -914,22 +947,25 @@ class Engine:
         u1 = self._new(dev, B, 2 * H, 2 * W, n, dtype=self._adt())
         self._conv("upconv1", [fz], u1, act=ACT_PRELU, slope_t=a_t, ps=True)
         if out is None:                                           # NCHW boundary tensor
-            out = self._new(dev, B, Cimg, 4 * H, 4 * W, dtype=torch.float32 if quant is None else torch.uint8)
+            out = self._new(dev, B, Cimg, 4 * H, 4 * W, dtype=odt)
         fuse_tail = (self.precision != "f32" and n == 64 and Cimg == 1 and self._par["upconv2.weight"].shape[-1] == 1
                      and m.fuse_tail)
-        # the fused tail evaluates the base skip itself from the centre frame (f32 frames -> f32 result, uint8 -> uint8): no base
-        # pass, and the uint8 result needs no f32 scratch
-        base_in_tail = fuse_tail and (x.dtype == torch.uint8) == (quant is not None)
-        # uint8 result otherwise: the f32 base and, where the last layer has no uint8 variant, the f32 result live in a scratch
+        # the fused tail evaluates the base skip itself from the centre frame (f32 frames -> f32 result, uint8 -> uint8, uint16 ->
+        # uint16): no base pass, and the integer result needs no f32 scratch
+        base_in_tail = fuse_tail and int_in == (quant is not None)
+        # integer result otherwise: the f32 base and, where the last layer has no integer variant, the f32 result live in a scratch
         res = out if (quant is None or base_in_tail) else self._new(dev, B, Cimg, 4 * H, 4 * W)
         out_v = res.permute(0, 2, 3, 1)
         centre = x[:, T // 2].permute(0, 2, 3, 1)                 # (B,H,W,Cimg) view of the centre LR frame
         cv, ov = view(centre), view(out_v)
         qv = view(out.permute(0, 2, 3, 1)) if quant is not None else None
+        if quant is not None:                                     # the last kernel's variant follows the result's dtype
+            osfx = _INT_IO[odt][0]
+            out_entry = lambda name: (getattr(L, f"{name}_{osfx}"), f"{name}_{osfx}")
         if not base_in_tail:
-            if x.dtype == torch.uint8:
-                check(L.fcvsr_bilinear_up4_u8(C.byref(cv), hip.u8_table(dev).data_ptr(), B, H, W, C.byref(ov), st),
-                      "fcvsr_bilinear_up4_u8")
+            if int_in:
+                fn, what = entry("fcvsr_bilinear_up4")
+                check(fn(C.byref(cv), tab.data_ptr(), B, H, W, C.byref(ov), st), what)
             else:
                 check(L.fcvsr_bilinear_up4(C.byref(cv), B, H, W, C.byref(ov), st), "fcvsr_bilinear_up4")
         if fuse_tail:
@@ -943,15 +979,16 @@ class Engine:
                 check(L.fcvsr_tail_fused_base(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl),
                                               C.byref(cv), B, 2 * H, 2 * W, C.byref(ov), st), "fcvsr_tail_fused_base")
             elif base_in_tail:
-                check(L.fcvsr_tail_fused_base_u8(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl),
-                                                 C.byref(cv), hip.u8_table(dev).data_ptr(), B, 2 * H, 2 * W, C.byref(qv), quant,
-                                                 st), "fcvsr_tail_fused_base_u8")
+                fn, what = entry("fcvsr_tail_fused_base")
+                check(fn(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), C.byref(cv), tab.data_ptr(),
+                         B, 2 * H, 2 * W, C.byref(qv), quant, st), what)
             elif quant is None:
                 check(L.fcvsr_tail_fused(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B,
                                          2 * H, 2 * W, C.byref(ov), st), "fcvsr_tail_fused")
             else:
-                check(L.fcvsr_tail_fused_u8(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B,
-                                            2 * H, 2 * W, C.byref(ov), C.byref(qv), quant, st), "fcvsr_tail_fused_u8")
+                fn, what = out_entry("fcvsr_tail_fused")
+                check(fn(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B, 2 * H, 2 * W, C.byref(ov),
+                         C.byref(qv), quant, st), what)
         else:
             u2 = self._new(dev, B, 4 * H, 4 * W, n, dtype=self._adt())
             self._conv("upconv2", [u1], u2, act=ACT_PRELU, slope_t=a_t, ps=True)
@@ -963,12 +1000,14 @@ class Engine:
                     check(L.fcvsr_conv_last(C.byref(u2v), wl.data_ptr(), ptr(self._par.get("conv_last0.bias")), B, 4 * H, 4 * W,
                                             Cimg, C.byref(ov), st), "fcvsr_conv_last")
                 else:
-                    check(L.fcvsr_conv_last_u8(C.byref(u2v), wl.data_ptr(), ptr(self._par.get("conv_last0.bias")), B, 4 * H,
-                                               4 * W, Cimg, C.byref(ov), C.byref(qv), quant, st), "fcvsr_conv_last_u8")
+                    fn, what = out_entry("fcvsr_conv_last")
+                    check(fn(C.byref(u2v), wl.data_ptr(), ptr(self._par.get("conv_last0.bias")), B, 4 * H, 4 * W, Cimg,
+                             C.byref(ov), C.byref(qv), quant, st), what)
             else:
                 self._conv("conv_last0", [u2], out_v, res=[out_v])
                 if quant is not None:
-                    check(L.fcvsr_quantise_u8(res.data_ptr(), res.numel(), quant, out.data_ptr(), st), "fcvsr_quantise_u8")
+                    fn, what = out_entry("fcvsr_quantise")
+                    check(fn(res.data_ptr(), res.numel(), quant, out.data_ptr(), st), what)
         if self.taps is not None:
-            self.taps["out"] = out.clone()
+            self.taps["out"] = self._copy_of(out)
         return out

@@ -9,6 +9,8 @@ GPUs, sharded by `fcvsr_amd.harness.sharding`.
 
 uint8 LR frames (decoded 8-bit video) take the model's uint8 path (`super_resolve_u8`): the window is read as bytes by the first
 kernels and the last kernel writes the quantised frames, with the same results as the float frames `lr.float() / 255`.
+uint16 LR frames (10-bit samples in 16-bit containers) take `super_resolve_u16` the same way: they stay 16-bit on the device, the
+results are uint16 arrays with samples in [0, 1023], equal to those of the float frames `lr.clamp(max=1023).float() / 1023`.
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ from typing import Iterable, List, Optional
 import numpy as np
 import torch
 
+from ..hip import bits16, frames_to_numpy
 from .metrics import psnr
 from .windows import window_indices
 
@@ -31,15 +34,46 @@ def pad_to_multiple(frames: torch.Tensor, mult: int = 4) -> torch.Tensor:
     return torch.nn.functional.pad(frames, (0, pw, 0, ph))
 
 
+_INT_FRAMES = (torch.uint8, torch.uint16)
+
+
+def _int_kind(t: torch.Tensor):
+    return t.dtype if t.dtype in _INT_FRAMES else None
+
+
 def _lr_frames(lr: torch.Tensor, dev) -> torch.Tensor:
-    """The padded LR sequence on the device: uint8 frames stay uint8 (the model's uint8 path), anything else becomes f32."""
-    return pad_to_multiple(lr if lr.dtype == torch.uint8 else lr.float(), 4).to(dev)
+    """The padded LR sequence on the device: uint8 / uint16 frames keep their dtype (the model's integer paths), anything else
+    becomes f32."""
+    if lr.dtype in _INT_FRAMES:
+        return pad_to_multiple(bits16(lr), 4).to(dev).view(lr.dtype)
+    return pad_to_multiple(lr.float(), 4).to(dev)
+
+
+def _windows(x: torch.Tensor, idx) -> torch.Tensor:
+    """(b, T, C, Hp, Wp) windows of the device sequence x, in x's dtype."""
+    xb = bits16(x)
+    return torch.stack([xb[j] for j in idx], 0).view(x.dtype)
+
+
+def super_resolve_int(model, win: torch.Tensor, quantise: str) -> torch.Tensor:
+    """The model's integer path for a uint8 or uint16 window."""
+    return model.super_resolve_u16(win, quantise) if win.dtype == torch.uint16 else model.super_resolve_u8(win, quantise)
+
+
+def _quantised(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> np.ndarray:
+    """The float path's frames the harness's way: clamp, * peak, optional round, integer cast (truncation)."""
+    sr = sr.clamp(0, 1) * peak
+    sr = sr.round() if quantise == "round" else sr
+    if peak == 255.0:
+        return sr.to(torch.uint8).cpu().numpy()
+    return sr.to(torch.int16).cpu().numpy().view(np.uint16)           # values in [0, 1023]: the bits of the uint16 cast
 
 
 @torch.no_grad()
 def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                            centres: Optional[Iterable[int]] = None, quantise: str = "truncate") -> np.ndarray:
-    """lr: (N,C,H,W) float in [0,1], or uint8 (host or device).  Returns uint8 (len(centres),C,4H,4W) SR frames."""
+    """lr: (N,C,H,W) float in [0,1], uint8, or uint16 (10-bit samples; host or device).  Returns uint8 (len(centres),C,4H,4W) SR
+    frames, uint16 for uint16 lr."""
     N, C, H, W = lr.shape
     dev = next(model.parameters()).device
     x = _lr_frames(lr, dev)
@@ -47,14 +81,11 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
     out: List[np.ndarray] = []
     for s in range(0, len(centres), batch):
         idx = [window_indices(i, num_frames, N, padding) for i in centres[s:s + batch]]
-        win = torch.stack([x[j] for j in idx], 0)                 # (b, 7, C, Hp, Wp)
-        if win.dtype == torch.uint8:                              # quantised by the model's last kernel
-            sr = model.super_resolve_u8(win, quantise)[:, :, :4 * H, :4 * W]
+        win = _windows(x, idx)                                    # (b, 7, C, Hp, Wp)
+        if win.dtype in _INT_FRAMES:                              # quantised by the model's last kernel
+            out.append(frames_to_numpy(super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]))
         else:
-            sr = model(win)[:, :, :4 * H, :4 * W]
-            sr = sr.clamp(0, 1) * 255.0
-            sr = (sr.round() if quantise == "round" else sr).to(torch.uint8)     # uint8 cast truncates
-        out.append(sr.cpu().numpy())
+            out.append(_quantised(model(win)[:, :, :4 * H, :4 * W], quantise))   # the integer cast truncates
     return np.concatenate(out, 0)
 
 
@@ -74,16 +105,21 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
-    lr: (N,C,H,W) float in [0,1], or uint8; hr: uint8 (N,C,4H,4W) (host or device).  Windows, padding, crop and quantisation are
-    those of `super_resolve_sequence`; each batch is scored straight from the model output (cropped by view, quantised in the
-    metric kernel - or, for uint8 lr, in the model's last kernel) by `device_metrics.frame_metrics`.  Without `return_frames` no
-    SR frame leaves the device."""
+    hr: (N,C,4H,4W) uint8 (8-bit frames, scored at peak 255) or uint16 (10-bit samples, scored by the 10-bit metric kernel at
+    peak 1023), host or device; it decides the bit depth of the run.  lr: (N,C,H,W) of hr's integer dtype, or float in [0,1] (then
+    quantised with hr's peak).  Windows, padding, crop and quantisation are those of `super_resolve_sequence`; each batch is
+    scored straight from the model output (cropped by view, quantised in the metric kernel - or, for integer lr, in the model's
+    last kernel) by `device_metrics.frame_metrics`.  Without `return_frames` no SR frame leaves the device; with it the frames
+    come back in hr's dtype."""
     from .device_metrics import frame_metrics
     N, C, H, W = lr.shape
     if tuple(hr.shape) != (N, C, 4 * H, 4 * W):
         raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, 4 * H, 4 * W)}, got {tuple(hr.shape)}")
-    if hr.dtype != torch.uint8:
-        raise ValueError(f"hr must be uint8, got {hr.dtype}")
+    if hr.dtype not in _INT_FRAMES:
+        raise ValueError(f"hr must be uint8 or uint16, got {hr.dtype}")
+    if lr.dtype in _INT_FRAMES and lr.dtype != hr.dtype:
+        raise ValueError(f"{lr.dtype} lr needs {lr.dtype} hr, got {hr.dtype}")
+    peak = 255.0 if hr.dtype == torch.uint8 else 1023.0
     if quantise not in ("truncate", "round"):
         raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
     dev = next(model.parameters()).device
@@ -91,23 +127,22 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     p_dev, s_dev, frames = [], [], []                             # per-batch device results, fetched once at the end
     for s in range(0, N, batch):
         idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
-        win = torch.stack([x[j] for j in idx], 0)                 # (b, 7, C, Hp, Wp)
-        if win.dtype == torch.uint8:
-            sr8 = model.super_resolve_u8(win, quantise)[:, :, :4 * H, :4 * W]
-            p, q = frame_metrics(sr8, hr[s:s + len(idx)].to(dev), crop_border=crop_border, quantise=None, convert_to=convert_to)
+        win = _windows(x, idx)                                    # (b, 7, C, Hp, Wp)
+        hr_b = bits16(hr[s:s + len(idx)]).to(dev).view(hr.dtype)
+        if win.dtype in _INT_FRAMES:
+            sr8 = super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]
+            p, q = frame_metrics(sr8, hr_b, crop_border=crop_border, quantise=None, convert_to=convert_to)
             p_dev.append(p)
             s_dev.append(q)
             if return_frames:
-                frames.append(sr8.cpu().numpy())
+                frames.append(frames_to_numpy(sr8))
             continue
         sr = model(win)[:, :, :4 * H, :4 * W]
-        p, q = frame_metrics(sr, hr[s:s + len(idx)].to(dev), crop_border=crop_border, quantise=quantise, convert_to=convert_to)
+        p, q = frame_metrics(sr, hr_b, crop_border=crop_border, quantise=quantise, convert_to=convert_to)
         p_dev.append(p)
         s_dev.append(q)
         if return_frames:
-            sr = sr.clamp(0, 1) * 255.0
-            sr = sr.round() if quantise == "round" else sr
-            frames.append(sr.to(torch.uint8).cpu().numpy())
+            frames.append(_quantised(sr, quantise, peak))
     psnr_np, ssim_np = torch.cat(p_dev).cpu().numpy(), torch.cat(s_dev).cpu().numpy()
     return SequenceScores(psnr_np, ssim_np, float(np.mean(psnr_np)), float(np.mean(ssim_np)),
                           np.concatenate(frames, 0) if return_frames else None)
@@ -141,7 +176,9 @@ class StreamedSuperResolver:
     * the last, partial batch is padded to the full batch size so that every call has the same shape (one hipGraph / one
       set of cached buffers in the engine), padded outputs are dropped;
     * uint8 sequences keep the staging buffers and the ring in uint8 (a quarter of the upload bytes) and take the model's
-      uint8 path: the quantised frames come from the last kernel, with no torch passes before the copy to the host.
+      uint8 path: the quantised frames come from the last kernel, with no torch passes before the copy to the host;
+    * uint16 sequences (10-bit samples) do the same in 16 bits (half the upload bytes) through `super_resolve_u16`, and the
+      results are uint16 arrays.
     `stats` (after run): frames uploaded, H2D / D2H bytes.
     """
 
@@ -157,21 +194,24 @@ class StreamedSuperResolver:
 
     @torch.no_grad()
     def run(self, sequences, rank: int = 0, world: int = 1):
-        """sequences: list of (N_s, C, H, W) float tensors in [0,1], or uint8 tensors (host; all of one frame size and dtype).
-        Returns {seq: (first_centre, uint8 array (n, C, 4H, 4W))} for the frames this rank owns."""
+        """sequences: list of (N_s, C, H, W) float tensors in [0,1], or uint8 / uint16 tensors (host; all of one frame size and
+        dtype).  Returns {seq: (first_centre, uint8 array (n, C, 4H, 4W))} for the frames this rank owns (uint16 arrays for
+        uint16 sequences)."""
         from .sharding import shard_sequences
         seq_lens = [int(s.shape[0]) for s in sequences]
         work = self.plan(seq_lens, rank, world)
         if not work:
             return {}
         C, H, W = sequences[0].shape[1:]
-        u8 = sequences[0].dtype == torch.uint8
+        idt = _int_kind(sequences[0])                                # uint8, uint16, or None for float frames
         for s in sequences:
             if tuple(s.shape[1:]) != (C, H, W):
                 raise ValueError("all sequences of one run must share the frame size")
-            if (s.dtype == torch.uint8) != u8:
-                raise ValueError("all sequences of one run must be uint8, or all float")
-        fdt = torch.uint8 if u8 else torch.float32
+            if _int_kind(s) != idt:
+                raise ValueError("all sequences of one run must be uint8, all uint16, or all float")
+        # uint16 frames are staged, gathered and copied as int16 views of the same bits (hip.bits16)
+        fdt = {None: torch.float32, torch.uint8: torch.uint8, torch.uint16: torch.int16}[idt]
+        odt = torch.int16 if idt == torch.uint16 else torch.uint8
         ph, pw = (-H) % 4, (-W) % 4
         Hp, Wp = H + ph, W + pw
         B, T = self.batch, self.num_frames
@@ -199,7 +239,7 @@ class StreamedSuperResolver:
                 slot_stage=[torch.zeros((max_new,), dtype=torch.int64, **pin) for _ in range(2)],
                 gidx_stage=[torch.zeros((B * T,), dtype=torch.int64, **pin) for _ in range(2)],
                 gidx_dev=[torch.zeros((B * T,), dtype=torch.int64, device=self.device) for _ in range(2)],
-                out_host=torch.empty((len(work), C, 4 * H, 4 * W), dtype=torch.uint8, **pin))
+                out_host=torch.empty((len(work), C, 4 * H, 4 * W), dtype=odt, **pin))
             self._buf_key = key
         ring, stage, slot_stage = self._bufs["ring"], self._bufs["stage"], self._bufs["slot_stage"]
         gidx_stage, gidx_dev, out_host = self._bufs["gidx_stage"], self._bufs["gidx_dev"], self._bufs["out_host"]
@@ -227,7 +267,7 @@ class StreamedSuperResolver:
                 slots.append(head)
                 head = (head + 1) % ring_n
             for q, (s, j) in enumerate(new):
-                buf[q, :, :H, :W].copy_(sequences[s][j])
+                buf[q, :, :H, :W].copy_(bits16(sequences[s][j]))
             up_frames += len(new)
             for k, row in enumerate(win_idx[bi]):
                 for t, f in enumerate(row):
@@ -261,9 +301,9 @@ class StreamedSuperResolver:
                     ready[(bi + 1) & 1].synchronize()                     # staging buffers of batch bi-1 have been consumed
                 fill(bi + 1)                                              # host work + upload overlap the model call below
             n = len(items)
-            if u8:                                                    # quantised by the model's last kernel
-                sr = self.model.super_resolve_u8(win, self.quantise)[:, :, :4 * H, :4 * W]
-                out_host[pos:pos + n].copy_(sr[:n], non_blocking=on_gpu)
+            if idt is not None:                                       # quantised by the model's last kernel
+                sr = super_resolve_int(self.model, win.view(idt), self.quantise)[:, :, :4 * H, :4 * W]
+                out_host[pos:pos + n].copy_(bits16(sr[:n]), non_blocking=on_gpu)
             else:
                 sr = self.model(win)[:, :, :4 * H, :4 * W]
                 sr = sr.clamp(0, 1) * 255.0
@@ -273,8 +313,10 @@ class StreamedSuperResolver:
         if on_gpu:
             torch.cuda.synchronize(self.device)
         self.stats = {"frames_uploaded": up_frames, "windows": len(work), "h2d_bytes": up_frames * C * Hp * Wp * ring.element_size(),
-                      "d2h_bytes": len(work) * C * 16 * H * W, "ring_slots": ring_n}
+                      "d2h_bytes": len(work) * C * 16 * H * W * out_host.element_size(), "ring_slots": ring_n}
         res, arr, k = {}, out_host.numpy(), 0
+        if idt == torch.uint16:
+            arr = arr.view(np.uint16)
         for (s, a, b) in shard_sequences(seq_lens, rank, world):
             res[s] = (a, arr[k:k + (b - a)].copy())
             k += b - a

@@ -4,9 +4,10 @@ from __future__ import annotations
 import numpy as np
 
 
-def psnr(img1: np.ndarray, img2: np.ndarray, crop_border: int = 4) -> float:
+def psnr(img1: np.ndarray, img2: np.ndarray, crop_border: int = 4, peak: float = 255.0) -> float:
     """PSNR on [0,255] images: 20*log10(255/sqrt(mse)), borders cropped first
-    (reference CVSR_train/metric/psnr_ssim.py:278-317)."""
+    (reference CVSR_train/metric/psnr_ssim.py:278-317).  `peak` replaces 255 for other sample ranges: 1023 for 10-bit frames
+    (full scale), or 1020 (255 * 4, HM's convention)."""
     a = np.asarray(img1, dtype=np.float64)
     b = np.asarray(img2, dtype=np.float64)
     if a.shape != b.shape:
@@ -17,7 +18,7 @@ def psnr(img1: np.ndarray, img2: np.ndarray, crop_border: int = 4) -> float:
     mse = np.mean((a - b) ** 2)
     if mse == 0:
         return float("inf")
-    return float(20.0 * np.log10(255.0 / np.sqrt(mse)))
+    return float(20.0 * np.log10(float(peak) / np.sqrt(mse)))
 
 
 def _gaussian_window(size: int = 11, sigma: float = 1.5) -> np.ndarray:
@@ -40,10 +41,10 @@ def _filter_valid(img: np.ndarray, g: np.ndarray) -> np.ndarray:
     return out
 
 
-def _ssim_plane(a: np.ndarray, b: np.ndarray) -> float:
+def _ssim_plane(a: np.ndarray, b: np.ndarray, peak: float = 255.0) -> float:
     """SSIM of one channel on [0,255] (reference CVSR_train/metric/psnr_ssim.py:320-350: 11x11 Gaussian, sigma 1.5,
-    C1 = (0.01*255)^2, C2 = (0.03*255)^2, border of 5 pixels dropped, mean of the map)."""
-    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    C1 = (0.01*255)^2, C2 = (0.03*255)^2, border of 5 pixels dropped, mean of the map); `peak` replaces 255 in C1 and C2."""
+    c1, c2 = (0.01 * peak) ** 2, (0.03 * peak) ** 2
     a = a.astype(np.float64)
     b = b.astype(np.float64)
     g = _gaussian_window()
@@ -63,10 +64,13 @@ def to_y_channel(img_hwc: np.ndarray) -> np.ndarray:
     return img @ np.array([24.966, 128.553, 65.481]) + 16.0
 
 
-def ssim(img1: np.ndarray, img2: np.ndarray, crop_border: int = 4, input_order: str = "HWC", convert_to=None) -> float:
+def ssim(img1: np.ndarray, img2: np.ndarray, crop_border: int = 4, input_order: str = "HWC", convert_to=None,
+         peak: float = 255.0) -> float:
     """Structural similarity on [0,255] images; channels averaged (reference CVSR_train/metric/psnr_ssim.py:353-398 for the
     single-plane Y images of the CVSR harness; mmedit/core/evaluation/metrics.py ssim for HWC / CHW and convert_to='Y').
-    Known answers: reference tests/test_metrics/test_metrics.py:79-106 (0.9130623, and 0.9987801 on Y)."""
+    Known answers: reference tests/test_metrics/test_metrics.py:79-106 (0.9130623, and 0.9987801 on Y).
+    `peak` sets the constants C1 = (0.01*peak)^2, C2 = (0.03*peak)^2 (1023 or 1020 for 10-bit frames); the Y conversion is
+    defined for [0,255] frames only."""
     a, b = np.asarray(img1), np.asarray(img2)
     if a.shape != b.shape:
         raise ValueError(f"Image shapes are different: {a.shape}, {b.shape}.")
@@ -76,6 +80,8 @@ def ssim(img1: np.ndarray, img2: np.ndarray, crop_border: int = 4, input_order: 
         a, b = a[..., None], b[..., None]
     elif input_order == "CHW":
         a, b = a.transpose(1, 2, 0), b.transpose(1, 2, 0)
+    if convert_to is not None and float(peak) != 255.0:
+        raise ValueError("convert_to is defined for [0,255] frames only (peak = 255)")
     if isinstance(convert_to, str) and convert_to.lower() == "y":
         a, b = to_y_channel(a)[..., None], to_y_channel(b)[..., None]
     elif convert_to is not None:
@@ -83,4 +89,4 @@ def ssim(img1: np.ndarray, img2: np.ndarray, crop_border: int = 4, input_order: 
     if crop_border:
         a = a[crop_border:-crop_border, crop_border:-crop_border, :]
         b = b[crop_border:-crop_border, crop_border:-crop_border, :]
-    return float(np.mean([_ssim_plane(a[..., c], b[..., c]) for c in range(a.shape[2])]))
+    return float(np.mean([_ssim_plane(a[..., c], b[..., c], float(peak)) for c in range(a.shape[2])]))

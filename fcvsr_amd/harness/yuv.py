@@ -1,9 +1,10 @@
-"""Planar 8-bit YUV 4:2:0 (I420) sequences: reader, writer, the reference's file naming, and 4x super-resolution from file to
-file (the test lists of reference CVSR_train/test_LD_freqCVSR_S_22.py:126-150 are raw sequences named ``Name_WxH_NF.yuv``).
+"""Planar 8-bit and 10-bit YUV 4:2:0 (I420) sequences: reader, writer, the reference's file naming, and 4x super-resolution from
+file to file (the test lists of reference CVSR_train/test_LD_freqCVSR_S_22.py:126-150 are raw sequences named ``Name_WxH_NF.yuv``).
 
-Frame layout: Y (H x W), then U and V (H/2 x W/2 each), one byte per sample, frames back to back.  Y is super-resolved by the
-model's uint8 path (windows of 7 frames, the reference's edge-replicate ``generate_input_index`` by default); U and V are
-up-sampled 4x by the bicubic chroma kernel (``hip.chroma_up4``).  10-bit sequences are not supported.
+Frame layout: Y (H x W), then U and V (H/2 x W/2 each), frames back to back; one byte per sample, or - ``bit_depth=10`` - two
+bytes, little-endian, the 10-bit value in the low bits (the JVET / HM ``_10bit`` raw files).  Y is super-resolved by the model's
+uint8 / uint16 path (windows of 7 frames, the reference's edge-replicate ``generate_input_index`` by default); U and V are
+up-sampled 4x by the bicubic chroma kernel (``hip.chroma_up4``).
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from .. import hip
-from .infer import pad_to_multiple
+from .infer import pad_to_multiple, super_resolve_int
 from .windows import window_indices
 
 
@@ -48,18 +49,37 @@ def _check_size(width: int, height: int):
         raise ValueError(f"4:2:0 frames need an even, positive width and height, got {width}x{height}")
 
 
+_BIT10 = re.compile(r"_10bit(?=_|\.|$)", re.IGNORECASE)
+
+
+def yuv_bit_depth(path: str) -> int:
+    """10 when the file name carries a ``_10bit`` token (any letter case, e.g. ``MarketPlace_1920x1080_60fps_10bit_420.yuv``),
+    else 8."""
+    return 10 if _BIT10.search(os.path.basename(path)) else 8
+
+
+def _sample_dtype(bit_depth: int):
+    if bit_depth not in (8, 10):
+        raise ValueError(f"bit_depth must be 8 or 10, got {bit_depth!r}")
+    return np.dtype(np.uint8) if bit_depth == 8 else np.dtype("<u2")
+
+
 def frame_bytes(width: int, height: int) -> int:
     _check_size(width, height)
     return width * height * 3 // 2
 
 
-def read_yuv420(path: str, width: int, height: int, frames: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+def read_yuv420(path: str, width: int, height: int, frames: Optional[int] = None,
+                bit_depth: int = 8) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Y (N,H,W), U and V (N,H/2,W/2) uint8 arrays of an I420 file: strided views of one read-only memory map (nothing is
-    copied).  `frames` reads the first N frames only."""
-    fb = frame_bytes(width, height)
+    copied).  `frames` reads the first N frames only.  ``bit_depth=10``: two bytes per sample, little-endian ``<u2`` views."""
+    dt = _sample_dtype(bit_depth)
+    fs = frame_bytes(width, height)                     # samples per frame
+    fb = fs * dt.itemsize
     size = os.path.getsize(path)
     if size % fb:
-        raise ValueError(f"{path}: {size} bytes is not a whole number of {width}x{height} 4:2:0 frames ({fb} bytes each)")
+        raise ValueError(f"{path}: {size} bytes is not a whole number of {width}x{height} {bit_depth}-bit 4:2:0 frames "
+                         f"({fb} bytes each)")
     n = size // fb
     if frames is not None:
         if frames < 0 or frames > n:
@@ -67,7 +87,7 @@ def read_yuv420(path: str, width: int, height: int, frames: Optional[int] = None
         n = frames
     if n == 0:
         raise ValueError(f"{path}: no frames")
-    mm = np.memmap(path, dtype=np.uint8, mode="r", shape=(n, fb))
+    mm = np.memmap(path, dtype=dt, mode="r", shape=(n, fs))
     ys, cs = width * height, (width // 2) * (height // 2)
     y = mm[:, :ys].reshape(n, height, width)
     u = mm[:, ys:ys + cs].reshape(n, height // 2, width // 2)
@@ -77,15 +97,14 @@ def read_yuv420(path: str, width: int, height: int, frames: Optional[int] = None
 
 def _write_frames(fh, y: np.ndarray, u: np.ndarray, v: np.ndarray):
     for i in range(y.shape[0]):
-        fh.write(np.ascontiguousarray(y[i]).tobytes())
-        fh.write(np.ascontiguousarray(u[i]).tobytes())
-        fh.write(np.ascontiguousarray(v[i]).tobytes())
+        for a in (y[i], u[i], v[i]):                      # uint16 planes go out little-endian whatever the host's byte order
+            fh.write(np.ascontiguousarray(a if a.dtype.itemsize == 1 else a.astype("<u2", copy=False)).tobytes())
 
 
 def _check_planes(y, u, v):
     y, u, v = (np.asarray(a) for a in (y, u, v))
-    if any(a.dtype != np.uint8 for a in (y, u, v)):
-        raise ValueError("planes must be uint8 (8-bit 4:2:0)")
+    if any(a.dtype != np.uint8 for a in (y, u, v)) and any(a.dtype != np.uint16 for a in (y, u, v)):
+        raise ValueError("planes must be all uint8 (8-bit 4:2:0) or all uint16 (10-bit 4:2:0)")
     if y.ndim == 2:
         y, u, v = y[None], u[None], v[None]
     if y.ndim != 3 or u.shape != v.shape or u.ndim != 3:
@@ -98,7 +117,8 @@ def _check_planes(y, u, v):
 
 
 def write_yuv420(path: str, y: np.ndarray, u: np.ndarray, v: np.ndarray) -> None:
-    """Write Y (N,H,W), U and V (N,H/2,W/2) uint8 planes (or single frames (H,W), (H/2,W/2)) as an I420 file."""
+    """Write Y (N,H,W), U and V (N,H/2,W/2) uint8 planes (or single frames (H,W), (H/2,W/2)) as an I420 file; uint16 planes
+    (10-bit samples) are written two bytes per sample, little-endian."""
     y, u, v = _check_planes(y, u, v)
     with open(path, "wb") as fh:
         _write_frames(fh, y, u, v)
@@ -106,36 +126,45 @@ def write_yuv420(path: str, y: np.ndarray, u: np.ndarray, v: np.ndarray) -> None
 
 @torch.no_grad()
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
-                         quantise: str = "truncate", num_frames: int = 7) -> dict:
+                         quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
-    Y: the frames go to the device once as uint8, windows of `num_frames` frames (`padding`, as `super_resolve_sequence`) run
-    through ``model.super_resolve_u8`` in batches of `batch`, rows / columns padded to a multiple of 4 as the reference pads
+    `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
+    name), for both files.  Y: the frames go to the device once in their integer dtype, windows of `num_frames` frames (`padding`,
+    as `super_resolve_sequence`) run through ``model.super_resolve_u8`` / ``super_resolve_u16`` in batches of `batch`, rows /
+    columns padded to a multiple of 4 as the reference pads
     270 -> 272 and cropped off again.  U, V: ``hip.chroma_up4`` (bicubic) on both planes of a batch in one launch.  Frames are
-    written in order as each batch completes.  Returns stats: frames, seconds, fps, bytes read and written."""
+    written in order as each batch completes.  Returns stats: frames, seconds, fps, bytes read and written.  No 10-bit
+    output sample exceeds 1023."""
     if getattr(model, "_img_ch", None) != 1:
         raise ValueError(f"super_resolve_yuv420 needs a one-channel (Y) model, got C={getattr(model, '_img_ch', None)}")
     if quantise not in hip.QUANTISE:
         raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
     if batch < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
-    y, u, v = read_yuv420(src, width, height)
+    y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
     N, H, W = y.shape
+    sdt, host_dt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.uint16, np.uint16)
+
+    def to_dev(a):
+        """Planes of the file on the device; uint16 samples as int16 bits (hip.bits16), viewed back for the kernels."""
+        return hip.bits16(torch.from_numpy(np.ascontiguousarray(a).astype(host_dt, copy=False))).to(dev)
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
-    x = pad_to_multiple(torch.from_numpy(np.ascontiguousarray(y)).to(dev)[:, None], 4)     # (N,1,Hp,Wp) uint8, zero padded
+    x = pad_to_multiple(to_dev(y)[:, None], 4)                                            # (N,1,Hp,Wp), zero padded
     written = 0
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             e = min(N, s + batch)
             idx = [window_indices(i, num_frames, N, padding) for i in range(s, e)]
-            win = torch.stack([x[j] for j in idx], 0)                                     # (b, 7, 1, Hp, Wp)
-            ysr = model.super_resolve_u8(win, quantise)[:, 0, :4 * H, :4 * W]
-            uv = torch.from_numpy(np.concatenate([u[s:e], v[s:e]], 0)).to(dev)            # (2b, H/2, W/2)
+            win = torch.stack([x[j] for j in idx], 0).view(sdt)                           # (b, 7, 1, Hp, Wp)
+            ysr = super_resolve_int(model, win, quantise)[:, 0, :4 * H, :4 * W]
+            uv = to_dev(np.concatenate([u[s:e], v[s:e]], 0)).view(sdt)                    # (2b, H/2, W/2)
             uvsr = hip.chroma_up4(uv)
-            ysr, uvsr = ysr.cpu().numpy(), uvsr.cpu().numpy()
+            ysr, uvsr = hip.frames_to_numpy(ysr), hip.frames_to_numpy(uvsr)
             _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
             written += ysr.nbytes + uvsr.nbytes
     dt = time.perf_counter() - t0
-    return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"), "bytes_read": N * frame_bytes(W, H),
+    return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
+            "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
             "bytes_written": written, "out_size": (4 * W, 4 * H)}

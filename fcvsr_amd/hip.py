@@ -10,14 +10,15 @@ import ctypes as C
 import os
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libfcvsr_hip.so")
 
-F32, BF16, F16, U8 = 0, 1, 2, 3
+F32, BF16, F16, U8, U16 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_PRELU = 0, 1, 2, 3
-_DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.uint8: U8}
+_DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.uint8: U8, torch.uint16: U16}
 
 
 class View(C.Structure):
@@ -187,6 +188,16 @@ SIGNATURES = {
     "fcvsr_quantise_u8": [_VP, C.c_longlong, _I, _VP, _VP],
     "fcvsr_chroma_up4": [_VP, _VP, _I, _I, _I, _VP, _VP],
     "fcvsr_clip_batch_u8": [_VP, _VP, _I, _I, _VP, _VP],
+    "fcvsr_frame_metrics_u16": [_VP, C.POINTER(C.c_int64), _I, _VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I,
+                                C.POINTER(C.c_double), C.c_double, _VP, _VP, C.c_longlong, _VP],
+    "fcvsr_feat_extract_u16": [_PV, _VP, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _VP],
+    "fcvsr_bilinear_up4_u16": [_PV, _VP, _I, _I, _I, _PV, _VP],
+    "fcvsr_tail_fused_u16": [_PV, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _PV, _PV, _I, _VP],
+    "fcvsr_tail_fused_base_u16": [_PV, _VP, _VP, _VP, _VP, _VP, _PV, _VP, _I, _I, _I, _PV, _I, _VP],
+    "fcvsr_conv_last_u16": [_PV, _VP, _VP, _I, _I, _I, _I, _PV, _PV, _I, _VP],
+    "fcvsr_u16_to_f32": [_VP, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_quantise_u16": [_VP, C.c_longlong, _I, _VP, _VP],
+    "fcvsr_chroma_up4_u16": [_VP, _VP, _I, _I, _I, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
@@ -403,13 +414,15 @@ def conv2d(srcs: Sequence[torch.Tensor], wpacked: torch.Tensor, ksize: int, cout
 
 
 QUANT_NONE, QUANT_TRUNCATE, QUANT_ROUND = 0, 1, 2
+PEAK10 = 1023                      # full scale of a 10-bit sample: the divisor of the uint16 path (2^10 - 1, not HM's 1020)
 
 
 def frame_metric_sums(sr: torch.Tensor, hr: torch.Tensor, quantise: int, crop_border: int, to_y: bool,
-                      window: Sequence[float]) -> torch.Tensor:
+                      window: Sequence[float], peak: Optional[float] = None) -> torch.Tensor:
     """fcvsr_frame_metrics: sr (N,C,H,W) uint8 (QUANT_NONE) or f32 (any strides), hr uint8 (N,C,H,W) on the same device.
-    Returns f64 (N, 2) on the device: per frame the squared-error sum over the PSNR region and the SSIM-map sum, both over all
-    scored planes.  Arguments are checked by the library (FCVSR_E_ARG -> HipError)."""
+    uint16 hr (10-bit frames) goes to fcvsr_frame_metrics_u16: sr is then uint16 or f32, and `peak` (default 1023) sets the SSIM
+    constants.  Returns f64 (N, 2) on the device: per frame the squared-error sum over the PSNR region and the SSIM-map sum, both
+    over all scored planes.  Arguments are checked by the library (FCVSR_E_ARG -> HipError)."""
     N, Cc, H, W = sr.shape
     to_y = int(bool(to_y))
     nbytes = lib().fcvsr_frame_metrics_scratch_bytes(N, Cc, H, W, crop_border, to_y)
@@ -417,6 +430,11 @@ def frame_metric_sums(sr: torch.Tensor, hr: torch.Tensor, quantise: int, crop_bo
     out = torch.empty((N, 2), dtype=torch.float64, device=sr.device)
     s_st, h_st = (C.c_int64 * 4)(*sr.stride()), (C.c_int64 * 4)(*hr.stride())
     win = (C.c_double * 11)(*[float(v) for v in window])
+    if hr.dtype == torch.uint16:
+        check(lib().fcvsr_frame_metrics_u16(sr.data_ptr(), s_st, quantise, hr.data_ptr(), h_st, N, Cc, H, W, crop_border, to_y, win,
+                                            float(PEAK10 if peak is None else peak), out.data_ptr(), scratch.data_ptr(),
+                                            scratch.numel() * 8, stream_ptr()), "fcvsr_frame_metrics_u16")
+        return out
     check(lib().fcvsr_frame_metrics(sr.data_ptr(), s_st, quantise, hr.data_ptr(), h_st, N, Cc, H, W, crop_border, to_y, win,
                                     out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, stream_ptr()), "fcvsr_frame_metrics")
     return out
@@ -439,23 +457,54 @@ def u8_table(device) -> torch.Tensor:
     return t
 
 
+_U16_TABLES = {}
+
+
+def u16_table(device) -> torch.Tensor:
+    """The 1024-entry f32 table of the uint16 (10-bit) entry points on `device`: entry k is the f32 that ``k.float() / 1023`` gives
+    on the host.  The kernels clamp the index to 1023, so a sample above 1023 in its 16-bit container reads the last entry (the
+    float path's ``x.clamp(max=1023)``).  Built once per device, outside stream fan-out and graph capture, as `u8_table`."""
+    key = str(torch.device(device))
+    t = _U16_TABLES.get(key)
+    if t is None:
+        t = (torch.arange(PEAK10 + 1, dtype=torch.int32).float() / PEAK10).to(device)
+        torch.cuda.synchronize(device)          # readers on any stream find it complete
+        _U16_TABLES[key] = t
+    return t
+
+
+def bits16(t: torch.Tensor) -> torch.Tensor:
+    """torch's uint16 has thin operator coverage on the device: uint16 tensors are padded, stacked, gathered and copied as int16
+    views of the same bits (no value is converted; view the result back with ``.view(torch.uint16)``).  Every other dtype is
+    returned as it is."""
+    return t.view(torch.int16) if t.dtype == torch.uint16 else t
+
+
+def frames_to_numpy(t: torch.Tensor) -> np.ndarray:
+    """Host numpy copy of a tensor of frames; uint16 frames travel as int16 bits (`bits16`) and come back as uint16."""
+    a = bits16(t).cpu().numpy()
+    return a.view(np.uint16) if t.dtype == torch.uint16 else a
+
+
 def chroma_up4(planes: torch.Tensor) -> torch.Tensor:
-    """fcvsr_chroma_up4: (P,h,w) uint8 planes on the HIP device -> (P,4h,4w) uint8, one launch.  Defined as
-    ``F.interpolate(p.float() / 255, scale_factor=4, mode="bicubic", align_corners=False)``, clamp(0, 1), * 255, rounded half to
-    even (within one code value of that torch expression: the kernel's f32 sums are not torch's)."""
-    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or planes.dim() != 3:
-        raise ValueError(f"expected uint8 (P,h,w) planes, got {getattr(planes, 'dtype', type(planes))} "
+    """fcvsr_chroma_up4 / fcvsr_chroma_up4_u16: (P,h,w) uint8 or uint16 (10-bit samples) planes on the HIP device -> (P,4h,4w) of
+    the same dtype, one launch.  Defined as ``F.interpolate(p.float() / peak, scale_factor=4, mode="bicubic",
+    align_corners=False)``, clamp(0, 1), * peak, rounded half to even, with peak = 255 or 1023 (within one code value of that torch
+    expression: the kernel's f32 sums are not torch's).  uint16 samples above 1023 read as 1023."""
+    if not isinstance(planes, torch.Tensor) or planes.dtype not in (torch.uint8, torch.uint16) or planes.dim() != 3:
+        raise ValueError(f"expected uint8 or uint16 (P,h,w) planes, got {getattr(planes, 'dtype', type(planes))} "
                          f"{tuple(getattr(planes, 'shape', ()))}")
     if not planes.is_cuda:
         raise RuntimeError("chroma_up4 runs on the HIP device only (there is no CPU fallback)")
     P, h, w = planes.shape
-    src = planes.contiguous()
-    out = torch.empty((P, 4 * h, 4 * w), dtype=torch.uint8, device=planes.device)
+    src = bits16(planes).contiguous()
+    out = torch.empty((P, 4 * h, 4 * w), dtype=planes.dtype, device=planes.device)
     if out.numel() == 0:
         return out
+    fn, name, table = ((lib().fcvsr_chroma_up4, "fcvsr_chroma_up4", u8_table) if planes.dtype == torch.uint8 else
+                       (lib().fcvsr_chroma_up4_u16, "fcvsr_chroma_up4_u16", u16_table))
     with torch.cuda.device(planes.device):
-        check(lib().fcvsr_chroma_up4(src.data_ptr(), u8_table(planes.device).data_ptr(), P, h, w, out.data_ptr(), stream_ptr()),
-              "fcvsr_chroma_up4")
+        check(fn(src.data_ptr(), table(planes.device).data_ptr(), P, h, w, out.data_ptr(), stream_ptr()), name)
     return out
 
 

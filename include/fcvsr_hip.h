@@ -31,6 +31,7 @@ extern "C" {
 enum { FCVSR_E_ARG = -1, FCVSR_E_UNSUPPORTED = -2, FCVSR_E_NOGPU = -3 };
 enum { FCVSR_F32 = 0, FCVSR_BF16 = 1, FCVSR_F16 = 2 };
 enum { FCVSR_U8 = 3 };   /* uint8 frames: accepted only by the *_u8 entry points */
+enum { FCVSR_U16 = 4 };  /* 10-bit samples in uint16 containers: accepted only by the *_u16 entry points */
 enum { FCVSR_ACT_NONE = 0, FCVSR_ACT_RELU = 1, FCVSR_ACT_LEAKY = 2, FCVSR_ACT_PRELU = 3 };
 
 /* strided (b,y,x,c) window; strides in ELEMENTS of `dtype`; ptr already points at element (0,0,0,0) */
@@ -38,7 +39,7 @@ typedef struct fcvsr_view {
   void*   ptr;
   int64_t sb, sy, sx, sc;
   int32_t c;      /* number of channels in this window */
-  int32_t dtype;  /* FCVSR_F32 | FCVSR_BF16 | FCVSR_F16 (| FCVSR_U8) */
+  int32_t dtype;  /* FCVSR_F32 | FCVSR_BF16 | FCVSR_F16 (| FCVSR_U8 | FCVSR_U16) */
 } fcvsr_view;
 
 /* One 2-D convolution with fused epilogue.  Replaces nn.Conv2d call sites of the path
@@ -513,6 +514,14 @@ long long fcvsr_frame_metrics_scratch_bytes(int N, int C, int H, int W, int crop
 int fcvsr_frame_metrics(const void* sr, const int64_t* host_sr_strides, int quantise, const uint8_t* hr,
                         const int64_t* host_hr_strides, int N, int C, int H, int W, int crop_border, int to_y,
                         const double* host_window, double* out, void* scratch, long long scratch_bytes, void* stream);
+/* The same for 10-bit frames: hr uint16; sr uint16 (FCVSR_QUANT_NONE) or f32 quantised as clamp(v, 0, 1) * 1023.0f.  peak sets
+ * the SSIM constants C1 = (0.01*peak)^2, C2 = (0.03*peak)^2 (1023 full scale; HM's 1020 if the caller scores that way; the host
+ * makes PSNR = 20 log10(peak / sqrt(mse)) from out[2n]).  to_y is not defined for 10-bit frames: to_y != 0 is FCVSR_E_ARG.
+ * Scratch size as fcvsr_frame_metrics_scratch_bytes(..., to_y = 0). */
+int fcvsr_frame_metrics_u16(const void* sr, const int64_t* host_sr_strides, int quantise, const uint16_t* hr,
+                            const int64_t* host_hr_strides, int N, int C, int H, int W, int crop_border, int to_y,
+                            const double* host_window, double peak, double* out, void* scratch, long long scratch_bytes,
+                            void* stream);
 
 /* ---- uint8 frame I/O (8-bit decoded frames in, 8-bit SR frames out; contract: Engine.forward_u8 in fcvsr_amd/engine.py) -------
  * tab: a device table of 256 floats, tab[k] = the f32 of pixel value k (the host builds it with torch as
@@ -545,6 +554,30 @@ int fcvsr_quantise_u8(const float* src, long long n, int quantise, uint8_t* dst,
  * F.interpolate(p.float() / 255, scale_factor=4, mode="bicubic", align_corners=False), clamp(0, 1), * 255, rounded half to even;
  * dst 4-byte aligned. */
 int fcvsr_chroma_up4(const uint8_t* src, const float* tab, int P, int h, int w, uint8_t* dst, void* stream);
+
+/* ---- 10-bit frame I/O (10-bit samples in little-endian 16-bit containers in, 10-bit SR samples out; contract:
+ * Engine.forward_u16 in fcvsr_amd/engine.py).  The entry points mirror the uint8 ones one for one, with
+ *   views of dtype FCVSR_U16 (strides in ELEMENTS, pointers 2-byte aligned);
+ *   tab: a device table of 1024 floats, tab[k] = the f32 of sample k (torch: k -> .float() / 1023; full scale 2^10 - 1), 16-byte
+ *        aligned.  A sample above 1023 reads tab[1023] (an index clamp, not a mask): the float path's x.clamp(max=1023);
+ *   quantise: an f32 result v is stored as clamp(v, 0, 1) * 1023.0f (f32), truncated toward zero / rounded half to even. */
+int fcvsr_feat_extract_u16(const fcvsr_view* x, const float* tab, int B, int H, int W, const void* w, const float* bias, int n_blk,
+                           void* const* dst, const int64_t* dst_pix_stride, const int32_t* dst_ch_off, int dst_dtype, void* stream);
+int fcvsr_bilinear_up4_u16(const fcvsr_view* src, const float* tab, int B, int H, int W, const fcvsr_view* dst, void* stream);
+int fcvsr_tail_fused_u16(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                         const float* bl, int B, int H2, int W2, const fcvsr_view* base, const fcvsr_view* out, int quantise,
+                         void* stream);
+/* out gets the samples of fcvsr_bilinear_up4_u16 followed by fcvsr_tail_fused_u16 */
+int fcvsr_tail_fused_base_u16(const fcvsr_view* u1, const void* w2, const float* b2, const float* slope, const void* wl,
+                              const float* bl, const fcvsr_view* centre, const float* tab, int B, int H2, int W2,
+                              const fcvsr_view* out, int quantise, void* stream);
+int fcvsr_conv_last_u16(const fcvsr_view* u, const void* w, const float* bias, int B, int H, int W, int C, const fcvsr_view* base,
+                        const fcvsr_view* out, int quantise, void* stream);
+int fcvsr_u16_to_f32(const uint16_t* src, const float* tab, long long n, float* dst, void* stream);
+int fcvsr_quantise_u16(const float* src, long long n, int quantise, uint16_t* dst, void* stream);
+/* P dense uint16 planes (P,h,w) -> (P,4h,4w): the bicubic kernel of fcvsr_chroma_up4 on k / 1023, clamp(0, 1), * 1023, rounded
+ * half to even; the four samples of a thread are one 8-byte store: dst 8-byte aligned. */
+int fcvsr_chroma_up4_u16(const uint16_t* src, const float* tab, int P, int h, int w, uint16_t* dst, void* stream);
 
 /* ---- training batches from device-resident uint8 sequences (reference CVSR_train/opt/data_LD_LR.py:248-344: RandomCrop, Augment,
  * ToTensor; the draws are made on the host, contract: fcvsr_amd/train/data.py) -----------------------------------------------
