@@ -62,7 +62,7 @@ class DivEnhStageArgs(C.Structure):
 
 
 class CropDesc(C.Structure):
-    """fcvsr_crop_desc: one output plane of fcvsr_clip_batch_u8 (``numpy.dtype(CropDesc)`` is its array form)."""
+    """fcvsr_crop_desc: one output plane of fcvsr_clip_batch_u8 / _u16 (``numpy.dtype(CropDesc)`` is its array form)."""
     _fields_ = [("src", C.c_void_p), ("pitch", C.c_int32), ("top", C.c_int32), ("left", C.c_int32), ("flags", C.c_int32)]
 
 
@@ -188,6 +188,7 @@ SIGNATURES = {
     "fcvsr_quantise_u8": [_VP, C.c_longlong, _I, _VP, _VP],
     "fcvsr_chroma_up4": [_VP, _VP, _I, _I, _I, _VP, _VP],
     "fcvsr_clip_batch_u8": [_VP, _VP, _I, _I, _VP, _VP],
+    "fcvsr_clip_batch_u16": [_VP, _VP, _I, _I, _VP, _VP],
     "fcvsr_frame_metrics_u16": [_VP, C.POINTER(C.c_int64), _I, _VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I,
                                 C.POINTER(C.c_double), C.c_double, _VP, _VP, C.c_longlong, _VP],
     "fcvsr_feat_extract_u16": [_PV, _VP, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _VP],
@@ -508,12 +509,19 @@ def chroma_up4(planes: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def clip_batch(desc: torch.Tensor, s: int, out: torch.Tensor) -> torch.Tensor:
-    """fcvsr_clip_batch_u8: `desc` is a uint8 tensor on the HIP device holding P = numel / sizeof(CropDesc) descriptors (the bytes
-    of a ``numpy.dtype(CropDesc)`` array), `out` a contiguous f32 tensor of P * s * s elements on the same device: plane p becomes
-    the s x s window descriptor p names, flipped / transposed by its flags, pixel k as ``u8_table[k]``.  One launch on the current
-    stream.  The descriptors are device memory nobody checks here: the caller keeps every window inside its plane (and keeps
+_CLIP_BATCH = {torch.uint8: ("fcvsr_clip_batch_u8", u8_table), torch.uint16: ("fcvsr_clip_batch_u16", u16_table)}
+
+
+def clip_batch(desc: torch.Tensor, s: int, out: torch.Tensor, dtype: torch.dtype = torch.uint8) -> torch.Tensor:
+    """fcvsr_clip_batch_u8 / fcvsr_clip_batch_u16: `desc` is a uint8 tensor on the HIP device holding P = numel / sizeof(CropDesc)
+    descriptors (the bytes of a ``numpy.dtype(CropDesc)`` array), `out` a contiguous f32 tensor of P * s * s elements on the same
+    device: plane p becomes the s x s window descriptor p names, flipped / transposed by its flags, pixel k as ``u8_table[k]``.
+    `dtype` is the sample type of the source planes: ``torch.uint16`` reads every descriptor as a window of 2-byte samples (`src`
+    2-byte aligned, `pitch` / `top` / `left` in samples) and gives pixel k as ``u16_table[min(k, 1023)]``.  One launch on the
+    current stream.  The descriptors are device memory nobody checks here: the caller keeps every window inside its plane (and keeps
     `desc` and the source planes alive until the launch has run)."""
+    if dtype not in _CLIP_BATCH:
+        raise ValueError(f"dtype: the source planes are torch.uint8 or torch.uint16, got {dtype!r}")
     for name, t, dt in (("desc", desc, torch.uint8), ("out", out, torch.float32)):
         if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous():
             raise ValueError(f"{name}: expected a contiguous {dt} tensor, got {getattr(t, 'dtype', type(t))}")
@@ -524,7 +532,7 @@ def clip_batch(desc: torch.Tensor, s: int, out: torch.Tensor) -> torch.Tensor:
     P, rem = divmod(desc.numel(), C.sizeof(CropDesc))
     if rem or P == 0 or out.numel() != P * s * s:
         raise ValueError(f"{desc.numel()} descriptor bytes / {out.numel()} output elements do not make whole {s} x {s} planes")
+    entry, table = _CLIP_BATCH[dtype]
     with torch.cuda.device(out.device):
-        check(lib().fcvsr_clip_batch_u8(desc.data_ptr(), u8_table(out.device).data_ptr(), P, s, out.data_ptr(), stream_ptr()),
-              "fcvsr_clip_batch_u8")
+        check(getattr(lib(), entry)(desc.data_ptr(), table(out.device).data_ptr(), P, s, out.data_ptr(), stream_ptr()), entry)
     return out

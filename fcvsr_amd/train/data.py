@@ -1,4 +1,4 @@
-"""Training batches built on the device from resident 8-bit sequences.
+"""Training batches built on the device from resident 8-bit or 10-bit sequences.
 
 The reference loader (CVSR_train/opt/data_LD_LR.py:83-127, :248-344) picks a 7-frame window of a sequence, crops it at a random
 place, flips / transposes it and converts it to float on a CPU worker, per clip.  Here the uint8 sequences go to the device once;
@@ -6,6 +6,11 @@ per batch the host only makes the draws (`DeviceClipSampler.plan`) and fills one
 (`hip.clip_batch`, csrc/clip_batch.hip) cuts, flips, transposes and converts every LR plane of the batch, a second launch every HR
 plane.  The values are the reference chain's bit for bit: `apply_plan_host` is that chain (`random_crop` / `augment` / `to_tensor`
 of `train/step.py`, fed the planned draws) and is what the kernel is tested against.
+
+10-bit sequences are uint16 containers (peak 1023): the same sampler, the same descriptors with `pitch` / `top` / `left` in samples,
+the 2-byte kernel and the 1024-entry table of `hip.u16_table`.  The reference has no 10-bit loader; the specification is this
+project's float contract for 10-bit frames, ``min(k, 1023).float() / 1023`` (`to_tensor`), the floats `super_resolve_u16` feeds the
+network for the same samples.  All sequences of one sampler share one dtype.
 """
 from __future__ import annotations
 
@@ -33,21 +38,25 @@ class BatchPlan(NamedTuple):
     rot90: np.ndarray    # the reference's name for transpose(0, 2, 1)
 
 
-def _as_u8(a, what: str):
+BIT_DEPTH = {torch.uint8: 8, torch.uint16: 10}
+
+
+def _as_frames(a, what: str):
     if isinstance(a, np.ndarray):
-        if a.dtype != np.uint8:
-            raise ValueError(f"{what}: frames must be uint8, got {a.dtype}")
-        a = torch.from_numpy(np.ascontiguousarray(a))
-    if not isinstance(a, torch.Tensor) or a.dtype != torch.uint8:
-        raise ValueError(f"{what}: frames must be a uint8 tensor or array, got {getattr(a, 'dtype', type(a))}")
+        if a.dtype.kind != "u" or a.dtype.itemsize > 2:
+            raise ValueError(f"{what}: frames must be uint8 or uint16, got {a.dtype}")
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=a.dtype.newbyteorder("=")))
+    if not isinstance(a, torch.Tensor) or a.dtype not in BIT_DEPTH:
+        raise ValueError(f"{what}: frames must be a uint8 or uint16 tensor or array, got {getattr(a, 'dtype', type(a))}")
     if a.dim() != 4:
         raise ValueError(f"{what}: expected (N,C,H,W), got {tuple(a.shape)}")
     return a
 
 
 def check_sequences(sequences, crop: int, frames: int, start: str):
-    """The constructor's checks (ValueError): uint8 (N,C,H,W) / (N,C,4H,4W) pairs of one channel count, frames larger than the crop
-    in both axes (the reference's randint(0, h - size) has an exclusive high end), enough frames for the window and the start mode."""
+    """The constructor's checks (ValueError): uint8 or uint16 (N,C,H,W) / (N,C,4H,4W) pairs of one dtype (LR and HR of every
+    sequence alike) and one channel count, frames larger than the crop in both axes (the reference's randint(0, h - size) has an
+    exclusive high end), enough frames for the window and the start mode."""
     if start not in STARTS:
         raise ValueError(f"start must be one of {STARTS}, got {start!r}")
     if crop <= 0 or crop % 4:
@@ -58,7 +67,12 @@ def check_sequences(sequences, crop: int, frames: int, start: str):
         raise ValueError("no sequences")
     out = []
     for i, pair in enumerate(sequences):
-        lr, hr = _as_u8(pair[0], f"sequence {i} lr"), _as_u8(pair[1], f"sequence {i} hr")
+        lr, hr = _as_frames(pair[0], f"sequence {i} lr"), _as_frames(pair[1], f"sequence {i} hr")
+        if lr.dtype != hr.dtype:
+            raise ValueError(f"sequence {i}: lr is {lr.dtype}, hr is {hr.dtype}; a pair must be all uint8 or all uint16")
+        if out and lr.dtype != out[0][0].dtype:
+            raise ValueError(f"sequence {i}: {lr.dtype} frames, sequence 0 has {out[0][0].dtype}; all sequences of a sampler must "
+                             "be uint8 or all uint16")
         N, C, H, W = lr.shape
         if tuple(hr.shape) != (N, C, 4 * H, 4 * W):
             raise ValueError(f"sequence {i}: hr must be 4x the lr frames, (N,C,4H,4W) = {(N, C, 4 * H, 4 * W)}, got {tuple(hr.shape)}")
@@ -135,12 +149,13 @@ class _Replay:
 def apply_plan_host(sequences, batch_plan: BatchPlan, crop: int, frames: int = 7) -> Dict[str, torch.Tensor]:
     """The batch of `batch_plan` made on the CPU by the reference chain, plane by plane: `random_crop`, `augment`, `to_tensor` with
     the planned draws in place of the random ones.  Returns {'lr_imgs': (b,C,frames,crop,crop), 'hr_imgs': (b,C,1,4crop,4crop)}
-    f32 CPU tensors.  This is the specification of the device path (which never calls it) and a debugging aid."""
+    f32 CPU tensors.  uint8 sequences are the reference's k / 255; uint16 (10-bit) ones give min(k, 1023) / 1023 (`to_tensor`).
+    This is the specification of the device path (which never calls it) for both depths, and a debugging aid."""
     lrs, hrs = [], []
     for k in range(len(batch_plan.item)):
         lr, hr = sequences[int(batch_plan.item[k])]
-        lr = lr.cpu().numpy() if isinstance(lr, torch.Tensor) else np.asarray(lr)
-        hr = hr.cpu().numpy() if isinstance(hr, torch.Tensor) else np.asarray(hr)
+        lr = hip.frames_to_numpy(lr) if isinstance(lr, torch.Tensor) else np.asarray(lr)
+        hr = hip.frames_to_numpy(hr) if isinstance(hr, torch.Tensor) else np.asarray(hr)
         first = int(batch_plan.first[k])
         centre = first + frames // 2
         lr_c, hr_c = [], []
@@ -161,15 +176,17 @@ _DESC = np.dtype(hip.CropDesc)
 _RING = 4
 
 
-def fill_descs(d: np.ndarray, lr_ptr, hr_ptr, first, top, left, flags, H, W, F: int, C: int) -> None:
+def fill_descs(d: np.ndarray, lr_ptr, hr_ptr, first, top, left, flags, H, W, F: int, C: int, itemsize: int = 1) -> None:
     """Write the b*F*C LR descriptors (clip, frame, channel order: the model's (b,F,C,s,s) layout) and then the b*C HR descriptors
     of a batch into `d` (a numpy.dtype(hip.CropDesc) array).  Per clip: lr_ptr / hr_ptr = first byte of its sequence's dense
-    (N,C,H,W) / (N,C,4H,4W) uint8 frames, H x W = its LR frame size; the HR window is the LR one times 4, on frame first + F // 2."""
+    (N,C,H,W) / (N,C,4H,4W) frames, H x W = its LR frame size; the HR window is the LR one times 4, on frame first + F // 2.
+    itemsize: bytes per sample (1: uint8, 2: uint16).  The `src` byte addresses scale with it; `pitch` / `top` / `left` are in
+    samples whatever it is."""
     b = len(first)
     n_lr = b * F * C
     lr, hr = d[:n_lr].reshape(b, F, C), d[n_lr:].reshape(b, C)
     lr_ptr, hr_ptr = np.asarray(lr_ptr, dtype=np.uint64), np.asarray(hr_ptr, dtype=np.uint64)
-    plane = (H * W).astype(np.uint64)
+    plane = (H * W).astype(np.uint64) * np.uint64(itemsize)                                      # bytes of one LR plane
     frame = (first[:, None] + np.arange(F)[None, :]).astype(np.uint64)                           # (b, F)
     chan = np.arange(C, dtype=np.uint64)
     lr["src"] = lr_ptr[:, None, None] + (frame[:, :, None] * np.uint64(C) + chan[None, None, :]) * plane[:, None, None]
@@ -180,9 +197,11 @@ def fill_descs(d: np.ndarray, lr_ptr, hr_ptr, first, top, left, flags, H, W, F: 
 
 
 class DeviceClipSampler:
-    """Random training clips cut on the device from uint8 sequences that live there.
+    """Random training clips cut on the device from uint8 or uint16 (10-bit) sequences that live there.
 
-    sequences: (lr_u8 (N,C,H,W), hr_u8 (N,C,4H,4W)) pairs, torch tensors or numpy arrays, host or device; uploaded once and kept.
+    sequences: (lr (N,C,H,W), hr (N,C,4H,4W)) pairs, all uint8 or all uint16, torch tensors or numpy arrays, host or device;
+    uploaded once and kept (uint16 frames as int16 views of the same bits, `hip.bits16`).  `dtype` is their torch dtype, `bit_depth`
+    8 or 10; a 10-bit pixel k becomes ``min(k, 1023) / 1023``, the float `super_resolve_u16` feeds the network for it.
     An item is a sequence.  `sampler(epoch)` yields {'lr_imgs': (b,C,frames,crop,crop), 'hr_imgs': (b,C,1,4crop,4crop)} f32 on the
     device - the `batches` callable of `fit`.  The draws of (seed, epoch, item) are those of `item_draws`, whatever `world`, `rank`
     and `batch` are; the epoch order and its sharding over ranks are `make_plan`'s: every rank yields the same number of batches of
@@ -207,11 +226,13 @@ class DeviceClipSampler:
                                "apply_plan_host is the CPU specification)")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self.sequences = [(lr.to(self.device).contiguous(), hr.to(self.device).contiguous()) for lr, hr in seqs]
+        self.dtype = seqs[0][0].dtype
+        self.bit_depth = BIT_DEPTH[self.dtype]
+        self.sequences = [(hip.bits16(lr).to(self.device).contiguous(), hip.bits16(hr).to(self.device).contiguous()) for lr, hr in seqs]
         self._lr_ptr = np.array([lr.data_ptr() for lr, _ in self.sequences], dtype=np.uint64)
         self._hr_ptr = np.array([hr.data_ptr() for _, hr in self.sequences], dtype=np.uint64)
         self._N, self._H, self._W = (np.array(v, dtype=np.int64) for v in zip(*self.shapes))
-        hip.u8_table(self.device)
+        (hip.u8_table if self.dtype == torch.uint8 else hip.u16_table)(self.device)     # built here, outside any capture
         # Descriptor lifetime: a ring of _RING (pinned host buffer, device buffer, event) slots per batch size.  A slot's event is
         # recorded behind the two launches that read its device buffer (and so behind the upload that read its host buffer);
         # build() waits for that event before it writes the slot again, so neither buffer changes under queued work, however
@@ -220,15 +241,28 @@ class DeviceClipSampler:
         self._turn: Dict[int, int] = {}
 
     @classmethod
-    def from_yuv420(cls, pairs, **kw) -> "DeviceClipSampler":
-        """pairs: (lr_path, hr_path) of I420 files named ``Name_WxH_NF.yuv``; the Y planes become one-channel sequences."""
-        from ..harness.yuv import parse_yuv_name, read_yuv420
+    def from_yuv420(cls, pairs, bit_depth=None, **kw) -> "DeviceClipSampler":
+        """pairs: (lr_path, hr_path) of I420 files named ``Name_WxH_NF.yuv``; the Y planes become one-channel sequences.
+        bit_depth: 8 (one byte per sample), 10 (two bytes, little-endian, uint16 sequences) or None: read off each file name
+        (`harness.yuv.yuv_bit_depth`, the ``_10bit`` token); then both files of a pair and all pairs must agree (ValueError)."""
+        from ..harness.yuv import parse_yuv_name, read_yuv420, yuv_bit_depth
+        if bit_depth is None:
+            depths = [(yuv_bit_depth(lr_path), yuv_bit_depth(hr_path)) for lr_path, hr_path in pairs]
+            for (lr_path, hr_path), (a, b) in zip(pairs, depths):
+                if a != b:
+                    raise ValueError(f"{lr_path} names {a}-bit samples, {hr_path} {b}-bit: both files of a pair must agree")
+                if a != depths[0][0]:
+                    raise ValueError(f"{lr_path} names {a}-bit samples, {pairs[0][0]} {depths[0][0]}-bit: all pairs must agree")
+            bit_depth = depths[0][0] if depths else 8
+        elif bit_depth not in (8, 10):
+            raise ValueError(f"bit_depth must be 8, 10 or None, got {bit_depth!r}")
         seqs = []
         for lr_path, hr_path in pairs:
             planes = []
             for path in (lr_path, hr_path):
                 n = parse_yuv_name(path)
-                planes.append(np.ascontiguousarray(read_yuv420(path, n.width, n.height, n.frames)[0])[:, None])
+                y = read_yuv420(path, n.width, n.height, n.frames, bit_depth=bit_depth)[0]
+                planes.append(np.ascontiguousarray(y, dtype=y.dtype.newbyteorder("="))[:, None])
             seqs.append(tuple(planes))
         return cls(seqs, **kw)
 
@@ -275,12 +309,13 @@ class DeviceClipSampler:
         n_lr, n_hr = b * F * C, b * C
         with torch.cuda.device(self.device):
             host, dev, event = self._slot(n_lr + n_hr)
-            fill_descs(host.numpy().view(_DESC), self._lr_ptr[item], self._hr_ptr[item], first, top, left, flags, H, W, F, C)
+            fill_descs(host.numpy().view(_DESC), self._lr_ptr[item], self._hr_ptr[item], first, top, left, flags, H, W, F, C,
+                       itemsize=self.dtype.itemsize)
             dev.copy_(host, non_blocking=True)
             frames = torch.empty((b, F, C, s, s), dtype=torch.float32, device=self.device)           # the model's layout
             target = torch.empty((b, C, 1, 4 * s, 4 * s), dtype=torch.float32, device=self.device)
-            hip.clip_batch(dev[:n_lr * _DESC.itemsize], s, frames)
-            hip.clip_batch(dev[n_lr * _DESC.itemsize:], 4 * s, target)
+            hip.clip_batch(dev[:n_lr * _DESC.itemsize], s, frames, dtype=self.dtype)
+            hip.clip_batch(dev[n_lr * _DESC.itemsize:], 4 * s, target, dtype=self.dtype)
             event.record()
         return {"lr_imgs": frames.permute(0, 2, 1, 3, 4), "hr_imgs": target}
 

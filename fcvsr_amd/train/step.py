@@ -185,10 +185,18 @@ def augment(sample: Dict[str, np.ndarray], rng=random) -> Dict[str, np.ndarray]:
     return dict(sample, lr_imgs=lr.copy(), hr_imgs=hr.copy())
 
 
+def _unit_float(a: np.ndarray) -> torch.Tensor:
+    if a.dtype == np.uint16:
+        # 10-bit samples in uint16 containers: the float contract of the uint16 kernels (`hip.u16_table`, built from this expression):
+        # a sample above 1023 reads as 1023, full scale is 1023
+        return torch.from_numpy(np.minimum(a, 1023).astype(np.int32)).float() / 1023.0
+    return torch.from_numpy(a).float() / 255.0
+
+
 def to_tensor(sample: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
-    """uint8 (f,h,w) -> float (1,f,h,w) / 255 (channel axis first, as the reference's ToTensor)."""
-    return {"lr_imgs": torch.from_numpy(sample["lr_imgs"][np.newaxis]).float() / 255.0,
-            "hr_imgs": torch.from_numpy(sample["hr_imgs"][np.newaxis]).float() / 255.0}
+    """uint8 (f,h,w) -> float (1,f,h,w) / 255 (channel axis first, as the reference's ToTensor); uint16 (10-bit samples) ->
+    min(k, 1023) as float / 1023."""
+    return {"lr_imgs": _unit_float(sample["lr_imgs"][np.newaxis]), "hr_imgs": _unit_float(sample["hr_imgs"][np.newaxis])}
 
 
 def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torch.Tensor]]], *, epochs: int, device,
@@ -200,7 +208,8 @@ def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torc
     Charbonnier-sum loss, Adam, `epoch-%d.pth` state_dict checkpoints every `val_itv` epochs (rank 0).
     `batches(epoch)` yields {'lr_imgs': (b,C,7,h,w), 'hr_imgs': (b,C,f',4h,4w)} like the reference DataLoader.
 
-    val_sequences: (lr (N,C,H,W) in [0,1], hr uint8 (N,C,4H,4W)) pairs scored after the checkpoint of every `val_itv`-th epoch
+    val_sequences: (lr (N,C,H,W), hr (N,C,4H,4W)) pairs, hr uint8 (8-bit frames, peak 255) or uint16 (10-bit samples, peak 1023),
+    lr float in [0,1] or of hr's integer dtype, torch tensors or numpy arrays, scored after the checkpoint of every `val_itv`-th epoch
     on rank 0 (the reference's eval_seq, :263-280): the average over the sequences of each one's mean per-frame PSNR / SSIM
     (`harness.infer.evaluate_sequence` with its defaults: crop border 4, truncating quantisation) is logged as
     `PSNR:%f, SSIM: %f` and passed to `on_validate(epoch, psnr, ssim)` (epoch counted from 1).  It runs under no_grad:
@@ -236,10 +245,17 @@ def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torc
     return history
 
 
+def _as_tensor(a) -> torch.Tensor:
+    if isinstance(a, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=a.dtype.newbyteorder("=")))
+    return a
+
+
 @torch.no_grad()
 def validate(model: torch.nn.Module, sequences: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> Tuple[float, float]:
     """Mean over `sequences` of each sequence's mean per-frame PSNR and SSIM, scored on the device (reference
-    test_LD_freqCVSR_S_22.py:118-119)."""
+    test_LD_freqCVSR_S_22.py:118-119).  sequences: (lr, hr) pairs as `fit`'s val_sequences: uint8 hr is scored at peak 255, uint16
+    hr (10-bit samples) at peak 1023; numpy arrays are taken as they are (no value is converted)."""
     from ..harness.infer import evaluate_sequence
-    scores = [evaluate_sequence(model, lr, hr) for lr, hr in sequences]
+    scores = [evaluate_sequence(model, _as_tensor(lr), _as_tensor(hr)) for lr, hr in sequences]
     return float(np.mean([s.psnr_mean for s in scores])), float(np.mean([s.ssim_mean for s in scores]))

@@ -579,23 +579,30 @@ int fcvsr_quantise_u16(const float* src, long long n, int quantise, uint16_t* ds
  * half to even; the four samples of a thread are one 8-byte store: dst 8-byte aligned. */
 int fcvsr_chroma_up4_u16(const uint16_t* src, const float* tab, int P, int h, int w, uint16_t* dst, void* stream);
 
-/* ---- training batches from device-resident uint8 sequences (reference CVSR_train/opt/data_LD_LR.py:248-344: RandomCrop, Augment,
+/* ---- training batches from device-resident uint8 / uint16 sequences (reference CVSR_train/opt/data_LD_LR.py:248-344: RandomCrop, Augment,
  * ToTensor; the draws are made on the host, contract: fcvsr_amd/train/data.py) -----------------------------------------------
  * One descriptor per output plane, in DEVICE memory: an s x s window of a uint8 plane whose rows are `pitch` bytes apart,
  *   crop[r][c] = src[(top + r) * pitch + left + c],   A[i][j] = crop[vflip ? s-1-i : i][hflip ? s-1-j : j],
  *   out[y][x]  = tab[ transpose ? A[x][y] : A[y][x] ]          (hflip, then vflip, then transpose(0, 2, 1), as the reference)
  * `src` is the plane's first byte (any alignment).  The library cannot see the descriptors: the caller guarantees that every
- * window lies inside its plane. */
+ * window lies inside its plane.
+ * fcvsr_clip_batch_u16 reads the same descriptor as a window of a plane of 2-byte samples (10-bit values in uint16 containers):
+ * `src` is the address of the plane's first sample and must be 2-byte aligned (it need not be 4-byte aligned); `pitch`, `top`
+ * and `left` count SAMPLES (the "strides in elements" convention of FCVSR_U16 views),
+ *   crop[r][c] = ((const uint16_t*)src)[(top + r) * pitch + left + c],
+ * and a sample k reads tab[min(k, 1023)] (an unsigned index clamp, not a mask: 0x8000 .. 0xFFFF read tab[1023]). */
 enum { FCVSR_CROP_HFLIP = 1, FCVSR_CROP_VFLIP = 2, FCVSR_CROP_TRANSPOSE = 4 };
 typedef struct fcvsr_crop_desc {
   const uint8_t* src;
-  int32_t        pitch;     /* bytes between rows of the source plane */
+  int32_t        pitch;     /* bytes (u8) / samples (u16) between rows of the source plane */
   int32_t        top, left;
   int32_t        flags;     /* FCVSR_CROP_* */
 } fcvsr_crop_desc;
 /* P planes of s x s f32, dense in dst (plane p at dst + p*s*s), one launch; desc: P descriptors (device); tab as above;
  * s % 4 == 0, dst 16-byte aligned. */
 int fcvsr_clip_batch_u8(const fcvsr_crop_desc* desc, const float* tab, int P, int s, float* dst, void* stream);
+/* the same for planes of uint16 samples; tab: the 1024-float table of the uint16 entry points above */
+int fcvsr_clip_batch_u16(const fcvsr_crop_desc* desc, const float* tab, int P, int s, float* dst, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,18 +1,22 @@
 """Training-batch production at bench.py's training shape (4 clips of 7x128x128 -> 512x512 from 32-frame 270x480 / 1080x1920
-uint8 sequences): the device clip sampler against the host chain the repository offered before it.
+uint8 sequences, or with --bits 10 uint16 sequences of 10-bit samples): the device clip sampler against the host chain the
+repository offered before it.
 
     python scripts/bench_sampler.py batch   [--batches 100] [--out FILE.json]
         (a) DeviceClipSampler: draws + descriptors + two launches, per batch, device-synchronised;
         (b) host chain: random_crop + augment + to_tensor per clip on frames ALREADY DECODED in RAM (no PNG decode: this flatters
             (b) against the reference loader), torch.stack, .to(device) from pageable and from pinned memory.
         The three alternate batch by batch in one process; medians, and the clips/s each sustains.
+        --bits 10: the sequences are 10-bit, and a DeviceClipSampler over 8-bit sequences of the same shapes ("sampler_8bit") takes
+        its turn in the same alternation: the 10-bit batch against the 8-bit batch in one run on one device.
     python scripts/bench_sampler.py fit     [--steps 64] [--out FILE.json]
         one `fit` epoch of --steps steps of 4 clips (eager step, no graph) fed by the sampler and by the host chain: time per step
         including the data, and the host time spent inside the data iterator; the two alternate --repeats times.
     rocprofv3 --kernel-trace --output-format csv -d DIR -o k -- python scripts/bench_sampler.py kernel --order DIR/order.json
     python scripts/bench_sampler.py summarise --trace DIR/..._kernel_trace.csv --order DIR/order.json [--out FILE.json]
         the kernel alone: launches of 4 and 64 clips, flag sets without and with the transpose bit, in a recorded order; `summarise`
-        cuts the trace by that order: time per launch, bytes (1 read + 4 written per pixel) and the share of HBM bandwidth.
+        cuts the trace by that order: time per launch, bytes (1 read + 4 written per pixel; --bits 10: 2 read) and the share of
+        HBM bandwidth.  Give `kernel` and `summarise` the same --bits.
 """
 import argparse
 import csv
@@ -29,12 +33,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 N, H, W, CROP, FRAMES, CLIPS = 32, 270, 480, 128, 7, 4
 HBM_PEAK, HBM_STREAM = 8.0e12, 6.3e12          # spec peak and what streaming kernels reach on this card (bytes/s)
-KERNEL = "clip_batch_u8_kernel"
+KERNELS = {8: "clip_batch_u8_kernel", 10: "clip_batch_u16_kernel"}
+DTYPES = {8: np.uint8, 10: np.uint16}
 
 
-def sequences(n, seed=0):
+def sequences(n, seed=0, bits=8):
     g = np.random.RandomState(seed)
-    return [(g.randint(0, 256, (N, 1, H, W), dtype=np.uint8), g.randint(0, 256, (N, 1, 4 * H, 4 * W), dtype=np.uint8)) for _ in range(n)]
+    dt = DTYPES[bits]
+    return [(g.randint(0, 1 << bits, (N, 1, H, W), dtype=dt), g.randint(0, 1 << bits, (N, 1, 4 * H, 4 * W), dtype=dt)) for _ in range(n)]
 
 
 def host_clip(seqs, rnd):
@@ -69,13 +75,16 @@ def stats(ms):
 
 def mode_batch(args, dev):
     from fcvsr_amd.train import DeviceClipSampler
-    seqs = sequences(args.sequences)
+    seqs = sequences(args.sequences, bits=args.bits)
     sampler = DeviceClipSampler(seqs, batch=CLIPS, crop=CROP, seed=1, device=dev)
     dev_it, rnd = forever(sampler), random.Random(2)
     np.random.seed(3)
     random.seed(4)
     makers = {"sampler": lambda: next(dev_it), "host_pageable": lambda: host_batch(seqs, rnd, False, dev),
               "host_pinned": lambda: host_batch(seqs, rnd, True, dev)}
+    if args.bits == 10:                                        # the 8-bit batch of the same shapes and draws, in the same alternation
+        it8 = forever(DeviceClipSampler(sequences(args.sequences, bits=8), batch=CLIPS, crop=CROP, seed=1, device=dev))
+        makers["sampler_8bit"] = lambda: next(it8)
     times = {k: [] for k in makers}
     for it in range(args.warmup + args.batches):
         for name, make in makers.items():
@@ -87,7 +96,7 @@ def mode_batch(args, dev):
             assert b["lr_imgs"].shape == (CLIPS, 1, FRAMES, CROP, CROP) and b["hr_imgs"].shape == (CLIPS, 1, 1, 4 * CROP, 4 * CROP)
             if it >= args.warmup:
                 times[name].append(dt)
-    rec = {"workload": f"{CLIPS} clips of {FRAMES}x{CROP}x{CROP} -> {4 * CROP}x{4 * CROP} from {args.sequences} uint8 sequences of {N} frames "
+    rec = {"workload": f"{CLIPS} clips of {FRAMES}x{CROP}x{CROP} -> {4 * CROP}x{4 * CROP} from {args.sequences} {np.dtype(DTYPES[args.bits]).name} sequences of {N} frames "
                        f"{H}x{W} / {4 * H}x{4 * W}; per batch, device-synchronised, {args.batches} batches after {args.warmup} warm-up",
            "note": "host chain works on frames already decoded in RAM (no per-clip PNG decode as in the reference loader): flatters it",
            "bytes_uploaded_per_batch": {"sampler_descriptors": (CLIPS * FRAMES + CLIPS) * 24,
@@ -102,8 +111,9 @@ def mode_fit(args, dev):
     from fcvsr_amd.train import DeviceClipSampler
     from fcvsr_amd.train.step import fit
     from fcvsr_amd.weights import synthetic_state_dict
-    seqs = sequences(args.sequences)
-    resident = [(torch.from_numpy(lr).to(dev), torch.from_numpy(hr).to(dev)) for lr, hr in seqs]     # uploaded once, shared below
+    seqs = sequences(args.sequences, bits=args.bits)
+    from fcvsr_amd.hip import bits16
+    resident = [tuple(bits16(torch.from_numpy(a)).to(dev).view(torch.from_numpy(a).dtype) for a in pair) for pair in seqs]   # uploaded once, shared below
 
     def model():
         m = GShiftNet_S()
@@ -161,7 +171,7 @@ def mode_kernel(args, dev):
     """Launches only (run under rocprofv3): per case `--iters` batches whose clips all carry flag sets without / with the transpose
     bit.  Every batch keeps its output alive, so a launch writes memory no earlier launch of the case wrote."""
     from fcvsr_amd.train import BatchPlan, DeviceClipSampler
-    seqs = sequences(args.sequences)
+    seqs = sequences(args.sequences, bits=args.bits)
     sampler = DeviceClipSampler(seqs, batch=64, crop=CROP, seed=1, device=dev)
     g = np.random.RandomState(7)
     order = []
@@ -184,6 +194,7 @@ def mode_kernel(args, dev):
 
 def mode_summarise(args):
     order = json.load(open(args.order))
+    KERNEL, src_bytes = KERNELS[args.bits], np.dtype(DTYPES[args.bits]).itemsize
     rows = [r for r in csv.DictReader(open(args.trace)) if KERNEL in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     assert len(rows) == len(order), f"{len(rows)} dispatches of {KERNEL} in the trace, {len(order)} launches recorded"
@@ -194,13 +205,13 @@ def mode_summarise(args):
     out = []
     for (clips, tr, s), ns in sorted(groups.items()):
         planes = clips * (FRAMES if s == CROP else 1)
-        nbytes = planes * s * s * 5
+        nbytes = planes * s * s * (src_bytes + 4)
         med = float(np.median(ns))
         out.append({"clips": clips, "transpose": tr, "plane": s, "planes": planes, "launches": len(ns), "median_us": round(med / 1e3, 2),
                     "min_us": round(min(ns) / 1e3, 2), "bytes": nbytes, "GB_per_s": round(nbytes / med, 1),
                     "share_of_8TBs_peak": round(nbytes / (med * 1e-9) / HBM_PEAK, 3),
                     "share_of_6.3TBs_streaming": round(nbytes / (med * 1e-9) / HBM_STREAM, 3)})
-    return {"kernel": KERNEL, "source": "rocprofv3 --kernel-trace", "bytes_model": "1 byte read + 4 bytes written per output pixel",
+    return {"kernel": KERNEL, "source": "rocprofv3 --kernel-trace", "bytes_model": f"{src_bytes} byte(s) read + 4 bytes written per output pixel",
             "cases": out}
 
 
@@ -213,6 +224,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--sequences", type=int, default=None)
+    ap.add_argument("--bits", type=int, choices=[8, 10], default=8, help="sample depth of the sequences (10: uint16 containers)")
     ap.add_argument("--order", default="order.json")
     ap.add_argument("--trace", default=None)
     ap.add_argument("--out", default=None)
