@@ -5,6 +5,10 @@
 // Same scheme as freq_mlp3_kernel: 128 pixels per workgroup, weights are the MFMA A operand (rows = couts), the wave's 32
 // pixels the B operand, hidden activations stay in LDS rows private to the wave.  The 4 output channels are rows 0..3 of
 // the last 32-row tile, i.e. acc[0..3] of lanes 0..31: one 16-byte store per pixel, no transposition.
+//   STRIP: convcorr on the columns x < xs of the spectrum grid, where the CorrBlock lookup is not identically zero.  Layer 0
+//   then has the 84 lookup channels (f32, rounded to bf16 while staged) as a second source: K = 128 + 84 in the order of the
+//   generic 1x1 kernel on the concatenation [off | corr] (64-channel chunks, ascending 16-channel steps, the last chunk
+//   32 channels wide).  Pixels are addressed through the row pitch of the full grid and the result lands in off4 in place.
 #include "common.h"
 #include "mfma_util.h"
 
@@ -20,10 +24,14 @@ struct FreqHeadArgs {
   const uint16_t* w0;       // [>=64][128] bf16, cin contiguous
   const uint16_t* w1;       // [>=64][64]   (NHID = 2 only)
   const uint16_t* wl;       // [>=32][64]: rows 0..3 live
+  // STRIP only: pixel p of the strip = (row p / xs, column p % xs) of a grid with Wf columns per row
+  const float* corr;        // (corr_npix, 84) f32 dense: the lookup of strip pixel p % corr_npix (both directions share it)
+  int xs, Wf, corr_npix;
 };
 
-template <bool SRC_F32, int NHID>
+template <bool SRC_F32, int NHID, bool STRIP = false>
 __global__ __launch_bounds__(256, 4) void freq_head_kernel(FreqHeadArgs a) {
+  static_assert(!STRIP || (!SRC_F32 && NHID == 2), "the strip variant is convcorr on the bf16 offset spectra");
   __shared__ __align__(16) uint16_t A_s[kFhPix * kFhLD];      // input chunk, later the hidden tile
   __shared__ __align__(16) uint16_t B_s[64 * kFhLD];
   const int tid = threadIdx.x;
@@ -50,10 +58,11 @@ __global__ __launch_bounds__(256, 4) void freq_head_kernel(FreqHeadArgs a) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) *reinterpret_cast<uint4*>(B_s + ((tid >> 3) + 32 * u) * kFhLD + (tid & 7) * 8) = v[u];
   };
-  auto mma_chunk = [&](const uint16_t* prow, int ntile) {
+  auto mma_chunk = [&](const uint16_t* prow, int ntile, int nk = 4) {
     const uint16_t* wrow = B_s + r * kFhLD + h * 8;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
+      if (STRIP && kk >= nk) break;
       const uint4 pf = *reinterpret_cast<const uint4*>(prow + kk * 16);
 #pragma unroll
       for (int nf = 0; nf < 2; ++nf)
@@ -72,11 +81,34 @@ __global__ __launch_bounds__(256, 4) void freq_head_kernel(FreqHeadArgs a) {
       }
   };
 
-  // ---- layer 0: 128 -> 64, relu (two 64-channel chunks) ------------------------------------------------------------------
+  // grid pixel (in pixels of the full grid) of the flat pixel index the workgroup works on
+  auto grid_pix = [&](int pix) -> long long {
+    if (!STRIP) return pix;
+    const int row = pix / a.xs;
+    return (long long)row * a.Wf + (pix - row * a.xs);
+  };
+  // ---- layer 0: 128 -> 64, relu (two 64-channel chunks; STRIP: two more from the lookup, 64 + 20 channels) -------------------
   zero_acc();
-  for (int c0 = 0; c0 < 128; c0 += 64) {
+  constexpr int CIN0 = STRIP ? 256 : 128;                 // row length of w0
+  for (int c0 = 0; c0 < CIN0; c0 += 64) {
     __syncthreads();
-    if (SRC_F32) {
+    if (STRIP && c0 >= 128) {
+      const int q = tid & 15, p0 = tid >> 4;
+      const int c = c0 - 128 + q * 4;                     // lookup channel of the lane's quad; 84 live, zeros beyond
+      const float* sb = a.corr + (c < 84 ? c : 0);
+      float4 v[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        int pix = flat0 + p0 + i * 16;
+        pix = pix < npix ? pix : npix - 1;
+        v[i] = *reinterpret_cast<const float4*>(sb + (long long)(pix % a.corr_npix) * 84);
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (c >= 84) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<uint2*>(A_s + (p0 + i * 16) * kFhLD + q * 4) = cvt4<true>(v[i]);
+      }
+    } else if (SRC_F32) {
       const int q = tid & 15, p0 = tid >> 4;
       const float* sb = reinterpret_cast<const float*>(a.x) + c0 + q * 4;
       float4 v[8];
@@ -96,14 +128,14 @@ __global__ __launch_bounds__(256, 4) void freq_head_kernel(FreqHeadArgs a) {
       for (int i = 0; i < 4; ++i) {
         int pix = flat0 + p0 + i * 32;
         pix = pix < npix ? pix : npix - 1;
-        v[i] = *reinterpret_cast<const uint4*>(sb + (long long)pix * a.sx);
+        v[i] = *reinterpret_cast<const uint4*>(sb + grid_pix(pix) * a.sx);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(A_s + (p0 + i * 32) * kFhLD + q * 8) = v[i];
     }
-    stage_w(a.w0, 128, c0, 64);
+    stage_w(a.w0, CIN0, c0, 64);
     __syncthreads();
-    mma_chunk(A_s + (wave * 32 + r) * kFhLD + h * 8, 2);
+    mma_chunk(A_s + (wave * 32 + r) * kFhLD + h * 8, 2, c0 == 192 ? 2 : 4);   // channels [192, 224) close the 212 of the concat
   }
   __syncthreads();                                        // every wave is done with the staged input: rows become hidden rows
   store_hidden();
@@ -127,7 +159,7 @@ __global__ __launch_bounds__(256, 4) void freq_head_kernel(FreqHeadArgs a) {
   mma_chunk(A_s + (wave * 32 + r) * kFhLD + h * 8, 1);
   const int pix = flat0 + wave * 32 + r;
   if (h == 0 && pix < npix)
-    *reinterpret_cast<float4*>(a.out + (long long)pix * 4) = make_float4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
+    *reinterpret_cast<float4*>(a.out + grid_pix(pix) * 4) = make_float4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
 }
 
 }  // namespace fcvsr
@@ -141,7 +173,7 @@ extern "C" int fcvsr_freq_head(const void* x, int x_dtype, int64_t x_pix_stride,
   FCVSR_CHECK_ARG(npix > 0 && npix < (1ll << 30) && x_pix_stride >= 128 && x_pix_stride % 8 == 0, "bad sizes / strides");
   FCVSR_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)w0 % 16) == 0 && ((uintptr_t)w_last % 16) == 0 &&
                       ((uintptr_t)out % 16) == 0 && (w_mid == nullptr || ((uintptr_t)w_mid % 16) == 0), "16-byte alignment");
-  FreqHeadArgs a;
+  FreqHeadArgs a = {};
   a.x = x; a.sx = x_pix_stride; a.out = out; a.npix = (int)npix;
   a.w0 = (const uint16_t*)w0; a.w1 = (const uint16_t*)w_mid; a.wl = (const uint16_t*)w_last;
   dim3 grid(cdiv(npix, kFhPix));
@@ -153,6 +185,22 @@ extern "C" int fcvsr_freq_head(const void* x, int x_dtype, int64_t x_pix_stride,
     if (w_mid) hipLaunchKernelGGL((freq_head_kernel<false, 2>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((freq_head_kernel<false, 1>), grid, dim3(256), 0, st, a);
   }
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fcvsr_convcorr_strip(const void* off, const float* corr, int B, int H, int Wf, int xs, const void* w0,
+                                    const void* w_mid, const void* w_last, float* off4, void* stream) {
+  FCVSR_CHECK_ARG(off && corr && w0 && w_mid && w_last && off4, "null argument");
+  FCVSR_CHECK_ARG(B > 0 && H > 0 && Wf > 0 && xs > 0 && xs <= Wf && 2ll * B * H * Wf < (1ll << 30), "bad sizes");
+  FCVSR_CHECK_ARG(((uintptr_t)off % 16) == 0 && ((uintptr_t)corr % 16) == 0 && ((uintptr_t)w0 % 16) == 0 &&
+                      ((uintptr_t)w_mid % 16) == 0 && ((uintptr_t)w_last % 16) == 0 && ((uintptr_t)off4 % 16) == 0,
+                  "16-byte alignment");
+  FreqHeadArgs a = {};
+  a.x = off; a.sx = 128; a.out = off4; a.npix = 2 * B * H * xs;
+  a.w0 = (const uint16_t*)w0; a.w1 = (const uint16_t*)w_mid; a.wl = (const uint16_t*)w_last;
+  a.corr = corr; a.xs = xs; a.Wf = Wf; a.corr_npix = B * H * xs;
+  hipLaunchKernelGGL((freq_head_kernel<false, 2, true>), dim3(cdiv(a.npix, kFhPix)), dim3(256), 0, (hipStream_t)stream, a);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

@@ -44,8 +44,19 @@ __global__ __launch_bounds__(256, 3) void freq_mlp3_kernel(FreqMlpArgs a) {
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const int gi = blockIdx.x / a.tiles_per_group;
-  const int flat0 = (blockIdx.x - gi * a.tiles_per_group) * kFmPix;
+  // Both directions read the same centre spectrum xb.  Direction-major numbering put the two reads of a tile a whole tensor
+  // apart (more than the Infinity Cache holds); here the two directions of a tile are 8 block indices apart, i.e. dispatched
+  // together and, with blocks dealt round-robin over the 8 XCDs, behind the same L2.
+  int gi, tile;
+  if (a.n_groups == 2) {
+    tile = (blockIdx.x >> 4) * 8 + (blockIdx.x & 7);
+    gi = (blockIdx.x >> 3) & 1;
+    if (tile >= a.tiles_per_group) return;                // tail of the last group of 8 tiles (uniform, before any barrier)
+  } else {
+    gi = 0;
+    tile = blockIdx.x;
+  }
+  const int flat0 = tile * kFmPix;
   const float* xa = a.xa[gi];
   const float* xb = a.xb[gi];
   const int npix = a.npix;
@@ -245,7 +256,7 @@ extern "C" int fcvsr_freq_mlp3(const float* const* xa, const float* const* xb, i
       return (int)e;
     }
   }
-  hipLaunchKernelGGL(freq_mlp3_kernel, dim3(a.tiles_per_group * n_dirs), dim3(256), kFmLds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(freq_mlp3_kernel, dim3(n_dirs == 2 ? cdiv(a.tiles_per_group, 8) * 16 : a.tiles_per_group), dim3(256), kFmLds, (hipStream_t)stream, a);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

@@ -342,7 +342,7 @@ class Engine:
             # The CorrBlock lookup is identically zero beyond column radius+1 = 5 (it samples a 2-pixel-wide image,
             # CVSR_freq.py:1318-1337), so its 81 input channels contribute exact zeros to convcorr.0 everywhere else:
             # the stack runs over both directions on the offset spectra alone, then the narrow strip x < 8 is recomputed
-            # with the lookup channels and pasted over - the same sums as the full concat (zeros add nothing to an f32 chain).
+            # with the lookup channels over it - the same sums as the full concat (zeros add nothing to an f32 chain).
             if fused:
                 check(L.fcvsr_freq_head(off.data_ptr(), hip.BF16, 2 * n, 2 * B * H * Wf,
                                         self._weights("MGAA.convcorr.0", torch.bfloat16, cols=(0, 2 * n))[0].data_ptr(),
@@ -358,37 +358,51 @@ class Engine:
             cv = view(corr)
             check(L.fcvsr_corr_lookup(x1f.data_ptr(), x2f.data_ptr(), fs, B, H, Wf, 2 * n, 4, xs, C.byref(cv), st),
                   "fcvsr_corr_lookup")
-            off_s = off[:, :, :xs].to(torch.float32, memory_format=torch.contiguous_format)   # (2B,H,xs,2n) strip copy
-            c0_s = self._new(dev, 2 * B, H, xs, n, dtype=fdt)
-            for d in range(2):
-                self._conv("MGAA.convcorr.0", [off_s[d * B:(d + 1) * B], corr], c0_s[d * B:(d + 1) * B], act=ACT_RELU,
-                           freq=True)
             if fused:
-                c1_s = self._new(dev, 2 * B, H, xs, n, dtype=fdt)
-                off4_s = self._new(dev, 2 * B, H, xs, 4)
-                self._conv("MGAA.convcorr.2", [c0_s], c1_s, act=ACT_RELU, freq=True)
-                self._conv("MGAA.convcorr.4", [c1_s], off4_s, freq=True)
-                off4[:, :, :xs].copy_(off4_s)
+                # the strip of both directions in one launch, written into off4 in place: the lookup channels are a second
+                # source of layer 0, summed in the order of the generic kernel on [off | corr] (the same bits)
+                check(L.fcvsr_convcorr_strip(off.data_ptr(), corr.data_ptr(), B, H, Wf, xs,
+                                             self._weights("MGAA.convcorr.0", torch.bfloat16)[0].data_ptr(),
+                                             self._weights("MGAA.convcorr.2", torch.bfloat16)[0].data_ptr(),
+                                             self._weights("MGAA.convcorr.4", torch.bfloat16)[0].data_ptr(), off4.data_ptr(), st),
+                      "fcvsr_convcorr_strip")
             else:
+                off_s = off[:, :, :xs].to(torch.float32, memory_format=torch.contiguous_format)   # (2B,H,xs,2n) strip copy
+                c0_s = self._new(dev, 2 * B, H, xs, n, dtype=fdt)
+                for d in range(2):
+                    self._conv("MGAA.convcorr.0", [off_s[d * B:(d + 1) * B], corr], c0_s[d * B:(d + 1) * B], act=ACT_RELU,
+                               freq=True)
                 c0[:, :, :xs].copy_(c0_s)
                 self._conv("MGAA.convcorr.2", [c0], c1, act=ACT_RELU, freq=True)
                 self._conv("MGAA.convcorr.4", [c1], off4, freq=True)
 
         # A multi-scale ConvBlk heads -> (real, imag) planes -> irfft2 -> pixel offsets
         ospec = self._new(dev, B, H, Wf, 8 * A)                  # re: [0,4A), im: [4A,8A); channel = (dir*A+i)*2 + j
-        u = self._new(dev, 2 * B, H, Wf, 4)
         ntile = ((H + 15) // 16) * ((Wf + 15) // 16)
-        partial = self._new(dev, 2 * B * ntile * 4)
-        for i in range(A):
-            pre = f"MGAA.MConvB.{i}"
-            # conv1 + PReLU + conv2 + channel sums in one launch, CALayer gate + (. * sim) + plane split in a second
-            w1 = self._weights(pre + ".conv1", "direct")[0]
-            w2 = self._weights(pre + ".conv2", "direct")[0]
-            check(L.fcvsr_convblk(off4.data_ptr(), w1.data_ptr(), w2.data_ptr(), par[pre + ".relu.weight"].data_ptr(),
-                                  par[pre + ".conv1.weight"].shape[-1], par[pre + ".CA.conv_du.0.weight"].data_ptr(),
-                                  par[pre + ".CA.conv_du.2.weight"].data_ptr(), sim.data_ptr(), B, 2, H, Wf, u.data_ptr(),
-                                  partial.data_ptr(), partial.numel(), ospec.data_ptr(), 8 * A, 0, 4 * A, A, i, st),
-                  "fcvsr_convblk")
+        heads = [f"MGAA.MConvB.{i}" for i in range(A)]
+        w1s = [self._weights(pre + ".conv1", "direct")[0] for pre in heads]
+        w2s = [self._weights(pre + ".conv2", "direct")[0] for pre in heads]
+        if A <= 6 and all(t.data_ptr() % 16 == 0 for t in (off4, sim, ospec)):
+            # every head of the call in two launches: the off4 tile is staged once, sim is read once, records are stored whole
+            u = self._new(dev, A, 2 * B, H, Wf, 4)
+            partial = self._new(dev, A * 2 * B * ntile * 4)
+            PA = C.c_void_p * A
+            check(L.fcvsr_convblk_heads(off4.data_ptr(), A, PA(*[w.data_ptr() for w in w1s]), PA(*[w.data_ptr() for w in w2s]),
+                                        PA(*[par[pre + ".relu.weight"].data_ptr() for pre in heads]),
+                                        PA(*[par[pre + ".CA.conv_du.0.weight"].data_ptr() for pre in heads]),
+                                        PA(*[par[pre + ".CA.conv_du.2.weight"].data_ptr() for pre in heads]), sim.data_ptr(), B, H,
+                                        Wf, u.data_ptr(), partial.data_ptr(), partial.numel(), ospec.data_ptr(), 8 * A, 0, 4 * A,
+                                        st), "fcvsr_convblk_heads")
+        else:
+            u = self._new(dev, 2 * B, H, Wf, 4)
+            partial = self._new(dev, 2 * B * ntile * 4)
+            for i, pre in enumerate(heads):
+                # conv1 + PReLU + conv2 + channel sums in one launch, CALayer gate + (. * sim) + plane split in a second
+                check(L.fcvsr_convblk(off4.data_ptr(), w1s[i].data_ptr(), w2s[i].data_ptr(), par[pre + ".relu.weight"].data_ptr(),
+                                      par[pre + ".conv1.weight"].shape[-1], par[pre + ".CA.conv_du.0.weight"].data_ptr(),
+                                      par[pre + ".CA.conv_du.2.weight"].data_ptr(), sim.data_ptr(), B, 2, H, Wf, u.data_ptr(),
+                                      partial.data_ptr(), partial.numel(), ospec.data_ptr(), 8 * A, 0, 4 * A, A, i, st),
+                      "fcvsr_convblk")
         offsets = self._new(dev, B, H, W, 4 * A)
         ov = view(offsets)
         check(L.fcvsr_irfft2(ospec.data_ptr(), 8 * A, 4 * A, 0, B, H, W, 4 * A, None, None, C.byref(ov), st),

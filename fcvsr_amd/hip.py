@@ -119,12 +119,14 @@ SIGNATURES = {
     "fcvsr_ca_gate": [_VP, _F, _VP, _VP, _I, _I, _I, _VP, _VP],
     "fcvsr_convblk_tail": [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I64, _I, _I, _I, _I, _VP],
     "fcvsr_convblk": [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _I64, _VP, _I64, _I, _I, _I, _I, _VP],
+    "fcvsr_convblk_heads": [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _I64, _VP, _I64, _I, _I, _VP],
     "fcvsr_warp": [_PV, _PV, _I, _I, _I, _PV, _VP],
     "fcvsr_sac_v": [_PV, _PV, _I, _I, _I, _PV, _VP],
     "fcvsr_sac_h": [_PV, _PV, _PV, _F, _I, _I, _I, _PV, _VP],
     "fcvsr_iac_step": [_PV, _PV, _PV, _PV, _F, _I, _I, _I, _PV, _VP],
     "fcvsr_feat_extract": [_PV, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _VP],
     "fcvsr_freq_head": [_VP, _I, _I64, _I64, _VP, _VP, _VP, _VP, _VP],
+    "fcvsr_convcorr_strip": [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP],
     "fcvsr_freq_mlp3": [_VP, _VP, _I, _I64, _I64, _VP, _VP, _VP, _VP, _I64, _VP],
     "fcvsr_iac_step2": [_PV, _PV, _PV, _PV, _F, _I, _I, _I, _PV, _VP],
     "fcvsr_iac_step2_fused": [_PV, _PV, _PV, _VP, _VP, _PV, _F, _I, _I, _I, _PV, _VP],

@@ -282,6 +282,16 @@ int fcvsr_convblk(const float* x, const float* w1, const float* w2, const float*
                   const float* ca_w2, const float* sim, int B, int ndir, int H, int Wf, float* u_scratch,
                   float* partial_scratch, int64_t partial_elems, float* spec, int64_t pix_stride, int re_off, int im_off,
                   int g_stride, int g0, void* stream);
+/* All n_heads (1..6) ConvBlk heads of one MGAA call in two launches; head i has k = 2i+1 and the arguments of fcvsr_convblk
+ * at index i of w1 / w2 / prelu_slope / ca_w1 / ca_w2 (host arrays of n_heads device pointers).  Two directions (x batch =
+ * dir*B + b).  Per head the arithmetic of fcvsr_convblk, in its order: results are bit-identical to n_heads calls with
+ * g_stride = n_heads, g0 = i.  u: (n_heads, 2B, H, Wf, 4); partial: (n_heads, 2B, tiles, 4), tiles = ceil(H/16)*ceil(Wf/16).
+ * The record of a pixel is written whole: re block [re_off, re_off + 4 n_heads), im block [im_off, im_off + 4 n_heads), channel
+ * (dir*n_heads + i)*2 + j inside each; spec, pix_stride, re_off, im_off 16-byte aligned. */
+int fcvsr_convblk_heads(const float* x, int n_heads, const float* const* w1, const float* const* w2,
+                        const float* const* prelu_slope, const float* const* ca_w1, const float* const* ca_w2, const float* sim,
+                        int B, int H, int Wf, float* u, float* partial, int64_t partial_elems, float* spec, int64_t pix_stride,
+                        int re_off, int im_off, void* stream);
 /* flow_warp (:1188-1227): bilinear, zeros padding, sample at (x+off[0], y+off[1]) */
 int fcvsr_warp(const fcvsr_view* src, const fcvsr_view* off, int B, int H, int W, const fcvsr_view* dst, void* stream);
 /* SAC (:1253-1276) vertical pass: v = sum_t s[clamp(y+t-1)] * k1[c*3+t] */
@@ -322,6 +332,14 @@ int fcvsr_freq_mlp3(const float* const* xa, const float* const* xb, int n_dirs, 
  * offset spectra with the first 128 input columns of convcorr.0. */
 int fcvsr_freq_head(const void* x, int x_dtype, int64_t x_pix_stride, int64_t npix, const void* w0, const void* w_mid,
                     const void* w_last, float* out, void* stream);
+/* convcorr (128 + 84 -> 64 -> 64 -> 4, relu between) on the strip x < xs of the spectrum grid, where the CorrBlock lookup is
+ * not identically zero, written into off4 in place (columns >= xs untouched): one launch for both directions.
+ * off: (2B, H, Wf, 128) bf16 dense; corr: (B, H, xs, 84) f32 dense (fcvsr_corr_lookup with x_count = xs), shared by the two
+ * directions; w0: [>=64][256] bf16 rows = convcorr.0 on the concatenation [off | corr]; w_mid, w_last as in fcvsr_freq_head.
+ * The sums run in the order of the generic 1x1 MFMA kernel on that concatenation, so the result equals the separate launches
+ * bit for bit. */
+int fcvsr_convcorr_strip(const void* off, const float* corr, int B, int H, int Wf, int xs, const void* w0, const void* w_mid,
+                         const void* w_last, float* off4, void* stream);
 
 /* ---- MultiFreq_Refinment pieces (CVSR_freq.py:2104-2133, :2201-2254) ---------------------------------------- */
 /* DivEnh expressions, i==0 (first=1): t=f-mean_f; e1=0.2*a*t*f+b*f.  i>0: t=f-s_f+0.2*s_o; e1 as above;
