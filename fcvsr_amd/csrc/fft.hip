@@ -13,6 +13,7 @@
 // Replaces torch.fft.rfft2 / irfft2 (CVSR_freq.py:1452-1454, :1499, :1504) and the per-channel
 // fftn/fftshift/mask/ifftshift/ifftn(.real) loop of Split_freq (:2082-2090, via the symmetrised half-spectrum mask).
 #include <stdlib.h>
+#include <string.h>
 #include <mutex>
 #include "common.h"
 
@@ -906,6 +907,30 @@ static int pick_lanes2(const TwoStage& ts, int lanes_needed) {
 }
 static int ilog2(int v) { int r = 0; while ((1 << r) < v) ++r; return r; }
 
+// fcvsr_last_fft_path(): the passes of the calling thread's last successful transform, in launch order.  Every launch site
+// appends its own pass from the variables it launches with; the entry point publishes the string when it returns 0.
+static thread_local char g_fft_path[192] = "";
+struct PathLog {
+  char s[sizeof(g_fft_path)];
+  size_t len = 0;
+  PathLog() { s[0] = 0; }
+  void add(const char* pass) {
+    const int w = snprintf(s + len, sizeof(s) - len, "%s%s", len ? ";" : "", pass);
+    if (w > 0) len = len + (size_t)w < sizeof(s) ? len + (size_t)w : sizeof(s) - 1;
+  }
+  void two_stage(const char* name, const TwoStage& ts, int L) {
+    char b[64];
+    snprintf(b, sizeof(b), "%s<%d,%d>/L%d", name, ts.R1, ts.R2, L);
+    add(b);
+  }
+  void plan(const char* name, int L, int vec) {
+    char b[64];
+    snprintf(b, sizeof(b), "%s/L%d/vec%d", name, L, vec);
+    add(b);
+  }
+  int publish() { memcpy(g_fft_path, s, sizeof(s)); return 0; }
+};
+
 #define FCVSR_FFT2_DISPATCH(ts, CALL)                                                                        \
   do {                                                                                                       \
     switch ((ts).N) {                                                                                        \
@@ -939,7 +964,7 @@ static const TwoStage* two_stage_cols(int N) { return (N == 240 || N == 320) ? n
 static const TwoStage* two_stage_bands(int N) { return (N == 192 || N == 240 || N == 256 || N == 320) ? nullptr : two_stage(N); }
 
 static int launch_cols2(const TwoStage& ts, const float* in, float* out, long long ps, int im_off, int re_off, int n, int Wf,
-                        int B, bool inverse, const float* mask, hipStream_t st) {
+                        int B, bool inverse, const float* mask, hipStream_t st, PathLog* log) {
   const float2* tw = twiddle_table(ts.N, st);
   if (!tw) return FCVSR_E_ARG;
   const int L = pick_lanes2(ts, n), logL = ilog2(L);
@@ -955,11 +980,12 @@ static int launch_cols2(const TwoStage& ts, const float* in, float* out, long lo
                           Wf, logL, mask, tw, B)
   FCVSR_FFT2_DISPATCH_COLS(ts, FCVSR_COLS2);
 #undef FCVSR_COLS2
+  if (log) log->two_stage("fft_cols2", ts, L);
   return 0;
 }
 
 static int launch_cols2_bands(const TwoStage& ts, const float* in, float* out, long long out_band_stride, long long ps, int im_off,
-                             int re_off, int n, int Wf, int B, const float* masks, int nm, hipStream_t st) {
+                             int re_off, int n, int Wf, int B, const float* masks, int nm, hipStream_t st, PathLog* log) {
   const float2* tw = twiddle_table(ts.N, st);
   if (!tw) return FCVSR_E_ARG;
   const int L = pick_lanes2(ts, n), logL = ilog2(L);
@@ -970,11 +996,12 @@ static int launch_cols2_bands(const TwoStage& ts, const float* in, float* out, l
   hipLaunchKernelGGL((fft_cols2_bands_kernel<A_, B_>), grid, block, lds, st, in, out, out_band_stride, ps, im_off, re_off, n, Wf, logL, masks, nm, tw, B)
   FCVSR_FFT2_DISPATCH_BANDS(ts, FCVSR_COLS2B);
 #undef FCVSR_COLS2B
+  if (log) log->two_stage("fft_cols2_bands", ts, L);
   return 0;
 }
 
 static int launch_rfft_rows2(const TwoStage& ts, const fcvsr_view* src, int n, int B, int H, float* spec, long long ps, int im_off,
-                             int re_off, hipStream_t st) {
+                             int re_off, hipStream_t st, PathLog* log) {
   const float2* tw = twiddle_table(ts.N, st);
   if (!tw) return FCVSR_E_ARG;
   const int L = pick_lanes2(ts, n / 2), logL = ilog2(L);
@@ -993,11 +1020,12 @@ static int launch_rfft_rows2(const TwoStage& ts, const fcvsr_view* src, int n, i
                        re_off, tw, B)
   FCVSR_FFT2_DISPATCH(ts, FCVSR_ROWS2);
 #undef FCVSR_ROWS2
+  if (log) log->two_stage("rfft_rows2", ts, L);
   return 0;
 }
 
 static int launch_irfft_rows2(const TwoStage& ts, const float* spec, long long ps, int im_off, int re_off, int n, int B, int H,
-                              const fcvsr_view* dst, float scale, hipStream_t st) {
+                              const fcvsr_view* dst, float scale, hipStream_t st, PathLog* log) {
   const float2* tw = twiddle_table(ts.N, st);
   if (!tw) return FCVSR_E_ARG;
   const int L = pick_lanes2(ts, n / 2), logL = ilog2(L);
@@ -1008,6 +1036,7 @@ static int launch_irfft_rows2(const TwoStage& ts, const float* spec, long long p
   hipLaunchKernelGGL((irfft_rows2_kernel<A_, B_>), grid, block, lds, st, spec, ps, im_off, re_off, n, H, logL, to_view(*dst), scale, tw, B)
   FCVSR_FFT2_DISPATCH(ts, FCVSR_IROWS2);
 #undef FCVSR_IROWS2
+  if (log) log->two_stage("irfft_rows2", ts, L);
   return 0;
 }
 
@@ -1050,8 +1079,9 @@ extern "C" int fcvsr_rfft2(const fcvsr_view* src, int B, int H, int W, int n, fl
   const bool spec_pair = pix_stride % 2 == 0 && im_off % 2 == 0 && re_off % 2 == 0 && ((uintptr_t)spec % 8) == 0;
   const TwoStage* tsw = two_stage(W);
   const TwoStage* tsh = two_stage_cols(H);
+  PathLog log;
   if (tsw && n % 2 == 0 && pair_ok(src) && spec_pair) {
-    const int rc = launch_rfft_rows2(*tsw, src, n, B, H, spec, (long long)pix_stride, im_off, re_off, st);
+    const int rc = launch_rfft_rows2(*tsw, src, n, B, H, spec, (long long)pix_stride, im_off, re_off, st, &log);
     if (rc) return rc;
     FCVSR_LAUNCH_CHECK();
   } else {
@@ -1066,9 +1096,10 @@ extern "C" int fcvsr_rfft2(const fcvsr_view* src, int B, int H, int W, int n, fl
     hipLaunchKernelGGL(rfft_rows_kernel, grid, dim3(512), lds, st, to_view(*src), (int)src->dtype, n, H, W, L, spec,
                        (long long)pix_stride, im_off, re_off, pw, vec, B);
     FCVSR_LAUNCH_CHECK();
+    log.plan("rfft_rows", L, vec);
   }
   if (tsh) {
-    const int rc = launch_cols2(*tsh, spec, spec, (long long)pix_stride, im_off, re_off, n, Wf, B, false, nullptr, st);
+    const int rc = launch_cols2(*tsh, spec, spec, (long long)pix_stride, im_off, re_off, n, Wf, B, false, nullptr, st, &log);
     if (rc) return rc;
     FCVSR_LAUNCH_CHECK();
   } else {
@@ -1081,18 +1112,19 @@ extern "C" int fcvsr_rfft2(const fcvsr_view* src, int B, int H, int W, int n, fl
     hipLaunchKernelGGL(fft_cols_kernel, grid, dim3(512), lds, st, (const float*)spec, spec, (long long)pix_stride, im_off,
                        re_off, n, H, Wf, L, 0, (const float*)nullptr, ph, vec, B);
     FCVSR_LAUNCH_CHECK();
+    log.plan("fft_cols", L, vec);
   }
-  return 0;
+  return log.publish();
 }
 
 // Inverse row pass of fcvsr_irfft2 / fcvsr_irfft2_bands: the transformed columns `mid` -> the real output dst (scaled by
 // 1 / (H W)).  Two-stage kernel for the listed lengths, else the plan kernel; mid_vec: `mid` may be read 16 bytes at a time.
 static int irfft_rows(const float* mid, long long pix_stride, int im_off, int re_off, int n, int B, int H, int W, const FftPlan& pw,
-                      bool mid_vec, const fcvsr_view* dst, hipStream_t st) {
+                      bool mid_vec, const fcvsr_view* dst, hipStream_t st, PathLog* log) {
   const TwoStage* tsw = two_stage(W);
   const bool mid_pair = pix_stride % 2 == 0 && im_off % 2 == 0 && re_off % 2 == 0 && ((uintptr_t)mid % 8) == 0;
   if (tsw && n % 2 == 0 && pair_ok(dst) && mid_pair) {
-    const int rc = launch_irfft_rows2(*tsw, mid, pix_stride, im_off, re_off, n, B, H, dst, 1.0f / ((float)H * (float)W), st);
+    const int rc = launch_irfft_rows2(*tsw, mid, pix_stride, im_off, re_off, n, B, H, dst, 1.0f / ((float)H * (float)W), st, log);
     if (rc) return rc;
     FCVSR_LAUNCH_CHECK();
   } else {
@@ -1106,6 +1138,7 @@ static int irfft_rows(const float* mid, long long pix_stride, int im_off, int re
     hipLaunchKernelGGL(irfft_rows_kernel, grid, dim3(512), lds, st, mid, pix_stride, im_off, re_off, n, H, W, L, to_view(*dst),
                        1.0f / ((float)H * (float)W), pw, vec, B);
     FCVSR_LAUNCH_CHECK();
+    if (log) log->plan("irfft_rows", L, vec);
   }
   return 0;
 }
@@ -1122,8 +1155,9 @@ extern "C" int fcvsr_irfft2(const float* spec, int64_t pix_stride, int im_off, i
   float* mid = work ? work : const_cast<float*>(spec);
   const bool spec_ok = pix_stride % 4 == 0 && im_off % 4 == 0 && re_off % 4 == 0 && ((uintptr_t)spec % 16) == 0;
   const TwoStage* tsh = two_stage_cols(H);
+  PathLog log;
   if (tsh) {
-    const int rc = launch_cols2(*tsh, spec, mid, (long long)pix_stride, im_off, re_off, n, Wf, B, true, mask, st);
+    const int rc = launch_cols2(*tsh, spec, mid, (long long)pix_stride, im_off, re_off, n, Wf, B, true, mask, st, &log);
     if (rc) return rc;
     FCVSR_LAUNCH_CHECK();
   } else {
@@ -1136,8 +1170,10 @@ extern "C" int fcvsr_irfft2(const float* spec, int64_t pix_stride, int im_off, i
     hipLaunchKernelGGL(fft_cols_kernel, grid, dim3(512), lds, st, spec, mid, (long long)pix_stride, im_off, re_off, n, H,
                        Wf, L, 1, mask, ph, vec, B);
     FCVSR_LAUNCH_CHECK();
+    log.plan("fft_cols", L, vec);
   }
-  return irfft_rows(mid, (long long)pix_stride, im_off, re_off, n, B, H, W, pw, spec_ok && ((uintptr_t)mid % 16) == 0, dst, st);
+  const int rc = irfft_rows(mid, (long long)pix_stride, im_off, re_off, n, B, H, W, pw, spec_ok && ((uintptr_t)mid % 16) == 0, dst, st, &log);
+  return rc ? rc : log.publish();
 }
 
 extern "C" int fcvsr_irfft2_bands(const float* spec, int64_t pix_stride, int im_off, int re_off, int B, int H, int W, int n,
@@ -1157,8 +1193,9 @@ extern "C" int fcvsr_irfft2_bands(const float* spec, int64_t pix_stride, int im_
   }
   for (int m = 0; m < n_bands; ++m)
     FCVSR_CHECK_ARG(dst[m].ptr && dst[m].dtype == FCVSR_F32 && n <= dst[m].c, "dst: f32 views with >= n channels");
+  PathLog log;
   {
-    const int rc = launch_cols2_bands(*tsh, spec, work, band, (long long)pix_stride, im_off, re_off, n, Wf, B, masks, n_bands, st);
+    const int rc = launch_cols2_bands(*tsh, spec, work, band, (long long)pix_stride, im_off, re_off, n, Wf, B, masks, n_bands, st, &log);
     if (rc) return rc;
     FCVSR_LAUNCH_CHECK();
   }
@@ -1167,8 +1204,10 @@ extern "C" int fcvsr_irfft2_bands(const float* spec, int64_t pix_stride, int im_
   for (int m = 0; m < n_bands; ++m) {
     const float* mid = work + (long long)m * band;
     const bool mid_vec = pix_stride % 4 == 0 && im_off % 4 == 0 && re_off % 4 == 0 && ((uintptr_t)mid % 16) == 0;
-    const int rc = irfft_rows(mid, (long long)pix_stride, im_off, re_off, n, B, H, W, pw, mid_vec, &dst[m], st);
+    const int rc = irfft_rows(mid, (long long)pix_stride, im_off, re_off, n, B, H, W, pw, mid_vec, &dst[m], st, m == 0 ? &log : nullptr);   // the row pass is named once
     if (rc) return rc;
   }
-  return 0;
+  return log.publish();
 }
+
+extern "C" const char* fcvsr_last_fft_path(void) { return g_fft_path; }

@@ -114,6 +114,7 @@ SIGNATURES = {
     "fcvsr_rfft2": [_PV, _I, _I, _I, _I, _VP, _I64, _I, _I, _VP],
     "fcvsr_irfft2": [_VP, _I64, _I, _I, _I, _I, _I, _I, _VP, _VP, _PV, _VP],
     "fcvsr_irfft2_bands": [_VP, _I64, _I, _I, _I, _I, _I, _I, _VP, _I, _VP, _PV, _VP],
+    "fcvsr_last_fft_path": [],
     "fcvsr_corr_lookup": [_VP, _VP, _I64, _I, _I, _I, _I, _I, _I, _PV, _VP],
     "fcvsr_channel_sum": [_PV, _I, _I, _I, _VP, _VP, _I64, _VP],
     "fcvsr_ca_gate": [_VP, _F, _VP, _VP, _I, _I, _I, _VP, _VP],
@@ -202,7 +203,8 @@ SIGNATURES = {
     "fcvsr_quantise_u16": [_VP, C.c_longlong, _I, _VP, _VP],
     "fcvsr_chroma_up4_u16": [_VP, _VP, _I, _I, _I, _VP, _VP],
 }
-_RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
+_RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
+             "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
              "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong,
              "fcvsr_frame_metrics_scratch_bytes": C.c_longlong}

@@ -246,6 +246,14 @@ int fcvsr_irfft2(const float* spec, int64_t pix_stride, int im_off, int re_off, 
  * calls of fcvsr_irfft2, which is also the fallback). */
 int fcvsr_irfft2_bands(const float* spec, int64_t pix_stride, int im_off, int re_off, int B, int H, int W, int n,
                        const float* masks, int n_bands, float* work, const fcvsr_view* dst, void* stream);
+/* The kernels the calling thread's last successful fcvsr_rfft2 / fcvsr_irfft2 / fcvsr_irfft2_bands call launched: its passes in
+ * launch order, joined by ';'.  A pass is "name<R1,R2>/L<lanes>" for a two-stage kernel (length R1 * R2, <lanes> channel lanes per
+ * workgroup) or "name/L<lanes>/vec<0|1>" for a multi-stage plan kernel (vec1 = 16-byte accesses); name is the kernel's name without
+ * "_kernel".  E.g. "rfft_rows2<16,20>/L16;fft_cols2<12,15>/L32" or "fft_cols/L8/vec1;irfft_rows/L4/vec0".  fcvsr_irfft2_bands on its
+ * fused column pass reports "fft_cols2_bands<R1,R2>/L<lanes>" and then the row pass once (not once per band); on its band-by-band
+ * fallback the string is that of the last fcvsr_irfft2 call.  "" before the first call.  Test and measurement aid like
+ * fcvsr_last_conv_kernel(), not part of the data path. */
+const char* fcvsr_last_fft_path(void);
 
 /* feat_extract (:2589, Conv2d(Cin, n_blk*64, 3, 1, 1), Cin = 7: 9*Cin <= 64) as one K = 64 GEMM step per output tile.
  * x: (B,H,W,Cin) f32 view of the planar frames; w: [n_blk*64][64] f16, column k = tap*Cin + c (zero beyond 9*Cin);

@@ -177,7 +177,8 @@ def test_rfft2_irfft2_vs_torch(H, W, n):
     dv = hip.view(dst)
     hip.check(L.fcvsr_irfft2(spec2.data_ptr(), 2 * n, 0, n, 1, H, W, n, None, None, C.byref(dv), hip.stream_ptr()),
               "irfft2")
-    assert float((nchw(dst) - refi).abs().max()) < 3e-6 * max(1.0, float(refi.abs().max()))
+    # relative to max|ref| (0.02 ... 0.2 for a random spectrum), no floor: measured <= 2.6e-7 at these shapes (tests/test_fft_paths_gpu.py)
+    assert float((nchw(dst) - refi).abs().max()) < 3e-6 * float(refi.abs().max())
 
 
 def test_fft_roundtrip_full_size():
@@ -716,4 +717,4 @@ def test_irfft2_bands_equals_band_by_band(H, W, n, Q):
     # and against torch
     sp = torch.complex(spec[..., n:], spec[..., :n])                    # [imag | real] packing
     tref = torch.fft.irfft2(sp * masks[0][None, :, :, None], s=(H, W), dim=(1, 2))
-    assert float((out[0] - tref).abs().max()) <= 2e-5 * max(1.0, float(tref.abs().max()))
+    assert float((out[0] - tref).abs().max()) <= 2e-5 * float(tref.abs().max())          # measured <= 2.2e-7
