@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from .colour import ColourSpec, i420_planes, rgb_to_i420, yuv420_to_rgb
 from .infer import pad_to_multiple, super_resolve_int
 from .windows import window_indices
 
@@ -69,10 +70,8 @@ def frame_bytes(width: int, height: int) -> int:
     return width * height * 3 // 2
 
 
-def read_yuv420(path: str, width: int, height: int, frames: Optional[int] = None,
-                bit_depth: int = 8) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """Y (N,H,W), U and V (N,H/2,W/2) uint8 arrays of an I420 file: strided views of one read-only memory map (nothing is
-    copied).  `frames` reads the first N frames only.  ``bit_depth=10``: two bytes per sample, little-endian ``<u2`` views."""
+def _map_frames(path: str, width: int, height: int, frames: Optional[int] = None, bit_depth: int = 8) -> np.ndarray:
+    """The (N, W*H*3/2) samples of an I420 file, one row per frame (``Y | U | V``): a read-only memory map."""
     dt = _sample_dtype(bit_depth)
     fs = frame_bytes(width, height)                     # samples per frame
     fb = fs * dt.itemsize
@@ -87,7 +86,15 @@ def read_yuv420(path: str, width: int, height: int, frames: Optional[int] = None
         n = frames
     if n == 0:
         raise ValueError(f"{path}: no frames")
-    mm = np.memmap(path, dtype=dt, mode="r", shape=(n, fs))
+    return np.memmap(path, dtype=dt, mode="r", shape=(n, fs))
+
+
+def read_yuv420(path: str, width: int, height: int, frames: Optional[int] = None,
+                bit_depth: int = 8) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Y (N,H,W), U and V (N,H/2,W/2) uint8 arrays of an I420 file: strided views of one read-only memory map (nothing is
+    copied).  `frames` reads the first N frames only.  ``bit_depth=10``: two bytes per sample, little-endian ``<u2`` views."""
+    mm = _map_frames(path, width, height, frames, bit_depth)
+    n = mm.shape[0]
     ys, cs = width * height, (width // 2) * (height // 2)
     y = mm[:, :ys].reshape(n, height, width)
     u = mm[:, ys:ys + cs].reshape(n, height // 2, width // 2)
@@ -164,6 +171,50 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
             ysr, uvsr = hip.frames_to_numpy(ysr), hip.frames_to_numpy(uvsr)
             _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
             written += ysr.nbytes + uvsr.nbytes
+    dt = time.perf_counter() - t0
+    return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
+            "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
+            "bytes_written": written, "out_size": (4 * W, 4 * H)}
+
+
+@torch.no_grad()
+def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int, *, colour: ColourSpec = ColourSpec(),
+                             batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7) -> dict:
+    """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
+    (`FCVSRNet`, `FCVSR_SNet`).
+
+    `colour` says how the stream maps to RGB (`harness.colour.ColourSpec`: matrix, range, chroma siting) and its bit depth, 8 or
+    10, for both files.  The LR frames go to the device once, as the file holds them, and are decoded there to planar RGB by one
+    launch (`harness.colour.yuv420_to_rgb`, reading the I420 frames in place); the RGB frames are zero-padded to a multiple of 4 as
+    the Y path pads, windows of `num_frames` frames (`padding`, as `super_resolve_sequence`) run through
+    ``model.super_resolve_u8`` / ``super_resolve_u16`` in batches of `batch`, and every batch of SR frames is cropped to
+    4 height x 4 width, encoded on the device into I420 frame layout (`harness.colour.rgb_to_i420`), downloaded and written in
+    order.  Returns the stats of `super_resolve_yuv420`."""
+    if getattr(model, "_img_ch", None) != 3:
+        raise ValueError(f"super_resolve_yuv420_rgb needs a three-channel (RGB) model, got C={getattr(model, '_img_ch', None)}")
+    if not isinstance(colour, ColourSpec):
+        raise ValueError(f"colour must be a ColourSpec, got {type(colour).__name__}")
+    if quantise not in hip.QUANTISE:
+        raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    bit_depth = colour.bit_depth
+    mm = _map_frames(src, width, height, bit_depth=bit_depth)
+    N, H, W = mm.shape[0], height, width
+    sdt, host_dt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.uint16, np.uint16)
+    dev = next(model.parameters()).device
+    t0 = time.perf_counter()
+    frames = hip.bits16(torch.from_numpy(np.array(mm, dtype=host_dt))).to(dev).view(sdt)      # one host copy of the mapped file
+    x = pad_to_multiple(hip.bits16(yuv420_to_rgb(*i420_planes(frames, H, W), colour)), 4)    # (N,3,Hp,Wp), zero padded
+    written = 0
+    with open(dst, "wb") as fh:
+        for s in range(0, N, batch):
+            idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
+            win = torch.stack([x[j] for j in idx], 0).view(sdt)                           # (b, 7, 3, Hp, Wp)
+            sr = super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]
+            out = hip.frames_to_numpy(rgb_to_i420(sr, colour))                            # (b, 16 W H 3/2)
+            fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())
+            written += out.nbytes
     dt = time.perf_counter() - t0
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),

@@ -69,6 +69,15 @@ class CropDesc(C.Structure):
 CROP_HFLIP, CROP_VFLIP, CROP_TRANSPOSE = 1, 2, 4
 
 
+class Colour(C.Structure):
+    """fcvsr_colour: the fixed-point constants of one YUV 4:2:0 <-> RGB conversion (`harness.colour.coefficients` makes them)."""
+    _fields_ = [(n, C.c_int32) for n in ("shift", "chroma_loc", "y_off", "c_off", "cy", "rv", "gu", "gv", "bu", "kr", "kg", "kb",
+                                         "ur", "ug", "ub", "vr", "vg", "vb")]
+
+
+CHROMA_LEFT, CHROMA_CENTER = 0, 1
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("n_src", C.c_int32), ("src", View * 3), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
@@ -202,6 +211,10 @@ SIGNATURES = {
     "fcvsr_u16_to_f32": [_VP, _VP, C.c_longlong, _VP, _VP],
     "fcvsr_quantise_u16": [_VP, C.c_longlong, _I, _VP, _VP],
     "fcvsr_chroma_up4_u16": [_VP, _VP, _I, _I, _I, _VP, _VP],
+    "fcvsr_yuv420_to_rgb": [_VP, _VP, _VP, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(Colour), _VP, _VP],
+    "fcvsr_yuv420_to_rgb_u16": [_VP, _VP, _VP, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(Colour), _VP, _VP],
+    "fcvsr_rgb_to_yuv420": [_VP, _I, _I, _I, C.POINTER(Colour), C.c_longlong, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP],
+    "fcvsr_rgb_to_yuv420_u16": [_VP, _I, _I, _I, C.POINTER(Colour), C.c_longlong, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,

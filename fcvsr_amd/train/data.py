@@ -266,6 +266,41 @@ class DeviceClipSampler:
             seqs.append(tuple(planes))
         return cls(seqs, **kw)
 
+    @classmethod
+    def from_yuv420_rgb(cls, pairs, colour=None, **kw) -> "DeviceClipSampler":
+        """pairs: (lr_path, hr_path) of I420 files named ``Name_WxH_NF.yuv``, for the RGB models: every file is uploaded as it is
+        and decoded once on the device to planar RGB (`harness.colour.yuv420_to_rgb`), so the sequences are 3-channel and `fit`
+        trains an RGB twin from them unchanged.  colour: a `harness.colour.ColourSpec` (matrix, range, chroma siting, bit depth),
+        or None: BT.709, limited range, left-sited chroma, the bit depth read off the file names under the rules of `from_yuv420`.
+        device: as the constructor's (the decode runs there)."""
+        from ..harness.colour import ColourSpec, i420_planes, yuv420_to_rgb
+        from ..harness.yuv import _map_frames, parse_yuv_name, yuv_bit_depth
+        if colour is None:
+            depths = [(yuv_bit_depth(lr_path), yuv_bit_depth(hr_path)) for lr_path, hr_path in pairs]
+            for (lr_path, hr_path), (a, b) in zip(pairs, depths):
+                if a != b:
+                    raise ValueError(f"{lr_path} names {a}-bit samples, {hr_path} {b}-bit: both files of a pair must agree")
+                if a != depths[0][0]:
+                    raise ValueError(f"{lr_path} names {a}-bit samples, {pairs[0][0]} {depths[0][0]}-bit: all pairs must agree")
+            colour = ColourSpec(bit_depth=depths[0][0] if depths else 8)
+        elif not isinstance(colour, ColourSpec):
+            raise ValueError(f"colour must be a ColourSpec or None, got {type(colour).__name__}")
+        device = torch.device(kw.get("device", "cpu"))
+        if device.type != "cuda":
+            raise RuntimeError("from_yuv420_rgb decodes on the HIP device only (there is no CPU fallback; "
+                               "harness.colour.yuv420_to_rgb_host is the CPU specification)")
+        seqs = []
+        for lr_path, hr_path in pairs:
+            frames = []
+            for path in (lr_path, hr_path):
+                n = parse_yuv_name(path)
+                mm = _map_frames(path, n.width, n.height, n.frames, bit_depth=colour.bit_depth)
+                host = torch.from_numpy(np.array(mm, dtype=mm.dtype.newbyteorder("=")))
+                dev = hip.bits16(host).to(device).view(colour.dtype)
+                frames.append(yuv420_to_rgb(*i420_planes(dev, n.height, n.width), colour))
+            seqs.append(tuple(frames))
+        return cls(seqs, **kw)
+
     def __len__(self) -> int:
         return len(self.shapes)
 

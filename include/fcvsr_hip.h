@@ -629,6 +629,46 @@ typedef struct fcvsr_crop_desc {
 int fcvsr_clip_batch_u8(const fcvsr_crop_desc* desc, const float* tab, int P, int s, float* dst, void* stream);
 /* the same for planes of uint16 samples; tab: the 1024-float table of the uint16 entry points above */
 int fcvsr_clip_batch_u16(const fcvsr_crop_desc* desc, const float* tab, int P, int s, float* dst, void* stream);
+
+/* ---- YUV 4:2:0 <-> planar RGB for the RGB models (specification: fcvsr_amd/harness/colour.py, which the kernels equal bit for
+ * bit) ---------------------------------------------------------------------------------------------------------------------------
+ * Integer arithmetic with 14-bit fixed-point coefficients r(x) = floor(x * 2^14 + 0.5), which the HOST computes for a matrix
+ * (Kr, Kb), a range and a bit depth d (P = 2^d - 1, s = 2^(d-8); limited range: y_off = 16s, luma span 219s, chroma span 224s; full
+ * range: y_off = 0, both spans P; c_off = 2^(d-1)); RGB is always full range 0..P.  `>>` is an arithmetic shift:
+ *   decode   Yt = cy*(y - y_off) + 2^13, U = up(u) - c_off, V = up(v) - c_off,
+ *            R = clip((Yt + rv*V) >> 14), G = clip((Yt - gu*U - gv*V) >> 14), B = clip((Yt + bu*U) >> 14)           (clip to 0..P)
+ *   encode   Y = clip(((kr*R + kg*G + kb*B + 2^13) >> 14) + y_off),
+ *            cb = -ur*R - ug*G + ub*B and cr = vr*R - vg*G - vb*B at full resolution, unrounded, summed over the two rows of a
+ *            chroma sample and over its columns, rounded once, + c_off, clipped.
+ * Chroma up-sampling (h x w -> 2h x 2w, indices clamped to the plane) is centre-sited vertically (taps 3 : 1) and, horizontally,
+ * FCVSR_CHROMA_CENTER: taps 3 : 1 (JPEG / MPEG-1 siting; the encoder averages the 2x2 block), or FCVSR_CHROMA_LEFT: co-sited with
+ * the even luma columns (MPEG-2 / H.264 / HEVC type 0; even columns take the sample, odd ones the mean of two; the encoder weighs
+ * columns 2i-1, 2i, 2i+1 by 1, 2, 1 with column -1 read as column 0).
+ * The struct is read on the host at call time. */
+enum { FCVSR_CHROMA_LEFT = 0, FCVSR_CHROMA_CENTER = 1 };
+typedef struct fcvsr_colour {
+  int32_t shift;                        /* fixed-point bits of every coefficient: 14 */
+  int32_t chroma_loc;                   /* FCVSR_CHROMA_* */
+  int32_t y_off, c_off;
+  int32_t cy, rv, gu, gv, bu;           /* decode */
+  int32_t kr, kg, kb;                   /* encode, luma */
+  int32_t ur, ug, ub, vr, vg, vb;       /* encode, chroma */
+} fcvsr_colour;
+/* N frames: planes y (H x W), u and v (H/2 x W/2), rows dense, frame n of a plane at base + n * stride (strides in samples: a
+ * batch of I420 frames in one buffer has y_stride = u_stride = v_stride = H*W*3/2) -> rgb, dense planar (N,3,H,W).  H, W even.
+ * One launch.  Rows are moved 8 or 16 bytes at a time when W % 8 == 0, the strides are multiples of 8 (y) and 4 (u, v) samples
+ * and the pointers are aligned to 8 (y, rgb) and 4 (u, v) samples; any other even W and any sample-aligned pointers take the
+ * scalar form of the same kernel.  The _u16 entry points take 10-bit samples in 16-bit containers (peak 1023; a sample above 1023
+ * reads as 1023), the others 8-bit samples. */
+int fcvsr_yuv420_to_rgb(const uint8_t* y, const uint8_t* u, const uint8_t* v, int N, int H, int W, long long y_stride,
+                        long long u_stride, long long v_stride, const fcvsr_colour* colour, uint8_t* rgb, void* stream);
+int fcvsr_yuv420_to_rgb_u16(const uint16_t* y, const uint16_t* u, const uint16_t* v, int N, int H, int W, long long y_stride,
+                            long long u_stride, long long v_stride, const fcvsr_colour* colour, uint16_t* rgb, void* stream);
+/* The other direction: rgb dense planar (N,3,H,W) -> planes y, u, v addressed as above. */
+int fcvsr_rgb_to_yuv420(const uint8_t* rgb, int N, int H, int W, const fcvsr_colour* colour, long long y_stride,
+                        long long u_stride, long long v_stride, uint8_t* y, uint8_t* u, uint8_t* v, void* stream);
+int fcvsr_rgb_to_yuv420_u16(const uint16_t* rgb, int N, int H, int W, const fcvsr_colour* colour, long long y_stride,
+                            long long u_stride, long long v_stride, uint16_t* y, uint16_t* u, uint16_t* v, void* stream);
 #ifdef __cplusplus
 }
 #endif
