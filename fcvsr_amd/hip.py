@@ -163,6 +163,8 @@ SIGNATURES = {
     "fcvsr_pack_weight_mfma": [_VP, _I, _I, _I, _I, _VP, _I, _I, _I, _I, _VP],
     "fcvsr_pack_weights_multi_block_elems": [],
     "fcvsr_pack_weights_mfma_multi": [_VP, _I, _I, _I, _VP],
+    "fcvsr_adam_multi_block_elems": [],
+    "fcvsr_adam_multi": [_VP, _I, _I, _VP, _VP, _VP, _I, _F, _F, _F, _F, _F, _F, _F, _VP],
     "fcvsr_act_bwd": [_VP, _VP, _VP, _F, C.c_longlong, _VP],
     "fcvsr_colsum_scratch_elems": [C.c_longlong, _I],
     "fcvsr_colsum": [_VP, C.c_longlong, _I, _VP, _VP, C.c_longlong, _I, _VP],

@@ -18,8 +18,11 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .loss import charbonnier_loss
+from .checkpoint import latest, load_checkpoint, save_checkpoint
+from .loss import charbonnier_loss, charbonnier_loss_mmedit
 from .ops import accumulate_into_grad
+from .schedule import schedule_lr
+from .optim import HipAdam
 
 
 def trainable_parameters(model: torch.nn.Module) -> List[Tuple[str, torch.nn.Parameter]]:
@@ -82,13 +85,16 @@ class TrainStep:
 
     def __init__(self, model: torch.nn.Module, *, lr: float = 1e-4, weight_decay: float = 1e-5,
                  loss_fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor] = charbonnier_loss, reduce_op: str = "sum",
-                 optimizer: Optional[torch.optim.Optimizer] = None, group=None, use_graph: bool = False,
-                 deterministic: Optional[bool] = None):
+                 optimizer=None, group=None, use_graph: bool = False, deterministic: Optional[bool] = None,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
         """use_graph: capture forward + loss + backward of the first batch shape in a hipGraph and replay it (the step is ~4 k
         small launches; replaying removes their host cost).  Gradients then live in static buffers; the all-reduce and the
         optimizer step stay eager.  Batches must keep the captured shape (a different shape is captured anew).
         deterministic: True / False sets `model.train_deterministic` (True: the backward uses no float atomics, so a step from the same
-        weights and batch gives the same gradients, loss and updated weights bit for bit, eager or replayed); None leaves it alone."""
+        weights and batch gives the same gradients, loss and updated weights bit for bit, eager or replayed); None leaves it alone.
+        optimizer: None (torch.optim.Adam over the trainable parameters, the default), a torch optimizer, "hip" (`HipAdam` with
+        `lr`, `betas`, `eps`, `weight_decay`: the whole update in one launch, the state two flat buffers) or a `HipAdam` over
+        `trainable_parameters(model)`."""
         self.model = model
         if deterministic is not None:
             if not hasattr(model, "train_deterministic"):
@@ -103,7 +109,14 @@ class TrainStep:
         # reference defaults: Adam(lr=1e-4, weight_decay=1e-5) (train_LD_freqCVSR_S_22.py:35,42,204)
         # (torch's fused=True Adam does not advance the parameters' version counters, which the inference engine's packed-weight
         # cache is keyed on: the default multi-tensor implementation stays)
-        self.optimizer = optimizer or torch.optim.Adam(params, lr=lr, weight_decay=weight_decay)
+        if isinstance(optimizer, str):
+            if optimizer != "hip":
+                raise ValueError(f'optimizer must be None, "hip", a HipAdam or a torch optimizer, got {optimizer!r}')
+            optimizer = HipAdam(params, self.names, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        elif isinstance(optimizer, HipAdam):
+            if len(optimizer.params) != len(params) or any(a is not b for a, b in zip(optimizer.params, params)):
+                raise ValueError("a HipAdam passed to TrainStep must be built over trainable_parameters(model), in that order")
+        self.optimizer = optimizer or torch.optim.Adam(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.loss_fn = loss_fn
         self.allreduce = FlatGradAllReduce(params, reduce_op, group)
 
@@ -121,8 +134,54 @@ class TrainStep:
 
     def reduce_and_update(self) -> None:
         """The collective half: ONE all-reduce of the flat gradient buffer, then the (replicated) optimizer step."""
-        self.allreduce()
-        self.optimizer.step()
+        flat = self.allreduce()
+        if isinstance(self.optimizer, HipAdam):
+            self.optimizer.step(flat)                      # one launch over the flat buffers (eager: not part of the captured graph)
+        else:
+            self.optimizer.step()
+
+    def set_lr(self, lr: float) -> None:
+        """The learning rate of the next update, for either kind of optimizer."""
+        if isinstance(self.optimizer, HipAdam):
+            self.optimizer.lr = float(lr)
+        else:
+            for group in self.optimizer.param_groups:
+                group["lr"] = float(lr)
+
+    def _meta(self) -> dict:
+        world = dist.get_world_size(self.allreduce.group) if dist.is_available() and dist.is_initialized() else 1
+        return {"names": list(self.names), "shapes": [list(p.shape) for p in self.allreduce.params],
+                "train_precision": getattr(self.model, "train_precision", None),
+                "deterministic": getattr(self.model, "train_deterministic", None), "world": world}
+
+    def state_dict(self) -> dict:
+        """{"optimizer": the optimizer's state (`HipAdam.state_dict()`, or {"kind": "torch", "state": optimizer.state_dict()} with
+        host tensors), "meta": what a resume must match - parameter names and shapes, the model's train_precision and deterministic
+        flag (None on a module without them) and the world size}.  The weights are the model's own state_dict, not part of this."""
+        if isinstance(self.optimizer, HipAdam):
+            opt = self.optimizer.state_dict()
+        else:
+            opt = {"kind": "torch", "state": _to_host(self.optimizer.state_dict())}
+        return {"optimizer": opt, "meta": self._meta()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restore `state_dict()`.  Every field of its meta must equal this TrainStep's (ValueError naming the field otherwise).  A
+        torch.optim.Adam state loads into a HipAdam (the run switches optimizers); a HipAdam state does not load into a torch
+        optimizer."""
+        mine, theirs = self._meta(), sd["meta"]
+        for field in ("names", "shapes", "train_precision", "deterministic", "world"):
+            a, b = theirs.get(field), mine[field]
+            if field == "shapes" and a is not None:
+                a = [list(s) for s in a]
+            if a != b:
+                raise ValueError(f"the saved training state does not match this TrainStep in `{field}`: saved {_brief(a)}, here {_brief(b)}")
+        opt = sd["optimizer"]
+        if isinstance(self.optimizer, HipAdam):
+            self.optimizer.load_state_dict(opt["state"] if opt.get("kind") == "torch" else opt)
+        elif opt.get("kind") == "torch":
+            self.optimizer.load_state_dict(opt["state"])
+        else:
+            raise ValueError(f"the saved optimizer state is of kind {opt.get('kind')!r}: it loads into TrainStep(optimizer=\"hip\") only")
 
     def __call__(self, lr_frames: torch.Tensor, hr: torch.Tensor) -> float:
         """lr_frames: (b, 7, C, h, w), hr: (b, C, 4h, 4w) - this rank's share of the batch."""
@@ -162,6 +221,22 @@ class TrainStep:
         sh.copy_(hr)
         graph.replay()
         return loss
+
+
+def _to_host(obj):
+    """`obj` with every tensor copied to the host (dicts, lists and tuples walked)."""
+    if isinstance(obj, torch.Tensor):
+        return obj.detach().cpu().clone()
+    if isinstance(obj, dict):
+        return {k: _to_host(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_host(v) for v in obj)
+    return obj
+
+
+def _brief(v) -> str:
+    s = repr(v)
+    return s if len(s) <= 120 else s[:117] + "..."
 
 
 # ---- data transforms of the reference loader (CVSR_train/opt/data_LD_LR.py:248-344), on {lr_imgs (f,h,w), hr_imgs (f',4h,4w)} ----
@@ -259,3 +334,103 @@ def validate(model: torch.nn.Module, sequences: Sequence[Tuple[torch.Tensor, tor
     from ..harness.infer import evaluate_sequence
     scores = [evaluate_sequence(model, _as_tensor(lr), _as_tensor(hr)) for lr, hr in sequences]
     return float(np.mean([s.psnr_mean for s in scores])), float(np.mean([s.ssim_mean for s in scores]))
+
+
+def iter_position(i: int, batches_per_epoch: int) -> Tuple[int, int]:
+    """(epoch, batch of that epoch) of iteration `i` (counted from 0) of a loop that walks `batches_per_epoch` batches per epoch."""
+    if i < 0 or batches_per_epoch < 1:
+        raise ValueError(f"iteration {i} of {batches_per_epoch} batches per epoch")
+    return i // batches_per_epoch, i % batches_per_epoch
+
+
+def _sampler_meta(sampler) -> dict:
+    return {"seed": int(sampler.seed), "len": len(sampler), "batches": len(sampler.plan(0)), "world": int(sampler.world)}
+
+
+def fit_iters(model: torch.nn.Module, sampler, *, total_iters: int, device, lr: float = 1e-5, betas: Tuple[float, float] = (0.9, 0.99),
+              weight_decay: float = 0.0, loss_fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor] = charbonnier_loss_mmedit,
+              reduce_op: str = "mean", schedule: Optional[dict] = None, optimizer="hip", use_graph: bool = False,
+              deterministic: Optional[bool] = None, ckpt_dir: Optional[str] = None, ckpt_interval: int = 5000, keep: Optional[int] = 2,
+              val_sequences: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None, val_interval: int = 5000,
+              log_interval: int = 100, resume: Optional[str] = None, on_iter: Optional[Callable[[int, float], None]] = None,
+              log: Callable[[str], None] = print, on_validate: Optional[Callable[[int, float, float], None]] = None) -> List[float]:
+    """Iteration loop of the reference's mmedit side (configs/restorers/fcvsr/fcvsr_s_redsLD_QP22.py:93-109): Adam with betas
+    (0.9, 0.99), a mean Charbonnier loss averaged over ranks, a cosine-restart schedule by iteration, and every `ckpt_interval`
+    iterations (and after the last) a checkpoint WITH the optimizer state, from which the run continues (`train/checkpoint.py`).
+
+    sampler: a `DeviceClipSampler` (anything with `seed`, `world`, `__len__`, `plan(epoch)` and `build(batch_plan)`).  An epoch is
+    one walk over this rank's batches, n = len(sampler.plan(0)) of them (the same on every rank); iteration i (from 0) is batch
+    i % n of epoch i // n, built with `sampler.build(sampler.plan(epoch)[i % n])` - a pure function of (seed, i), so a resumed run
+    builds no skipped batch.  The update of iteration i uses the learning rate `schedule` gives for position i.
+    schedule: {"name": "cosine_restart" | "multistep", **arguments} (`train/schedule.py`); None: one cosine period of `total_iters`
+    down to 1e-7, as the configs have.
+    resume: a checkpoint path, or "auto": `latest(ckpt_dir)`, a fresh start when there is none.  The checkpoint's parameter names
+    and shapes, train precision, deterministic flag, world size, schedule and sampler (seed, length, batches per epoch, world)
+    must be this call's: ValueError otherwise (a resume at another world size is refused).
+    on_iter(done, loss): called after every update and whatever checkpoint or validation that iteration makes, done = the number of
+    updates so far.  Validation: `validate(model, val_sequences)` on rank 0 every `val_interval` iterations, logged and passed to
+    `on_validate(done, psnr, ssim)` as in `fit`.
+    Returns the loss of every iteration, those before a resume included.
+
+    With deterministic=True and a seeded sampler, a run stopped at any checkpoint and resumed gives the losses, moments and weights
+    of the uninterrupted run bit for bit, eager or with use_graph.  Without it the restored state is exact and the steps that
+    follow differ as any two runs do."""
+    if total_iters < 0 or ckpt_interval < 1 or val_interval < 1 or log_interval < 1:
+        raise ValueError("total_iters must be >= 0 and the intervals >= 1")
+    if schedule is None:
+        schedule = {"name": "cosine_restart", "periods": [int(total_iters)], "restart_weights": [1.0], "min_lr": 1e-7}
+    schedule = dict(schedule)
+    step = TrainStep(model, lr=lr, weight_decay=weight_decay, loss_fn=loss_fn, reduce_op=reduce_op, optimizer=optimizer,
+                     use_graph=use_graph, deterministic=deterministic, betas=betas)
+    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    meta = _sampler_meta(sampler)
+    n_batches = meta["batches"]
+    if n_batches < 1:
+        raise ValueError("the sampler plans no batch for this rank")
+    history: List[float] = []
+    start = 0
+    if resume == "auto":
+        resume = latest(ckpt_dir) if ckpt_dir is not None else None
+    if resume is not None:
+        ckpt = load_checkpoint(resume)
+        for field in ("world", "len", "batches", "seed"):
+            if ckpt["sampler"].get(field) != meta[field]:
+                raise ValueError(f"{resume} was written with sampler {field} {ckpt['sampler'].get(field)}, this run has {meta[field]}: "
+                                 "a run resumes with the data order it was started with (the same world size and sampler)")
+        if dict(ckpt["schedule"]) != schedule:
+            raise ValueError(f"{resume} was written under the schedule {ckpt['schedule']}, this run asks for {schedule}")
+        if ckpt["iter"] > total_iters:
+            raise ValueError(f"{resume} is at iteration {ckpt['iter']}, past total_iters = {total_iters}")
+        model.load_state_dict(ckpt["model"], strict=True)
+        step.load_state_dict(ckpt["train_step"])
+        history = [float(v) for v in ckpt["loss_history"]]
+        start = int(ckpt["iter"])
+        log("resumed from %s at iteration %d" % (resume, start))
+    model.train()
+    plans, plans_epoch = None, -1
+    for i in range(start, total_iters):
+        epoch, k = iter_position(i, n_batches)
+        if epoch != plans_epoch:
+            plans, plans_epoch = sampler.plan(epoch), epoch
+        data = sampler.build(plans[k])
+        frames = data["lr_imgs"].permute(0, 2, 1, 3, 4).to(device)          # (b, frames, chn, h, w)
+        hr = data["hr_imgs"].to(device)[:, :, 0]
+        cur_lr = schedule_lr(schedule, lr, i)
+        step.set_lr(cur_lr)
+        loss = step(frames, hr)
+        history.append(loss)
+        done = i + 1
+        if done % log_interval == 0:
+            log("Iter: %d/%d | lr: %.3e | loss: %f" % (done, total_iters, cur_lr, loss))
+        if ckpt_dir is not None and rank == 0 and (done % ckpt_interval == 0 or done == total_iters):
+            save_checkpoint(ckpt_dir, done, {"model": _to_host(model.state_dict()), "train_step": step.state_dict(),
+                                             "schedule": schedule, "sampler": meta, "loss_history": list(history)}, keep=keep)
+        if done % val_interval == 0 and val_sequences and rank == 0:
+            psnr, ssim = validate(model, val_sequences)
+            model.train()
+            log("PSNR:%f, SSIM: %f" % (psnr, ssim))
+            if on_validate is not None:
+                on_validate(done, psnr, ssim)
+        if on_iter is not None:
+            on_iter(done, loss)
+    return history

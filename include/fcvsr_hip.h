@@ -153,6 +153,19 @@ int fcvsr_pack_weight_mfma(const float* w, int cout, int cin, int kh, int kw, vo
  * item i owns ceil(kh*kw*rows_pad*cols_pad / fcvsr_pack_weights_multi_block_elems()) consecutive blocks; total_blocks = their sum. */
 int fcvsr_pack_weights_multi_block_elems(void);
 int fcvsr_pack_weights_mfma_multi(const long long* tab, int n_items, int total_blocks, int dtype, void* stream);
+/* One Adam step (torch.optim.Adam's L2 form: no amsgrad, no decoupled decay) over n_items parameters in ONE launch.  grad (read),
+ * exp_avg and exp_avg_sq (read and written) are flat f32 buffers, 16-byte aligned, that share one set of offsets.  tab: device memory,
+ * 4 x int64 per item = {parameter pointer (f32 contiguous, 16-byte aligned), offset of the parameter in the flat buffers (elements),
+ * element count, first block}; item i owns ceil(count / fcvsr_adam_multi_block_elems()) consecutive blocks; total_blocks = their sum.
+ * Per element, in f32 with every operation rounded once, correctly rounded division and square root, subnormals kept:
+ *   g' = g + wd * p;  m' = m + (g' - m) * one_minus_b1;  v' = v * b2 + (g' * g') * one_minus_b2;
+ *   p' = p - step_size * (m' / (sqrt(v') / bc2_sqrt + eps))
+ * with step_size = lr / (1 - b1^t) and bc2_sqrt = sqrt(1 - b2^t) computed by the caller in f64 and rounded once (t >= 1 is the
+ * number of this step).  A null pointer, an empty table or t < 1 is FCVSR_E_ARG. */
+int fcvsr_adam_multi_block_elems(void);
+int fcvsr_adam_multi(const long long* tab, int n_items, int total_blocks, const float* grad, float* exp_avg, float* exp_avg_sq,
+                     int t, float step_size, float bc2_sqrt, float one_minus_b1, float b2, float one_minus_b2, float eps, float wd,
+                     void* stream);
 int fcvsr_act_bwd(const float* g, const float* y, float* out, float slope, long long n, void* stream);
 long long fcvsr_colsum_scratch_elems(long long npix, int C);
 int fcvsr_colsum(const float* x, long long npix, int C, float* out, float* scratch, long long scratch_elems, int accumulate, void* stream);
