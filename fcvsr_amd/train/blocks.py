@@ -1,6 +1,7 @@
 """Fused training blocks: sub-graphs of the forward whose forward AND backward are hand-written HIP kernels wrapped as
 torch.autograd Functions (the convolutions live in `ops.py`).  Each replaces a chain of device-side torch operators of
-`graph.py` and is tested against that chain (tests/test_train_gpu.py)."""
+`graph.py` and is tested against that chain (tests/test_train_gpu.py) and, per element and at the shapes where its kernels change
+branch, against a float64 reference (tests/test_train_blocks_gpu.py with tests/train_block_refs.py)."""
 from __future__ import annotations
 
 import torch
