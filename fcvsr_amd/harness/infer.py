@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from ..hip import bits16, frames_to_numpy
+from .ensemble import check_mode, for_mode
 from .metrics import psnr
 from .windows import window_indices
 
@@ -49,6 +50,13 @@ def _lr_frames(lr: torch.Tensor, dev) -> torch.Tensor:
     return pad_to_multiple(lr.float(), 4).to(dev)
 
 
+def _lr_frames_dense(lr: torch.Tensor, dev) -> torch.Tensor:
+    """The UNPADDED LR sequence on the device (the self-ensemble pads every variant itself), dtypes as `_lr_frames`."""
+    if lr.dtype in _INT_FRAMES:
+        return bits16(lr).to(dev).contiguous().view(lr.dtype)
+    return lr.float().to(dev).contiguous()
+
+
 def _windows(x: torch.Tensor, idx) -> torch.Tensor:
     """(b, T, C, Hp, Wp) windows of the device sequence x, in x's dtype."""
     xb = bits16(x)
@@ -71,14 +79,26 @@ def _quantised(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> np.ndarr
 
 @torch.no_grad()
 def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
-                           centres: Optional[Iterable[int]] = None, quantise: str = "truncate") -> np.ndarray:
+                           centres: Optional[Iterable[int]] = None, quantise: str = "truncate",
+                           ensemble: Optional[str] = None) -> np.ndarray:
     """lr: (N,C,H,W) float in [0,1], uint8, or uint16 (10-bit samples; host or device).  Returns uint8 (len(centres),C,4H,4W) SR
-    frames, uint16 for uint16 lr."""
+    frames, uint16 for uint16 lr.  ``ensemble``: None, "spatial" (x8 self-ensemble, `harness.ensemble`) or "spatial+temporal"
+    (x16); the windows are then built as variants straight from the resident sequence and never materialised."""
+    check_mode(ensemble)
     N, C, H, W = lr.shape
     dev = next(model.parameters()).device
-    x = _lr_frames(lr, dev)
     centres = list(range(N)) if centres is None else list(centres)
     out: List[np.ndarray] = []
+    if ensemble is not None:
+        ens, x = for_mode(model, ensemble), _lr_frames_dense(lr, dev)
+        for s in range(0, len(centres), batch):
+            idx = [window_indices(i, num_frames, N, padding) for i in centres[s:s + batch]]
+            if x.dtype in _INT_FRAMES:                                # quantised by the merge kernel
+                out.append(frames_to_numpy(ens.sequence(x, idx, dtype=x.dtype, quantise=quantise)))
+            else:
+                out.append(_quantised(ens.sequence(x, idx), quantise))
+        return np.concatenate(out, 0)
+    x = _lr_frames(lr, dev)
     for s in range(0, len(centres), batch):
         idx = [window_indices(i, num_frames, N, padding) for i in centres[s:s + batch]]
         win = _windows(x, idx)                                    # (b, 7, C, Hp, Wp)
@@ -101,7 +121,8 @@ class SequenceScores:
 
 @torch.no_grad()
 def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
-                      quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False) -> SequenceScores:
+                      quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
+                      ensemble: Optional[str] = None) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -110,8 +131,10 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     quantised with hr's peak).  Windows, padding, crop and quantisation are those of `super_resolve_sequence`; each batch is
     scored straight from the model output (cropped by view, quantised in the metric kernel - or, for integer lr, in the model's
     last kernel) by `device_metrics.frame_metrics`.  Without `return_frames` no SR frame leaves the device; with it the frames
-    come back in hr's dtype."""
+    come back in hr's dtype.  ``ensemble`` as in `super_resolve_sequence`: the merge kernel's output is scored in place of the
+    model's."""
     from .device_metrics import frame_metrics
+    check_mode(ensemble)
     N, C, H, W = lr.shape
     if tuple(hr.shape) != (N, C, 4 * H, 4 * W):
         raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, 4 * H, 4 * W)}, got {tuple(hr.shape)}")
@@ -123,21 +146,23 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     if quantise not in ("truncate", "round"):
         raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
     dev = next(model.parameters()).device
-    x = _lr_frames(lr, dev)
+    ens = for_mode(model, ensemble)
+    x = _lr_frames(lr, dev) if ens is None else _lr_frames_dense(lr, dev)
     p_dev, s_dev, frames = [], [], []                             # per-batch device results, fetched once at the end
     for s in range(0, N, batch):
         idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
-        win = _windows(x, idx)                                    # (b, 7, C, Hp, Wp)
+        win = _windows(x, idx) if ens is None else None           # (b, 7, C, Hp, Wp)
         hr_b = bits16(hr[s:s + len(idx)]).to(dev).view(hr.dtype)
-        if win.dtype in _INT_FRAMES:
-            sr8 = super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]
+        if x.dtype in _INT_FRAMES:
+            sr8 = (super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W] if ens is None else
+                   ens.sequence(x, idx, dtype=x.dtype, quantise=quantise))
             p, q = frame_metrics(sr8, hr_b, crop_border=crop_border, quantise=None, convert_to=convert_to)
             p_dev.append(p)
             s_dev.append(q)
             if return_frames:
                 frames.append(frames_to_numpy(sr8))
             continue
-        sr = model(win)[:, :, :4 * H, :4 * W]
+        sr = model(win)[:, :, :4 * H, :4 * W] if ens is None else ens.sequence(x, idx)
         p, q = frame_metrics(sr, hr_b, crop_border=crop_border, quantise=quantise, convert_to=convert_to)
         p_dev.append(p)
         s_dev.append(q)

@@ -18,6 +18,7 @@ import torch
 
 from .. import hip
 from .colour import ColourSpec, i420_planes, rgb_to_i420, yuv420_to_rgb
+from .ensemble import for_mode
 from .infer import pad_to_multiple, super_resolve_int
 from .windows import window_indices
 
@@ -133,7 +134,8 @@ def write_yuv420(path: str, y: np.ndarray, u: np.ndarray, v: np.ndarray) -> None
 
 @torch.no_grad()
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
-                         quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8) -> dict:
+                         quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
+                         ensemble: Optional[str] = None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -142,7 +144,9 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     columns padded to a multiple of 4 as the reference pads
     270 -> 272 and cropped off again.  U, V: ``hip.chroma_up4`` (bicubic) on both planes of a batch in one launch.  Frames are
     written in order as each batch completes.  Returns stats: frames, seconds, fps, bytes read and written.  No 10-bit
-    output sample exceeds 1023."""
+    output sample exceeds 1023.  ``ensemble`` (None, "spatial", "spatial+temporal": `harness.ensemble`) runs Y through the
+    self-ensemble; chroma is unchanged."""
+    ens = for_mode(model, ensemble)
     if getattr(model, "_img_ch", None) != 1:
         raise ValueError(f"super_resolve_yuv420 needs a one-channel (Y) model, got C={getattr(model, '_img_ch', None)}")
     if quantise not in hip.QUANTISE:
@@ -158,14 +162,18 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
         return hip.bits16(torch.from_numpy(np.ascontiguousarray(a).astype(host_dt, copy=False))).to(dev)
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
-    x = pad_to_multiple(to_dev(y)[:, None], 4)                                            # (N,1,Hp,Wp), zero padded
+    x = to_dev(y)[:, None]                                                                # (N,1,H,W)
+    x = pad_to_multiple(x, 4) if ens is None else x.contiguous().view(sdt)                # zero padded to (N,1,Hp,Wp); unpadded
     written = 0
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             e = min(N, s + batch)
             idx = [window_indices(i, num_frames, N, padding) for i in range(s, e)]
-            win = torch.stack([x[j] for j in idx], 0).view(sdt)                           # (b, 7, 1, Hp, Wp)
-            ysr = super_resolve_int(model, win, quantise)[:, 0, :4 * H, :4 * W]
+            if ens is None:
+                win = torch.stack([x[j] for j in idx], 0).view(sdt)                       # (b, 7, 1, Hp, Wp)
+                ysr = super_resolve_int(model, win, quantise)[:, 0, :4 * H, :4 * W]
+            else:
+                ysr = ens.sequence(x, idx, dtype=sdt, quantise=quantise)[:, 0]
             uv = to_dev(np.concatenate([u[s:e], v[s:e]], 0)).view(sdt)                    # (2b, H/2, W/2)
             uvsr = hip.chroma_up4(uv)
             ysr, uvsr = hip.frames_to_numpy(ysr), hip.frames_to_numpy(uvsr)
@@ -179,7 +187,8 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
 
 @torch.no_grad()
 def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int, *, colour: ColourSpec = ColourSpec(),
-                             batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7) -> dict:
+                             batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
+                             ensemble: Optional[str] = None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -189,7 +198,9 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     the Y path pads, windows of `num_frames` frames (`padding`, as `super_resolve_sequence`) run through
     ``model.super_resolve_u8`` / ``super_resolve_u16`` in batches of `batch`, and every batch of SR frames is cropped to
     4 height x 4 width, encoded on the device into I420 frame layout (`harness.colour.rgb_to_i420`), downloaded and written in
-    order.  Returns the stats of `super_resolve_yuv420`."""
+    order.  Returns the stats of `super_resolve_yuv420`.  ``ensemble`` (None, "spatial", "spatial+temporal") runs the decoded RGB
+    frames through the self-ensemble (`harness.ensemble`) between the two colour conversions."""
+    ens = for_mode(model, ensemble)
     if getattr(model, "_img_ch", None) != 3:
         raise ValueError(f"super_resolve_yuv420_rgb needs a three-channel (RGB) model, got C={getattr(model, '_img_ch', None)}")
     if not isinstance(colour, ColourSpec):
@@ -205,13 +216,17 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
     frames = hip.bits16(torch.from_numpy(np.array(mm, dtype=host_dt))).to(dev).view(sdt)      # one host copy of the mapped file
-    x = pad_to_multiple(hip.bits16(yuv420_to_rgb(*i420_planes(frames, H, W), colour)), 4)    # (N,3,Hp,Wp), zero padded
+    x = yuv420_to_rgb(*i420_planes(frames, H, W), colour)                                     # (N,3,H,W)
+    x = pad_to_multiple(hip.bits16(x), 4) if ens is None else x.contiguous()                  # zero padded to (N,3,Hp,Wp); unpadded
     written = 0
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
-            win = torch.stack([x[j] for j in idx], 0).view(sdt)                           # (b, 7, 3, Hp, Wp)
-            sr = super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]
+            if ens is None:
+                win = torch.stack([x[j] for j in idx], 0).view(sdt)                       # (b, 7, 3, Hp, Wp)
+                sr = super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]
+            else:
+                sr = ens.sequence(x, idx, dtype=sdt, quantise=quantise)
             out = hip.frames_to_numpy(rgb_to_i420(sr, colour))                            # (b, 16 W H 3/2)
             fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())
             written += out.nbytes

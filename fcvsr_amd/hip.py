@@ -217,6 +217,10 @@ SIGNATURES = {
     "fcvsr_yuv420_to_rgb_u16": [_VP, _VP, _VP, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(Colour), _VP, _VP],
     "fcvsr_rgb_to_yuv420": [_VP, _I, _I, _I, C.POINTER(Colour), C.c_longlong, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP],
     "fcvsr_rgb_to_yuv420_u16": [_VP, _I, _I, _I, C.POINTER(Colour), C.c_longlong, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP],
+    "fcvsr_ensemble_windows": [_VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP],
+    "fcvsr_ensemble_windows_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP],
+    "fcvsr_ensemble_windows_u16": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP],
+    "fcvsr_ensemble_merge": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
@@ -554,4 +558,85 @@ def clip_batch(desc: torch.Tensor, s: int, out: torch.Tensor, dtype: torch.dtype
     entry, table = _CLIP_BATCH[dtype]
     with torch.cuda.device(out.device):
         check(getattr(lib(), entry)(desc.data_ptr(), table(out.device).data_ptr(), P, s, out.data_ptr(), stream_ptr()), entry)
+    return out
+
+
+def _ceil4(v: int) -> int:
+    return (v + 3) // 4 * 4
+
+
+def ensemble_windows(frames: torch.Tensor, idx: torch.Tensor, reverse: bool = False):
+    """fcvsr_ensemble_windows / _u8 / _u16: the 8 self-ensemble variants (`harness.ensemble.variant_host`) of b windows, one launch.
+    `frames` is the dense UNPADDED sequence (N,C,h,w) on the HIP device, f32, uint8 or uint16 (integer samples enter as
+    ``u8_table`` / ``u16_table[min(k, 1023)]``); `idx` an int32 (b,T) tensor on the same device, row i the frame numbers of window
+    i (``reverse`` reads every row backwards).  Returns f32 ``(4,b,T,C,ceil4(h),ceil4(w))`` (variants 0..3) and
+    ``(4,b,T,C,ceil4(w),ceil4(h))`` (variants 4..7), each variant zero-padded at its own bottom / right."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype not in (torch.float32, torch.uint8, torch.uint16):
+        raise ValueError(f"frames: expected an f32, uint8 or uint16 (N,C,h,w) tensor, got {getattr(frames, 'dtype', type(frames))} "
+                         f"{tuple(getattr(frames, 'shape', ()))}")
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32:
+        raise ValueError(f"idx: expected an int32 (b,T) tensor, got {getattr(idx, 'dtype', type(idx))}")
+    if not frames.is_cuda or not idx.is_cuda:
+        raise RuntimeError("ensemble_windows runs on the HIP device only (there is no CPU fallback)")
+    if frames.device != idx.device:
+        raise ValueError(f"frames on {frames.device}, idx on {idx.device}")
+    if min(frames.shape) == 0 or idx.numel() == 0:
+        raise ValueError(f"empty input: frames {tuple(frames.shape)}, idx {tuple(idx.shape)}")
+    N, Cc, h, w = frames.shape
+    (b, T), dev = idx.shape, frames.device
+    src, idx = bits16(frames).contiguous(), idx.contiguous()
+    out_a = torch.empty((4, b, T, Cc, _ceil4(h), _ceil4(w)), dtype=torch.float32, device=dev)
+    out_t = torch.empty((4, b, T, Cc, _ceil4(w), _ceil4(h)), dtype=torch.float32, device=dev)
+    tail = (N, Cc, h, w, idx.data_ptr(), b, T, int(bool(reverse)), out_a.data_ptr(), out_t.data_ptr())
+    with torch.cuda.device(dev):
+        if frames.dtype == torch.float32:
+            check(lib().fcvsr_ensemble_windows(src.data_ptr(), *tail, stream_ptr()), "fcvsr_ensemble_windows")
+        elif frames.dtype == torch.uint8:
+            check(lib().fcvsr_ensemble_windows_u8(src.data_ptr(), u8_table(dev).data_ptr(), *tail, stream_ptr()),
+                  "fcvsr_ensemble_windows_u8")
+        else:
+            check(lib().fcvsr_ensemble_windows_u16(src.data_ptr(), u16_table(dev).data_ptr(), *tail, stream_ptr()),
+                  "fcvsr_ensemble_windows_u16")
+    return out_a, out_t
+
+
+def ensemble_merge(a: torch.Tensor, at: torch.Tensor, h: int, w: int, *, ra: Optional[torch.Tensor] = None,
+                   rat: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.float32, quantise: Optional[str] = None) -> torch.Tensor:
+    """fcvsr_ensemble_merge: `a` (4,b,C,4 ceil4(h),4 ceil4(w)) and `at` (4,b,C,4 ceil4(w),4 ceil4(h)), f32 on the HIP device, are the
+    model's outputs for variants 0..3 and 4..7 of b windows of h x w frames.  Returns the dense (b,C,4h,4w) self-ensemble result
+    (`harness.ensemble.ensemble_host`: crop, inverse transform, the fixed-order f32 sum, * 0.125): f32, or - `dtype` uint8 / uint16
+    with `quantise` "truncate" / "round" - quantised as the model's integer paths quantise.  `ra` / `rat`: the same pair for the
+    time-reversed windows; the result is then the mean of the two means.  One launch."""
+    ts = [("a", a), ("at", at)] + ([("ra", ra), ("rat", rat)] if ra is not None or rat is not None else [])
+    for name, t in ts:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 5:
+            raise ValueError(f"{name}: expected an f32 (4,b,C,rows,cols) tensor, got {getattr(t, 'dtype', type(t))}")
+        if not t.is_cuda:
+            raise RuntimeError("ensemble_merge runs on the HIP device only (there is no CPU fallback)")
+    if h < 1 or w < 1:
+        raise ValueError(f"h, w must be positive, got {h}, {w}")
+    b, Cc = a.shape[1], a.shape[2]
+    sa, st = (4, b, Cc, 4 * _ceil4(h), 4 * _ceil4(w)), (4, b, Cc, 4 * _ceil4(w), 4 * _ceil4(h))
+    for name, t in ts:
+        want = sa if name in ("a", "ra") else st
+        if tuple(t.shape) != want or t.device != a.device:
+            raise ValueError(f"{name}: expected {want} on {a.device}, got {tuple(t.shape)} on {t.device}")
+    if b == 0 or Cc == 0:
+        raise ValueError(f"empty input: {tuple(a.shape)}")
+    if dtype == torch.float32:
+        if quantise is not None:
+            raise ValueError("quantise applies to uint8 / uint16 results only")
+        code, q = F32, QUANT_NONE
+    elif dtype in (torch.uint8, torch.uint16):
+        if quantise not in QUANTISE:
+            raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+        code, q = _DT[dtype], QUANTISE[quantise]
+    else:
+        raise ValueError(f"dtype: torch.float32, torch.uint8 or torch.uint16, got {dtype!r}")
+    a, at = a.contiguous(), at.contiguous()
+    ra, rat = (ra.contiguous(), rat.contiguous()) if ra is not None else (None, None)
+    out = torch.empty((b, Cc, 4 * h, 4 * w), dtype=dtype, device=a.device)
+    with torch.cuda.device(a.device):
+        check(lib().fcvsr_ensemble_merge(a.data_ptr(), at.data_ptr(), ptr(ra), ptr(rat), b, Cc, h, w, code, q, out.data_ptr(),
+                                         stream_ptr()), "fcvsr_ensemble_merge")
     return out

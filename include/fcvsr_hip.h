@@ -682,6 +682,33 @@ int fcvsr_rgb_to_yuv420(const uint8_t* rgb, int N, int H, int W, const fcvsr_col
                         long long u_stride, long long v_stride, uint8_t* y, uint8_t* u, uint8_t* v, void* stream);
 int fcvsr_rgb_to_yuv420_u16(const uint16_t* rgb, int N, int H, int W, const fcvsr_colour* colour, long long y_stride,
                             long long u_stride, long long v_stride, uint16_t* y, uint16_t* u, uint16_t* v, void* stream);
+
+/* ---- test-time self-ensemble (reference mmedit_train/mmedit/models/common/ensemble.py, SpatialTemporalEnsemble; specification:
+ * fcvsr_amd/harness/ensemble.py, which the kernels equal bit for bit) -------------------------------------------------------------
+ * Variant i = 0..7 of a frame f (h x w):  A[r][c] = f[i & 2 ? h-1-r : r][i & 1 ? w-1-c : c],  v_i = i & 4 ? transpose(A) : A
+ * (reverse columns, then rows, then transpose: the list order of the reference).
+ * fcvsr_ensemble_windows: all 8 variants of b windows of T frames, one launch.  src: the dense UNPADDED sequence (N,C,h,w); idx: a
+ * DEVICE table (b,T) of frame numbers (a number outside 0..N-1 is clamped), row bi read backwards when reverse = 1.
+ *   out_a (4,b,T,C,ceil4(h),ceil4(w)) f32: variants 0..3;   out_t (4,b,T,C,ceil4(w),ceil4(h)) f32: variants 4..7
+ * (ceil4: the next multiple of 4), each variant zero-padded at its own bottom / right; every element is written, the padding
+ * included.  h and w are arbitrary.  out_a, out_t 16-byte aligned.  The _u8 / _u16 entry points read uint8 / uint16 samples through
+ * tab, the table of the uint8 / uint16 entry points above (a uint16 sample above 1023 reads tab[1023]). */
+int fcvsr_ensemble_windows(const float* src, int N, int C, int h, int w, const int32_t* idx, int b, int T, int reverse,
+                           float* out_a, float* out_t, void* stream);
+int fcvsr_ensemble_windows_u8(const uint8_t* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b, int T,
+                              int reverse, float* out_a, float* out_t, void* stream);
+int fcvsr_ensemble_windows_u16(const uint16_t* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b, int T,
+                               int reverse, float* out_a, float* out_t, void* stream);
+/* The other end, one launch: a (4,b,C,4 ceil4(h),4 ceil4(w)) and at (4,b,C,4 ceil4(w),4 ceil4(h)), dense f32, 16-byte aligned, are
+ * the model's outputs o_i for variants 0..3 and 4..7.  Each is cropped to its top-left 4h x 4w (4w x 4h), the inverse of its variant
+ * is applied (transpose if i & 4, then reverse rows if i & 2, then reverse columns if i & 1), and
+ *   acc = o_0;  acc = acc + o_i for i = 1..7 (each sum rounded once in f32, no FMA);  mean8 = acc * 0.125f.
+ * ra / rat (both or neither): the same pair for the time-reversed windows; the result is then (mean8 + mean8_rev) * 0.5f.
+ * out: dense (b,C,4h,4w).  out_dtype FCVSR_F32 (quantise = FCVSR_QUANT_NONE; 16-byte aligned), FCVSR_U8 or FCVSR_U16 (quantise =
+ * FCVSR_QUANT_TRUNCATE / _ROUND: clamp(v, 0, 1) * 255.0f or * 1023.0f, as the uint8 / uint16 entry points above; aligned to 4
+ * samples). */
+int fcvsr_ensemble_merge(const float* a, const float* at, const float* ra, const float* rat, int b, int C, int h, int w,
+                         int out_dtype, int quantise, void* out, void* stream);
 #ifdef __cplusplus
 }
 #endif
