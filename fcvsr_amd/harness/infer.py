@@ -111,18 +111,21 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
 
 @dataclass
 class SequenceScores:
-    """Per-frame PSNR / SSIM (f64) of one sequence, their means, and the uint8 SR frames when they were asked for."""
+    """Per-frame PSNR / SSIM (f64) of one sequence, their means, the uint8 SR frames when they were asked for, and the per-frame
+    NIQE of the SR frames and its mean when a `NiqeModel` was given."""
     psnr: np.ndarray
     ssim: np.ndarray
     psnr_mean: float
     ssim_mean: float
     frames: Optional[np.ndarray] = None
+    niqe: Optional[np.ndarray] = None
+    niqe_mean: Optional[float] = None
 
 
 @torch.no_grad()
 def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
-                      ensemble: Optional[str] = None) -> SequenceScores:
+                      ensemble: Optional[str] = None, niqe=None) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -132,10 +135,21 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     scored straight from the model output (cropped by view, quantised in the metric kernel - or, for integer lr, in the model's
     last kernel) by `device_metrics.frame_metrics`.  Without `return_frames` no SR frame leaves the device; with it the frames
     come back in hr's dtype.  ``ensemble`` as in `super_resolve_sequence`: the merge kernel's output is scored in place of the
-    model's."""
+    model's.
+
+    ``niqe``: a `harness.niqe.NiqeModel` adds the no-reference NIQE of every SR frame (`SequenceScores.niqe`, `.niqe_mean`), computed
+    by `niqe.frame_niqe_features` from the tensors the PSNR kernel reads (no extra model pass; the whole frame, NIQE's crop_border 0;
+    the Y channel of 3-channel frames); the features stay on the device and are fetched once at the end with the PSNR / SSIM
+    vectors.  8-bit only: uint16 hr with ``niqe`` raises ValueError."""
     from .device_metrics import frame_metrics
+    from . import niqe as niqe_mod
     check_mode(ensemble)
     N, C, H, W = lr.shape
+    if niqe is not None:
+        if hr.dtype == torch.uint16:
+            raise ValueError("NIQE is defined on 8-bit frames: niqe= cannot be used with uint16 (10-bit) hr")
+        niqe_mod.crop_geometry(4 * H, 4 * W, 0)                      # ValueError up front when the SR frame holds < 2 blocks
+    niqe_y = "Y" if C == 3 else None
     if tuple(hr.shape) != (N, C, 4 * H, 4 * W):
         raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, 4 * H, 4 * W)}, got {tuple(hr.shape)}")
     if hr.dtype not in _INT_FRAMES:
@@ -148,7 +162,7 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     dev = next(model.parameters()).device
     ens = for_mode(model, ensemble)
     x = _lr_frames(lr, dev) if ens is None else _lr_frames_dense(lr, dev)
-    p_dev, s_dev, frames = [], [], []                             # per-batch device results, fetched once at the end
+    p_dev, s_dev, n_dev, frames = [], [], [], []                  # per-batch device results, fetched once at the end
     for s in range(0, N, batch):
         idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
         win = _windows(x, idx) if ens is None else None           # (b, 7, C, Hp, Wp)
@@ -159,6 +173,8 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
             p, q = frame_metrics(sr8, hr_b, crop_border=crop_border, quantise=None, convert_to=convert_to)
             p_dev.append(p)
             s_dev.append(q)
+            if niqe is not None:
+                n_dev.append(niqe_mod.frame_niqe_features(sr8, niqe, convert_to=niqe_y))
             if return_frames:
                 frames.append(frames_to_numpy(sr8))
             continue
@@ -166,11 +182,15 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
         p, q = frame_metrics(sr, hr_b, crop_border=crop_border, quantise=quantise, convert_to=convert_to)
         p_dev.append(p)
         s_dev.append(q)
+        if niqe is not None:
+            n_dev.append(niqe_mod.frame_niqe_features(sr, niqe, quantise=quantise, convert_to=niqe_y))
         if return_frames:
             frames.append(_quantised(sr, quantise, peak))
     psnr_np, ssim_np = torch.cat(p_dev).cpu().numpy(), torch.cat(s_dev).cpu().numpy()
+    niqe_np = niqe_mod.scores_from_features(torch.cat(n_dev).cpu().numpy(), niqe) if niqe is not None else None
     return SequenceScores(psnr_np, ssim_np, float(np.mean(psnr_np)), float(np.mean(ssim_np)),
-                          np.concatenate(frames, 0) if return_frames else None)
+                          np.concatenate(frames, 0) if return_frames else None, niqe_np,
+                          float(np.mean(niqe_np)) if niqe is not None else None)
 
 
 def sequence_psnr(sr_u8: np.ndarray, hr_u8: np.ndarray, crop_border: int = 4) -> float:

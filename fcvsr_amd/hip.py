@@ -221,12 +221,16 @@ SIGNATURES = {
     "fcvsr_ensemble_windows_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP],
     "fcvsr_ensemble_windows_u16": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP],
     "fcvsr_ensemble_merge": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP],
+    "fcvsr_niqe_scratch_bytes": [_I] * 4,
+    "fcvsr_niqe_features": [_VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _VP, _VP, _VP, C.c_longlong,
+                            _VP],
+    "fcvsr_bicubic_downscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
              "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong,
-             "fcvsr_frame_metrics_scratch_bytes": C.c_longlong}
+             "fcvsr_frame_metrics_scratch_bytes": C.c_longlong, "fcvsr_niqe_scratch_bytes": C.c_longlong}
 
 
 def lib() -> C.CDLL:
@@ -461,6 +465,49 @@ def frame_metric_sums(sr: torch.Tensor, hr: torch.Tensor, quantise: int, crop_bo
         return out
     check(lib().fcvsr_frame_metrics(sr.data_ptr(), s_st, quantise, hr.data_ptr(), h_st, N, Cc, H, W, crop_border, to_y, win,
                                     out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, stream_ptr()), "fcvsr_frame_metrics")
+    return out
+
+
+def niqe_features(frames: torch.Tensor, quantise: int, crop_border: int, to_y: bool, taps, tables: torch.Tensor) -> torch.Tensor:
+    """fcvsr_niqe_features: frames (N,C,H,W) uint8 (QUANT_NONE) or f32 (any strides) on the HIP device; `taps` the 7 x 7 MSCN window
+    as correlation taps (the model's window flipped in both axes); `tables` the device (4, 9801) f64 tensor of
+    `harness.niqe.aggd_tables`.  Returns the (N, blocks, 36) f64 block features on the device, with no host sync.  Arguments are
+    checked by the library (FCVSR_E_ARG -> HipError)."""
+    N, Cc, H, W = frames.shape
+    blocks = (max(H - 2 * crop_border, 0) // 96) * (max(W - 2 * crop_border, 0) // 96)
+    nbytes = lib().fcvsr_niqe_scratch_bytes(N, H, W, crop_border)
+    scratch = torch.empty((max(8, nbytes) + 7) // 8, dtype=torch.float64, device=frames.device)
+    out = torch.empty((N, blocks, 36), dtype=torch.float64, device=frames.device)
+    strides = (C.c_int64 * 4)(*frames.stride())
+    win = (C.c_double * 49)(*[float(v) for v in np.asarray(taps, dtype=np.float64).reshape(-1)])
+    if tables.dtype != torch.float64 or tuple(tables.shape) != (4, 9801) or not tables.is_contiguous() or tables.device != frames.device:
+        raise ValueError("tables must be the contiguous (4, 9801) f64 tensor of harness.niqe.aggd_tables on the frames' device")
+    check(lib().fcvsr_niqe_features(frames.data_ptr(), strides, quantise, N, Cc, H, W, crop_border, int(bool(to_y)), win,
+                                    tables.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, stream_ptr()),
+          "fcvsr_niqe_features")
+    return out
+
+
+def bicubic_downscale(x: torch.Tensor, factor: int) -> torch.Tensor:
+    """fcvsr_bicubic_downscale: x (..., H, W) uint8 or f32 on the HIP device, H and W multiples of factor (2 or 4) -> f32
+    (..., H/factor, W/factor), the MATLAB-style antialiased bicubic down-scale (`harness.niqe.bicubic_downscale` is the contract),
+    one launch."""
+    if not x.is_cuda:
+        raise RuntimeError("bicubic_downscale runs on the HIP device only (there is no CPU fallback)")
+    if x.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"x must be uint8 or f32, got {x.dtype}")
+    if factor not in (2, 4):
+        raise ValueError(f"factor must be 2 or 4, got {factor!r}")
+    if x.dim() < 2 or x.shape[-2] % factor or x.shape[-1] % factor or 0 in x.shape[-2:]:
+        raise ValueError(f"the last two dimensions must be non-empty multiples of {factor}, got {tuple(x.shape)}")
+    x = x.contiguous()
+    H, W = x.shape[-2:]
+    out = torch.empty((*x.shape[:-2], H // factor, W // factor), dtype=torch.float32, device=x.device)
+    planes = out.numel() // ((H // factor) * (W // factor))
+    if planes:
+        with torch.cuda.device(x.device):
+            check(lib().fcvsr_bicubic_downscale(x.data_ptr(), _DT[x.dtype], planes, H, W, factor, out.data_ptr(), stream_ptr()),
+                  "fcvsr_bicubic_downscale")
     return out
 
 

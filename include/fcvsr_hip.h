@@ -709,6 +709,33 @@ int fcvsr_ensemble_windows_u16(const uint16_t* src, const float* tab, int N, int
  * samples). */
 int fcvsr_ensemble_merge(const float* a, const float* at, const float* ra, const float* rat, int b, int C, int h, int w,
                          int out_dtype, int quantise, void* out, void* stream);
+/* ---- NIQE block features and the MATLAB-style bicubic down-scale (reference mmedit/core/evaluation/metrics.py:398-590
+ * estimate_aggd_param / compute_feature / niqe_core / niqe, used by CVSR_train/metric/cal_VideoLQ.py; the down-scale is
+ * mmedit/datasets/pipelines/matlab_like_resize.py; the contract is fcvsr_amd/harness/niqe.py) ------------------------------------
+ * frames: N frames (N,C,H,W) with element strides host_strides[4] = {n, c, y, x}: uint8 (quantise = FCVSR_QUANT_NONE), or f32 in
+ * [0,1] quantised as fcvsr_frame_metrics does (FCVSR_QUANT_TRUNCATE / _ROUND).  C = 1 (to_y = 0), or C = 3 in RGB order with
+ * to_y = 1: the plane is then Y = (65.481 R + 128.553 G + 24.966 B) / 255 + 16 rounded half to even (metrics.py:576-585).
+ * The scored plane is the frame with crop_border pixels removed on each side, cropped to the top-left (floor(h/96) 96,
+ * floor(w/96) 96); FCVSR_E_ARG when it holds fewer than 2 blocks.  host_window[49]: the 7 x 7 MSCN window as CORRELATION taps
+ * (the model's gaussian_window flipped in both axes), borders replicated.  tables: DEVICE (4, 9801) f64 over the grid
+ * g = 0.2, 0.201 .. 10: G(2/g)^2 / (G(1/g) G(3/g)), sqrt(G(1/g) / G(3/g)), G(2/g) / G(1/g), g (harness/niqe.py aggd_tables).
+ * out: DEVICE (N, blocks, 36) f64, blocks in row-major order: per block the 18 AGGD features of compute_feature (:428-451) at
+ * scale 1, then at scale 2 (the 2x down-scale below applied to plane / 255, times 255; blocks of 48 x 48).  A block side with no
+ * sample (no negative or no positive value) gives alpha = 0.2 and NaN in the block's other entries of that distribution, as the
+ * reference's argmin over NaN does.  Everything from the integer samples on is f64 except the down-scale, which has the
+ * reference's f32 arithmetic; reductions have a fixed shape and use no atomics: two calls give the same bits.  No host sync.
+ * scratch: >= fcvsr_niqe_scratch_bytes(...) bytes, 8-byte aligned. */
+long long fcvsr_niqe_scratch_bytes(int N, int H, int W, int crop_border);
+int fcvsr_niqe_features(const void* frames, const int64_t* host_strides, int quantise, int N, int C, int H, int W, int crop_border,
+                        int to_y, const double* host_window, const double* tables, double* out, void* scratch,
+                        long long scratch_bytes, void* stream);
+/* MATLABLikeResize at scale 1/factor (matlab_like_resize.py:72-165), factor 2 or 4, of `planes` dense H x W planes (H, W multiples
+ * of factor; src_dtype FCVSR_U8 or FCVSR_F32) into dense f32 (H/factor, W/factor) planes, both passes in one launch: rows first,
+ * then columns; output i reads the 4 factor inputs factor i - 3 factor / 2 .. with the antialiased cubic taps
+ * [-3,-9,29,111,111,29,-9,-3]/256 (2x) or [-7,-45,-75,-49,93,399,745,987,...mirrored]/4096 (4x), out-of-range indices reflected
+ * with edge repeat (-1 -> 0, n -> n-1).  The reference's arithmetic and bits: f32 products added in tap order in f32, no FMA.  At 4x
+ * this is the standard "BI" LR maker. */
+int fcvsr_bicubic_downscale(const void* src, int src_dtype, long long planes, int H, int W, int factor, float* out, void* stream);
 #ifdef __cplusplus
 }
 #endif
