@@ -1,0 +1,167 @@
+// MATLAB-style bicubic up-scale (imresize, a = -0.5, symmetric border: the "Bicubic" row of SR tables), the counterpart of the
+// down-scale in niqe.hip: the reference's mmedit/datasets/pipelines/matlab_like_resize.py MATLABLikeResize at scale 2 or 4.  The
+// contract is fcvsr_amd/harness/niqe.py bicubic_upscale.
+//
+// Output o of an axis has its centre at c = (o + 0.5) / F - 0.5 and reads the inputs floor(c) - 1 .. floor(c) + 2, reflected with
+// edge repeat, with the weights cubic(c - i): they depend on o mod F only and are exact in f32 (UpTaps below).  The reference runs
+// two passes (rows, then columns) through an f64 buffer that holds f32 values; here both passes are one launch and the intermediate
+// stays in registers, with the same roundings: for one output row the vertical f32 sum of every source column (products added in
+// tap order), then the horizontal f32 sum of four of those.  No FMA: the library is built with -ffp-contract=off.
+//
+// A pure streaming kernel that writes F^2 times what it reads, so it is shaped for the stores.  A thread owns 4 consecutive, 4-aligned
+// outputs of a row (one input column at 4x, two at 2x): one 16-byte store for f32, 8 bytes for uint16, 4 for uint8, and consecutive
+// lanes write consecutive groups.  The aligned group 4q .. 4q+3 straddles two source-column groups (outputs 4m+2 .. 4m+5 share
+// their four columns), so a thread holds the 5 (4x) or 6 (2x) columns its outputs touch.  It makes the F output rows F n + F/2 ..
+// F n + 3F/2 - 1, which share their four source rows n-1 .. n+2 (n = -1 .. H-1: the first and last row group are half outside and
+// skip those rows), so the 4 x 5 samples are loaded once for 16 outputs.  The loads hit L1 / L2 (neighbours share columns); no LDS,
+// no atomics, no scratch.  At 2x with an odd W a row is 2 W = 4k + 2 outputs long: rows are then not 4-aligned and the last thread
+// of a row owns one column, so that shape takes scalar stores.
+#include "common.h"
+
+namespace {
+
+template <int F> struct UpTaps;
+template <> struct UpTaps<2> {
+  __device__ static float w(int phase, int k) {
+    constexpr float t[2][4] = {{-3.f / 128, 29.f / 128, 111.f / 128, -9.f / 128}, {-9.f / 128, 111.f / 128, 29.f / 128, -3.f / 128}};
+    return t[phase][k];
+  }
+};
+template <> struct UpTaps<4> {
+  __device__ static float w(int phase, int k) {
+    constexpr float t[4][4] = {{-45.f / 1024, 399.f / 1024, 745.f / 1024, -75.f / 1024},
+                               {-7.f / 1024, 93.f / 1024, 987.f / 1024, -49.f / 1024},
+                               {-49.f / 1024, 987.f / 1024, 93.f / 1024, -7.f / 1024},
+                               {-75.f / 1024, 745.f / 1024, 399.f / 1024, -45.f / 1024}};
+    return t[phase][k];
+  }
+};
+
+// out-of-range indices reflected with edge repeat (-1 -> 0, -2 -> 1, n -> n-1), periodic in 2n as the reference's index table
+__device__ inline int up_reflect(int i, int n) {
+  if ((unsigned)i < (unsigned)n) return i;
+  int m = i % (2 * n);
+  if (m < 0) m += 2 * n;
+  return m < n ? m : 2 * n - 1 - m;
+}
+
+__device__ inline float up_sample(const unsigned char* p, long long off) { return (float)p[off]; }
+__device__ inline float up_sample(const unsigned short* p, long long off) {   // 10-bit: a sample above 1023 reads as 1023
+  const unsigned short v = p[off];
+  return (float)(v > 1023 ? 1023 : v);
+}
+__device__ inline float up_sample(const float* p, long long off) { return p[off]; }
+
+// np.around(np.clip(v, 0, peak)) for the integer forms; f32 as it is
+__device__ inline void up_result(float v, float& o) { o = v; }
+__device__ inline void up_result(float v, unsigned char& o) { o = (unsigned char)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
+__device__ inline void up_result(float v, unsigned short& o) { o = (unsigned short)rintf(fminf(fmaxf(v, 0.f), 1023.f)); }
+
+__device__ inline void up_store4(float* p, const float o[4]) { *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]); }
+__device__ inline void up_store4(unsigned char* p, const unsigned char o[4]) {
+  *reinterpret_cast<uchar4*>(p) = make_uchar4(o[0], o[1], o[2], o[3]);
+}
+__device__ inline void up_store4(unsigned short* p, const unsigned short o[4]) {
+  *reinterpret_cast<ushort4*>(p) = make_ushort4(o[0], o[1], o[2], o[3]);
+}
+
+// (H + 1) * Wq threads per plane (blockIdx.y), Wq = ceil(W / CPT): thread (n + 1, q) makes output rows F n + F/2 + j (j < F) x output
+// columns 4q .. 4q+3.
+template <int F, class TI, class TO>
+__global__ __launch_bounds__(256) void upscale_kernel(const TI* __restrict__ src, int H, int W, TO* __restrict__ dst) {
+  constexpr int CPT = 4 / F, NC = CPT + 4;                  // input columns a thread owns; source columns it reads: m0-2 .. m0+CPT+1
+  const int Wq = (W + CPT - 1) / CPT, Ho = F * H, Wo = F * W;
+  const unsigned t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= (unsigned)(H + 1) * (unsigned)Wq) return;
+  const int q = (int)(t % (unsigned)Wq);
+  const int n = (int)(t / (unsigned)Wq) - 1;
+  const long long p = blockIdx.y;
+  const TI* sp = src + p * H * W;
+  const int m0 = q * CPT;
+  int cx[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) cx[k] = up_reflect(m0 - 2 + k, W);
+  float v[4][NC];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const long long row = (long long)up_reflect(n - 1 + r, H) * W;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) v[r][k] = up_sample(sp, row + cx[k]);
+  }
+  const bool vec = (W % CPT) == 0;                          // every row 4-aligned and whole (always at 4x)
+#pragma unroll
+  for (int j = 0; j < F; ++j) {
+    const int oy = F * n + F / 2 + j, py = (F / 2 + j) % F;
+    if (oy < 0 || oy >= Ho) continue;
+    float s[NC];                                            // the row pass of the contract at output row oy, per source column
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      float a = UpTaps<F>::w(py, 0) * v[0][k];
+#pragma unroll
+      for (int r = 1; r < 4; ++r) a = a + UpTaps<F>::w(py, r) * v[r][k];
+      s[k] = a;
+    }
+    TO o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int px = i % F, k0 = i / F + (px >= F / 2 ? 1 : 0);   // output 4q + i = F (m0 + i / F) + px reads s[k0 .. k0+3]
+      float a = UpTaps<F>::w(px, 0) * s[k0];
+#pragma unroll
+      for (int k = 1; k < 4; ++k) a = a + UpTaps<F>::w(px, k) * s[k0 + k];
+      up_result(a, o[i]);
+    }
+    TO* dp = dst + p * Ho * Wo + (long long)oy * Wo + 4 * q;
+    if (vec) {
+      up_store4(dp, o);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (4 * q + i < Wo) dp[i] = o[i];
+    }
+  }
+}
+
+template <int F, class TI, class TO>
+void launch_upscale(const void* src, long long planes, int H, int W, void* dst, hipStream_t stream) {
+  const long long per_plane = (long long)(H + 1) * ((W + 4 / F - 1) / (4 / F));
+  for (long long p0 = 0; p0 < planes; p0 += 65535) {        // grid.y holds 65535 planes
+    const long long np = planes - p0 < 65535 ? planes - p0 : 65535;
+    hipLaunchKernelGGL((upscale_kernel<F, TI, TO>), dim3((unsigned)((per_plane + 255) / 256), (unsigned)np), dim3(256), 0, stream,
+                       (const TI*)src + p0 * H * W, H, W, (TO*)dst + p0 * H * W * F * F);
+  }
+}
+
+template <int F>
+void dispatch_upscale(const void* src, int src_dtype, long long planes, int H, int W, void* out, int out_dtype, hipStream_t st) {
+  if (src_dtype == FCVSR_U8) {
+    if (out_dtype == FCVSR_U8) launch_upscale<F, unsigned char, unsigned char>(src, planes, H, W, out, st);
+    else launch_upscale<F, unsigned char, float>(src, planes, H, W, out, st);
+  } else if (src_dtype == FCVSR_U16) {
+    if (out_dtype == FCVSR_U16) launch_upscale<F, unsigned short, unsigned short>(src, planes, H, W, out, st);
+    else launch_upscale<F, unsigned short, float>(src, planes, H, W, out, st);
+  } else {
+    launch_upscale<F, float, float>(src, planes, H, W, out, st);
+  }
+}
+
+}  // namespace
+
+extern "C" int fcvsr_bicubic_upscale(const void* src, int src_dtype, long long planes, int H, int W, int factor, void* out, int out_dtype,
+                                     void* stream) {
+  FCVSR_CHECK_ARG(src && out, "null device pointer");
+  FCVSR_CHECK_ARG(src_dtype == FCVSR_U8 || src_dtype == FCVSR_U16 || src_dtype == FCVSR_F32, "src_dtype: FCVSR_U8, FCVSR_U16 or FCVSR_F32");
+  FCVSR_CHECK_ARG(out_dtype == FCVSR_F32 || (out_dtype == src_dtype), "out_dtype: FCVSR_F32, or the integer src_dtype");
+  FCVSR_CHECK_ARG(factor == 2 || factor == 4, "factor: 2 or 4");
+  FCVSR_CHECK_ARG(planes >= 1 && H >= 1 && W >= 1, "planes, H and W: at least 1");
+  // a thread per 4 outputs of a row and `factor` rows, numbered in 32 bits inside a plane
+  FCVSR_CHECK_ARG(H <= (1 << 20) && W <= (1 << 20) && (long long)(H + 1) * W < (1ll << 31), "plane too large");
+  const int src_elem = src_dtype == FCVSR_U8 ? 1 : src_dtype == FCVSR_U16 ? 2 : 4;
+  const int out_elem = out_dtype == FCVSR_U8 ? 1 : out_dtype == FCVSR_U16 ? 2 : 4;
+  FCVSR_CHECK_ARG(((uintptr_t)src % src_elem) == 0, "src: aligned to its sample size");
+  FCVSR_CHECK_ARG(((uintptr_t)out % (4 * out_elem)) == 0, "out: aligned to four samples (16 bytes for f32, 8 for uint16, 4 for uint8)");
+  hipStream_t st = (hipStream_t)stream;
+  if (factor == 2) dispatch_upscale<2>(src, src_dtype, planes, H, W, out, out_dtype, st);
+  else dispatch_upscale<4>(src, src_dtype, planes, H, W, out, out_dtype, st);
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}

@@ -112,7 +112,8 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
 @dataclass
 class SequenceScores:
     """Per-frame PSNR / SSIM (f64) of one sequence, their means, the uint8 SR frames when they were asked for, and the per-frame
-    NIQE of the SR frames and its mean when a `NiqeModel` was given."""
+    NIQE of the SR frames and its mean when a `NiqeModel` was given.  The `baseline_*` fields are the same scores of the bicubic
+    baseline (`evaluate_sequence(baseline="bicubic")`), None without it."""
     psnr: np.ndarray
     ssim: np.ndarray
     psnr_mean: float
@@ -120,12 +121,20 @@ class SequenceScores:
     frames: Optional[np.ndarray] = None
     niqe: Optional[np.ndarray] = None
     niqe_mean: Optional[float] = None
+    # the bicubic baseline's scores: per frame f64 / float, None without baseline=.  Plain attributes that `evaluate_sequence` sets,
+    # kept out of the dataclass's field list so that `dataclasses.fields` / `astuple` of existing callers keep their seven entries
+    baseline_psnr = None
+    baseline_ssim = None
+    baseline_psnr_mean = None
+    baseline_ssim_mean = None
+    baseline_niqe = None
+    baseline_niqe_mean = None
 
 
 @torch.no_grad()
 def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
-                      ensemble: Optional[str] = None, niqe=None) -> SequenceScores:
+                      ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -140,10 +149,19 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     ``niqe``: a `harness.niqe.NiqeModel` adds the no-reference NIQE of every SR frame (`SequenceScores.niqe`, `.niqe_mean`), computed
     by `niqe.frame_niqe_features` from the tensors the PSNR kernel reads (no extra model pass; the whole frame, NIQE's crop_border 0;
     the Y channel of 3-channel frames); the features stay on the device and are fetched once at the end with the PSNR / SSIM
-    vectors.  8-bit only: uint16 hr with ``niqe`` raises ValueError."""
+    vectors.  8-bit only: uint16 hr with ``niqe`` raises ValueError.
+
+    ``baseline="bicubic"`` adds the "Bicubic" row of SR tables (`SequenceScores.baseline_*`): every batch's LR centre frames, unpadded
+    (the border rule sees the true edge), go through `resize.bicubic_upscale(., 4)` (MATLAB `imresize`) and are scored by the same
+    `frame_metrics` call as the SR frames, with the same `crop_border` and `convert_to`, and the same NIQE with ``niqe``.  Integer lr
+    is up-scaled with out="int" (clipped, rounded half to even) and scored as it is; float lr gives f32 frames that are quantised as
+    the SR frames are.  No model pass and no host round trip is added, and the baseline does not depend on ``ensemble``."""
     from .device_metrics import frame_metrics
     from . import niqe as niqe_mod
+    from .resize import bicubic_upscale
     check_mode(ensemble)
+    if baseline not in (None, "bicubic"):
+        raise ValueError(f'baseline must be "bicubic" or None, got {baseline!r}')
     N, C, H, W = lr.shape
     if niqe is not None:
         if hr.dtype == torch.uint16:
@@ -163,10 +181,20 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     ens = for_mode(model, ensemble)
     x = _lr_frames(lr, dev) if ens is None else _lr_frames_dense(lr, dev)
     p_dev, s_dev, n_dev, frames = [], [], [], []                  # per-batch device results, fetched once at the end
+    bp_dev, bs_dev, bn_dev = [], [], []                           # the same for the bicubic baseline
     for s in range(0, N, batch):
         idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
         win = _windows(x, idx) if ens is None else None           # (b, 7, C, Hp, Wp)
         hr_b = bits16(hr[s:s + len(idx)]).to(dev).view(hr.dtype)
+        if baseline is not None:
+            lr_b = bits16(x)[s:s + len(idx), :, :H, :W].view(x.dtype)     # the unpadded centre frames
+            as_int = x.dtype in _INT_FRAMES
+            up = bicubic_upscale(lr_b, 4, out="int" if as_int else "f32")
+            p, q = frame_metrics(up, hr_b, crop_border=crop_border, quantise=None if as_int else quantise, convert_to=convert_to)
+            bp_dev.append(p)
+            bs_dev.append(q)
+            if niqe is not None:
+                bn_dev.append(niqe_mod.frame_niqe_features(up, niqe, quantise=None if as_int else quantise, convert_to=niqe_y))
         if x.dtype in _INT_FRAMES:
             sr8 = (super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W] if ens is None else
                    ens.sequence(x, idx, dtype=x.dtype, quantise=quantise))
@@ -188,9 +216,16 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
             frames.append(_quantised(sr, quantise, peak))
     psnr_np, ssim_np = torch.cat(p_dev).cpu().numpy(), torch.cat(s_dev).cpu().numpy()
     niqe_np = niqe_mod.scores_from_features(torch.cat(n_dev).cpu().numpy(), niqe) if niqe is not None else None
-    return SequenceScores(psnr_np, ssim_np, float(np.mean(psnr_np)), float(np.mean(ssim_np)),
-                          np.concatenate(frames, 0) if return_frames else None, niqe_np,
-                          float(np.mean(niqe_np)) if niqe is not None else None)
+    scores = SequenceScores(psnr_np, ssim_np, float(np.mean(psnr_np)), float(np.mean(ssim_np)),
+                            np.concatenate(frames, 0) if return_frames else None, niqe_np,
+                            float(np.mean(niqe_np)) if niqe is not None else None)
+    if baseline is not None:
+        scores.baseline_psnr, scores.baseline_ssim = torch.cat(bp_dev).cpu().numpy(), torch.cat(bs_dev).cpu().numpy()
+        scores.baseline_psnr_mean, scores.baseline_ssim_mean = float(np.mean(scores.baseline_psnr)), float(np.mean(scores.baseline_ssim))
+        if niqe is not None:
+            scores.baseline_niqe = niqe_mod.scores_from_features(torch.cat(bn_dev).cpu().numpy(), niqe)
+            scores.baseline_niqe_mean = float(np.mean(scores.baseline_niqe))
+    return scores
 
 
 def sequence_psnr(sr_u8: np.ndarray, hr_u8: np.ndarray, crop_border: int = 4) -> float:

@@ -1,7 +1,8 @@
 """NIQE (Natural Image Quality Evaluator), the no-reference score of SR frames that have no ground truth (reference
 mmedit/core/evaluation/metrics.py:398-590 estimate_aggd_param / compute_feature / niqe_core / niqe, used by
 CVSR_train/metric/cal_VideoLQ.py; known answers at tests/test_metrics/test_metrics.py:107-138), and the MATLAB-style antialiased
-bicubic down-scale it needs between its two scales (mmedit/datasets/pipelines/matlab_like_resize.py).
+bicubic down-scale it needs between its two scales (mmedit/datasets/pipelines/matlab_like_resize.py), with the up-scale half of the
+same function (`bicubic_upscale`: MATLAB `imresize`, the bicubic baseline of SR tables) next to it.
 
 The numpy functions here are the contract (f64, gamma from `math`); `frame_niqe` / `frame_niqe_features` compute the 36 features
 per 96 x 96 block on the HIP device (fcvsr_niqe_features) and only the 36 x 36 multivariate-Gaussian distance runs on the host.
@@ -104,6 +105,54 @@ def bicubic_downscale(img: np.ndarray, factor: int) -> np.ndarray:
             acc = acc + w[k] * np.take(x, _reflect(base + k, n), axis=axis)
         x = acc
     assert x.dtype == np.float32
+    return x.astype(np.float64)
+
+
+# cubic(x) taps of the up-scale (a = -0.5, no antialiasing): row `o mod factor` holds the weights of inputs floor(c) - 1 .. floor(c) + 2
+# around the centre c = (o + 0.5) / factor - 0.5 of output o.  Multiples of 1/128 (2x) and 1/1024 (4x), exact in f32.
+UPSCALE_TAPS = {2: np.array([[-3, 29, 111, -9], [-9, 111, 29, -3]], dtype=np.float64) / 128.0,
+                4: np.array([[-45, 399, 745, -75], [-7, 93, 987, -49], [-49, 987, 93, -7], [-75, 745, 399, -45]],
+                            dtype=np.float64) / 1024.0}
+_INT_PEAK = {np.dtype(np.uint8): 255, np.dtype(np.uint16): 1023}
+
+
+def bicubic_upscale(img: np.ndarray, factor: int, out: str = "f32") -> np.ndarray:
+    """MATLAB-style bicubic up-scale (`imresize`, a = -0.5, symmetric border: the "Bicubic" row of SR tables) of the last two axes
+    by 2 or 4, on the input's scale; any H, W >= 1.  Rows first, then columns, with the reference's arithmetic and so its bits:
+    the input of each pass is rounded to f32, every tap's product is an f32, and the four products are added in tap order in f32.
+    Out-of-range taps are reflected with edge repeat (period 2n, so a plane narrower than the kernel reflects several times).
+    uint16 input is 10-bit: a sample above 1023 is read as 1023.
+
+    out="f32": f64 in which every value is an f32, neither clipped nor rounded (uint8 input gives values around [0, 255]).
+    out="int" (uint8 / uint16 input only): clipped to [0, peak] (255 or 1023), rounded half to even, in the input's dtype - what
+    `imresize` returns for an integer image."""
+    if factor not in UPSCALE_TAPS:
+        raise ValueError(f"factor must be 2 or 4, got {factor!r}")
+    if out not in ("f32", "int"):
+        raise ValueError(f'out must be "f32" or "int", got {out!r}')
+    x = np.asarray(img)
+    if x.ndim < 2 or 0 in x.shape[-2:]:
+        raise ValueError(f"the last two axes must be non-empty, got shape {x.shape}")
+    peak = _INT_PEAK.get(x.dtype)
+    if out == "int" and peak is None:
+        raise ValueError(f'out="int" needs uint8 or uint16 input, got {x.dtype}')
+    src_dtype = x.dtype
+    if x.dtype == np.uint16:
+        x = np.minimum(x, 1023)
+    w = UPSCALE_TAPS[factor].astype(np.float32)
+    x = x.astype(np.float32)
+    for axis in (-2, -1):
+        n = x.shape[axis]
+        o = np.arange(n * factor)
+        first = (o - factor // 2) // factor - 1             # floor(c) - 1
+        shape = (-1, 1) if axis == -2 else (-1,)
+        acc = w[o % factor, 0].reshape(shape) * np.take(x, _reflect(first, n), axis=axis)
+        for k in range(1, 4):
+            acc = acc + w[o % factor, k].reshape(shape) * np.take(x, _reflect(first + k, n), axis=axis)
+        x = acc
+    assert x.dtype == np.float32
+    if out == "int":
+        return np.around(np.clip(x, 0, peak)).astype(src_dtype)
     return x.astype(np.float64)
 
 

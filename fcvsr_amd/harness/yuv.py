@@ -4,7 +4,8 @@ file to file (the test lists of reference CVSR_train/test_LD_freqCVSR_S_22.py:12
 Frame layout: Y (H x W), then U and V (H/2 x W/2 each), frames back to back; one byte per sample, or - ``bit_depth=10`` - two
 bytes, little-endian, the 10-bit value in the low bits (the JVET / HM ``_10bit`` raw files).  Y is super-resolved by the model's
 uint8 / uint16 path (windows of 7 frames, the reference's edge-replicate ``generate_input_index`` by default); U and V are
-up-sampled 4x by the bicubic chroma kernel (``hip.chroma_up4``).
+up-sampled 4x by the bicubic chroma kernel (``hip.chroma_up4``).  `upscale_yuv420` writes the bicubic baseline of a file (MATLAB
+`imresize` on all three planes, no model): the "Bicubic" video to put next to the SR one.
 """
 from __future__ import annotations
 
@@ -263,3 +264,39 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
             "bytes_written": written, "out_size": (4 * W, 4 * H), **niqe_stats}
+
+
+@torch.no_grad()
+def upscale_yuv420(src: str, dst: str, width: int, height: int, *, factor: int = 4, bit_depth: int = 8, batch: int = 8,
+                   device=None) -> dict:
+    """Write the bicubic baseline of the I420 sequence `src` (width x height) into the I420 file `dst` (factor width x factor
+    height), `factor` 2 or 4: Y, U and V all go through `resize.bicubic_upscale(out="int")`, the MATLAB-style `imresize` (clipped to
+    [0, peak], rounded half to even), on the device (`device`, default the current HIP device).  No model is involved.  `bit_depth`
+    is 8 or 10 for both files, as in `super_resolve_yuv420`; frames are uploaded in their integer dtype, `batch` at a time, and
+    written in order.  Returns the stats keys of `super_resolve_yuv420`.  No 10-bit output sample exceeds 1023."""
+    from .resize import bicubic_upscale
+    if factor not in (2, 4):
+        raise ValueError(f"factor must be 2 or 4, got {factor!r}")
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
+    N, H, W = y.shape
+    sdt, host_dt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.uint16, np.uint16)
+    dev = torch.device("cuda" if device is None else device)
+
+    def up(a):
+        """Planes of the file through the kernel and back; uint16 samples travel as int16 bits (hip.bits16)."""
+        t = hip.bits16(torch.from_numpy(np.array(a, dtype=host_dt))).to(dev).view(sdt)    # a copy: the file map is read-only
+        return hip.frames_to_numpy(bicubic_upscale(t, factor, out="int"))
+    t0 = time.perf_counter()
+    written = 0
+    with open(dst, "wb") as fh:
+        for s in range(0, N, batch):
+            e = min(N, s + batch)
+            ysr, uvsr = up(y[s:e]), up(np.concatenate([u[s:e], v[s:e]], 0))              # (b, fH, fW), (2b, fH/2, fW/2)
+            _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
+            written += ysr.nbytes + uvsr.nbytes
+    dt = time.perf_counter() - t0
+    return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
+            "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
+            "bytes_written": written, "out_size": (factor * W, factor * H)}

@@ -225,6 +225,7 @@ SIGNATURES = {
     "fcvsr_niqe_features": [_VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _VP, _VP, _VP, C.c_longlong,
                             _VP],
     "fcvsr_bicubic_downscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _VP],
+    "fcvsr_bicubic_upscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _I, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
@@ -509,6 +510,34 @@ def bicubic_downscale(x: torch.Tensor, factor: int) -> torch.Tensor:
             check(lib().fcvsr_bicubic_downscale(x.data_ptr(), _DT[x.dtype], planes, H, W, factor, out.data_ptr(), stream_ptr()),
                   "fcvsr_bicubic_downscale")
     return out
+
+
+def bicubic_upscale(x: torch.Tensor, factor: int, out: str = "f32") -> torch.Tensor:
+    """fcvsr_bicubic_upscale: x (..., H, W) uint8, uint16 (10-bit samples) or f32 on the HIP device, any H, W >= 1 ->
+    (..., factor H, factor W), the MATLAB-style bicubic up-scale at factor 2 or 4 (`harness.niqe.bicubic_upscale` is the contract),
+    one launch.  out="f32": the f32 sums on x's scale; out="int" (integer x only): clipped to [0, peak], rounded half to even, in
+    x's dtype.  Non-contiguous x is made dense first."""
+    if not x.is_cuda:
+        raise RuntimeError("bicubic_upscale runs on the HIP device only (there is no CPU fallback)")
+    if x.dtype not in (torch.uint8, torch.uint16, torch.float32):
+        raise ValueError(f"x must be uint8, uint16 or f32, got {x.dtype}")
+    if factor not in (2, 4):
+        raise ValueError(f"factor must be 2 or 4, got {factor!r}")
+    if out not in ("f32", "int"):
+        raise ValueError(f'out must be "f32" or "int", got {out!r}')
+    if out == "int" and x.dtype == torch.float32:
+        raise ValueError('out="int" needs uint8 or uint16 input, got f32')
+    if x.dim() < 2:
+        raise ValueError(f"expected (..., H, W), got {tuple(x.shape)}")
+    src = bits16(x).contiguous()
+    H, W = x.shape[-2:]
+    odt = x.dtype if out == "int" else torch.float32
+    res = torch.empty((*x.shape[:-2], factor * H, factor * W), dtype=odt, device=x.device)
+    if res.numel():
+        with torch.cuda.device(x.device):
+            check(lib().fcvsr_bicubic_upscale(src.data_ptr(), _DT[x.dtype], res.numel() // (factor * factor * H * W), H, W, factor,
+                                              res.data_ptr(), _DT[odt], stream_ptr()), "fcvsr_bicubic_upscale")
+    return res
 
 
 QUANTISE = {"truncate": QUANT_TRUNCATE, "round": QUANT_ROUND}

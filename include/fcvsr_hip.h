@@ -736,6 +736,20 @@ int fcvsr_niqe_features(const void* frames, const int64_t* host_strides, int qua
  * with edge repeat (-1 -> 0, n -> n-1).  The reference's arithmetic and bits: f32 products added in tap order in f32, no FMA.  At 4x
  * this is the standard "BI" LR maker. */
 int fcvsr_bicubic_downscale(const void* src, int src_dtype, long long planes, int H, int W, int factor, float* out, void* stream);
+/* MATLABLikeResize at scale factor (matlab_like_resize.py:72-165), factor 2 or 4: MATLAB imresize's bicubic (a = -0.5), the
+ * "Bicubic" row of SR tables.  `planes` dense H x W planes (any H, W >= 1; src_dtype FCVSR_U8, FCVSR_U16 or FCVSR_F32; a uint16
+ * sample above 1023 reads as 1023) into dense (factor H, factor W) planes, both passes in one launch: rows first, then columns.
+ * Output o has its centre at c = (o + 0.5) / factor - 0.5 and reads the 4 inputs floor(c) - 1 .. floor(c) + 2 with the cubic taps of
+ * phase o mod factor,
+ *   2x: [-3,29,111,-9]/128, [-9,111,29,-3]/128
+ *   4x: [-45,399,745,-75]/1024, [-7,93,987,-49]/1024, [-49,987,93,-7]/1024, [-75,745,399,-45]/1024
+ * out-of-range indices reflected with edge repeat (-1 -> 0, -2 -> 1, n -> n-1; period 2n).  The reference's arithmetic and bits: f32
+ * products added in tap order in f32, no FMA.  out_dtype FCVSR_F32: the sums as they are, on the input's scale (out 16-byte
+ * aligned).  out_dtype = src_dtype for FCVSR_U8 / FCVSR_U16: clipped to [0, 255] / [0, 1023] and rounded half to even, what imresize
+ * returns for an integer image (out aligned to four samples).  FCVSR_E_ARG: a null pointer, another factor or dtype pair, H, W or
+ * planes < 1. */
+int fcvsr_bicubic_upscale(const void* src, int src_dtype, long long planes, int H, int W, int factor, void* out, int out_dtype,
+                          void* stream);
 #ifdef __cplusplus
 }
 #endif
