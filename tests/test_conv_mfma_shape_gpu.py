@@ -7,21 +7,17 @@ sums in f64 and applies bias, activation, residuals and pixel shuffle.  Every en
     |got - ref| <= tau(n) * S + u * |ref|,
 S = the same operation on absolute values, n = the products summed into the entry, tau(n) as in test_train_conv_gpu.py, and u the
 rounding of the destination (one unit in the last place: 2^-7 bf16, 2^-10 f16, 0 f32)."""
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
+
+from tolerance import tau
 
 pytestmark = pytest.mark.gpu
 
 DT = {"bf16": torch.bfloat16, "f16": torch.float16}
 ULP = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10, torch.float32: 0.0}
 RS = [1.0, -0.5]
-
-
-def tau(n: int) -> float:
-    return 2.0 ** -16 if n <= 4096 else 2.0 ** -22 * math.sqrt(n)
 
 
 def _problem(cin, cout, levels, B, dst16, nres, mdt, ps, seed):

@@ -81,13 +81,13 @@ dw2 0.009; divenh_band ga 0.21, gb 0.23, dw1 0.006, dw2 0.031 (the largest at HW
 gslope 0.004; xscale out 0.17, gup 0.052; corr_lookup 0.53; the adjoint identities hold to 1.2e-8 of sum |u| |A^T g| (signed data), up2's to 1.1e-8 of the product (positive data)."""
 import contextlib
 import ctypes as C
-import math
 import re
 
 import pytest
 import torch
 
 import train_block_refs as R
+from tolerance import tau, worst_ratio
 
 pytestmark = pytest.mark.gpu
 
@@ -111,17 +111,6 @@ def _measured():
 
 
 MEASURED = _measured()
-
-
-def tau(n: int) -> float:
-    return 2.0 ** -16 if n <= 4096 else 2.0 ** -22 * math.sqrt(n)
-
-
-def worst_ratio(got, ref, S):
-    """max over entries of |got - ref| / S; an entry with S = 0 must be exact."""
-    err = (got.double().cpu() - ref).abs()
-    r = torch.where(S > 0, err / S.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, math.inf), torch.zeros_like(err)))
-    return float(r.max()) if r.numel() else 0.0
 
 
 def check_sum(tag, name, got, triple):

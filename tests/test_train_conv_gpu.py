@@ -18,21 +18,18 @@ missing or duplicated product exceeds it, at the large ones a missing tile does.
 next to tau(n) (run with -s)."""
 import ctypes as C
 import contextlib
-import math
 import zlib
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tolerance import tau, worst_ratio
+
 pytestmark = pytest.mark.gpu
 
 MMA = {"bf16": torch.bfloat16, "f16": torch.float16}
 SLOPE = 0.1
-
-
-def tau(n: int) -> float:
-    return 2.0 ** -16 if n <= 4096 else 2.0 ** -22 * math.sqrt(n)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -101,13 +98,6 @@ def reference(prec, x, w, b, gy, y_kernel, stride, act):
         g64 = gp.double()
         out["db"] = (g64.sum((0, 2, 3)), g64.abs().sum((0, 2, 3)), B * Ho * Wo)
     return out
-
-
-def worst_ratio(got, ref, S):
-    """max over entries of |got - ref| / S; an entry with S = 0 must be exact."""
-    err = (got.double().cpu() - ref).abs()
-    r = torch.where(S > 0, err / S.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, math.inf), torch.zeros_like(err)))
-    return float(r.max()) if r.numel() else 0.0
 
 
 def check(tag, got: dict, refs: dict):
