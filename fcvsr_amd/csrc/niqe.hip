@@ -297,6 +297,13 @@ NiqeGeometry niqe_geometry(int H, int W, int crop) {
 
 }  // namespace
 
+namespace fcvsr {
+// the NIQE form of the down-scale for brisque.hip: f64 planes of integers in, f64(f32 result) * 255 out
+void niqe_downscale2_f64(const double* src, long long planes, int H, int W, double* dst, hipStream_t stream) {
+  launch_downscale<2, SRC_NIQE>(src, planes, H, W, dst, stream);
+}
+}  // namespace fcvsr
+
 extern "C" long long fcvsr_niqe_scratch_bytes(int N, int H, int W, int crop_border) {
   if (N < 1 || H < 1 || W < 1 || crop_border < 0) return 0;
   const NiqeGeometry g = niqe_geometry(H, W, crop_border);

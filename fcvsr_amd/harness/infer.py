@@ -113,7 +113,8 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
 class SequenceScores:
     """Per-frame PSNR / SSIM (f64) of one sequence, their means, the uint8 SR frames when they were asked for, and the per-frame
     NIQE of the SR frames and its mean when a `NiqeModel` was given.  The `baseline_*` fields are the same scores of the bicubic
-    baseline (`evaluate_sequence(baseline="bicubic")`), None without it."""
+    baseline (`evaluate_sequence(baseline="bicubic")`), None without it; `brisque` / `brisque_mean` are the per-frame BRISQUE of the
+    SR frames and its mean when a `BrisqueModel` was given."""
     psnr: np.ndarray
     ssim: np.ndarray
     psnr_mean: float
@@ -129,12 +130,17 @@ class SequenceScores:
     baseline_ssim_mean = None
     baseline_niqe = None
     baseline_niqe_mean = None
+    # BRISQUE (brisque=): plain attributes for the same reason
+    brisque = None
+    brisque_mean = None
+    baseline_brisque = None
+    baseline_brisque_mean = None
 
 
 @torch.no_grad()
 def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
-                      ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None) -> SequenceScores:
+                      ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None, brisque=None) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -151,12 +157,18 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     the Y channel of 3-channel frames); the features stay on the device and are fetched once at the end with the PSNR / SSIM
     vectors.  8-bit only: uint16 hr with ``niqe`` raises ValueError.
 
+    ``brisque``: a `harness.brisque.BrisqueModel` adds the no-reference BRISQUE of every SR frame (`SequenceScores.brisque`,
+    `.brisque_mean`, and `.baseline_brisque` / `.baseline_brisque_mean` with ``baseline``) in the same way, by
+    `brisque.frame_brisque_features` from the same tensors; 3-channel frames are scored on their YIQ luma, which is not NIQE's Y.
+    8-bit only, even frame sizes of at least 16; it may be given together with ``niqe``.
+
     ``baseline="bicubic"`` adds the "Bicubic" row of SR tables (`SequenceScores.baseline_*`): every batch's LR centre frames, unpadded
     (the border rule sees the true edge), go through `resize.bicubic_upscale(., 4)` (MATLAB `imresize`) and are scored by the same
     `frame_metrics` call as the SR frames, with the same `crop_border` and `convert_to`, and the same NIQE with ``niqe``.  Integer lr
     is up-scaled with out="int" (clipped, rounded half to even) and scored as it is; float lr gives f32 frames that are quantised as
     the SR frames are.  No model pass and no host round trip is added, and the baseline does not depend on ``ensemble``."""
     from .device_metrics import frame_metrics
+    from . import brisque as brisque_mod
     from . import niqe as niqe_mod
     from .resize import bicubic_upscale
     check_mode(ensemble)
@@ -167,6 +179,11 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
         if hr.dtype == torch.uint16:
             raise ValueError("NIQE is defined on 8-bit frames: niqe= cannot be used with uint16 (10-bit) hr")
         niqe_mod.crop_geometry(4 * H, 4 * W, 0)                      # ValueError up front when the SR frame holds < 2 blocks
+    if brisque is not None:
+        brisque = brisque_mod._check_model(brisque)
+        if hr.dtype == torch.uint16:
+            raise ValueError("BRISQUE is defined on 8-bit frames: brisque= cannot be used with uint16 (10-bit) hr")
+        brisque_mod._check_size(4 * H, 4 * W)
     niqe_y = "Y" if C == 3 else None
     if tuple(hr.shape) != (N, C, 4 * H, 4 * W):
         raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, 4 * H, 4 * W)}, got {tuple(hr.shape)}")
@@ -182,6 +199,7 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     x = _lr_frames(lr, dev) if ens is None else _lr_frames_dense(lr, dev)
     p_dev, s_dev, n_dev, frames = [], [], [], []                  # per-batch device results, fetched once at the end
     bp_dev, bs_dev, bn_dev = [], [], []                           # the same for the bicubic baseline
+    q_dev, bq_dev = [], []                                        # BRISQUE features of the SR frames and of the baseline
     for s in range(0, N, batch):
         idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
         win = _windows(x, idx) if ens is None else None           # (b, 7, C, Hp, Wp)
@@ -195,6 +213,8 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
             bs_dev.append(q)
             if niqe is not None:
                 bn_dev.append(niqe_mod.frame_niqe_features(up, niqe, quantise=None if as_int else quantise, convert_to=niqe_y))
+            if brisque is not None:
+                bq_dev.append(brisque_mod.frame_brisque_features(up, quantise=None if as_int else quantise, convert_to=niqe_y))
         if x.dtype in _INT_FRAMES:
             sr8 = (super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W] if ens is None else
                    ens.sequence(x, idx, dtype=x.dtype, quantise=quantise))
@@ -203,6 +223,8 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
             s_dev.append(q)
             if niqe is not None:
                 n_dev.append(niqe_mod.frame_niqe_features(sr8, niqe, convert_to=niqe_y))
+            if brisque is not None:
+                q_dev.append(brisque_mod.frame_brisque_features(sr8, convert_to=niqe_y))
             if return_frames:
                 frames.append(frames_to_numpy(sr8))
             continue
@@ -212,6 +234,8 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
         s_dev.append(q)
         if niqe is not None:
             n_dev.append(niqe_mod.frame_niqe_features(sr, niqe, quantise=quantise, convert_to=niqe_y))
+        if brisque is not None:
+            q_dev.append(brisque_mod.frame_brisque_features(sr, quantise=quantise, convert_to=niqe_y))
         if return_frames:
             frames.append(_quantised(sr, quantise, peak))
     psnr_np, ssim_np = torch.cat(p_dev).cpu().numpy(), torch.cat(s_dev).cpu().numpy()
@@ -219,12 +243,18 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     scores = SequenceScores(psnr_np, ssim_np, float(np.mean(psnr_np)), float(np.mean(ssim_np)),
                             np.concatenate(frames, 0) if return_frames else None, niqe_np,
                             float(np.mean(niqe_np)) if niqe is not None else None)
+    if brisque is not None:
+        scores.brisque = brisque_mod.scores_from_features(torch.cat(q_dev).cpu().numpy(), brisque)
+        scores.brisque_mean = float(np.mean(scores.brisque))
     if baseline is not None:
         scores.baseline_psnr, scores.baseline_ssim = torch.cat(bp_dev).cpu().numpy(), torch.cat(bs_dev).cpu().numpy()
         scores.baseline_psnr_mean, scores.baseline_ssim_mean = float(np.mean(scores.baseline_psnr)), float(np.mean(scores.baseline_ssim))
         if niqe is not None:
             scores.baseline_niqe = niqe_mod.scores_from_features(torch.cat(bn_dev).cpu().numpy(), niqe)
             scores.baseline_niqe_mean = float(np.mean(scores.baseline_niqe))
+        if brisque is not None:
+            scores.baseline_brisque = brisque_mod.scores_from_features(torch.cat(bq_dev).cpu().numpy(), brisque)
+            scores.baseline_brisque_mean = float(np.mean(scores.baseline_brisque))
     return scores
 
 

@@ -21,6 +21,7 @@ from .. import hip
 from .colour import ColourSpec, i420_planes, rgb_to_i420, yuv420_to_rgb
 from .ensemble import for_mode
 from .infer import pad_to_multiple, super_resolve_int
+from . import brisque as brisque_mod
 from .niqe import crop_geometry, frame_niqe_features, scores_from_features
 from .windows import window_indices
 
@@ -143,6 +144,26 @@ def _check_niqe(niqe, bit_depth: int, width: int, height: int):
     crop_geometry(4 * height, 4 * width, 0)
 
 
+def _check_brisque(brisque, bit_depth: int, width: int, height: int):
+    """The `brisque=` keyword of the file-to-file paths, checked before anything is read: a BrisqueModel, 8-bit only, and an SR
+    frame of even sides >= 16."""
+    if brisque is None:
+        return None
+    brisque = brisque_mod._check_model(brisque)
+    if bit_depth != 8:
+        raise ValueError("BRISQUE is defined on 8-bit frames: brisque= cannot be used with a 10-bit run")
+    brisque_mod._check_size(4 * height, 4 * width)
+    return brisque
+
+
+def _brisque_stats(feats, brisque) -> dict:
+    """One download of the per-batch device features, then the host's range scaling and RBF regressor per frame."""
+    if brisque is None:
+        return {}
+    scores = brisque_mod.scores_from_features(torch.cat(feats).cpu().numpy(), brisque)
+    return {"brisque": scores, "brisque_mean": float(np.mean(scores))}
+
+
 def _niqe_stats(feats, niqe) -> dict:
     """One download of the per-batch device features, then the host's 36 x 36 Gaussian distance per frame."""
     if niqe is None:
@@ -154,7 +175,7 @@ def _niqe_stats(feats, niqe) -> dict:
 @torch.no_grad()
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
                          quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
-                         ensemble: Optional[str] = None, niqe=None) -> dict:
+                         ensemble: Optional[str] = None, niqe=None, brisque=None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -166,9 +187,11 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     output sample exceeds 1023.  ``ensemble`` (None, "spatial", "spatial+temporal": `harness.ensemble`) runs Y through the
     self-ensemble; chroma is unchanged.  ``niqe`` (a `harness.niqe.NiqeModel`) scores every SR luma frame with NIQE on the device
     before it is downloaded and adds ``"niqe"`` (per frame, f64) and ``"niqe_mean"`` to the stats; the written bytes are the same.
-    NIQE is 8-bit only: ``bit_depth=10`` with ``niqe`` raises ValueError."""
+    NIQE is 8-bit only: ``bit_depth=10`` with ``niqe`` raises ValueError.  ``brisque`` (a `harness.brisque.BrisqueModel`) does the
+    same with BRISQUE (``"brisque"``, ``"brisque_mean"``), 8-bit only as well; the two may be given together."""
     ens = for_mode(model, ensemble)
     _check_niqe(niqe, bit_depth, width, height)
+    brisque = _check_brisque(brisque, bit_depth, width, height)
     if getattr(model, "_img_ch", None) != 1:
         raise ValueError(f"super_resolve_yuv420 needs a one-channel (Y) model, got C={getattr(model, '_img_ch', None)}")
     if quantise not in hip.QUANTISE:
@@ -186,7 +209,7 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     t0 = time.perf_counter()
     x = to_dev(y)[:, None]                                                                # (N,1,H,W)
     x = pad_to_multiple(x, 4) if ens is None else x.contiguous().view(sdt)                # zero padded to (N,1,Hp,Wp); unpadded
-    written, niqe_feats = 0, []
+    written, niqe_feats, brisque_feats = 0, [], []
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             e = min(N, s + batch)
@@ -198,12 +221,14 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
                 ysr = ens.sequence(x, idx, dtype=sdt, quantise=quantise)[:, 0]
             if niqe is not None:
                 niqe_feats.append(frame_niqe_features(ysr[:, None], niqe))
+            if brisque is not None:
+                brisque_feats.append(brisque_mod.frame_brisque_features(ysr[:, None]))
             uv = to_dev(np.concatenate([u[s:e], v[s:e]], 0)).view(sdt)                    # (2b, H/2, W/2)
             uvsr = hip.chroma_up4(uv)
             ysr, uvsr = hip.frames_to_numpy(ysr), hip.frames_to_numpy(uvsr)
             _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
             written += ysr.nbytes + uvsr.nbytes
-    niqe_stats = _niqe_stats(niqe_feats, niqe)
+    niqe_stats = {**_niqe_stats(niqe_feats, niqe), **_brisque_stats(brisque_feats, brisque)}
     dt = time.perf_counter() - t0
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
@@ -213,7 +238,7 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
 @torch.no_grad()
 def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int, *, colour: ColourSpec = ColourSpec(),
                              batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
-                             ensemble: Optional[str] = None, niqe=None) -> dict:
+                             ensemble: Optional[str] = None, niqe=None, brisque=None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -225,9 +250,12 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     4 height x 4 width, encoded on the device into I420 frame layout (`harness.colour.rgb_to_i420`), downloaded and written in
     order.  Returns the stats of `super_resolve_yuv420`.  ``ensemble`` (None, "spatial", "spatial+temporal") runs the decoded RGB
     frames through the self-ensemble (`harness.ensemble`) between the two colour conversions.  ``niqe`` as in
-    `super_resolve_yuv420`: the Y of YCbCr of the SR RGB frames (convert_to="Y") is scored before the encode; 8-bit only."""
+    `super_resolve_yuv420`: the Y of YCbCr of the SR RGB frames (convert_to="Y") is scored before the encode; 8-bit only.
+    ``brisque`` as in `super_resolve_yuv420`: the YIQ luma of the SR RGB frames (BRISQUE's own "Y", not NIQE's) is scored before
+    the encode; 8-bit only."""
     ens = for_mode(model, ensemble)
     _check_niqe(niqe, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
+    brisque = _check_brisque(brisque, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
     if getattr(model, "_img_ch", None) != 3:
         raise ValueError(f"super_resolve_yuv420_rgb needs a three-channel (RGB) model, got C={getattr(model, '_img_ch', None)}")
     if not isinstance(colour, ColourSpec):
@@ -245,7 +273,7 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     frames = hip.bits16(torch.from_numpy(np.array(mm, dtype=host_dt))).to(dev).view(sdt)      # one host copy of the mapped file
     x = yuv420_to_rgb(*i420_planes(frames, H, W), colour)                                     # (N,3,H,W)
     x = pad_to_multiple(hip.bits16(x), 4) if ens is None else x.contiguous()                  # zero padded to (N,3,Hp,Wp); unpadded
-    written, niqe_feats = 0, []
+    written, niqe_feats, brisque_feats = 0, [], []
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
@@ -256,10 +284,12 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
                 sr = ens.sequence(x, idx, dtype=sdt, quantise=quantise)
             if niqe is not None:
                 niqe_feats.append(frame_niqe_features(sr, niqe, convert_to="Y"))
+            if brisque is not None:
+                brisque_feats.append(brisque_mod.frame_brisque_features(sr, convert_to="Y"))
             out = hip.frames_to_numpy(rgb_to_i420(sr, colour))                            # (b, 16 W H 3/2)
             fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())
             written += out.nbytes
-    niqe_stats = _niqe_stats(niqe_feats, niqe)
+    niqe_stats = {**_niqe_stats(niqe_feats, niqe), **_brisque_stats(brisque_feats, brisque)}
     dt = time.perf_counter() - t0
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),

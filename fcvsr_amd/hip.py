@@ -224,6 +224,9 @@ SIGNATURES = {
     "fcvsr_niqe_scratch_bytes": [_I] * 4,
     "fcvsr_niqe_features": [_VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _VP, _VP, _VP, C.c_longlong,
                             _VP],
+    "fcvsr_brisque_scratch_bytes": [_I] * 3,
+    "fcvsr_brisque_features": [_VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _VP, _VP, C.c_longlong, _VP,
+                               _VP],
     "fcvsr_bicubic_downscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _VP],
     "fcvsr_bicubic_upscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _I, _VP],
 }
@@ -231,7 +234,8 @@ _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
              "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong,
-             "fcvsr_frame_metrics_scratch_bytes": C.c_longlong, "fcvsr_niqe_scratch_bytes": C.c_longlong}
+             "fcvsr_frame_metrics_scratch_bytes": C.c_longlong, "fcvsr_niqe_scratch_bytes": C.c_longlong,
+             "fcvsr_brisque_scratch_bytes": C.c_longlong}
 
 
 def lib() -> C.CDLL:
@@ -486,6 +490,24 @@ def niqe_features(frames: torch.Tensor, quantise: int, crop_border: int, to_y: b
     check(lib().fcvsr_niqe_features(frames.data_ptr(), strides, quantise, N, Cc, H, W, crop_border, int(bool(to_y)), win,
                                     tables.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, stream_ptr()),
           "fcvsr_niqe_features")
+    return out
+
+
+def brisque_features(frames: torch.Tensor, quantise: int, to_y: bool, taps, tables: torch.Tensor) -> torch.Tensor:
+    """fcvsr_brisque_features: frames (N,C,H,W) uint8 (QUANT_NONE) or f32 (any strides) on the HIP device; `taps` the 7 x 7 MSCN
+    window as correlation taps; `tables` the device (4, 9801) f64 tensor of `harness.brisque.brisque_tables`.  Returns the (N, 36)
+    f64 features on the device, with no host sync.  Arguments are checked by the library (FCVSR_E_ARG -> HipError)."""
+    N, Cc, H, W = frames.shape
+    nbytes = lib().fcvsr_brisque_scratch_bytes(N, H, W)
+    scratch = torch.empty((max(8, nbytes) + 7) // 8, dtype=torch.float64, device=frames.device)
+    out = torch.empty((N, 36), dtype=torch.float64, device=frames.device)
+    strides = (C.c_int64 * 4)(*frames.stride())
+    win = (C.c_double * 49)(*[float(v) for v in np.asarray(taps, dtype=np.float64).reshape(-1)])
+    if tables.dtype != torch.float64 or tuple(tables.shape) != (4, 9801) or not tables.is_contiguous() or tables.device != frames.device:
+        raise ValueError("tables must be the contiguous (4, 9801) f64 tensor of harness.brisque.brisque_tables on the frames' device")
+    check(lib().fcvsr_brisque_features(frames.data_ptr(), strides, quantise, N, Cc, H, W, int(bool(to_y)), win, tables.data_ptr(),
+                                       scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), stream_ptr()),
+          "fcvsr_brisque_features")
     return out
 
 

@@ -729,6 +729,24 @@ long long fcvsr_niqe_scratch_bytes(int N, int H, int W, int crop_border);
 int fcvsr_niqe_features(const void* frames, const int64_t* host_strides, int quantise, int N, int C, int H, int W, int crop_border,
                         int to_y, const double* host_window, const double* tables, double* out, void* scratch,
                         long long scratch_bytes, void* stream);
+/* ---- BRISQUE features (reference CVSR_train/metric/brisque.py natural_scene_statistics / estimate_ggd_param /
+ * estimate_aggd_param / normalize_img_with_guass; the contract is fcvsr_amd/harness/brisque.py) -----------------------------------
+ * frames, host_strides, quantise as fcvsr_niqe_features.  C = 1 (to_y = 0), or C = 3 in RGB order with to_y = 1: the plane is then
+ * the luma of YIQ in integers, round_half_even((299 R + 587 G + 114 B) / 1000) - not the Y of YCbCr that NIQE scores.  The whole
+ * frame is scored; H and W even and >= 16, else FCVSR_E_ARG.  host_window[49]: the 7 x 7 MSCN window as correlation taps; the
+ * plane's border is ZERO-padded and sigma = sqrt(|E[x^2] - mu^2| + 2^-23).  tables: DEVICE (4, 9801) f64 over the grid
+ * g = 0.2, 0.201 .. 10: G(1/g) G(3/g) / G(2/g)^2, G(2/g)^2 / (G(1/g) G(3/g)), G(2/g) / sqrt(G(1/g) G(3/g)), g (harness/brisque.py
+ * brisque_tables).
+ * out: DEVICE (N, 36) f64: per scale (the frame, then the 2x down-scale above applied to plane / 255, times 255) alpha and sigma^2
+ * of the MSCN plane's GGD fit and (alpha, eta, sigma_l^2, sigma_r^2) of the AGGD fit of the MSCN plane times itself rolled by
+ * (0,1), (1,0), (1,1), (-1,1) circularly over the whole plane.  A product with no negative or no positive sample gives
+ * alpha = 0.2 and NaN where the formulas give NaN.  f64 from the integer samples on, except the down-scale; reductions have a fixed
+ * shape and use no atomics: two calls give the same bits.  No host sync.
+ * scratch: >= fcvsr_brisque_scratch_bytes(...) bytes, 8-byte aligned. */
+long long fcvsr_brisque_scratch_bytes(int N, int H, int W);
+int fcvsr_brisque_features(const void* frames, const int64_t* host_strides, int quantise, int N, int C, int H, int W, int to_y,
+                           const double* host_window, const double* tables, void* scratch, long long scratch_bytes, double* out,
+                           void* stream);
 /* MATLABLikeResize at scale 1/factor (matlab_like_resize.py:72-165), factor 2 or 4, of `planes` dense H x W planes (H, W multiples
  * of factor; src_dtype FCVSR_U8 or FCVSR_F32) into dense f32 (H/factor, W/factor) planes, both passes in one launch: rows first,
  * then columns; output i reads the 4 factor inputs factor i - 3 factor / 2 .. with the antialiased cubic taps
