@@ -23,7 +23,7 @@ import torch
 from ..hip import bits16, frames_to_numpy
 from .ensemble import check_mode, for_mode
 from .metrics import psnr
-from .windows import window_indices
+from .shots import check_auto, cuts_from_sad, device_pair_sad, resolve_cuts, shot_ranges, windows_for
 
 
 def pad_to_multiple(frames: torch.Tensor, mult: int = 4) -> torch.Tensor:
@@ -57,6 +57,12 @@ def _lr_frames_dense(lr: torch.Tensor, dev) -> torch.Tensor:
     return lr.float().to(dev).contiguous()
 
 
+def _auto_cuts(x: torch.Tensor, count: int, threshold: float):
+    """`shots.detect_cuts` of the resident integer sequence x on the device.  x may carry the zero padding of `_lr_frames`, which adds
+    nothing to the sums: `count` is C*H*W of the unpadded frames."""
+    return lambda: cuts_from_sad(device_pair_sad(x), count, 8 if x.dtype == torch.uint8 else 10, threshold)
+
+
 def _windows(x: torch.Tensor, idx) -> torch.Tensor:
     """(b, T, C, Hp, Wp) windows of the device sequence x, in x's dtype."""
     xb = bits16(x)
@@ -80,27 +86,35 @@ def _quantised(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> np.ndarr
 @torch.no_grad()
 def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                            centres: Optional[Iterable[int]] = None, quantise: str = "truncate",
-                           ensemble: Optional[str] = None) -> np.ndarray:
+                           ensemble: Optional[str] = None, cuts=None, cut_threshold: float = 10.0) -> np.ndarray:
     """lr: (N,C,H,W) float in [0,1], uint8, or uint16 (10-bit samples; host or device).  Returns uint8 (len(centres),C,4H,4W) SR
     frames, uint16 for uint16 lr.  ``ensemble``: None, "spatial" (x8 self-ensemble, `harness.ensemble`) or "spatial+temporal"
-    (x16); the windows are then built as variants straight from the resident sequence and never materialised."""
+    (x16); the windows are then built as variants straight from the resident sequence and never materialised.
+
+    ``cuts``: None (every window is built by `window_indices`, as the reference builds them), a sequence of frame numbers at which a
+    new shot starts (validated by `shots.shot_ranges`), or "auto": `shots.detect_cuts` with ``cut_threshold`` on the resident integer
+    frames ("auto" with float lr raises ValueError before any model pass: pass explicit cuts).  With cuts, every window stays inside
+    the shot of its centre frame (`shots.shot_window_indices`), with and without ``ensemble``."""
     check_mode(ensemble)
+    check_auto(cuts, lr.dtype)
     N, C, H, W = lr.shape
     dev = next(model.parameters()).device
     centres = list(range(N)) if centres is None else list(centres)
     out: List[np.ndarray] = []
     if ensemble is not None:
         ens, x = for_mode(model, ensemble), _lr_frames_dense(lr, dev)
+        cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
         for s in range(0, len(centres), batch):
-            idx = [window_indices(i, num_frames, N, padding) for i in centres[s:s + batch]]
+            idx = windows_for(centres[s:s + batch], num_frames, N, padding, cuts)
             if x.dtype in _INT_FRAMES:                                # quantised by the merge kernel
                 out.append(frames_to_numpy(ens.sequence(x, idx, dtype=x.dtype, quantise=quantise)))
             else:
                 out.append(_quantised(ens.sequence(x, idx), quantise))
         return np.concatenate(out, 0)
     x = _lr_frames(lr, dev)
+    cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
     for s in range(0, len(centres), batch):
-        idx = [window_indices(i, num_frames, N, padding) for i in centres[s:s + batch]]
+        idx = windows_for(centres[s:s + batch], num_frames, N, padding, cuts)
         win = _windows(x, idx)                                    # (b, 7, C, Hp, Wp)
         if win.dtype in _INT_FRAMES:                              # quantised by the model's last kernel
             out.append(frames_to_numpy(super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]))
@@ -135,12 +149,15 @@ class SequenceScores:
     brisque_mean = None
     baseline_brisque = None
     baseline_brisque_mean = None
+    # the scene cuts that were used (cuts=): a list of frame numbers, None without the keyword; a plain attribute as well
+    cuts = None
 
 
 @torch.no_grad()
 def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
-                      ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None, brisque=None) -> SequenceScores:
+                      ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None, brisque=None,
+                      cuts=None, cut_threshold: float = 10.0) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -166,12 +183,16 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     (the border rule sees the true edge), go through `resize.bicubic_upscale(., 4)` (MATLAB `imresize`) and are scored by the same
     `frame_metrics` call as the SR frames, with the same `crop_border` and `convert_to`, and the same NIQE with ``niqe``.  Integer lr
     is up-scaled with out="int" (clipped, rounded half to even) and scored as it is; float lr gives f32 frames that are quantised as
-    the SR frames are.  No model pass and no host round trip is added, and the baseline does not depend on ``ensemble``."""
+    the SR frames are.  No model pass and no host round trip is added, and the baseline does not depend on ``ensemble``.
+
+    ``cuts`` / ``cut_threshold`` as in `super_resolve_sequence`; the list that was used comes back as `SequenceScores.cuts` (None
+    without the keyword)."""
     from .device_metrics import frame_metrics
     from . import brisque as brisque_mod
     from . import niqe as niqe_mod
     from .resize import bicubic_upscale
     check_mode(ensemble)
+    check_auto(cuts, lr.dtype)
     if baseline not in (None, "bicubic"):
         raise ValueError(f'baseline must be "bicubic" or None, got {baseline!r}')
     N, C, H, W = lr.shape
@@ -197,11 +218,12 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     dev = next(model.parameters()).device
     ens = for_mode(model, ensemble)
     x = _lr_frames(lr, dev) if ens is None else _lr_frames_dense(lr, dev)
+    cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
     p_dev, s_dev, n_dev, frames = [], [], [], []                  # per-batch device results, fetched once at the end
     bp_dev, bs_dev, bn_dev = [], [], []                           # the same for the bicubic baseline
     q_dev, bq_dev = [], []                                        # BRISQUE features of the SR frames and of the baseline
     for s in range(0, N, batch):
-        idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
+        idx = windows_for(range(s, min(N, s + batch)), num_frames, N, padding, cuts)
         win = _windows(x, idx) if ens is None else None           # (b, 7, C, Hp, Wp)
         hr_b = bits16(hr[s:s + len(idx)]).to(dev).view(hr.dtype)
         if baseline is not None:
@@ -243,6 +265,8 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     scores = SequenceScores(psnr_np, ssim_np, float(np.mean(psnr_np)), float(np.mean(ssim_np)),
                             np.concatenate(frames, 0) if return_frames else None, niqe_np,
                             float(np.mean(niqe_np)) if niqe is not None else None)
+    if cuts is not None:
+        scores.cuts = cuts
     if brisque is not None:
         scores.brisque = brisque_mod.scores_from_features(torch.cat(q_dev).cpu().numpy(), brisque)
         scores.brisque_mean = float(np.mean(scores.brisque))
@@ -288,11 +312,19 @@ class StreamedSuperResolver:
     * uint8 sequences keep the staging buffers and the ring in uint8 (a quarter of the upload bytes) and take the model's
       uint8 path: the quantised frames come from the last kernel, with no torch passes before the copy to the host;
     * uint16 sequences (10-bit samples) do the same in 16 bits (half the upload bytes) through `super_resolve_u16`, and the
-      results are uint16 arrays.
+      results are uint16 arrays;
+    * ``cuts``: None, or one explicit list of scene cuts per sequence (None for a sequence without cuts; `shots.shot_ranges` validates
+      them in `run`): the windows then stay inside the shot of their centre frame (`shots.shot_window_indices`).  "auto" is refused
+      with ValueError: the frames live on the host, run `shots.detect_cuts` on them first.
     `stats` (after run): frames uploaded, H2D / D2H bytes.
     """
 
-    def __init__(self, model, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8, quantise: str = "truncate"):
+    def __init__(self, model, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8, quantise: str = "truncate",
+                 cuts=None):
+        if isinstance(cuts, str) or (cuts is not None and any(isinstance(c, str) for c in cuts)):
+            raise ValueError('StreamedSuperResolver takes explicit cuts only (one list per sequence): its frames live on the host, '
+                             'run harness.shots.detect_cuts on them first')
+        self.cuts = None if cuts is None else [None if c is None else list(c) for c in cuts]
         self.model, self.num_frames, self.padding, self.batch, self.quantise = model, num_frames, padding, batch, quantise
         self.device = next(model.parameters()).device
         self.stats = {}
@@ -309,6 +341,12 @@ class StreamedSuperResolver:
         uint16 sequences)."""
         from .sharding import shard_sequences
         seq_lens = [int(s.shape[0]) for s in sequences]
+        if self.cuts is not None:
+            if len(self.cuts) != len(seq_lens):
+                raise ValueError(f"cuts must hold one list per sequence: {len(self.cuts)} lists for {len(seq_lens)} sequences")
+            for n, c in zip(seq_lens, self.cuts):
+                if c is not None:
+                    shot_ranges(n, c)
         work = self.plan(seq_lens, rank, world)
         if not work:
             return {}
@@ -334,7 +372,8 @@ class StreamedSuperResolver:
             rows = []
             for k in range(B):
                 s, c = items[min(k, len(items) - 1)]
-                rows.append([(s, j) for j in window_indices(c, T, seq_lens[s], self.padding)])
+                sc = None if self.cuts is None else self.cuts[s]
+                rows.append([(s, j) for j in windows_for([c], T, seq_lens[s], self.padding, sc)[0]])
             win_idx.append(rows)
         need = [sorted({f for row in rows for f in row}) for rows in win_idx]
         max_new = max(len(n) for n in need)

@@ -23,7 +23,7 @@ from .ensemble import for_mode
 from .infer import pad_to_multiple, super_resolve_int
 from . import brisque as brisque_mod
 from .niqe import crop_geometry, frame_niqe_features, scores_from_features
-from .windows import window_indices
+from .shots import check_auto, detect_cuts, resolve_cuts, windows_for
 
 
 class YuvName(NamedTuple):
@@ -175,7 +175,7 @@ def _niqe_stats(feats, niqe) -> dict:
 @torch.no_grad()
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
                          quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
-                         ensemble: Optional[str] = None, niqe=None, brisque=None) -> dict:
+                         ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -188,8 +188,12 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     self-ensemble; chroma is unchanged.  ``niqe`` (a `harness.niqe.NiqeModel`) scores every SR luma frame with NIQE on the device
     before it is downloaded and adds ``"niqe"`` (per frame, f64) and ``"niqe_mean"`` to the stats; the written bytes are the same.
     NIQE is 8-bit only: ``bit_depth=10`` with ``niqe`` raises ValueError.  ``brisque`` (a `harness.brisque.BrisqueModel`) does the
-    same with BRISQUE (``"brisque"``, ``"brisque_mean"``), 8-bit only as well; the two may be given together."""
+    same with BRISQUE (``"brisque"``, ``"brisque_mean"``), 8-bit only as well; the two may be given together.  ``cuts``: None, a
+    sequence of frame numbers at which a new shot starts, or "auto" (`shots.detect_cuts` with ``cut_threshold`` on the file's luma
+    plane, on the device): every window then stays inside the shot of its centre frame (`shots.shot_window_indices`), and the list
+    that was used is added to the stats as ``"cuts"``.  Chroma does not depend on it."""
     ens = for_mode(model, ensemble)
+    check_auto(cuts, "uint8")
     _check_niqe(niqe, bit_depth, width, height)
     brisque = _check_brisque(brisque, bit_depth, width, height)
     if getattr(model, "_img_ch", None) != 1:
@@ -208,12 +212,13 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
     x = to_dev(y)[:, None]                                                                # (N,1,H,W)
+    cuts = resolve_cuts(cuts, N, lambda: detect_cuts(x.view(sdt), threshold=cut_threshold))
     x = pad_to_multiple(x, 4) if ens is None else x.contiguous().view(sdt)                # zero padded to (N,1,Hp,Wp); unpadded
     written, niqe_feats, brisque_feats = 0, [], []
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             e = min(N, s + batch)
-            idx = [window_indices(i, num_frames, N, padding) for i in range(s, e)]
+            idx = windows_for(range(s, e), num_frames, N, padding, cuts)
             if ens is None:
                 win = torch.stack([x[j] for j in idx], 0).view(sdt)                       # (b, 7, 1, Hp, Wp)
                 ysr = super_resolve_int(model, win, quantise)[:, 0, :4 * H, :4 * W]
@@ -232,13 +237,14 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     dt = time.perf_counter() - t0
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
-            "bytes_written": written, "out_size": (4 * W, 4 * H), **niqe_stats}
+            "bytes_written": written, "out_size": (4 * W, 4 * H), **niqe_stats, **({} if cuts is None else {"cuts": cuts})}
 
 
 @torch.no_grad()
 def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int, *, colour: ColourSpec = ColourSpec(),
                              batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
-                             ensemble: Optional[str] = None, niqe=None, brisque=None) -> dict:
+                             ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None,
+                             cut_threshold: float = 10.0) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -252,8 +258,10 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     frames through the self-ensemble (`harness.ensemble`) between the two colour conversions.  ``niqe`` as in
     `super_resolve_yuv420`: the Y of YCbCr of the SR RGB frames (convert_to="Y") is scored before the encode; 8-bit only.
     ``brisque`` as in `super_resolve_yuv420`: the YIQ luma of the SR RGB frames (BRISQUE's own "Y", not NIQE's) is scored before
-    the encode; 8-bit only."""
+    the encode; 8-bit only.  ``cuts`` / ``cut_threshold`` as in `super_resolve_yuv420`: "auto" detects on the luma plane of the file,
+    before the colour conversion."""
     ens = for_mode(model, ensemble)
+    check_auto(cuts, "uint8")
     _check_niqe(niqe, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
     brisque = _check_brisque(brisque, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
     if getattr(model, "_img_ch", None) != 3:
@@ -271,12 +279,14 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
     frames = hip.bits16(torch.from_numpy(np.array(mm, dtype=host_dt))).to(dev).view(sdt)      # one host copy of the mapped file
+    cuts = resolve_cuts(cuts, N, lambda: detect_cuts(hip.bits16(frames)[:, :H * W].reshape(N, 1, H, W).view(sdt),
+                                                     threshold=cut_threshold))    # the file's luma plane, made dense
     x = yuv420_to_rgb(*i420_planes(frames, H, W), colour)                                     # (N,3,H,W)
     x = pad_to_multiple(hip.bits16(x), 4) if ens is None else x.contiguous()                  # zero padded to (N,3,Hp,Wp); unpadded
     written, niqe_feats, brisque_feats = 0, [], []
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
-            idx = [window_indices(i, num_frames, N, padding) for i in range(s, min(N, s + batch))]
+            idx = windows_for(range(s, min(N, s + batch)), num_frames, N, padding, cuts)
             if ens is None:
                 win = torch.stack([x[j] for j in idx], 0).view(sdt)                       # (b, 7, 3, Hp, Wp)
                 sr = super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]
@@ -293,7 +303,7 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     dt = time.perf_counter() - t0
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
-            "bytes_written": written, "out_size": (4 * W, 4 * H), **niqe_stats}
+            "bytes_written": written, "out_size": (4 * W, 4 * H), **niqe_stats, **({} if cuts is None else {"cuts": cuts})}
 
 
 @torch.no_grad()

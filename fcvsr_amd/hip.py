@@ -229,6 +229,7 @@ SIGNATURES = {
                                _VP],
     "fcvsr_bicubic_downscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _VP],
     "fcvsr_bicubic_upscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _I, _VP],
+    "fcvsr_frame_pair_sad": [_VP, _I, _I, C.c_longlong, _VP, C.c_longlong, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
@@ -560,6 +561,36 @@ def bicubic_upscale(x: torch.Tensor, factor: int, out: str = "f32") -> torch.Ten
             check(lib().fcvsr_bicubic_upscale(src.data_ptr(), _DT[x.dtype], res.numel() // (factor * factor * H * W), H, W, factor,
                                               res.data_ptr(), _DT[odt], stream_ptr()), "fcvsr_bicubic_upscale")
     return res
+
+
+PAIR_SAD_TILE_BYTES = 1024          # FCVSR_PAIR_SAD_TILE_BYTES of include/fcvsr_hip.h: sizes the scratch of fcvsr_frame_pair_sad
+
+
+def frame_pair_sad(frames: torch.Tensor) -> torch.Tensor:
+    """fcvsr_frame_pair_sad: frames (N,C,H,W) uint8, or uint16 (10-bit samples; int16 views of the same bits, `bits16`, are taken
+    as uint16) on the HIP device -> (N-1,) int64 on the device, element i the sum over all channels and pixels of
+    |frames[i+1] - frames[i]| in exact integers, uint16 samples read as min(k, 1023) (`harness.shots.pair_sad_host` is the
+    contract).  Two launches, no host sync.  Any C, H, W >= 1; N = 1 gives an empty result; non-contiguous frames are made dense
+    first."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, torch.uint16, torch.int16) or frames.dim() != 4:
+        raise ValueError(f"expected uint8 or uint16 (N,C,H,W) frames, got {getattr(frames, 'dtype', type(frames))} "
+                         f"{tuple(getattr(frames, 'shape', ()))}")
+    if not frames.is_cuda:
+        raise RuntimeError("frame_pair_sad runs on the HIP device only (the host path is harness.shots.pair_sad_host)")
+    N, samples = frames.shape[0], frames.shape[1] * frames.shape[2] * frames.shape[3]
+    if N < 1 or samples < 1:
+        raise ValueError(f"frames must hold at least one frame of at least one sample, got {tuple(frames.shape)}")
+    out = torch.empty((N - 1,), dtype=torch.int64, device=frames.device)
+    if N == 1:
+        return out
+    src = bits16(frames).contiguous()
+    elem = src.element_size()
+    tiles = (samples * elem + PAIR_SAD_TILE_BYTES - 1) // PAIR_SAD_TILE_BYTES
+    scratch = torch.empty(((N - 1) * tiles,), dtype=torch.int64, device=frames.device)
+    with torch.cuda.device(frames.device):
+        check(lib().fcvsr_frame_pair_sad(src.data_ptr(), elem, N, samples, scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(),
+                                         stream_ptr()), "fcvsr_frame_pair_sad")
+    return out
 
 
 QUANTISE = {"truncate": QUANT_TRUNCATE, "round": QUANT_ROUND}

@@ -768,6 +768,16 @@ int fcvsr_bicubic_downscale(const void* src, int src_dtype, long long planes, in
  * planes < 1. */
 int fcvsr_bicubic_upscale(const void* src, int src_dtype, long long planes, int H, int W, int factor, void* out, int out_dtype,
                           void* stream);
+/* ---- scene-cut statistic (no counterpart in the reference, whose clips are single shots; the contract is
+ * fcvsr_amd/harness/shots.py, pair_sad_host) ----------------------------------------------------------------------------------------
+ * frames: N dense frames of `samples` samples each (samples = C H W, any value >= 1), elem_size 1 (uint8) or 2 (uint16, a sample
+ * above 1023 reads as 1023); aligned to elem_size.  out: DEVICE (N - 1) int64, out[i] = sum over all samples of
+ * |frame[i + 1] - frame[i]|, in exact integers: two launches, u64 partial sums per workgroup added in a fixed order, no atomics.
+ * N = 1 writes nothing.  scratch: DEVICE, 8-byte aligned, at least (N - 1) * ceil(samples * elem_size / FCVSR_PAIR_SAD_TILE_BYTES) * 8
+ * bytes.  No host sync.  FCVSR_E_ARG: a null pointer, another elem_size, N or samples < 1, a scratch that is too small. */
+#define FCVSR_PAIR_SAD_TILE_BYTES 1024
+int fcvsr_frame_pair_sad(const void* frames, int elem_size, int N, long long samples, void* scratch, long long scratch_bytes,
+                         long long* out, void* stream);
 #ifdef __cplusplus
 }
 #endif
