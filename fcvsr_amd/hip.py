@@ -124,6 +124,10 @@ SIGNATURES = {
     "fcvsr_irfft2": [_VP, _I64, _I, _I, _I, _I, _I, _I, _VP, _VP, _PV, _VP],
     "fcvsr_irfft2_bands": [_VP, _I64, _I, _I, _I, _I, _I, _I, _VP, _I, _VP, _PV, _VP],
     "fcvsr_last_fft_path": [],
+    "fcvsr_ffl_workspace_elems": [_I, _I, _I],
+    "fcvsr_ffl_diff": [_VP, _VP, _I, _I, _I, _I, _I, _VP, _I, _VP],
+    "fcvsr_ffl_weight": [_VP, _I64, _I, _I, _I, _I, _I, _F, _F, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_ffl_grad": [_VP, _I, _VP, _F, _I, _I, _I, _I, _I, _VP, _VP, _VP],
     "fcvsr_corr_lookup": [_VP, _VP, _I64, _I, _I, _I, _I, _I, _I, _PV, _VP],
     "fcvsr_channel_sum": [_PV, _I, _I, _I, _VP, _VP, _I64, _VP],
     "fcvsr_ca_gate": [_VP, _F, _VP, _VP, _I, _I, _I, _VP, _VP],
@@ -236,7 +240,7 @@ _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
              "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong,
              "fcvsr_frame_metrics_scratch_bytes": C.c_longlong, "fcvsr_niqe_scratch_bytes": C.c_longlong,
-             "fcvsr_brisque_scratch_bytes": C.c_longlong}
+             "fcvsr_brisque_scratch_bytes": C.c_longlong, "fcvsr_ffl_workspace_elems": C.c_longlong}
 
 
 def lib() -> C.CDLL:

@@ -278,7 +278,8 @@ def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torc
         lr: float = 1e-4, weight_decay: float = 1e-5, milestones: Sequence[int] = (2000, 8000, 12000, 20000), gamma: float = 0.5,
         val_itv: int = 1, ckpt_dir: Optional[str] = None, warm_start_epoch: int = 0, log: Callable[[str], None] = print,
         val_sequences: Optional[Sequence[Tuple[torch.Tensor, torch.Tensor]]] = None,
-        on_validate: Optional[Callable[[int, float, float], None]] = None, deterministic: Optional[bool] = None) -> List[float]:
+        on_validate: Optional[Callable[[int, float, float], None]] = None, deterministic: Optional[bool] = None,
+        loss_fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor] = charbonnier_loss, reduce_op: str = "sum") -> List[float]:
     """Epoch loop of the reference (train_LD_freqCVSR_S_22.py:239-266): MultiStepLR stepped at the START of every epoch,
     Charbonnier-sum loss, Adam, `epoch-%d.pth` state_dict checkpoints every `val_itv` epochs (rank 0).
     `batches(epoch)` yields {'lr_imgs': (b,C,7,h,w), 'hr_imgs': (b,C,f',4h,4w)} like the reference DataLoader.
@@ -290,8 +291,10 @@ def fit(model: torch.nn.Module, batches: Callable[[int], Iterable[Dict[str, torc
     `PSNR:%f, SSIM: %f` and passed to `on_validate(epoch, psnr, ssim)` (epoch counted from 1).  It runs under no_grad:
     parameters, gradients and optimizer state are not touched.
 
-    deterministic: passed to `TrainStep` (True: bit-repeatable steps; None leaves `model.train_deterministic` as it is)."""
-    step = TrainStep(model, lr=lr, weight_decay=weight_decay, deterministic=deterministic)
+    deterministic: passed to `TrainStep` (True: bit-repeatable steps; None leaves `model.train_deterministic` as it is).
+    loss_fn, reduce_op: passed to `TrainStep`; the defaults are the reference loop's Charbonnier sum with summed gradients (a mean-type
+    loss such as `charbonnier_ffl_loss` goes with reduce_op="mean")."""
+    step = TrainStep(model, lr=lr, weight_decay=weight_decay, deterministic=deterministic, loss_fn=loss_fn, reduce_op=reduce_op)
     sched = torch.optim.lr_scheduler.MultiStepLR(step.optimizer, milestones=list(milestones), gamma=gamma)
     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
     model.train()

@@ -267,6 +267,30 @@ int fcvsr_irfft2_bands(const float* spec, int64_t pix_stride, int im_off, int re
  * fallback the string is that of the last fcvsr_irfft2 call.  "" before the first call.  Test and measurement aid like
  * fcvsr_last_conv_kernel(), not part of the data path. */
 const char* fcvsr_last_fft_path(void);
+/* ---- focal frequency loss (training): FFL of the reference's Charbonnier_FFL_Loss (CVSR_train/opt/deep_learning.py:192-220) -------
+ * For pred, target (B,C,H,W) contiguous f32 and patch_factor f (f | H, f | W): h = H/f, w = W/f, P = B*f*f*C planes, plane
+ * p = (b*f*f + i*f + j)*C + c being patch (i,j) of channel c of image b.  With U = rfft2 of pred - target per plane (unnormalised),
+ * N = h*w, s = |U|^2 and cw = 1 on the columns kx = 0 and kx = w/2 (even w), 2 elsewhere:
+ *   wgt = (s / max over the plane of s)^(alpha/2), 0 where the max is 0;   loss = loss_weight / (P*N*N) * sum cw * wgt * s
+ * which equals loss_weight * mean(wgt * |fft2(pred, ortho) - fft2(target, ortho)|^2) over the full spectra, and
+ *   d loss / d pred = 2*loss_weight / (P*N) * irfft2 of wgt * U  (wgt taken as a constant),   d loss / d target = -d loss / d pred.
+ * Call order: fcvsr_ffl_diff, fcvsr_rfft2 on d as one image (1,h,w,d_channels), fcvsr_ffl_weight; for the gradients fcvsr_irfft2 on the
+ * spectrum fcvsr_ffl_weight left, then fcvsr_ffl_grad.  Sums run in a fixed order (no float atomics): results are bit-repeatable.
+ * Nothing synchronises or allocates; the loss and the upstream gradient are device scalars.
+ *
+ * fcvsr_ffl_diff:   d (h,w,d_channels) NHWC f32, d_channels >= P: channel p = the difference of plane p, channels beyond P zero.
+ * fcvsr_ffl_weight: spec as fcvsr_rfft2 wrote it for B = 1 (plane p: imaginary part at im_off+p, real at re_off+p, the two ranges
+ *                   disjoint); on return it holds wgt * U and *loss the loss.  workspace: at least the number of floats the
+ *                   _workspace_elems query returns for the same h, w, P.  alpha > 0.
+ * fcvsr_ffl_grad:   r (h,w,r_channels) NHWC f32 = fcvsr_irfft2 of that spectrum; g_up: the upstream gradient (one f32 on the device);
+ *                   grad_pred / grad_target: (B,C,H,W) contiguous f32, either may be NULL; grad_target is the exact negation. */
+long long fcvsr_ffl_workspace_elems(int h, int w, int P);
+int fcvsr_ffl_diff(const float* pred, const float* target, int B, int C, int H, int W, int patch_factor, float* d, int d_channels,
+                   void* stream);
+int fcvsr_ffl_weight(float* spec, int64_t pix_stride, int im_off, int re_off, int h, int w, int P, float alpha, float loss_weight,
+                     float* workspace, long long workspace_elems, float* loss, void* stream);
+int fcvsr_ffl_grad(const float* r, int r_channels, const float* g_up, float loss_weight, int B, int C, int H, int W, int patch_factor,
+                   float* grad_pred, float* grad_target, void* stream);
 
 /* feat_extract (:2589, Conv2d(Cin, n_blk*64, 3, 1, 1), Cin = 7: 9*Cin <= 64) as one K = 64 GEMM step per output tile.
  * x: (B,H,W,Cin) f32 view of the planar frames; w: [n_blk*64][64] f16, column k = tap*Cin + c (zero beyond 9*Cin);
