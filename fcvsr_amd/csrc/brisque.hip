@@ -5,9 +5,9 @@
 //
 // fcvsr_brisque_features, eight launches on one stream, no host sync:
 //   1. plane      the whole frame as f64 integers: uint8 samples, or f32 samples quantised as the frame metrics do, or the integer
-//                 YIQ luma of RGB;
-//   2. mscn       mu and E[x^2] from the 7 x 7 window over a ZERO-padded plane (49 taps from a haloed LDS tile, accumulated from 0
-//                 in row-major tap order as the contract does), sigma = sqrt(|E[x^2] - mu^2| + 2^-23), mscn = (img - mu) / (sigma + 1);
+//                 YIQ luma of RGB (score_common.h plane_kernel, crop 0);
+//   2. mscn       mu and E[x^2] from the 7 x 7 window over a ZERO-padded plane, sigma = sqrt(|E[x^2] - mu^2| + 2^-23),
+//                 mscn = (img - mu) / (sigma + 1) (score_common.h mscn_kernel);
 //   3. stats      one pass over the MSCN plane: a workgroup owns a fixed 32 x 64 tile, reads it with the rows above and below and
 //                 the column to the left, their coordinates wrapped modulo H and W (the four products are circular over the whole
 //                 plane), and forms 22 sums (x^2, |x|; per product the counts and squared sums of the negatives and of the
@@ -15,93 +15,16 @@
 //                 into one row of partials per tile: no atomics, the same input gives the same bits;
 //   4. finish     one workgroup per frame: the tile partials (staged through LDS 128 tiles at a time) added in tile order, the
 //                 five 9801-entry first-minimum searches (index 0 for a NaN target) and the 18 features of the scale;
-//   5. downscale  the 2x down-scale of plane / 255, times 255 (niqe.hip's kernel), then 2, 3 and 4 on the half-size plane.
+//   5. downscale  the 2x down-scale of plane / 255, times 255 (resize.hip), then 2, 3 and 4 on the half-size plane.
 // The planes travel through HBM as f64.  LDS tiles are rows of f64 read by 32 consecutive lanes at consecutive addresses: a
 // ds_read_b64 of half a wave then covers the 64 dword banks once, whatever the row pitch.
-#include "common.h"
+#include "score_common.h"
 
-namespace fcvsr {
-void niqe_downscale2_f64(const double* src, long long planes, int H, int W, double* dst, hipStream_t stream);   // niqe.hip
-}
+using namespace fcvsr;
 
 namespace {
 
-constexpr int kGrid = 9801, kMY = 16, kMX = 64, kHalo = 3, kSY = 32, kSX = 64, kDbl = 14, kCnt = 8, kChunk = 128;
-
-struct BrisqueSrc {
-  const void* p;
-  long long sn, sc, sy, sx;
-  int quantise, to_y;
-};
-
-struct Window49 {
-  double f[49];
-};
-
-// one sample as the uint8 frame the harness would write (quality.hip sr_value, niqe.hip niqe_sample)
-__device__ inline int brisque_sample(const BrisqueSrc& a, long long off) {
-  if (a.quantise == FCVSR_QUANT_NONE) return (int)((const unsigned char*)a.p)[off];
-  const float q = fminf(fmaxf(((const float*)a.p)[off], 0.f), 1.f) * 255.0f;
-  return (int)(a.quantise == FCVSR_QUANT_TRUNCATE ? truncf(q) : rintf(q));
-}
-
-__global__ __launch_bounds__(256) void brisque_plane_kernel(BrisqueSrc a, int H, int W, double* __restrict__ plane) {
-  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
-  if (x >= W) return;
-  const long long off = n * a.sn + (long long)y * a.sy + (long long)x * a.sx;
-  int v;
-  if (a.to_y) {
-    // the luma of YIQ, round_half_even((299 R + 587 G + 114 B) / 1000), in integers
-    const int s = 299 * brisque_sample(a, off) + 587 * brisque_sample(a, off + a.sc) + 114 * brisque_sample(a, off + 2 * a.sc);
-    const int q = s / 1000, r = s % 1000;
-    v = q + ((r > 500 || (r == 500 && (q & 1))) ? 1 : 0);
-  } else {
-    v = brisque_sample(a, off);
-  }
-  plane[((long long)n * H + y) * W + x] = (double)v;
-}
-
-__global__ __launch_bounds__(256) void brisque_mscn_kernel(const double* __restrict__ img, int H, int W, Window49 w,
-                                                           double* __restrict__ out) {
-  __shared__ double s[kMY + 2 * kHalo][kMX + 2 * kHalo];
-  const int y0 = blockIdx.y * kMY, x0 = blockIdx.x * kMX;
-  const double* p = img + (long long)blockIdx.z * H * W;
-  double* o = out + (long long)blockIdx.z * H * W;
-  for (int i = threadIdx.x; i < (kMY + 2 * kHalo) * (kMX + 2 * kHalo); i += 256) {
-    const int r = i / (kMX + 2 * kHalo), q = i % (kMX + 2 * kHalo);
-    const int yy = y0 + r - kHalo, xx = x0 + q - kHalo;
-    s[r][q] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? p[(long long)yy * W + xx] : 0.0;     // zero border
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kMY * kMX; i += 256) {
-    const int r = i / kMX, q = i % kMX;
-    if (y0 + r >= H || x0 + q >= W) continue;
-    double mu = 0.0, e2 = 0.0;
-#pragma unroll
-    for (int ky = 0; ky < 7; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 7; ++kx) {
-        const double v = s[r + ky][q + kx];
-        mu += w.f[ky * 7 + kx] * v;
-        e2 += w.f[ky * 7 + kx] * (v * v);
-      }
-    const double sigma = sqrt(fabs(e2 - mu * mu) + 0x1p-23);
-    o[(long long)(y0 + r) * W + x0 + q] = (s[r + kHalo][q + kHalo] - mu) / (sigma + 1.0);
-  }
-}
-
-__device__ inline double wave_sum(double v) {
-  // xor butterfly: every lane ends with the same sum, formed in a fixed shape
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ inline int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+constexpr int kSY = 32, kSX = 64, kDbl = 14, kCnt = 8, kChunk = 128;
 
 // Partials of one tile.  dsum: x^2, |x|, then per product (p^2 where p < 0, p^2 where p > 0, |p|); cnt: per product (p < 0, p > 0).
 __global__ __launch_bounds__(256) void brisque_stats_kernel(const double* __restrict__ mscn, int H, int W, int tiles,
@@ -170,10 +93,7 @@ __global__ __launch_bounds__(256) void brisque_finish_kernel(const double* __res
   __shared__ long long sc[kCnt];
   __shared__ double stage_d[kChunk * kDbl];
   __shared__ long long stage_c[kChunk * kCnt];
-  __shared__ double best_v[4][5];
-  __shared__ int best_i[4][5];
   const int n = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // the partials of kChunk tiles at a time come into LDS with coalesced loads; one thread per sum then adds them in tile order
   const double* pd = dsum + (long long)n * tiles * kDbl;
   const long long* pc = cnt + (long long)n * tiles * kCnt;
@@ -227,24 +147,10 @@ __global__ __launch_bounds__(256) void brisque_finish_kernel(const double* __res
       if (df < bv[d]) { bv[d] = df; bi[d] = i; }
     }
   }
-#pragma unroll
-  for (int d = 0; d < 5; ++d) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ov = __shfl_xor(bv[d], o);
-      const int oi = __shfl_xor(bi[d], o);
-      if (ov < bv[d] || (ov == bv[d] && oi < bi[d])) { bv[d] = ov; bi[d] = oi; }
-    }
-    if (lane == 0) { best_v[wave][d] = bv[d]; best_i[wave][d] = bi[d]; }
-  }
-  __syncthreads();
+  const int idx = first_min_pick(bv, bi);
 
   if (threadIdx.x < 5) {
     const int d = threadIdx.x;
-    double v = best_v[0][d];
-    int idx = best_i[0][d];
-    for (int wv = 1; wv < 4; ++wv)
-      if (best_v[wv][d] < v || (best_v[wv][d] == v && best_i[wv][d] < idx)) { v = best_v[wv][d]; idx = best_i[wv][d]; }
     const double alpha = tab[3 * kGrid + idx];
     double* o = out + (long long)n * 36;
     if (d == 0) {
@@ -260,7 +166,7 @@ __global__ __launch_bounds__(256) void brisque_finish_kernel(const double* __res
   }
 }
 
-long long tiles_of(int H, int W) { return (long long)fcvsr::cdiv(H, kSY) * fcvsr::cdiv(W, kSX); }
+long long tiles_of(int H, int W) { return (long long)cdiv(H, kSY) * cdiv(W, kSX); }
 
 }  // namespace
 
@@ -292,21 +198,20 @@ extern "C" int fcvsr_brisque_features(const void* frames, const int64_t* host_st
   double* plane2 = mscn + px;
   double* dsum = plane2 + px2;
   long long* cnt = (long long*)(dsum + (long long)N * tiles_of(H, W) * kDbl);
-  BrisqueSrc s;
+  FrameSrc s;
   s.p = frames;
   s.sn = host_strides[0]; s.sc = host_strides[1]; s.sy = host_strides[2]; s.sx = host_strides[3];
-  s.quantise = quantise; s.to_y = to_y;
+  s.quantise = quantise; s.to_y = to_y; s.crop = 0;
   Window49 w;
   for (int k = 0; k < 49; ++k) w.f[k] = host_window[k];
-  hipLaunchKernelGGL(brisque_plane_kernel, dim3((unsigned)fcvsr::cdiv(W, 256), (unsigned)H, (unsigned)N), dim3(256), 0, st, s, H, W, plane1);
+  hipLaunchKernelGGL(plane_kernel<LumaYIQ>, dim3((unsigned)cdiv(W, 256), (unsigned)H, (unsigned)N), dim3(256), 0, st, s, H, W, plane1);
   for (int scale = 0; scale < 2; ++scale) {
     const int h = H >> scale, wd = W >> scale;
     const double* plane = scale ? plane2 : plane1;
     const int tiles = (int)tiles_of(h, wd);
-    if (scale) fcvsr::niqe_downscale2_f64(plane1, N, H, W, plane2, st);
-    hipLaunchKernelGGL(brisque_mscn_kernel, dim3((unsigned)fcvsr::cdiv(wd, kMX), (unsigned)fcvsr::cdiv(h, kMY), (unsigned)N), dim3(256), 0, st,
-                       plane, h, wd, w, mscn);
-    hipLaunchKernelGGL(brisque_stats_kernel, dim3((unsigned)fcvsr::cdiv(wd, kSX), (unsigned)fcvsr::cdiv(h, kSY), (unsigned)N), dim3(256), 0, st,
+    if (scale) downscale2_f64(plane1, N, H, W, plane2, st);
+    launch_mscn<true, true>(plane, N, h, wd, w, mscn, st);
+    hipLaunchKernelGGL(brisque_stats_kernel, dim3((unsigned)cdiv(wd, kSX), (unsigned)cdiv(h, kSY), (unsigned)N), dim3(256), 0, st,
                        (const double*)mscn, h, wd, tiles, dsum, cnt);
     hipLaunchKernelGGL(brisque_finish_kernel, dim3((unsigned)N), dim3(256), 0, st, (const double*)dsum, (const long long*)cnt, tiles, h, wd,
                        tables, out + 18 * scale);

@@ -12,18 +12,19 @@
 // frame's partials in a fixed order (no atomics: bit-reproducible).
 // U16 (fcvsr_frame_metrics_u16): the frames hold 10-bit samples in uint16; f32 SR values are quantised with the 1023 scale and the
 // SSIM constants come from the caller's peak (1023, or HM's 1020); there is no Y conversion.
-#include "common.h"
+#include "score_common.h"
+
+using namespace fcvsr;
 
 namespace {
 
 constexpr int kTY = 16, kTX = 64, kWin = 11, kLY = kTY + kWin - 1, kLX = kTX + kWin - 1;
 
 struct QualityArgs {
-  const void* sr;
-  long long s_sn, s_sc, s_sy, s_sx;
+  FrameSrc sr;
   const unsigned char* hr;
   long long h_sn, h_sc, h_sy, h_sx;
-  int planes_per_frame, crop, Hc, Wc, Hm, Wm, tiles_x, tiles, quantise, to_y;
+  int planes_per_frame, Hc, Wc, Hm, Wm, tiles_x, tiles;
   double peak;                           // U16: the peak of the SSIM constants
   double g[kWin];
   double* part;                          // [plane][tile][2] = {squared-error sum, SSIM-map sum}
@@ -34,14 +35,7 @@ struct QualityArgs {
 // (U16: uint16 samples, scale 1023.0f)
 template <bool U16>
 __device__ inline double sr_value(const QualityArgs& a, long long off) {
-  if (a.quantise == FCVSR_QUANT_NONE) return U16 ? (double)((const unsigned short*)a.sr)[off] : (double)((const unsigned char*)a.sr)[off];
-  const float q = fminf(fmaxf(((const float*)a.sr)[off], 0.f), 1.f) * (U16 ? 1023.0f : 255.0f);
-  return (double)(a.quantise == FCVSR_QUANT_TRUNCATE ? truncf(q) : rintf(q));
-}
-
-// Y of YCbCr (metrics.py to_y_channel of the BGR-flipped frame): (24.966 B + 128.553 G + 65.481 R) / 255 + 16, in f64
-__device__ inline double y_of(double r, double g, double b) {
-  return (b / 255.0) * 24.966 + (g / 255.0) * 128.553 + (r / 255.0) * 65.481 + 16.0;
+  return frame_sample<U16 ? kPeak10 : kPeak8>(a.sr, off);
 }
 
 __device__ inline double block_sum(double v, double* sm) {
@@ -71,16 +65,16 @@ __global__ __launch_bounds__(256) void quality_tile_kernel(QualityArgs a) {
     const int r = i / kLX, q = i % kLX;
     double xv = 0.0, yv = 0.0;
     if (r < ly && q < lx) {
-      const long long iy = a.crop + my0 + r, ix = a.crop + mx0 + q;
-      const long long so = n * a.s_sn + iy * a.s_sy + ix * a.s_sx, ho = n * a.h_sn + iy * a.h_sy + ix * a.h_sx;
+      const long long iy = a.sr.crop + my0 + r, ix = a.sr.crop + mx0 + q;
+      const long long so = n * a.sr.sn + iy * a.sr.sy + ix * a.sr.sx, ho = n * a.h_sn + iy * a.h_sy + ix * a.h_sx;
       if constexpr (U16) {
-        xv = sr_value<true>(a, so + c * a.s_sc);
+        xv = sr_value<true>(a, so + c * a.sr.sc);
         yv = (double)((const unsigned short*)a.hr)[ho + c * a.h_sc];
-      } else if (a.to_y) {
-        xv = y_of(sr_value<false>(a, so), sr_value<false>(a, so + a.s_sc), sr_value<false>(a, so + 2 * a.s_sc));
-        yv = y_of((double)a.hr[ho], (double)a.hr[ho + a.h_sc], (double)a.hr[ho + 2 * a.h_sc]);
+      } else if (a.sr.to_y) {
+        xv = ycbcr_y(sr_value<false>(a, so), sr_value<false>(a, so + a.sr.sc), sr_value<false>(a, so + 2 * a.sr.sc));
+        yv = ycbcr_y((double)a.hr[ho], (double)a.hr[ho + a.h_sc], (double)a.hr[ho + 2 * a.h_sc]);
       } else {
-        xv = sr_value<false>(a, so + c * a.s_sc);
+        xv = sr_value<false>(a, so + c * a.sr.sc);
         yv = (double)a.hr[ho + c * a.h_sc];
       }
     }
@@ -205,17 +199,15 @@ static int frame_metrics_launch(const void* sr, const int64_t* host_sr_strides, 
   FCVSR_CHECK_ARG(((uintptr_t)out % 8) == 0 && ((uintptr_t)scratch % 8) == 0, "out / scratch must be 8-byte aligned");
   FCVSR_CHECK_ARG(scratch_bytes >= fcvsr_frame_metrics_scratch_bytes(N, C, H, W, crop_border, to_y), "scratch too small");
   QualityArgs a;
-  a.sr = sr;
-  a.s_sn = host_sr_strides[0]; a.s_sc = host_sr_strides[1]; a.s_sy = host_sr_strides[2]; a.s_sx = host_sr_strides[3];
+  a.sr.p = sr;
+  a.sr.sn = host_sr_strides[0]; a.sr.sc = host_sr_strides[1]; a.sr.sy = host_sr_strides[2]; a.sr.sx = host_sr_strides[3];
+  a.sr.quantise = quantise; a.sr.to_y = to_y; a.sr.crop = crop_border;
   a.hr = (const unsigned char*)hr;
   a.h_sn = host_hr_strides[0]; a.h_sc = host_hr_strides[1]; a.h_sy = host_hr_strides[2]; a.h_sx = host_hr_strides[3];
   a.planes_per_frame = g.P;
-  a.crop = crop_border;
   a.Hc = g.Hc; a.Wc = g.Wc; a.Hm = g.Hm; a.Wm = g.Wm;
   a.tiles_x = g.tiles_x;
   a.tiles = g.tiles_x * g.tiles_y;
-  a.quantise = quantise;
-  a.to_y = to_y;
   a.peak = peak;
   for (int k = 0; k < kWin; ++k) a.g[k] = host_window[k];
   a.part = (double*)scratch;

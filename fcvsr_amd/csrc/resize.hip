@@ -1,12 +1,14 @@
-// MATLAB-style bicubic up-scale (imresize, a = -0.5, symmetric border: the "Bicubic" row of SR tables), the counterpart of the
-// down-scale in niqe.hip: the reference's mmedit/datasets/pipelines/matlab_like_resize.py MATLABLikeResize at scale 2 or 4.  The
-// contract is fcvsr_amd/harness/niqe.py bicubic_upscale.
+// The MATLAB-style bicubic resizers (imresize, a = -0.5, symmetric border) at scale 2 or 4: the reference's
+// mmedit/datasets/pipelines/matlab_like_resize.py MATLABLikeResize.  The contracts are fcvsr_amd/harness/niqe.py bicubic_upscale and
+// bicubic_downscale.  Both have the reference's arithmetic and so its bits: every pass reads f32, every tap's product is an f32 and
+// the products are added in tap order in f32 (no FMA: the library is built with -ffp-contract=off).
 //
+// Up-scale (the "Bicubic" row of SR tables).
 // Output o of an axis has its centre at c = (o + 0.5) / F - 0.5 and reads the inputs floor(c) - 1 .. floor(c) + 2, reflected with
 // edge repeat, with the weights cubic(c - i): they depend on o mod F only and are exact in f32 (UpTaps below).  The reference runs
 // two passes (rows, then columns) through an f64 buffer that holds f32 values; here both passes are one launch and the intermediate
 // stays in registers, with the same roundings: for one output row the vertical f32 sum of every source column (products added in
-// tap order), then the horizontal f32 sum of four of those.  No FMA: the library is built with -ffp-contract=off.
+// tap order), then the horizontal f32 sum of four of those.
 //
 // A pure streaming kernel that writes F^2 times what it reads, so it is shaped for the stores.  A thread owns 4 consecutive, 4-aligned
 // outputs of a row (one input column at 4x, two at 2x): one 16-byte store for f32, 8 bytes for uint16, 4 for uint8, and consecutive
@@ -16,7 +18,12 @@
 // skip those rows), so the 4 x 5 samples are loaded once for 16 outputs.  The loads hit L1 / L2 (neighbours share columns); no LDS,
 // no atomics, no scratch.  At 2x with an odd W a row is 2 W = 4k + 2 outputs long: rows are then not 4-aligned and the last thread
 // of a row owns one column, so that shape takes scalar stores.
-#include "common.h"
+//
+// Down-scale (antialiased; NIQE and BRISQUE need it between their two scales).  Output i of an axis reads the 4 F inputs from
+// F i + F/2 - 2F with the weights cubic(x / F) / F (Taps below), reflected the same way.  One launch makes both passes: a workgroup
+// brings the inputs of 8 x 32 outputs to LDS, makes the row pass there and the column pass from it.  fcvsr_bicubic_downscale runs
+// it on uint8 / f32 planes; downscale2_f64 (resize.h) is the 2x form on the f64 planes of integers of the scores.
+#include "resize.h"
 
 namespace {
 
@@ -38,7 +45,7 @@ template <> struct UpTaps<4> {
 };
 
 // out-of-range indices reflected with edge repeat (-1 -> 0, -2 -> 1, n -> n-1), periodic in 2n as the reference's index table
-__device__ inline int up_reflect(int i, int n) {
+__device__ inline int reflect(int i, int n) {
   if ((unsigned)i < (unsigned)n) return i;
   int m = i % (2 * n);
   if (m < 0) m += 2 * n;
@@ -80,11 +87,11 @@ __global__ __launch_bounds__(256) void upscale_kernel(const TI* __restrict__ src
   const int m0 = q * CPT;
   int cx[NC];
 #pragma unroll
-  for (int k = 0; k < NC; ++k) cx[k] = up_reflect(m0 - 2 + k, W);
+  for (int k = 0; k < NC; ++k) cx[k] = reflect(m0 - 2 + k, W);
   float v[4][NC];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const long long row = (long long)up_reflect(n - 1 + r, H) * W;
+    const long long row = (long long)reflect(n - 1 + r, H) * W;
 #pragma unroll
     for (int k = 0; k < NC; ++k) v[r][k] = up_sample(sp, row + cx[k]);
   }
@@ -144,7 +151,105 @@ void dispatch_upscale(const void* src, int src_dtype, long long planes, int H, i
   }
 }
 
+// antialiased cubic taps cubic(x / F) / F: multiples of 1/256 (2x) and 1/4096 (4x), exact in f32
+template <int F> struct Taps;
+template <> struct Taps<2> {
+  static constexpr int K = 8;
+  __device__ static float w(int k) {
+    constexpr float t[8] = {-3.f / 256, -9.f / 256, 29.f / 256, 111.f / 256, 111.f / 256, 29.f / 256, -9.f / 256, -3.f / 256};
+    return t[k];
+  }
+};
+template <> struct Taps<4> {
+  static constexpr int K = 16;
+  __device__ static float w(int k) {
+    constexpr float t[16] = {-7.f / 4096,  -45.f / 4096, -75.f / 4096, -49.f / 4096, 93.f / 4096,  399.f / 4096, 745.f / 4096, 987.f / 4096,
+                             987.f / 4096, 745.f / 4096, 399.f / 4096, 93.f / 4096,  -49.f / 4096, -75.f / 4096, -45.f / 4096, -7.f / 4096};
+    return t[k];
+  }
+};
+
+constexpr int kOY = 8, kOX = 32;
+enum { SRC_U8 = 0, SRC_F32 = 1, SRC_NIQE = 2 };   // SRC_NIQE: f64 plane of integers, read as f32(v / 255), stored as f64 * 255
+
+// One launch, both passes: a workgroup makes kOY x kOX outputs of one plane.  Rows first (dim 0), then columns; every pass's input
+// is an f32, products are f32 and are added in tap order.
+template <int F, int MODE>
+__global__ __launch_bounds__(256) void downscale_kernel(const void* __restrict__ src, int H, int W, void* __restrict__ dst) {
+  constexpr int K = Taps<F>::K, first = F / 2 - K / 2;      // tap 0 of output i reads input F i + first
+  constexpr int IY = (kOY - 1) * F + K, IX = (kOX - 1) * F + K;
+  __shared__ float in[IY][IX];
+  __shared__ float mid[kOY][IX];
+  const int Ho = H / F, Wo = W / F;
+  const int oy0 = blockIdx.y * kOY, ox0 = blockIdx.x * kOX;
+  const long long pl = blockIdx.z;
+  for (int i = threadIdx.x; i < IY * IX; i += 256) {
+    const int r = i / IX, q = i % IX;
+    const long long off = pl * H * W + (long long)reflect(oy0 * F + first + r, H) * W + reflect(ox0 * F + first + q, W);
+    float v;
+    if constexpr (MODE == SRC_U8) v = (float)((const unsigned char*)src)[off];
+    else if constexpr (MODE == SRC_F32) v = ((const float*)src)[off];
+    else v = (float)(((const double*)src)[off] / 255.0);
+    in[r][q] = v;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kOY * IX; i += 256) {
+    const int r = i / IX, q = i % IX;
+    float acc = Taps<F>::w(0) * in[r * F][q];
+#pragma unroll
+    for (int k = 1; k < K; ++k) acc = acc + Taps<F>::w(k) * in[r * F + k][q];
+    mid[r][q] = acc;
+  }
+  __syncthreads();
+  const int r = threadIdx.x / kOX, c = threadIdx.x % kOX;   // 256 threads = kOY x kOX outputs
+  if (oy0 + r < Ho && ox0 + c < Wo) {
+    float acc = Taps<F>::w(0) * mid[r][c * F];
+#pragma unroll
+    for (int k = 1; k < K; ++k) acc = acc + Taps<F>::w(k) * mid[r][c * F + k];
+    const long long o = pl * Ho * Wo + (long long)(oy0 + r) * Wo + ox0 + c;
+    if constexpr (MODE == SRC_NIQE) ((double*)dst)[o] = (double)acc * 255.0;
+    else ((float*)dst)[o] = acc;
+  }
+}
+static_assert(kOY * kOX == 256, "one thread per output");
+
+template <int F, int MODE>
+void launch_downscale(const void* src, long long planes, int H, int W, void* dst, hipStream_t stream) {
+  const long long in_elem = MODE == SRC_U8 ? 1 : MODE == SRC_F32 ? 4 : 8, out_elem = MODE == SRC_NIQE ? 8 : 4;
+  const int Ho = H / F, Wo = W / F;
+  for (long long p0 = 0; p0 < planes; p0 += 65535) {        // grid.z holds 65535 planes
+    const long long np = planes - p0 < 65535 ? planes - p0 : 65535;
+    hipLaunchKernelGGL((downscale_kernel<F, MODE>), dim3((unsigned)fcvsr::cdiv(Wo, kOX), (unsigned)fcvsr::cdiv(Ho, kOY), (unsigned)np),
+                       dim3(256), 0, stream, (const void*)((const char*)src + p0 * H * W * in_elem), H, W,
+                       (void*)((char*)dst + p0 * Ho * Wo * out_elem));
+  }
+}
+
 }  // namespace
+
+void fcvsr::downscale2_f64(const double* src, long long planes, int H, int W, double* dst, hipStream_t stream) {
+  launch_downscale<2, SRC_NIQE>(src, planes, H, W, dst, stream);
+}
+
+extern "C" int fcvsr_bicubic_downscale(const void* src, int src_dtype, long long planes, int H, int W, int factor, float* out,
+                                       void* stream) {
+  FCVSR_CHECK_ARG(src && out, "null device pointer");
+  FCVSR_CHECK_ARG(src_dtype == FCVSR_U8 || src_dtype == FCVSR_F32, "src_dtype: FCVSR_U8 or FCVSR_F32");
+  FCVSR_CHECK_ARG(factor == 2 || factor == 4, "factor: 2 or 4");
+  FCVSR_CHECK_ARG(planes >= 1 && H >= factor && W >= factor && H % factor == 0 && W % factor == 0, "H and W: positive multiples of factor");
+  FCVSR_CHECK_ARG(H <= (1 << 20) && W <= (1 << 20), "plane too large");
+  FCVSR_CHECK_ARG(((uintptr_t)out % 4) == 0 && (src_dtype == FCVSR_U8 || ((uintptr_t)src % 4) == 0), "f32 planes must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (factor == 2) {
+    if (src_dtype == FCVSR_U8) launch_downscale<2, SRC_U8>(src, planes, H, W, out, st);
+    else launch_downscale<2, SRC_F32>(src, planes, H, W, out, st);
+  } else {
+    if (src_dtype == FCVSR_U8) launch_downscale<4, SRC_U8>(src, planes, H, W, out, st);
+    else launch_downscale<4, SRC_F32>(src, planes, H, W, out, st);
+  }
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int fcvsr_bicubic_upscale(const void* src, int src_dtype, long long planes, int H, int W, int factor, void* out, int out_dtype,
                                      void* stream) {

@@ -29,11 +29,18 @@ __device__ __forceinline__ float sample_value(const float* tab, T k) {
   return tab[i < PEAK ? i : PEAK];
 }
 
+// the out rule, in f32; `mode` is FCVSR_QUANT_TRUNCATE or FCVSR_QUANT_ROUND, known at compile time (quantise) or at run time
+// (score_common.h frame_sample)
+template <int PEAK>
+__device__ __forceinline__ float quantised(float v, int mode) {
+  const float q = fminf(fmaxf(v, 0.f), 1.f) * (float)PEAK;
+  return mode == FCVSR_QUANT_TRUNCATE ? truncf(q) : rintf(q);
+}
+
 template <int Q, int PEAK, class T>
 __device__ __forceinline__ T quantise(float v) {
   static_assert(Q == FCVSR_QUANT_TRUNCATE || Q == FCVSR_QUANT_ROUND, "quantise mode");
-  const float q = fminf(fmaxf(v, 0.f), 1.f) * (float)PEAK;
-  return (T)(Q == FCVSR_QUANT_TRUNCATE ? truncf(q) : rintf(q));
+  return (T)quantised<PEAK>(v, Q);
 }
 
 template <int Q>

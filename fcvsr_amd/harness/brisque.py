@@ -24,8 +24,8 @@ from typing import Optional
 import numpy as np
 
 from .niqe import bicubic_downscale
+from .nss import GAM, check_frames, corr7, device_tables
 
-GAM = np.arange(0.2, 10.001, 0.001)                         # the shape grid of the GGD and AGGD fits, 9801 entries
 SHIFTS = ((0, 1), (1, 0), (1, 1), (-1, 1))                  # np.roll shifts of the four paired products, over the whole plane
 EPS32 = 2.0 ** -23                                          # the reference's safe_sqrt adds the f32 epsilon under the root
 ALPHA = (0, 2, 6, 10, 14, 18, 20, 24, 28, 32)               # the entries of the 36 features that are grid values
@@ -128,20 +128,9 @@ def yiq_luma(rgb: np.ndarray) -> np.ndarray:
     return (q + ((r > 500) | ((r == 500) & (q % 2 == 1)))).astype(np.uint8)
 
 
-def _corr7_zero(img: np.ndarray, w: np.ndarray) -> np.ndarray:
-    """Correlation with the 7 x 7 window over a zero-padded plane (the reference's padding='same' is F.pad 'constant'),
-    accumulated from 0 in row-major tap order."""
-    H, W = img.shape
-    p = np.pad(img, 3, mode="constant")
-    acc = np.zeros((H, W), dtype=np.float64)
-    for ky in range(7):
-        for kx in range(7):
-            acc += w[ky, kx] * p[ky:ky + H, kx:kx + W]
-    return acc
-
-
 def _mscn(img: np.ndarray, w: np.ndarray) -> np.ndarray:
-    mu, e2 = _corr7_zero(img, w), _corr7_zero(img * img, w)
+    """(img - mu) / (sigma + 1) over a zero-padded plane: the reference's padding='same' is F.pad 'constant'."""
+    mu, e2 = corr7(img, w, "constant"), corr7(img * img, w, "constant")
     return (img - mu) / (np.sqrt(np.abs(e2 - mu * mu) + EPS32) + 1.0)
 
 
@@ -245,20 +234,6 @@ def brisque(y: np.ndarray, model: BrisqueModel) -> float:
 
 
 # ---- device ------------------------------------------------------------------------------------------------------------------------
-_DEVICE_TABLES = {}
-
-
-def _device_tables(device):
-    import torch
-    key = str(torch.device(device))
-    t = _DEVICE_TABLES.get(key)
-    if t is None:
-        t = torch.from_numpy(brisque_tables().copy()).to(device)
-        torch.cuda.synchronize(device)                      # readers on any stream find it complete
-        _DEVICE_TABLES[key] = t
-    return t
-
-
 def frame_brisque_features(frames, *, quantise: Optional[str] = None, convert_to: Optional[str] = None):
     """frames: (N,C,H,W) on the HIP device, uint8 with `quantise=None`, or f32 model output in [0,1] with any strides, quantised in
     the kernel ("truncate" / "round", as `device_metrics.frame_metrics`).  C = 1, or 3 (RGB) with convert_to="Y": the integer luma
@@ -267,30 +242,14 @@ def frame_brisque_features(frames, *, quantise: Optional[str] = None, convert_to
     import torch
     from .. import hip
     from .device_metrics import _QUANTISE
-    if quantise not in _QUANTISE:
-        raise ValueError(f'quantise must be "truncate", "round" or None, got {quantise!r}')
-    if convert_to is not None and not (isinstance(convert_to, str) and convert_to.lower() == "y"):
-        raise ValueError('Wrong color model. Supported values are "Y" and None')
-    to_y = convert_to is not None
-    if not isinstance(frames, torch.Tensor):
-        raise TypeError("frames must be a torch tensor")
-    if frames.dtype == torch.uint16:
-        raise ValueError("BRISQUE is defined on 8-bit frames: uint16 (10-bit) frames are not supported")
-    if not frames.is_cuda:
-        raise RuntimeError("frame_brisque runs on the HIP device only (there is no CPU fallback)")
-    if frames.dim() != 4:
-        raise ValueError(f"expected (N,C,H,W) frames, got shape {tuple(frames.shape)}")
-    want = torch.uint8 if quantise is None else torch.float32
-    if frames.dtype != want:
-        raise ValueError(f"frames must be {want} with quantise={quantise!r}, got {frames.dtype}")
-    N, C, H, W = frames.shape
-    if C != (3 if to_y else 1):
-        raise ValueError(f"BRISQUE scores one plane: C must be 1, or 3 with convert_to='Y', got C={C}")
+    to_y = check_frames(frames, quantise, convert_to, "BRISQUE")
+    N, _, H, W = frames.shape
     _check_size(H, W)
     if N == 0:
         return torch.empty((0, 36), dtype=torch.float64, device=frames.device)
     with torch.cuda.device(frames.device):
-        return hip.brisque_features(frames, _QUANTISE[quantise], to_y, gaussian_window(), _device_tables(frames.device))
+        return hip.brisque_features(frames, _QUANTISE[quantise], to_y, gaussian_window(),
+                                    device_tables("brisque", brisque_tables(), frames.device))
 
 
 def scores_from_features(features: np.ndarray, model: BrisqueModel) -> np.ndarray:

@@ -19,8 +19,9 @@ from typing import Optional
 
 import numpy as np
 
+from .nss import GAM, check_frames, corr7, device_tables
+
 BLOCK = 96                                                  # block side at scale 1 (the official value; 48 at scale 2)
-GAM = np.arange(0.2, 10.001, 0.001)                         # the AGGD shape grid, 9801 entries
 _SHIFTS = ((0, 1), (1, 0), (1, 1), (1, -1))                 # np.roll shifts of the four paired products
 # antialiased cubic taps 0.5 cubic(0.5 x) at 2x (inputs 2i-3 .. 2i+4) and 0.25 cubic(0.25 x) at 4x (inputs 4i-6 .. 4i+9)
 _TAPS = {2: np.array([-3, -9, 29, 111, 111, 29, -9, -3], dtype=np.float64) / 256.0,
@@ -159,14 +160,7 @@ def bicubic_upscale(img: np.ndarray, factor: int, out: str = "f32") -> np.ndarra
 def _conv7(img: np.ndarray, window: np.ndarray) -> np.ndarray:
     """scipy.ndimage.convolve(img, window, mode='nearest'): a true convolution (flipped window) with replicated borders,
     accumulated from 0 in the row-major order of the flipped window."""
-    H, W = img.shape
-    p = np.pad(img, 3, mode="edge")
-    f = window[::-1, ::-1]
-    acc = np.zeros((H, W), dtype=np.float64)
-    for ky in range(7):
-        for kx in range(7):
-            acc += f[ky, kx] * p[ky:ky + H, kx:kx + W]
-    return acc
+    return corr7(img, window[::-1, ::-1], "edge")
 
 
 def _mscn(img: np.ndarray, window: np.ndarray, f32: bool = False) -> np.ndarray:
@@ -277,20 +271,6 @@ def niqe(y: np.ndarray, model: NiqeModel, crop_border: int = 0) -> float:
 
 
 # ---- device ------------------------------------------------------------------------------------------------------------------------
-_DEVICE_TABLES = {}
-
-
-def _device_tables(device):
-    import torch
-    key = str(torch.device(device))
-    t = _DEVICE_TABLES.get(key)
-    if t is None:
-        t = torch.from_numpy(aggd_tables().copy()).to(device)
-        torch.cuda.synchronize(device)                      # readers on any stream find it complete
-        _DEVICE_TABLES[key] = t
-    return t
-
-
 def frame_niqe_features(frames, model: NiqeModel, *, crop_border: int = 0, quantise: Optional[str] = None,
                         convert_to: Optional[str] = None):
     """frames: (N,C,H,W) on the HIP device, uint8 with `quantise=None`, or f32 model output in [0,1] with any strides, quantised in
@@ -301,31 +281,14 @@ def frame_niqe_features(frames, model: NiqeModel, *, crop_border: int = 0, quant
     from .. import hip
     from .device_metrics import _QUANTISE
     model = _check_model(model)
-    if quantise not in _QUANTISE:
-        raise ValueError(f'quantise must be "truncate", "round" or None, got {quantise!r}')
-    if convert_to is not None and not (isinstance(convert_to, str) and convert_to.lower() == "y"):
-        raise ValueError('Wrong color model. Supported values are "Y" and None')
-    to_y = convert_to is not None
-    if not isinstance(frames, torch.Tensor):
-        raise TypeError("frames must be a torch tensor")
-    if frames.dtype == torch.uint16:
-        raise ValueError("NIQE is defined on 8-bit frames: uint16 (10-bit) frames are not supported")
-    if not frames.is_cuda:
-        raise RuntimeError("frame_niqe runs on the HIP device only (there is no CPU fallback)")
-    if frames.dim() != 4:
-        raise ValueError(f"expected (N,C,H,W) frames, got shape {tuple(frames.shape)}")
-    want = torch.uint8 if quantise is None else torch.float32
-    if frames.dtype != want:
-        raise ValueError(f"frames must be {want} with quantise={quantise!r}, got {frames.dtype}")
-    N, C, H, W = frames.shape
-    if C != (3 if to_y else 1):
-        raise ValueError(f"NIQE scores one plane: C must be 1, or 3 with convert_to='Y', got C={C}")
+    to_y = check_frames(frames, quantise, convert_to, "NIQE")
+    N, _, H, W = frames.shape
     _, _, nbh, nbw = crop_geometry(H, W, crop_border)
     if N == 0:
         return torch.empty((0, nbh * nbw, 36), dtype=torch.float64, device=frames.device)
     with torch.cuda.device(frames.device):
         return hip.niqe_features(frames, _QUANTISE[quantise], int(crop_border), to_y, model.window[::-1, ::-1],
-                                 _device_tables(frames.device))
+                                 device_tables("niqe", aggd_tables(), frames.device))
 
 
 def scores_from_features(features: np.ndarray, model: NiqeModel) -> np.ndarray:

@@ -478,6 +478,17 @@ def frame_metric_sums(sr: torch.Tensor, hr: torch.Tensor, quantise: int, crop_bo
     return out
 
 
+def _score_args(frames: torch.Tensor, nbytes: int, taps, tables: torch.Tensor, tables_of: str):
+    """What fcvsr_niqe_features and fcvsr_brisque_features take alike: the f64 scratch tensor, the frames' strides and the 49
+    correlation taps as C arrays; `tables` is checked against the (4, 9801) f64 layout of `tables_of`."""
+    scratch = torch.empty((max(8, nbytes) + 7) // 8, dtype=torch.float64, device=frames.device)
+    strides = (C.c_int64 * 4)(*frames.stride())
+    win = (C.c_double * 49)(*[float(v) for v in np.asarray(taps, dtype=np.float64).reshape(-1)])
+    if tables.dtype != torch.float64 or tuple(tables.shape) != (4, 9801) or not tables.is_contiguous() or tables.device != frames.device:
+        raise ValueError(f"tables must be the contiguous (4, 9801) f64 tensor of {tables_of} on the frames' device")
+    return scratch, strides, win
+
+
 def niqe_features(frames: torch.Tensor, quantise: int, crop_border: int, to_y: bool, taps, tables: torch.Tensor) -> torch.Tensor:
     """fcvsr_niqe_features: frames (N,C,H,W) uint8 (QUANT_NONE) or f32 (any strides) on the HIP device; `taps` the 7 x 7 MSCN window
     as correlation taps (the model's window flipped in both axes); `tables` the device (4, 9801) f64 tensor of
@@ -485,13 +496,9 @@ def niqe_features(frames: torch.Tensor, quantise: int, crop_border: int, to_y: b
     checked by the library (FCVSR_E_ARG -> HipError)."""
     N, Cc, H, W = frames.shape
     blocks = (max(H - 2 * crop_border, 0) // 96) * (max(W - 2 * crop_border, 0) // 96)
-    nbytes = lib().fcvsr_niqe_scratch_bytes(N, H, W, crop_border)
-    scratch = torch.empty((max(8, nbytes) + 7) // 8, dtype=torch.float64, device=frames.device)
+    scratch, strides, win = _score_args(frames, lib().fcvsr_niqe_scratch_bytes(N, H, W, crop_border), taps, tables,
+                                        "harness.niqe.aggd_tables")
     out = torch.empty((N, blocks, 36), dtype=torch.float64, device=frames.device)
-    strides = (C.c_int64 * 4)(*frames.stride())
-    win = (C.c_double * 49)(*[float(v) for v in np.asarray(taps, dtype=np.float64).reshape(-1)])
-    if tables.dtype != torch.float64 or tuple(tables.shape) != (4, 9801) or not tables.is_contiguous() or tables.device != frames.device:
-        raise ValueError("tables must be the contiguous (4, 9801) f64 tensor of harness.niqe.aggd_tables on the frames' device")
     check(lib().fcvsr_niqe_features(frames.data_ptr(), strides, quantise, N, Cc, H, W, crop_border, int(bool(to_y)), win,
                                     tables.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, stream_ptr()),
           "fcvsr_niqe_features")
@@ -503,13 +510,9 @@ def brisque_features(frames: torch.Tensor, quantise: int, to_y: bool, taps, tabl
     window as correlation taps; `tables` the device (4, 9801) f64 tensor of `harness.brisque.brisque_tables`.  Returns the (N, 36)
     f64 features on the device, with no host sync.  Arguments are checked by the library (FCVSR_E_ARG -> HipError)."""
     N, Cc, H, W = frames.shape
-    nbytes = lib().fcvsr_brisque_scratch_bytes(N, H, W)
-    scratch = torch.empty((max(8, nbytes) + 7) // 8, dtype=torch.float64, device=frames.device)
+    scratch, strides, win = _score_args(frames, lib().fcvsr_brisque_scratch_bytes(N, H, W), taps, tables,
+                                        "harness.brisque.brisque_tables")
     out = torch.empty((N, 36), dtype=torch.float64, device=frames.device)
-    strides = (C.c_int64 * 4)(*frames.stride())
-    win = (C.c_double * 49)(*[float(v) for v in np.asarray(taps, dtype=np.float64).reshape(-1)])
-    if tables.dtype != torch.float64 or tuple(tables.shape) != (4, 9801) or not tables.is_contiguous() or tables.device != frames.device:
-        raise ValueError("tables must be the contiguous (4, 9801) f64 tensor of harness.brisque.brisque_tables on the frames' device")
     check(lib().fcvsr_brisque_features(frames.data_ptr(), strides, quantise, N, Cc, H, W, int(bool(to_y)), win, tables.data_ptr(),
                                        scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), stream_ptr()),
           "fcvsr_brisque_features")
