@@ -21,9 +21,10 @@ import numpy as np
 import torch
 
 from ..hip import bits16, frames_to_numpy
-from .ensemble import check_mode, for_mode
+from .ensemble import check_mode
 from .metrics import psnr
 from .shots import check_auto, cuts_from_sad, device_pair_sad, resolve_cuts, shot_ranges, windows_for
+from .tiles import check_tile, resolver_for
 
 
 def pad_to_multiple(frames: torch.Tensor, mult: int = 4) -> torch.Tensor:
@@ -86,7 +87,8 @@ def _quantised(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> np.ndarr
 @torch.no_grad()
 def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                            centres: Optional[Iterable[int]] = None, quantise: str = "truncate",
-                           ensemble: Optional[str] = None, cuts=None, cut_threshold: float = 10.0) -> np.ndarray:
+                           ensemble: Optional[str] = None, cuts=None, cut_threshold: float = 10.0,
+                           tile=None, tile_overlap=16) -> np.ndarray:
     """lr: (N,C,H,W) float in [0,1], uint8, or uint16 (10-bit samples; host or device).  Returns uint8 (len(centres),C,4H,4W) SR
     frames, uint16 for uint16 lr.  ``ensemble``: None, "spatial" (x8 self-ensemble, `harness.ensemble`) or "spatial+temporal"
     (x16); the windows are then built as variants straight from the resident sequence and never materialised.
@@ -94,15 +96,23 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
     ``cuts``: None (every window is built by `window_indices`, as the reference builds them), a sequence of frame numbers at which a
     new shot starts (validated by `shots.shot_ranges`), or "auto": `shots.detect_cuts` with ``cut_threshold`` on the resident integer
     frames ("auto" with float lr raises ValueError before any model pass: pass explicit cuts).  With cuts, every window stays inside
-    the shot of its centre frame (`shots.shot_window_indices`), with and without ``ensemble``."""
+    the shot of its centre frame (`shots.shot_window_indices`), with and without ``ensemble``.
+
+    ``tile`` / ``tile_overlap``: None (the model sees whole frames), or a tile size - an int or (th, tw), multiples of 4 - and the
+    overlap of neighbouring tiles - an int or (oy, ox), at most half the tile (`harness.tiles`): the model then runs on overlapping
+    tiles of the frame, at most `batch` tile windows per pass, and the tile outputs are blended with feathered weights.  A tiled
+    result is a different estimator from the full-frame result, not an approximation of it (the network has global operators); a
+    frame that fits one tile gives the untiled frames.  With ``ensemble`` every tile is ensembled."""
     check_mode(ensemble)
     check_auto(cuts, lr.dtype)
+    check_tile(tile, tile_overlap)
     N, C, H, W = lr.shape
     dev = next(model.parameters()).device
     centres = list(range(N)) if centres is None else list(centres)
     out: List[np.ndarray] = []
-    if ensemble is not None:
-        ens, x = for_mode(model, ensemble), _lr_frames_dense(lr, dev)
+    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
+    if ens is not None:
+        x = _lr_frames_dense(lr, dev)
         cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
         for s in range(0, len(centres), batch):
             idx = windows_for(centres[s:s + batch], num_frames, N, padding, cuts)
@@ -157,7 +167,7 @@ class SequenceScores:
 def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
                       ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None, brisque=None,
-                      cuts=None, cut_threshold: float = 10.0) -> SequenceScores:
+                      cuts=None, cut_threshold: float = 10.0, tile=None, tile_overlap=16) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -186,7 +196,10 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     the SR frames are.  No model pass and no host round trip is added, and the baseline does not depend on ``ensemble``.
 
     ``cuts`` / ``cut_threshold`` as in `super_resolve_sequence`; the list that was used comes back as `SequenceScores.cuts` (None
-    without the keyword)."""
+    without the keyword).
+
+    ``tile`` / ``tile_overlap`` as in `super_resolve_sequence`: the blended frame is scored in place of the model's; the bicubic
+    baseline does not depend on it."""
     from .device_metrics import frame_metrics
     from . import brisque as brisque_mod
     from . import niqe as niqe_mod
@@ -215,8 +228,9 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     peak = 255.0 if hr.dtype == torch.uint8 else 1023.0
     if quantise not in ("truncate", "round"):
         raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+    check_tile(tile, tile_overlap)
     dev = next(model.parameters()).device
-    ens = for_mode(model, ensemble)
+    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
     x = _lr_frames(lr, dev) if ens is None else _lr_frames_dense(lr, dev)
     cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
     p_dev, s_dev, n_dev, frames = [], [], [], []                  # per-batch device results, fetched once at the end

@@ -19,11 +19,12 @@ import torch
 
 from .. import hip
 from .colour import ColourSpec, i420_planes, rgb_to_i420, yuv420_to_rgb
-from .ensemble import for_mode
+from .ensemble import check_mode
 from .infer import pad_to_multiple, super_resolve_int
 from . import brisque as brisque_mod
 from .niqe import crop_geometry, frame_niqe_features, scores_from_features
 from .shots import check_auto, detect_cuts, resolve_cuts, windows_for
+from .tiles import check_tile, resolver_for
 
 
 class YuvName(NamedTuple):
@@ -175,7 +176,8 @@ def _niqe_stats(feats, niqe) -> dict:
 @torch.no_grad()
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
                          quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
-                         ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0) -> dict:
+                         ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0,
+                         tile=None, tile_overlap=16) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -191,8 +193,10 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     same with BRISQUE (``"brisque"``, ``"brisque_mean"``), 8-bit only as well; the two may be given together.  ``cuts``: None, a
     sequence of frame numbers at which a new shot starts, or "auto" (`shots.detect_cuts` with ``cut_threshold`` on the file's luma
     plane, on the device): every window then stays inside the shot of its centre frame (`shots.shot_window_indices`), and the list
-    that was used is added to the stats as ``"cuts"``.  Chroma does not depend on it."""
-    ens = for_mode(model, ensemble)
+    that was used is added to the stats as ``"cuts"``.  Chroma does not depend on it.  ``tile`` / ``tile_overlap`` as in
+    `super_resolve_sequence` (`harness.tiles`): Y runs through the model in overlapping tiles, with ``ensemble`` every tile
+    ensembled; chroma is unchanged."""
+    check_mode(ensemble)
     check_auto(cuts, "uint8")
     _check_niqe(niqe, bit_depth, width, height)
     brisque = _check_brisque(brisque, bit_depth, width, height)
@@ -202,6 +206,8 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
         raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
     if batch < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
+    check_tile(tile, tile_overlap)
+    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
     y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
     N, H, W = y.shape
     sdt, host_dt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.uint16, np.uint16)
@@ -244,7 +250,7 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
 def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int, *, colour: ColourSpec = ColourSpec(),
                              batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
                              ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None,
-                             cut_threshold: float = 10.0) -> dict:
+                             cut_threshold: float = 10.0, tile=None, tile_overlap=16) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -259,8 +265,9 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     `super_resolve_yuv420`: the Y of YCbCr of the SR RGB frames (convert_to="Y") is scored before the encode; 8-bit only.
     ``brisque`` as in `super_resolve_yuv420`: the YIQ luma of the SR RGB frames (BRISQUE's own "Y", not NIQE's) is scored before
     the encode; 8-bit only.  ``cuts`` / ``cut_threshold`` as in `super_resolve_yuv420`: "auto" detects on the luma plane of the file,
-    before the colour conversion."""
-    ens = for_mode(model, ensemble)
+    before the colour conversion.  ``tile`` / ``tile_overlap`` as in `super_resolve_sequence` (`harness.tiles`): the decoded RGB
+    frames run through the model in overlapping tiles between the two colour conversions."""
+    check_mode(ensemble)
     check_auto(cuts, "uint8")
     _check_niqe(niqe, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
     brisque = _check_brisque(brisque, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
@@ -272,6 +279,8 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
         raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
     if batch < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
+    check_tile(tile, tile_overlap)
+    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
     bit_depth = colour.bit_depth
     mm = _map_frames(src, width, height, bit_depth=bit_depth)
     N, H, W = mm.shape[0], height, width

@@ -225,6 +225,10 @@ SIGNATURES = {
     "fcvsr_ensemble_windows_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP],
     "fcvsr_ensemble_windows_u16": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP],
     "fcvsr_ensemble_merge": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP],
+    "fcvsr_tile_windows": [_VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP],
+    "fcvsr_tile_windows_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP],
+    "fcvsr_tile_windows_u16": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP],
+    "fcvsr_tile_merge": [_VP, _VP, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP],
     "fcvsr_niqe_scratch_bytes": [_I] * 4,
     "fcvsr_niqe_features": [_VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _VP, _VP, _VP, C.c_longlong,
                             _VP],
@@ -775,4 +779,81 @@ def ensemble_merge(a: torch.Tensor, at: torch.Tensor, h: int, w: int, *, ra: Opt
     with torch.cuda.device(a.device):
         check(lib().fcvsr_ensemble_merge(a.data_ptr(), at.data_ptr(), ptr(ra), ptr(rat), b, Cc, h, w, code, q, out.data_ptr(),
                                          stream_ptr()), "fcvsr_ensemble_merge")
+    return out
+
+
+def _tile_plan_for(plan, h: int, w: int, what: str):
+    if (plan.h, plan.w) != (h, w):
+        raise ValueError(f"{what}: the plan is for {plan.h} x {plan.w} frames, got {h} x {w}")
+
+
+def tile_windows(frames: torch.Tensor, idx: torch.Tensor, plan) -> torch.Tensor:
+    """fcvsr_tile_windows / _u8 / _u16: the tile windows (`harness.tiles`) of b windows, one launch.  `frames` is the dense UNPADDED
+    sequence (N,C,h,w) on the HIP device, f32, uint8 or uint16 (integer samples enter as ``u8_table`` / ``u16_table[min(k, 1023)]``);
+    `idx` an int32 (b,T) tensor on the same device, row i the frame numbers of window i; `plan` the `harness.tiles.TilePlan` of
+    h x w frames.  Returns f32 ``(b,ny,nx,T,C,th,tw)``: tile (ky,kx) is the window cut at ``(plan.ys[ky], plan.xs[kx])`` out of the
+    frames zero-padded at the bottom / right to multiples of 4."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype not in (torch.float32, torch.uint8, torch.uint16):
+        raise ValueError(f"frames: expected an f32, uint8 or uint16 (N,C,h,w) tensor, got {getattr(frames, 'dtype', type(frames))} "
+                         f"{tuple(getattr(frames, 'shape', ()))}")
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int32:
+        raise ValueError(f"idx: expected an int32 (b,T) tensor, got {getattr(idx, 'dtype', type(idx))}")
+    if not frames.is_cuda or not idx.is_cuda:
+        raise RuntimeError("tile_windows runs on the HIP device only (there is no CPU fallback)")
+    if frames.device != idx.device:
+        raise ValueError(f"frames on {frames.device}, idx on {idx.device}")
+    if min(frames.shape) == 0 or idx.numel() == 0:
+        raise ValueError(f"empty input: frames {tuple(frames.shape)}, idx {tuple(idx.shape)}")
+    N, Cc, h, w = frames.shape
+    _tile_plan_for(plan, h, w, "tile_windows")
+    (b, T), dev = idx.shape, frames.device
+    src, idx = bits16(frames).contiguous(), idx.contiguous()
+    ys, xs, _, _ = plan.device_tables(dev)
+    out = torch.empty((b, plan.ny, plan.nx, T, Cc, plan.th, plan.tw), dtype=torch.float32, device=dev)
+    tail = (N, Cc, h, w, idx.data_ptr(), b, T, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx, plan.th, plan.tw, out.data_ptr())
+    with torch.cuda.device(dev):
+        if frames.dtype == torch.float32:
+            check(lib().fcvsr_tile_windows(src.data_ptr(), *tail, stream_ptr()), "fcvsr_tile_windows")
+        elif frames.dtype == torch.uint8:
+            check(lib().fcvsr_tile_windows_u8(src.data_ptr(), u8_table(dev).data_ptr(), *tail, stream_ptr()), "fcvsr_tile_windows_u8")
+        else:
+            check(lib().fcvsr_tile_windows_u16(src.data_ptr(), u16_table(dev).data_ptr(), *tail, stream_ptr()),
+                  "fcvsr_tile_windows_u16")
+    return out
+
+
+def tile_merge(tiles: torch.Tensor, plan, h: int, w: int, *, dtype: torch.dtype = torch.float32,
+               quantise: Optional[str] = None) -> torch.Tensor:
+    """fcvsr_tile_merge: `tiles` (b,ny,nx,C,4th,4tw), f32 on the HIP device, are the model's outputs for the tile windows of b
+    windows of h x w frames (`plan`: their `harness.tiles.TilePlan`).  Returns the dense (b,C,4h,4w) blend (`harness.tiles.blend_host`:
+    crop, the normalised feathered weights, the fixed-order f32 sum): f32, or - `dtype` uint8 / uint16 with `quantise` "truncate" /
+    "round" - quantised as the model's integer paths quantise.  One launch."""
+    if not isinstance(tiles, torch.Tensor) or tiles.dtype != torch.float32 or tiles.dim() != 6:
+        raise ValueError(f"tiles: expected an f32 (b,ny,nx,C,4th,4tw) tensor, got {getattr(tiles, 'dtype', type(tiles))} "
+                         f"{tuple(getattr(tiles, 'shape', ()))}")
+    if not tiles.is_cuda:
+        raise RuntimeError("tile_merge runs on the HIP device only (there is no CPU fallback)")
+    _tile_plan_for(plan, h, w, "tile_merge")
+    b, Cc = tiles.shape[0], tiles.shape[3]
+    want = (b, plan.ny, plan.nx, Cc, 4 * plan.th, 4 * plan.tw)
+    if tuple(tiles.shape) != want:
+        raise ValueError(f"tiles: expected {want}, got {tuple(tiles.shape)}")
+    if b == 0 or Cc == 0:
+        raise ValueError(f"empty input: {tuple(tiles.shape)}")
+    if dtype == torch.float32:
+        if quantise is not None:
+            raise ValueError("quantise applies to uint8 / uint16 results only")
+        code, q = F32, QUANT_NONE
+    elif dtype in (torch.uint8, torch.uint16):
+        if quantise not in QUANTISE:
+            raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+        code, q = _DT[dtype], QUANTISE[quantise]
+    else:
+        raise ValueError(f"dtype: torch.float32, torch.uint8 or torch.uint16, got {dtype!r}")
+    tiles = tiles.contiguous()
+    ys, xs, wy, wx = plan.device_tables(tiles.device)
+    out = torch.empty((b, Cc, 4 * h, 4 * w), dtype=dtype, device=tiles.device)
+    with torch.cuda.device(tiles.device):
+        check(lib().fcvsr_tile_merge(tiles.data_ptr(), ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx, plan.th, plan.tw, wy.data_ptr(),
+                                     wx.data_ptr(), b, Cc, h, w, code, q, out.data_ptr(), stream_ptr()), "fcvsr_tile_merge")
     return out

@@ -733,6 +733,28 @@ int fcvsr_ensemble_windows_u16(const uint16_t* src, const float* tab, int N, int
  * samples). */
 int fcvsr_ensemble_merge(const float* a, const float* at, const float* ra, const float* rat, int b, int C, int h, int w,
                          int out_dtype, int quantise, void* out, void* stream);
+/* ---- tiled inference (specification: fcvsr_amd/harness/tiles.py, which the kernels equal bit for bit) ---------------------------
+ * Geometry in LR pixels on the frame zero-padded at its bottom / right to multiples of 4, Hp x Wp = ceil4(h) x ceil4(w).  Every tile
+ * is th x tw (multiples of 4, th <= Hp, tw <= Wp); tile (ky, kx) of the ny x nx grid starts at (ys[ky], xs[kx]).  ys (ny) and xs (nx)
+ * are int32 DEVICE tables; a start outside [0, Hp - th] / [0, Wp - tw] is clamped into it.
+ * fcvsr_tile_windows: all tile windows of b windows of T frames, one launch.  src: the dense UNPADDED sequence (N,C,h,w); idx: a
+ * DEVICE table (b,T) of frame numbers (a number outside 0..N-1 is clamped).  out (b,ny,nx,T,C,th,tw) f32, 16-byte aligned: sample
+ * (y, x) of tile (ky, kx) is the frame's sample (ys[ky] + y, xs[kx] + x), 0 outside h x w; every element is written.  The _u8 / _u16
+ * entry points read uint8 / uint16 samples through tab, as fcvsr_ensemble_windows_u8 / _u16 do. */
+int fcvsr_tile_windows(const float* src, int N, int C, int h, int w, const int32_t* idx, int b, int T, const int32_t* ys, int ny,
+                       const int32_t* xs, int nx, int th, int tw, float* out, void* stream);
+int fcvsr_tile_windows_u8(const uint8_t* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b, int T,
+                          const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, float* out, void* stream);
+int fcvsr_tile_windows_u16(const uint16_t* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b, int T,
+                           const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, float* out, void* stream);
+/* The other end, one launch: tiles (b,ny,nx,C,4th,4tw), dense f32, 16-byte aligned, are the model's outputs for the tile windows;
+ * wy (ny,4Hp) and wx (nx,4Wp; 16-byte aligned) are the normalised per-axis f32 blend weights (harness/tiles.py axis_weights).  For
+ * the output pixel (Y, X) of plane (bi, c), in f32, each operation rounded once, no FMA:
+ *   acc = 0;  for ky ascending, then kx ascending, over the tiles with 4 ys[ky] <= Y < 4 (ys[ky] + th), 4 xs[kx] <= X < 4 (xs[kx] + tw):
+ *     acc = acc + (wy[ky][Y] * wx[kx][X]) * tiles[bi][ky][kx][c][Y - 4 ys[ky]][X - 4 xs[kx]]
+ * out: dense (b,C,4h,4w) (the crop of the padded frame), out_dtype / quantise / alignment as fcvsr_ensemble_merge. */
+int fcvsr_tile_merge(const float* tiles, const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, const float* wy,
+                     const float* wx, int b, int C, int h, int w, int out_dtype, int quantise, void* out, void* stream);
 /* ---- NIQE block features and the MATLAB-style bicubic down-scale (reference mmedit/core/evaluation/metrics.py:398-590
  * estimate_aggd_param / compute_feature / niqe_core / niqe, used by CVSR_train/metric/cal_VideoLQ.py; the down-scale is
  * mmedit/datasets/pipelines/matlab_like_resize.py; the contract is fcvsr_amd/harness/niqe.py) ------------------------------------
