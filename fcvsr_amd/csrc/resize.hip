@@ -23,6 +23,14 @@
 // F i + F/2 - 2F with the weights cubic(x / F) / F (Taps below), reflected the same way.  One launch makes both passes: a workgroup
 // brings the inputs of 8 x 32 outputs to LDS, makes the row pass there and the column pass from it.  fcvsr_bicubic_downscale runs
 // it on uint8 / f32 planes; downscale2_f64 (resize.h) is the 2x form on the f64 planes of integers of the scores.
+//
+// Any size (fcvsr_imresize; the contract is fcvsr_amd/harness/resize.py imresize_host).  The same operator with scale= or
+// output_shape= free: the taps are no longer constants but two per-axis tables (f32 weights and the first, unreflected input of every
+// output) that the host computes with the reference's arithmetic and uploads once per size.  One launch, table-driven, both passes
+// through an LDS tile, the axis with the smaller scale first (rows on a tie) - see imresize_kernel below.  The rule is the same
+// everywhere: f32 products added in TAP ORDER.  The reference itself leaves that order in one degenerate class - a pass of 8 or
+// more stored taps over a plane whose other extent is 1, where numpy collapses the axes and sums pairwise in blocks of 8, 1 ulp
+// away; the contract and this kernel keep tap order there too.
 #include "resize.h"
 
 namespace {
@@ -225,6 +233,165 @@ void launch_downscale(const void* src, long long planes, int H, int W, void* dst
   }
 }
 
+// The general resize (fcvsr_imresize): any output size, from two per-axis tap tables the host makes (harness/resize.py
+// resize_taps).  Output o of an axis reads the P consecutive inputs first[o] .. first[o] + P - 1, reflected, with the weights
+// w[o][0 .. P-1].  One launch makes both passes: a workgroup owns kOY x kOX outputs of one plane, brings its slices of the two tables
+// to LDS, makes the first pass for the source span of its tile straight from global memory into an LDS tile, and the second pass
+// from there.  The first pass is the axis with the smaller scale (ROWS_FIRST: the row pass, dim 0), as the reference orders them.
+// The first pass reads a tap as one 8-byte LDS word, its weight and the REFLECTED input it reads (the row's offset in the plane
+// when rows go first, the column otherwise; reflection is applied once per workgroup, when the tables are staged), adds the
+// element's own reflected column or row offset and loads; offsets inside a plane are 32-bit.
+// Neighbouring outputs are at most kMaxStep inputs apart (scale >= 1/8) and P <= kMaxTaps, which bounds the span of a tile; the
+// span is read off the table and clamped to that bound, and the first LDS index of an output is clamped so that its P taps stay
+// inside the tile: a table that breaks the rule gives wrong samples, never an access outside the tile.
+constexpr int kMaxTaps = 34, kMaxStep = 8;
+constexpr int kSpanY = (kOY - 1) * kMaxStep + 2 + kMaxTaps, kSpanX = (kOX - 1) * kMaxStep + 2 + kMaxTaps;   // 92 rows, 284 columns
+
+struct Tap {
+  float w;
+  int off;
+};
+
+__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// i / n for 0 <= i < 4096, 1 <= n <= 4096 without the integer division: (i + 0.5) / n is at least 0.5 / n from an integer and the
+// two f32 roundings move it by less than 2^-22 of its value
+__device__ inline int small_div(int i, float inv_n) { return (int)(((float)i + 0.5f) * inv_n); }
+
+// The sum over k < P of w(k) * v(k), one f32 product per tap, products added in tap order.  A dependent load per tap would make the
+// loop a chain of P memory round trips, so the terms are fetched kChunk at a time, their loads in flight together, and then added in
+// order; a tap past the end re-reads the last one and is not added.
+constexpr int kChunk = 4;
+template <class Term>
+__device__ inline float tap_sum(int P, Term term) {
+  float a = 0.f;
+  for (int k0 = 0; k0 < P; k0 += kChunk) {
+    float w[kChunk], v[kChunk];
+#pragma unroll
+    for (int j = 0; j < kChunk; ++j) term(k0 + j < P ? k0 + j : P - 1, w[j], v[j]);
+#pragma unroll
+    for (int j = 0; j < kChunk; ++j) {
+      const float p = w[j] * v[j];
+      if (k0 + j == 0) a = p;
+      else if (k0 + j < P) a = a + p;
+    }
+  }
+  return a;
+}
+
+// grid.x: the tiles of a plane, row-major (tiles_x per row); grid.y: planes
+template <bool ROWS_FIRST, class TI, class TO>
+__global__ __launch_bounds__(256) void imresize_kernel(const TI* __restrict__ src, int H, int W, int Ho, int Wo,
+                                                       const float* __restrict__ wy, const int* __restrict__ firsty, int Py,
+                                                       const float* __restrict__ wx, const int* __restrict__ firstx, int Px,
+                                                       int tiles_x, TO* __restrict__ dst) {
+  // first-pass taps: rows first [row of the tile][tap], off = reflected row * W; columns first [tap][column of the tile], off =
+  // reflected column.  second-pass weights: rows first [tap][column]; columns first [row][tap]
+  constexpr int kTap1 = ROWS_FIRST ? kOY * kMaxTaps : kMaxTaps * kOX, kW2 = ROWS_FIRST ? kMaxTaps * kOX : kOY * kMaxTaps;
+  __shared__ float mid[ROWS_FIRST ? kOY * kSpanX : kSpanY * kOX];
+  __shared__ Tap tap1[kTap1];
+  __shared__ float w2[kW2];
+  __shared__ int sfy[kOY], sfx[kOX];
+  const int tid = threadIdx.x;
+  const int oy0 = (int)(blockIdx.x / (unsigned)tiles_x) * kOY, ox0 = (int)(blockIdx.x % (unsigned)tiles_x) * kOX;
+  const int ny = Ho - oy0 < kOY ? Ho - oy0 : kOY, nx = Wo - ox0 < kOX ? Wo - ox0 : kOX;
+  const long long pl = blockIdx.y;
+  const TI* sp = src + pl * H * W;
+  const int r = tid / kOX, c = tid % kOX;                   // 256 threads = kOY x kOX outputs
+  const bool live = r < ny && c < nx;
+  if (r < ny) {                                             // the tables of the tile: thread (r, c) brings taps c, c + 32 of row r
+    const int f = firsty[oy0 + r];
+    if (c == 0) sfy[r] = f;
+    for (int k = c; k < Py; k += kOX) {
+      const float w = wy[(long long)(oy0 + r) * Py + k];
+      if constexpr (ROWS_FIRST) tap1[r * Py + k] = Tap{w, reflect(f + k, H) * W};
+      else w2[r * Py + k] = w;
+    }
+  }
+  if (c < nx) {                                             // ... and taps r, r + 8, .. of column c
+    const int f = firstx[ox0 + c];
+    if (r == 0) sfx[c] = f;
+    for (int k = r; k < Px; k += kOY) {
+      const float w = wx[(long long)(ox0 + c) * Px + k];
+      if constexpr (ROWS_FIRST) w2[k * kOX + c] = w;
+      else tap1[k * kOX + c] = Tap{w, reflect(f + k, W)};
+    }
+  }
+  __syncthreads();
+  float acc = 0.f;
+  if constexpr (ROWS_FIRST) {
+    const int lox = sfx[0], span = clampi(sfx[nx - 1] - lox + Px, 0, kSpanX);
+    const float inv = 1.f / (float)span;
+    for (int i = tid; i < ny * span; i += 256) {            // the row pass at the tile's output rows, per source column of its span
+      const int rr = small_div(i, inv), q = i - rr * span;
+      const unsigned col = (unsigned)reflect(lox + q, W);
+      const Tap* tp = tap1 + rr * Py;
+      mid[rr * kSpanX + q] = tap_sum(Py, [&](int k, float& w, float& v) {
+        const Tap t = tp[k];
+        w = t.w;
+        v = up_sample(sp, (unsigned)t.off + col);
+      });
+    }
+    __syncthreads();
+    if (live) {
+      const float* m = mid + r * kSpanX + clampi(sfx[c] - lox, 0, kSpanX - Px);
+      acc = tap_sum(Px, [&](int k, float& w, float& v) {
+        w = w2[k * kOX + c];
+        v = m[k];
+      });
+    }
+  } else {
+    const int loy = sfy[0], span = clampi(sfy[ny - 1] - loy + Py, 0, kSpanY);
+    const float inv = 1.f / (float)nx;
+    for (int i = tid; i < span * nx; i += 256) {            // the column pass at the tile's output columns, per source row of its span
+      const int q = small_div(i, inv), cc = i - q * nx;
+      const unsigned row = (unsigned)(reflect(loy + q, H) * W);
+      const Tap* tp = tap1 + cc;
+      mid[q * kOX + cc] = tap_sum(Px, [&](int k, float& w, float& v) {
+        const Tap t = tp[k * kOX];
+        w = t.w;
+        v = up_sample(sp, row + (unsigned)t.off);
+      });
+    }
+    __syncthreads();
+    if (live) {
+      const float* m = mid + clampi(sfy[r] - loy, 0, kSpanY - Py) * kOX + c;
+      acc = tap_sum(Py, [&](int k, float& w, float& v) {
+        w = w2[r * Py + k];
+        v = m[k * kOX];
+      });
+    }
+  }
+  if (live) up_result(acc, dst[pl * Ho * Wo + (long long)(oy0 + r) * Wo + ox0 + c]);
+}
+
+struct ResizeArgs {
+  const void* src;
+  long long planes;
+  int H, W, Ho, Wo;
+  const float *wy, *wx;
+  const int *firsty, *firstx;
+  int Py, Px;
+  void* out;
+};
+
+template <bool ROWS_FIRST, class TI, class TO>
+void launch_imresize(const ResizeArgs& a, hipStream_t stream) {
+  const int tiles_x = fcvsr::cdiv(a.Wo, kOX), tiles_y = fcvsr::cdiv(a.Ho, kOY);
+  for (long long p0 = 0; p0 < a.planes; p0 += 65535) {      // grid.y holds 65535 planes
+    const long long np = a.planes - p0 < 65535 ? a.planes - p0 : 65535;
+    hipLaunchKernelGGL((imresize_kernel<ROWS_FIRST, TI, TO>), dim3((unsigned)tiles_x * (unsigned)tiles_y, (unsigned)np), dim3(256), 0,
+                       stream, (const TI*)a.src + p0 * a.H * a.W, a.H, a.W, a.Ho, a.Wo, a.wy, a.firsty, a.Py, a.wx, a.firstx, a.Px,
+                       tiles_x, (TO*)a.out + p0 * a.Ho * a.Wo);
+  }
+}
+
+template <class TI, class TO>
+void order_imresize(const ResizeArgs& a, int rows_first, hipStream_t stream) {
+  if (rows_first) launch_imresize<true, TI, TO>(a, stream);
+  else launch_imresize<false, TI, TO>(a, stream);
+}
+
 }  // namespace
 
 void fcvsr::downscale2_f64(const double* src, long long planes, int H, int W, double* dst, hipStream_t stream) {
@@ -267,6 +434,41 @@ extern "C" int fcvsr_bicubic_upscale(const void* src, int src_dtype, long long p
   hipStream_t st = (hipStream_t)stream;
   if (factor == 2) dispatch_upscale<2>(src, src_dtype, planes, H, W, out, out_dtype, st);
   else dispatch_upscale<4>(src, src_dtype, planes, H, W, out, out_dtype, st);
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fcvsr_imresize(const void* src, int src_dtype, long long planes, int H, int W, int Ho, int Wo, const float* wy,
+                              const int* firsty, int Py, const float* wx, const int* firstx, int Px, int rows_first, void* out,
+                              int out_dtype, void* stream) {
+  FCVSR_CHECK_ARG(src && out && wy && firsty && wx && firstx, "null device pointer");
+  FCVSR_CHECK_ARG(src_dtype == FCVSR_U8 || src_dtype == FCVSR_U16 || src_dtype == FCVSR_F32, "src_dtype: FCVSR_U8, FCVSR_U16 or FCVSR_F32");
+  FCVSR_CHECK_ARG(out_dtype == FCVSR_F32 || (out_dtype == src_dtype), "out_dtype: FCVSR_F32, or the integer src_dtype");
+  FCVSR_CHECK_ARG(planes >= 1 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1, "planes, H, W, Ho and Wo: at least 1");
+  FCVSR_CHECK_ARG(Py >= 1 && Py <= kMaxTaps && Px >= 1 && Px <= kMaxTaps, "Py and Px: 1 .. 34 taps");
+  // 32-bit offsets inside a plane
+  FCVSR_CHECK_ARG(H <= (1 << 20) && W <= (1 << 20) && Ho <= (1 << 20) && Wo <= (1 << 20) && (long long)H * W < (1ll << 31),
+                  "plane too large");
+  // neighbouring outputs at most 8 inputs apart (the span of a tile in LDS)
+  FCVSR_CHECK_ARG((long long)H <= 8ll * Ho && (long long)W <= 8ll * Wo && (long long)Ho <= 8ll * H && (long long)Wo <= 8ll * W,
+                  "per-axis scale outside [1/8, 8]");
+  FCVSR_CHECK_ARG((long long)fcvsr::cdiv(Wo, kOX) * fcvsr::cdiv(Ho, kOY) < (1ll << 31), "too many tiles in a plane");
+  const int src_elem = src_dtype == FCVSR_U8 ? 1 : src_dtype == FCVSR_U16 ? 2 : 4;
+  const int out_elem = out_dtype == FCVSR_U8 ? 1 : out_dtype == FCVSR_U16 ? 2 : 4;
+  FCVSR_CHECK_ARG(((uintptr_t)src % src_elem) == 0 && ((uintptr_t)out % out_elem) == 0, "src and out: aligned to their sample size");
+  FCVSR_CHECK_ARG(((uintptr_t)wy % 4) == 0 && ((uintptr_t)wx % 4) == 0 && ((uintptr_t)firsty % 4) == 0 && ((uintptr_t)firstx % 4) == 0,
+                  "tables: 4-byte aligned");
+  const ResizeArgs a{src, planes, H, W, Ho, Wo, wy, wx, firsty, firstx, Py, Px, out};
+  hipStream_t st = (hipStream_t)stream;
+  if (src_dtype == FCVSR_U8) {
+    if (out_dtype == FCVSR_U8) order_imresize<unsigned char, unsigned char>(a, rows_first, st);
+    else order_imresize<unsigned char, float>(a, rows_first, st);
+  } else if (src_dtype == FCVSR_U16) {
+    if (out_dtype == FCVSR_U16) order_imresize<unsigned short, unsigned short>(a, rows_first, st);
+    else order_imresize<unsigned short, float>(a, rows_first, st);
+  } else {
+    order_imresize<float, float>(a, rows_first, st);
+  }
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

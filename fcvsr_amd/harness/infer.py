@@ -75,20 +75,25 @@ def super_resolve_int(model, win: torch.Tensor, quantise: str) -> torch.Tensor:
     return model.super_resolve_u16(win, quantise) if win.dtype == torch.uint16 else model.super_resolve_u8(win, quantise)
 
 
-def _quantised(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> np.ndarray:
-    """The float path's frames the harness's way: clamp, * peak, optional round, integer cast (truncation)."""
+def _quantised_dev(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> torch.Tensor:
+    """The float path's frames the harness's way, on the device: clamp, * peak, optional round, integer cast (truncation)."""
     sr = sr.clamp(0, 1) * peak
     sr = sr.round() if quantise == "round" else sr
     if peak == 255.0:
-        return sr.to(torch.uint8).cpu().numpy()
-    return sr.to(torch.int16).cpu().numpy().view(np.uint16)           # values in [0, 1023]: the bits of the uint16 cast
+        return sr.to(torch.uint8)
+    return sr.to(torch.int16).view(torch.uint16)                      # values in [0, 1023]: the bits of the uint16 cast
+
+
+def _quantised(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> np.ndarray:
+    """`_quantised_dev`, downloaded."""
+    return frames_to_numpy(_quantised_dev(sr, quantise, peak))
 
 
 @torch.no_grad()
 def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                            centres: Optional[Iterable[int]] = None, quantise: str = "truncate",
                            ensemble: Optional[str] = None, cuts=None, cut_threshold: float = 10.0,
-                           tile=None, tile_overlap=16) -> np.ndarray:
+                           tile=None, tile_overlap=16, output_shape=None) -> np.ndarray:
     """lr: (N,C,H,W) float in [0,1], uint8, or uint16 (10-bit samples; host or device).  Returns uint8 (len(centres),C,4H,4W) SR
     frames, uint16 for uint16 lr.  ``ensemble``: None, "spatial" (x8 self-ensemble, `harness.ensemble`) or "spatial+temporal"
     (x16); the windows are then built as variants straight from the resident sequence and never materialised.
@@ -102,11 +107,22 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
     overlap of neighbouring tiles - an int or (oy, ox), at most half the tile (`harness.tiles`): the model then runs on overlapping
     tiles of the frame, at most `batch` tile windows per pass, and the tile outputs are blended with feathered weights.  A tiled
     result is a different estimator from the full-frame result, not an approximation of it (the network has global operators); a
-    frame that fits one tile gives the untiled frames.  With ``ensemble`` every tile is ensembled."""
+    frame that fits one tile gives the untiled frames.  With ``ensemble`` every tile is ensembled.
+
+    ``output_shape``: None (the 4x frames), or (Ho, Wo): every quantised SR frame is resized on the device by `resize.imresize`
+    (MATLAB `imresize`, out="int") before it is downloaded, so the result is `resize.imresize_host(frames without the keyword,
+    output_shape=..., out="int")` bit for bit and only (Ho, Wo) frames cross to the host.  Ho / 4H and Wo / 4W must lie in
+    [1/8, 8] (ValueError before any model pass).  Orthogonal to ``ensemble``, ``cuts`` and ``tile``: it acts on the final frames."""
+    from .resize import check_output_shape, imresize
     check_mode(ensemble)
     check_auto(cuts, lr.dtype)
     check_tile(tile, tile_overlap)
     N, C, H, W = lr.shape
+    shape = check_output_shape(output_shape, 4 * H, 4 * W)
+
+    def deliver(sr: torch.Tensor) -> np.ndarray:
+        """Quantised frames on the device -> host, through the resize when one was asked for."""
+        return frames_to_numpy(sr if shape is None else imresize(sr, output_shape=shape, out="int"))
     dev = next(model.parameters()).device
     centres = list(range(N)) if centres is None else list(centres)
     out: List[np.ndarray] = []
@@ -117,9 +133,9 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
         for s in range(0, len(centres), batch):
             idx = windows_for(centres[s:s + batch], num_frames, N, padding, cuts)
             if x.dtype in _INT_FRAMES:                                # quantised by the merge kernel
-                out.append(frames_to_numpy(ens.sequence(x, idx, dtype=x.dtype, quantise=quantise)))
+                out.append(deliver(ens.sequence(x, idx, dtype=x.dtype, quantise=quantise)))
             else:
-                out.append(_quantised(ens.sequence(x, idx), quantise))
+                out.append(deliver(_quantised_dev(ens.sequence(x, idx), quantise)))
         return np.concatenate(out, 0)
     x = _lr_frames(lr, dev)
     cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
@@ -127,9 +143,9 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
         idx = windows_for(centres[s:s + batch], num_frames, N, padding, cuts)
         win = _windows(x, idx)                                    # (b, 7, C, Hp, Wp)
         if win.dtype in _INT_FRAMES:                              # quantised by the model's last kernel
-            out.append(frames_to_numpy(super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]))
+            out.append(deliver(super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]))
         else:
-            out.append(_quantised(model(win)[:, :, :4 * H, :4 * W], quantise))   # the integer cast truncates
+            out.append(deliver(_quantised_dev(model(win)[:, :, :4 * H, :4 * W], quantise)))   # the integer cast truncates
     return np.concatenate(out, 0)
 
 
@@ -167,7 +183,7 @@ class SequenceScores:
 def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
                       ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None, brisque=None,
-                      cuts=None, cut_threshold: float = 10.0, tile=None, tile_overlap=16) -> SequenceScores:
+                      cuts=None, cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -199,28 +215,39 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     without the keyword).
 
     ``tile`` / ``tile_overlap`` as in `super_resolve_sequence`: the blended frame is scored in place of the model's; the bicubic
-    baseline does not depend on it."""
+    baseline does not depend on it.
+
+    ``output_shape``: None, or (Ho, Wo) as in `super_resolve_sequence`: hr is then (N,C,Ho,Wo); the SR frames are quantised on the
+    device, resized there (`resize.imresize`, out="int") and scored as integer frames; ``niqe``, ``brisque`` and their size checks
+    see (Ho, Wo), and ``return_frames`` gives the resized frames.  ``baseline="bicubic"`` becomes `resize.imresize` of the unpadded LR
+    centre frames straight to (Ho, Wo) - a true 3x bicubic row for 3x delivery -, out="int" for integer lr, f32 frames quantised by
+    the metric kernel for float lr.  Ho / 4H, Wo / 4W (and Ho / H, Wo / W with the baseline) must lie in [1/8, 8]."""
     from .device_metrics import frame_metrics
     from . import brisque as brisque_mod
     from . import niqe as niqe_mod
-    from .resize import bicubic_upscale
+    from .resize import bicubic_upscale, check_output_shape, imresize
     check_mode(ensemble)
     check_auto(cuts, lr.dtype)
     if baseline not in (None, "bicubic"):
         raise ValueError(f'baseline must be "bicubic" or None, got {baseline!r}')
     N, C, H, W = lr.shape
+    shape = check_output_shape(output_shape, 4 * H, 4 * W)
+    if shape is not None and baseline is not None:
+        check_output_shape(shape, H, W)
+    Ho, Wo = (4 * H, 4 * W) if shape is None else shape
     if niqe is not None:
         if hr.dtype == torch.uint16:
             raise ValueError("NIQE is defined on 8-bit frames: niqe= cannot be used with uint16 (10-bit) hr")
-        niqe_mod.crop_geometry(4 * H, 4 * W, 0)                      # ValueError up front when the SR frame holds < 2 blocks
+        niqe_mod.crop_geometry(Ho, Wo, 0)                            # ValueError up front when the SR frame holds < 2 blocks
     if brisque is not None:
         brisque = brisque_mod._check_model(brisque)
         if hr.dtype == torch.uint16:
             raise ValueError("BRISQUE is defined on 8-bit frames: brisque= cannot be used with uint16 (10-bit) hr")
-        brisque_mod._check_size(4 * H, 4 * W)
+        brisque_mod._check_size(Ho, Wo)
     niqe_y = "Y" if C == 3 else None
-    if tuple(hr.shape) != (N, C, 4 * H, 4 * W):
-        raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, 4 * H, 4 * W)}, got {tuple(hr.shape)}")
+    if tuple(hr.shape) != (N, C, Ho, Wo):
+        raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, Ho, Wo)}, got {tuple(hr.shape)}" if shape is None else
+                         f"hr must be (N,C,Ho,Wo) = {(N, C, Ho, Wo)}, got {tuple(hr.shape)}")
     if hr.dtype not in _INT_FRAMES:
         raise ValueError(f"hr must be uint8 or uint16, got {hr.dtype}")
     if lr.dtype in _INT_FRAMES and lr.dtype != hr.dtype:
@@ -243,7 +270,8 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
         if baseline is not None:
             lr_b = bits16(x)[s:s + len(idx), :, :H, :W].view(x.dtype)     # the unpadded centre frames
             as_int = x.dtype in _INT_FRAMES
-            up = bicubic_upscale(lr_b, 4, out="int" if as_int else "f32")
+            up = (bicubic_upscale(lr_b, 4, out="int" if as_int else "f32") if shape is None else
+                  imresize(lr_b, output_shape=shape, out="int" if as_int else "f32"))
             p, q = frame_metrics(up, hr_b, crop_border=crop_border, quantise=None if as_int else quantise, convert_to=convert_to)
             bp_dev.append(p)
             bs_dev.append(q)
@@ -251,9 +279,14 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
                 bn_dev.append(niqe_mod.frame_niqe_features(up, niqe, quantise=None if as_int else quantise, convert_to=niqe_y))
             if brisque is not None:
                 bq_dev.append(brisque_mod.frame_brisque_features(up, quantise=None if as_int else quantise, convert_to=niqe_y))
-        if x.dtype in _INT_FRAMES:
-            sr8 = (super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W] if ens is None else
-                   ens.sequence(x, idx, dtype=x.dtype, quantise=quantise))
+        if x.dtype in _INT_FRAMES or shape is not None:
+            if x.dtype in _INT_FRAMES:
+                sr8 = (super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W] if ens is None else
+                       ens.sequence(x, idx, dtype=x.dtype, quantise=quantise))
+            else:                                                     # float lr: quantised first, then resized
+                sr8 = _quantised_dev(model(win)[:, :, :4 * H, :4 * W] if ens is None else ens.sequence(x, idx), quantise, peak)
+            if shape is not None:
+                sr8 = imresize(sr8, output_shape=shape, out="int")
             p, q = frame_metrics(sr8, hr_b, crop_border=crop_border, quantise=None, convert_to=convert_to)
             p_dev.append(p)
             s_dev.append(q)

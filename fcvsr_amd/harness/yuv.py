@@ -177,7 +177,7 @@ def _niqe_stats(feats, niqe) -> dict:
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
                          quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
                          ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0,
-                         tile=None, tile_overlap=16) -> dict:
+                         tile=None, tile_overlap=16, output_shape=None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -195,7 +195,15 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     plane, on the device): every window then stays inside the shot of its centre frame (`shots.shot_window_indices`), and the list
     that was used is added to the stats as ``"cuts"``.  Chroma does not depend on it.  ``tile`` / ``tile_overlap`` as in
     `super_resolve_sequence` (`harness.tiles`): Y runs through the model in overlapping tiles, with ``ensemble`` every tile
-    ensembled; chroma is unchanged."""
+    ensembled; chroma is unchanged.
+
+    ``output_shape``: None, or (Ho, Wo), both even: the file is written at Wo x Ho in place of 4 width x 4 height.  The SR luma
+    frames are resized on the device by `resize.imresize` (MATLAB `imresize`, out="int") before they are downloaded, as in
+    `super_resolve_sequence`; U and V go ONCE from the LR chroma planes to (Ho/2, Wo/2) by the same function, in place of
+    ``hip.chroma_up4``.  Ho / (4 height), Wo / (4 width) must lie in [1/8, 8] and the chroma step Ho / height, Wo / width in
+    [1/8, 8] as well, so at most 2x beyond the 4x frame (ValueError before any model pass).  ``niqe`` / ``brisque`` score the 4x
+    luma the model made, as without the keyword.  ``"out_size"`` is (Wo, Ho)."""
+    shape = _check_output_shape_420(output_shape, width, height)
     check_mode(ensemble)
     check_auto(cuts, "uint8")
     _check_niqe(niqe, bit_depth, width, height)
@@ -235,7 +243,11 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
             if brisque is not None:
                 brisque_feats.append(brisque_mod.frame_brisque_features(ysr[:, None]))
             uv = to_dev(np.concatenate([u[s:e], v[s:e]], 0)).view(sdt)                    # (2b, H/2, W/2)
-            uvsr = hip.chroma_up4(uv)
+            if shape is None:
+                uvsr = hip.chroma_up4(uv)
+            else:                                                                         # resized on the device, then downloaded
+                ysr = hip.imresize(ysr, output_shape=shape, out="int")
+                uvsr = hip.imresize(uv, output_shape=(shape[0] // 2, shape[1] // 2), out="int")
             ysr, uvsr = hip.frames_to_numpy(ysr), hip.frames_to_numpy(uvsr)
             _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
             written += ysr.nbytes + uvsr.nbytes
@@ -243,14 +255,25 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     dt = time.perf_counter() - t0
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
-            "bytes_written": written, "out_size": (4 * W, 4 * H), **niqe_stats, **({} if cuts is None else {"cuts": cuts})}
+            "bytes_written": written, "out_size": (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), **niqe_stats,
+            **({} if cuts is None else {"cuts": cuts})}
+
+
+def _check_output_shape_420(output_shape, width: int, height: int, chroma: bool = True):
+    """The `output_shape=` of the SR entry points that write I420 files: None, or (Ho, Wo), both even, within [1/8, 8] of the 4x
+    frame and - where the LR chroma planes are resized straight to (Ho/2, Wo/2) - within [1/8, 8] of the LR frame."""
+    from .resize import check_output_shape
+    shape = check_output_shape(output_shape, 4 * height, 4 * width, even=True)
+    if shape is not None and chroma:
+        check_output_shape(shape, height, width)
+    return shape
 
 
 @torch.no_grad()
 def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int, *, colour: ColourSpec = ColourSpec(),
                              batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
                              ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None,
-                             cut_threshold: float = 10.0, tile=None, tile_overlap=16) -> dict:
+                             cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -266,7 +289,12 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     ``brisque`` as in `super_resolve_yuv420`: the YIQ luma of the SR RGB frames (BRISQUE's own "Y", not NIQE's) is scored before
     the encode; 8-bit only.  ``cuts`` / ``cut_threshold`` as in `super_resolve_yuv420`: "auto" detects on the luma plane of the file,
     before the colour conversion.  ``tile`` / ``tile_overlap`` as in `super_resolve_sequence` (`harness.tiles`): the decoded RGB
-    frames run through the model in overlapping tiles between the two colour conversions."""
+    frames run through the model in overlapping tiles between the two colour conversions.
+
+    ``output_shape``: None, or (Ho, Wo), both even, Ho / (4 height) and Wo / (4 width) in [1/8, 8]: the SR RGB frames are resized
+    plane by plane on the device (`resize.imresize`, out="int") before the encode, and the file is written at Wo x Ho.  ``niqe`` /
+    ``brisque`` score the 4x frames, as without the keyword."""
+    shape = _check_output_shape_420(output_shape, width, height, chroma=False)
     check_mode(ensemble)
     check_auto(cuts, "uint8")
     _check_niqe(niqe, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
@@ -305,6 +333,8 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
                 niqe_feats.append(frame_niqe_features(sr, niqe, convert_to="Y"))
             if brisque is not None:
                 brisque_feats.append(brisque_mod.frame_brisque_features(sr, convert_to="Y"))
+            if shape is not None:
+                sr = hip.imresize(sr, output_shape=shape, out="int")
             out = hip.frames_to_numpy(rgb_to_i420(sr, colour))                            # (b, 16 W H 3/2)
             fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())
             written += out.nbytes
@@ -312,20 +342,28 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     dt = time.perf_counter() - t0
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
-            "bytes_written": written, "out_size": (4 * W, 4 * H), **niqe_stats, **({} if cuts is None else {"cuts": cuts})}
+            "bytes_written": written, "out_size": (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), **niqe_stats,
+            **({} if cuts is None else {"cuts": cuts})}
 
 
 @torch.no_grad()
 def upscale_yuv420(src: str, dst: str, width: int, height: int, *, factor: int = 4, bit_depth: int = 8, batch: int = 8,
-                   device=None) -> dict:
+                   device=None, output_shape=None) -> dict:
     """Write the bicubic baseline of the I420 sequence `src` (width x height) into the I420 file `dst` (factor width x factor
     height), `factor` 2 or 4: Y, U and V all go through `resize.bicubic_upscale(out="int")`, the MATLAB-style `imresize` (clipped to
     [0, peak], rounded half to even), on the device (`device`, default the current HIP device).  No model is involved.  `bit_depth`
     is 8 or 10 for both files, as in `super_resolve_yuv420`; frames are uploaded in their integer dtype, `batch` at a time, and
-    written in order.  Returns the stats keys of `super_resolve_yuv420`.  No 10-bit output sample exceeds 1023."""
-    from .resize import bicubic_upscale
+    written in order.  Returns the stats keys of `super_resolve_yuv420`.  No 10-bit output sample exceeds 1023.
+
+    ``output_shape``: None, or (Ho, Wo), both even, Ho / height and Wo / width in [1/8, 8]: the file is written at Wo x Ho, Y through
+    `resize.imresize(output_shape=(Ho, Wo), out="int")` and U, V to (Ho/2, Wo/2) - the bicubic baseline of any delivery size, 3x
+    among them.  `factor` must then be left at its default (ValueError otherwise)."""
+    from .resize import bicubic_upscale, check_output_shape, imresize
     if factor not in (2, 4):
         raise ValueError(f"factor must be 2 or 4, got {factor!r}")
+    if output_shape is not None and factor != 4:
+        raise ValueError(f"output_shape and factor cannot both be given (factor={factor!r})")
+    shape = check_output_shape(output_shape, height, width, even=True)
     if batch < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
     y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
@@ -333,19 +371,21 @@ def upscale_yuv420(src: str, dst: str, width: int, height: int, *, factor: int =
     sdt, host_dt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.uint16, np.uint16)
     dev = torch.device("cuda" if device is None else device)
 
-    def up(a):
+    def up(a, div=1):
         """Planes of the file through the kernel and back; uint16 samples travel as int16 bits (hip.bits16)."""
         t = hip.bits16(torch.from_numpy(np.array(a, dtype=host_dt))).to(dev).view(sdt)    # a copy: the file map is read-only
+        if shape is not None:
+            return hip.frames_to_numpy(imresize(t, output_shape=(shape[0] // div, shape[1] // div), out="int"))
         return hip.frames_to_numpy(bicubic_upscale(t, factor, out="int"))
     t0 = time.perf_counter()
     written = 0
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             e = min(N, s + batch)
-            ysr, uvsr = up(y[s:e]), up(np.concatenate([u[s:e], v[s:e]], 0))              # (b, fH, fW), (2b, fH/2, fW/2)
+            ysr, uvsr = up(y[s:e]), up(np.concatenate([u[s:e], v[s:e]], 0), 2)           # (b, fH, fW), (2b, fH/2, fW/2)
             _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
             written += ysr.nbytes + uvsr.nbytes
     dt = time.perf_counter() - t0
     return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
             "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
-            "bytes_written": written, "out_size": (factor * W, factor * H)}
+            "bytes_written": written, "out_size": (factor * W, factor * H) if shape is None else (shape[1], shape[0])}

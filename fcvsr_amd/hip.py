@@ -237,6 +237,7 @@ SIGNATURES = {
                                _VP],
     "fcvsr_bicubic_downscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _VP],
     "fcvsr_bicubic_upscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _I, _VP],
+    "fcvsr_imresize": [_VP, _I, C.c_longlong, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _I, _VP],
     "fcvsr_frame_pair_sad": [_VP, _I, _I, C.c_longlong, _VP, C.c_longlong, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
@@ -574,7 +575,58 @@ def bicubic_upscale(x: torch.Tensor, factor: int, out: str = "f32") -> torch.Ten
     return res
 
 
-PAIR_SAD_TILE_BYTES = 1024          # FCVSR_PAIR_SAD_TILE_BYTES of include/fcvsr_hip.h: sizes the scratch of fcvsr_frame_pair_sad
+_RESIZE_TABLES = {}
+
+
+def resize_device_tables(n_in: int, n_out: int, scale: float, device):
+    """(weights f32 (n_out, P), first int32 (n_out,), P) of one axis of fcvsr_imresize on `device`: `harness.resize.resize_taps`,
+    uploaded once per (n_in, n_out, scale, device) and kept, so a sequence of frames of one size uploads nothing after its first
+    frame."""
+    key = (int(n_in), int(n_out), float(scale), str(torch.device(device)))
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        from .harness.resize import resize_taps
+        w, first = resize_taps(n_in, n_out, scale)
+        t = (torch.from_numpy(w).to(device), torch.from_numpy(first).to(device), int(w.shape[1]))
+        torch.cuda.synchronize(device)          # readers on any stream find them complete
+        _RESIZE_TABLES[key] = t
+    return t
+
+
+def imresize(x: torch.Tensor, scale=None, output_shape=None, out: str = "f32") -> torch.Tensor:
+    """fcvsr_imresize: x (..., H, W) uint8, uint16 (10-bit samples) or f32 on the HIP device -> (..., Ho, Wo), MATLAB `imresize`
+    at any size (`harness.resize.imresize_host` is the contract), one launch.  Exactly one of `scale` (output ceil(scale * n)) and
+    `output_shape` = (Ho, Wo); per-axis scales in [1/8, 8].  out="f32": the f32 sums on x's scale; out="int" (integer x only):
+    clipped to [0, peak], rounded half to even, in x's dtype.  Non-contiguous x is made dense first."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch tensor")
+    if not x.is_cuda:
+        raise RuntimeError("imresize runs on the HIP device only (there is no CPU fallback)")
+    if x.dtype not in (torch.uint8, torch.uint16, torch.float32):
+        raise ValueError(f"x must be uint8, uint16 or f32, got {x.dtype}")
+    if out not in ("f32", "int"):
+        raise ValueError(f'out must be "f32" or "int", got {out!r}')
+    if out == "int" and x.dtype == torch.float32:
+        raise ValueError('out="int" needs uint8 or uint16 input, got f32')
+    if x.dim() < 2:
+        raise ValueError(f"expected (..., H, W), got {tuple(x.shape)}")
+    from .harness.resize import resize_geometry
+    H, W = x.shape[-2:]
+    (Ho, Wo), (sy, sx), rows_first = resize_geometry(H, W, scale, output_shape)
+    odt = x.dtype if out == "int" else torch.float32
+    res = torch.empty((*x.shape[:-2], Ho, Wo), dtype=odt, device=x.device)
+    if res.numel():
+        src = bits16(x).contiguous()
+        wy, fy, Py = resize_device_tables(H, Ho, sy, x.device)
+        wx, fx, Px = resize_device_tables(W, Wo, sx, x.device)
+        with torch.cuda.device(x.device):
+            check(lib().fcvsr_imresize(src.data_ptr(), _DT[x.dtype], res.numel() // (Ho * Wo), H, W, Ho, Wo, wy.data_ptr(),
+                                       fy.data_ptr(), Py, wx.data_ptr(), fx.data_ptr(), Px, int(rows_first), bits16(res).data_ptr(),
+                                       _DT[odt], stream_ptr()), "fcvsr_imresize")
+    return res
+
+
+PAIR_SAD_TILE_BYTES = 1024         # FCVSR_PAIR_SAD_TILE_BYTES of include/fcvsr_hip.h: sizes the scratch of fcvsr_frame_pair_sad
 
 
 def frame_pair_sad(frames: torch.Tensor) -> torch.Tensor:

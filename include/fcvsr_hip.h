@@ -814,6 +814,20 @@ int fcvsr_bicubic_downscale(const void* src, int src_dtype, long long planes, in
  * planes < 1. */
 int fcvsr_bicubic_upscale(const void* src, int src_dtype, long long planes, int H, int W, int factor, void* out, int out_dtype,
                           void* stream);
+/* MATLABLikeResize at any output size (matlab_like_resize.py:72-250, scale= or output_shape=): `planes` dense H x W planes (src_dtype
+ * FCVSR_U8, FCVSR_U16 or FCVSR_F32; a uint16 sample above 1023 reads as 1023) into dense Ho x Wo planes, both passes in one launch.
+ * The taps come from two DEVICE tables per axis that the host makes (fcvsr_amd/harness/resize.py resize_tables): output o of the
+ * row axis reads the Py consecutive input rows firsty[o] .. firsty[o] + Py - 1, out-of-range indices reflected with edge repeat
+ * (period 2 H), with the f32 weights wy[o * Py + k]; wx (Wo, Px) and firstx (Wo) do the same for columns.  firsty / firstx do not
+ * decrease, and neighbouring outputs are at most 8 inputs apart (per-axis scale >= 1/8).  rows_first != 0: the row pass (dim 0)
+ * first, then the column pass; 0: columns first - the reference runs the axis with the smaller scale first, rows on a tie.  The
+ * reference's arithmetic and bits: the first pass reads the samples as f32, every product is an f32, products are added in tap
+ * order in f32 (no FMA), the intermediate is an f32.  out_dtype FCVSR_F32: the sums as they are; out_dtype = src_dtype for FCVSR_U8 /
+ * FCVSR_U16: clipped to [0, 255] / [0, 1023] and rounded half to even.  Scalar stores: src and out aligned to their sample size, the
+ * tables to 4 bytes.  FCVSR_E_ARG before any device call: a null pointer, a size < 1, Py or Px outside 1 .. 34, another dtype pair,
+ * Ho / H or Wo / W outside [1/8, 8], a misaligned pointer. */
+int fcvsr_imresize(const void* src, int src_dtype, long long planes, int H, int W, int Ho, int Wo, const float* wy, const int* firsty,
+                   int Py, const float* wx, const int* firstx, int Px, int rows_first, void* out, int out_dtype, void* stream);
 /* ---- scene-cut statistic (no counterpart in the reference, whose clips are single shots; the contract is
  * fcvsr_amd/harness/shots.py, pair_sad_host) ----------------------------------------------------------------------------------------
  * frames: N dense frames of `samples` samples each (samples = C H W, any value >= 1), elem_size 1 (uint8) or 2 (uint16, a sample
