@@ -239,6 +239,8 @@ SIGNATURES = {
     "fcvsr_bicubic_upscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _I, _VP],
     "fcvsr_imresize": [_VP, _I, C.c_longlong, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _I, _VP],
     "fcvsr_frame_pair_sad": [_VP, _I, _I, C.c_longlong, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_surface_unpack": [_VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],
+    "fcvsr_surface_pack": [_VP, _VP, _VP, C.c_longlong, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
@@ -721,6 +723,99 @@ def chroma_up4(planes: torch.Tensor) -> torch.Tensor:
                        (lib().fcvsr_chroma_up4_u16, "fcvsr_chroma_up4_u16", u16_table))
     with torch.cuda.device(planes.device):
         check(fn(src.data_ptr(), table(planes.device).data_ptr(), P, h, w, out.data_ptr(), stream_ptr()), name)
+    return out
+
+
+SURFACE_FMTS = {"yuv420p": 0, "yuv420p10le": 1, "nv12": 2, "p010le": 3}      # enum fcvsr_surface of include/fcvsr_hip.h
+
+
+def _surface_fmt(fmt):
+    """(enum value, sample dtype) of a surface format name; ValueError for anything else."""
+    if fmt not in SURFACE_FMTS:
+        raise ValueError(f"pix_fmt must be one of {tuple(SURFACE_FMTS)}, got {fmt!r}")
+    return SURFACE_FMTS[fmt], (torch.uint8 if fmt in ("yuv420p", "nv12") else torch.uint16)
+
+
+def _surface_planes(name: str, dt: torch.dtype, *tensors):
+    """The dtype and device checks of the two surface wrappers; int16 views of uint16 planes (`bits16`) are taken as uint16."""
+    for t in tensors:
+        ok = (torch.uint8,) if dt == torch.uint8 else (torch.uint16, torch.int16)
+        if not isinstance(t, torch.Tensor) or t.dtype not in ok:
+            raise ValueError(f"{name}: expected {dt} tensors, got {getattr(t, 'dtype', type(t))}")
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on the HIP device only (the host path is harness.surfaces)")
+        if t.device != tensors[0].device:
+            raise ValueError(f"{name}: tensors on {tensors[0].device} and {t.device}")
+
+
+def surface_unpack(raw: torch.Tensor, fmt: str, width: int, height: int, slots: torch.Tensor, ring_y: torch.Tensor,
+                   ring_u: torch.Tensor, ring_v: torch.Tensor) -> None:
+    """fcvsr_surface_unpack: `raw`, a dense uint8 tensor on the HIP device holding n whole `width` x `height` frames of `fmt` as they
+    were read, is taken apart into plane rings (`harness.surfaces.unpack_host` is the contract): the luma of frame i goes to slot
+    ``slots[i]`` of `ring_y` (R,1,Hp,Wp) - Hp >= height, Wp >= width; the rows and columns beyond the frame are never written -, U
+    and V to the same slot of `ring_u` / `ring_v` (R,height/2,width/2).  `slots`: n int32 on the device, distinct, each in
+    [0, R) (a number outside the ring writes nothing).  The rings are contiguous uint8 (yuv420p, nv12) or uint16 (yuv420p10le,
+    p010le) tensors.  One launch on the current stream, no host sync."""
+    code, dt = _surface_fmt(fmt)
+    if width <= 0 or height <= 0 or width % 2 or height % 2:
+        raise ValueError(f"4:2:0 frames need an even, positive width and height, got {width}x{height}")
+    if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint8 or not raw.is_contiguous():
+        raise ValueError(f"raw: expected a contiguous uint8 tensor, got {getattr(raw, 'dtype', type(raw))}")
+    if not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or slots.dim() != 1 or not slots.is_contiguous():
+        raise ValueError(f"slots: expected a contiguous 1-D int32 tensor, got {getattr(slots, 'dtype', type(slots))}")
+    _surface_planes("surface_unpack", dt, ring_y, ring_u, ring_v)
+    if not raw.is_cuda or not slots.is_cuda:
+        raise RuntimeError("surface_unpack runs on the HIP device only (the host path is harness.surfaces.unpack_host)")
+    if raw.device != ring_y.device or slots.device != ring_y.device:
+        raise ValueError(f"surface_unpack: raw on {raw.device}, slots on {slots.device}, rings on {ring_y.device}")
+    n, fb = slots.numel(), width * height * 3 // 2 * (1 if dt == torch.uint8 else 2)
+    if raw.numel() != n * fb:
+        raise ValueError(f"raw holds {raw.numel()} bytes, {n} {width}x{height} {fmt} frames are {n * fb}")
+    if ring_y.dim() != 4 or ring_y.shape[1] != 1 or ring_y.shape[2] < height or ring_y.shape[3] < width:
+        raise ValueError(f"ring_y must be (R,1,Hp,Wp) with Hp >= {height}, Wp >= {width}, got {tuple(ring_y.shape)}")
+    R, _, Hp, Wp = ring_y.shape
+    for name, t in (("ring_u", ring_u), ("ring_v", ring_v)):
+        if tuple(t.shape) != (R, height // 2, width // 2):
+            raise ValueError(f"{name} must be (R,H/2,W/2) = {(R, height // 2, width // 2)}, got {tuple(t.shape)}")
+    if R < 1 or not all(t.is_contiguous() for t in (ring_y, ring_u, ring_v)):
+        raise ValueError("the rings must be contiguous and hold at least one slot")
+    if n == 0:
+        return
+    with torch.cuda.device(raw.device):
+        check(lib().fcvsr_surface_unpack(raw.data_ptr(), code, n, height, width, slots.data_ptr(), R, Hp, Wp, ring_y.data_ptr(),
+                                         ring_u.data_ptr(), ring_v.data_ptr(), stream_ptr()), "fcvsr_surface_unpack")
+
+
+def _dense_frames(t: torch.Tensor) -> torch.Tensor:
+    """`t` (b,h,w) if its frames are dense (any frame stride: a plane of a batch of I420 frames), else a dense copy."""
+    b, h, w = t.shape
+    if t.stride(2) == 1 and t.stride(1) == w and (b == 1 or t.stride(0) >= h * w):
+        return t
+    return bits16(t).contiguous().view(t.dtype)
+
+
+def surface_pack(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, fmt: str) -> torch.Tensor:
+    """fcvsr_surface_pack: y (b,H,W), u and v (b,H/2,W/2) uint8 (yuv420p, nv12) or uint16 (yuv420p10le, p010le) planes on the HIP
+    device -> a dense uint8 (b, frame bytes) buffer in the layout of `fmt`, equal to `harness.surfaces.pack_host`: one copy to
+    the host and one ``write`` deliver the batch.  Planes whose frames are dense are read where they lie at any frame stride (three
+    tensors, slices of one, or the planes `harness.colour.i420_planes` gives).  One launch on the current stream."""
+    code, dt = _surface_fmt(fmt)
+    _surface_planes("surface_pack", dt, y, u, v)
+    if y.dim() != 3 or u.dim() != 3 or u.shape != v.shape:
+        raise ValueError(f"expected Y (b,H,W), U and V (b,H/2,W/2), got {tuple(y.shape)}, {tuple(u.shape)}, {tuple(v.shape)}")
+    b, H, W = y.shape
+    if W <= 0 or H <= 0 or W % 2 or H % 2:
+        raise ValueError(f"4:2:0 frames need an even, positive width and height, got {W}x{H}")
+    if tuple(u.shape) != (b, H // 2, W // 2):
+        raise ValueError(f"chroma planes must be (b,H/2,W/2) = {(b, H // 2, W // 2)}, got {tuple(u.shape)}")
+    out = torch.empty((b, W * H * 3 // 2 * (1 if dt == torch.uint8 else 2)), dtype=torch.uint8, device=y.device)
+    if b == 0:
+        return out
+    y, u, v = _dense_frames(y), _dense_frames(u), _dense_frames(v)
+    with torch.cuda.device(y.device):
+        check(lib().fcvsr_surface_pack(y.data_ptr(), u.data_ptr(), v.data_ptr(), y.stride(0), u.stride(0), v.stride(0), code, b, H,
+                                       W, out.data_ptr(), stream_ptr()), "fcvsr_surface_pack")
     return out
 
 

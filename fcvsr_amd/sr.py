@@ -1,0 +1,86 @@
+"""``python -m fcvsr_amd.sr``: raw 4:2:0 video in, 4x super-resolved raw video out, through pipes or files.
+
+    ffmpeg -i in.mp4 -f rawvideo -pix_fmt nv12 - | \\
+        python -m fcvsr_amd.sr --model FCVSR_SNet --weights fcvsr_s.pth --size 480x270 --pix-fmt nv12 - - | \\
+        ffmpeg -f rawvideo -pix_fmt nv12 -s 1920x1080 -r 24 -i - out.mkv
+
+Nothing but the model and `harness.stream.stream_yuv420` (its docstring says what every option means); the stats go to stderr as
+one JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+
+MODELS = ("GShiftNet_S", "GShiftNet", "FCVSR_SNet", "FCVSRNet")
+PIX_FMTS = ("yuv420p", "yuv420p10le", "nv12", "p010le")                   # harness.surfaces.PIX_FMTS (that module needs numpy)
+
+
+def _size(text: str):
+    try:
+        w, h = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected WxH, got {text!r}")
+    return w, h
+
+
+def _cuts(text: str):
+    return "auto" if text == "auto" else [int(v) for v in text.split(",") if v]
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m fcvsr_amd.sr", description="4x video super-resolution of raw YUV 4:2:0, "
+                                "streamed: SRC and DST are files, or - for stdin / stdout.")
+    p.add_argument("--model", choices=MODELS, required=True)
+    p.add_argument("--weights", required=True, metavar="W.pth", help="the model's state dict (torch.load, weights only)")
+    p.add_argument("--size", type=_size, required=True, metavar="WxH", help="size of the source frames")
+    p.add_argument("--pix-fmt", choices=PIX_FMTS, default="yuv420p")
+    p.add_argument("--out-pix-fmt", choices=PIX_FMTS, default=None, help="default: --pix-fmt (same bit depth)")
+    p.add_argument("--batch", type=int, default=8)
+    p.add_argument("--padding", default="replicate", choices=("replicate", "reflection", "reflection_circle", "circle"))
+    p.add_argument("--quantise", default="truncate", choices=("truncate", "round"))
+    p.add_argument("--ensemble", default=None, choices=("spatial", "spatial+temporal"))
+    p.add_argument("--tile", type=_size, default=None, metavar="WxH", help="run the model on overlapping tiles of this size")
+    p.add_argument("--tile-overlap", type=int, default=16)
+    p.add_argument("--cuts", type=_cuts, default=None, metavar="auto|N,N,...", help="scene cuts: detect them, or frame numbers")
+    p.add_argument("--cut-threshold", type=float, default=10.0)
+    p.add_argument("--output-size", type=_size, default=None, metavar="WxH", help="deliver this size in place of 4x")
+    p.add_argument("--matrix", default="bt709", choices=("bt601", "bt709"), help="RGB models: the stream's matrix")
+    p.add_argument("--full-range", action="store_true", help="RGB models: full-range code values")
+    p.add_argument("--chroma-loc", default="left", choices=("left", "center"), help="RGB models: chroma siting")
+    p.add_argument("--max-frames", type=int, default=None)
+    p.add_argument("--device", default="cuda")
+    p.add_argument("src", metavar="SRC")
+    p.add_argument("dst", metavar="DST")
+    return p
+
+
+def main(argv=None) -> int:
+    a = parser().parse_args(argv)
+    import torch
+
+    from .arch import CVSR_freq, fcvsr_rgb
+    from .harness.colour import ColourSpec
+    from .harness.stream import stream_yuv420
+    model = getattr(fcvsr_rgb if a.model.startswith("FCVSR") else CVSR_freq, a.model)()
+    sd = torch.load(a.weights, map_location="cpu", weights_only=True)
+    sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+    model.load_state_dict({k[len("generator."):] if k.startswith("generator.") else k: v for k, v in sd.items()})
+    model = model.to(a.device)
+    bits = 10 if a.pix_fmt in ("yuv420p10le", "p010le") else 8
+    stats = stream_yuv420(model, sys.stdin.buffer if a.src == "-" else a.src, sys.stdout.buffer if a.dst == "-" else a.dst,
+                          a.size[0], a.size[1], pix_fmt=a.pix_fmt, out_pix_fmt=a.out_pix_fmt,
+                          colour=ColourSpec(a.matrix, a.full_range, a.chroma_loc, bits), batch=a.batch, padding=a.padding,
+                          quantise=a.quantise, ensemble=a.ensemble, tile=None if a.tile is None else (a.tile[1], a.tile[0]),
+                          tile_overlap=a.tile_overlap, cuts=a.cuts, cut_threshold=a.cut_threshold,
+                          output_shape=None if a.output_size is None else (a.output_size[1], a.output_size[0]),
+                          max_frames=a.max_frames)
+    if a.dst == "-":
+        sys.stdout.buffer.flush()
+    print(json.dumps({k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in stats.items()}), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

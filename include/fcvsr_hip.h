@@ -838,6 +838,26 @@ int fcvsr_imresize(const void* src, int src_dtype, long long planes, int H, int 
 #define FCVSR_PAIR_SAD_TILE_BYTES 1024
 int fcvsr_frame_pair_sad(const void* frames, int elem_size, int N, long long samples, void* scratch, long long scratch_bytes,
                          long long* out, void* stream);
+/* ---- raw 4:2:0 surfaces <-> plane rings: the two ends of the streamed YUV path (no counterpart in the reference; the contract is
+ * fcvsr_amd/harness/surfaces.py, unpack_host / pack_host) -------------------------------------------------------------------------
+ * The formats carry ffmpeg's names: planar I420 in 8 bits and in little-endian 16-bit words (10-bit value in the low bits), NV12
+ * (Y plane, then H/2 rows of W bytes U0 V0 U1 V1 ...) and P010 (the NV12 layout in 16-bit words, the 10-bit value in the HIGH bits:
+ * word = value << 6; the low six bits are ignored on the way in and zero on the way out).  A frame is H W 3/2 samples, H and W even.
+ *
+ * fcvsr_surface_unpack: raw holds n frames back to back as they were read (aligned to the sample size, nothing more); slots n
+ * DEVICE ints.  The luma of frame i goes to slot slots[i] of ring_y, R slots of Hp x Wp samples (Hp >= H, Wp >= W: the rows and
+ * columns beyond H, W are never written), U and V to the same slot of ring_u / ring_v, R slots of H/2 x W/2 samples.  Planar 16-bit
+ * samples pass through unchanged, values above 1023 included.  A slot number outside [0, R) writes nothing; two frames of one call
+ * must not share a slot.
+ * fcvsr_surface_pack: y (b,H,W), u and v (b,H/2,W/2), dense planes whose frames are y_stride / u_stride / v_stride SAMPLES apart
+ * (three tensors, or the planes of a batch of I420 frames) -> out, b dense frames of the format's layout.
+ * One launch each on `stream`, no host sync; neither reads or writes outside a frame.  FCVSR_E_ARG before any device call: an
+ * unknown format, an odd or non-positive size, more than 65535 frames, a null or misaligned pointer, a ring smaller than a frame. */
+enum fcvsr_surface { FCVSR_SURFACE_YUV420P = 0, FCVSR_SURFACE_YUV420P10LE = 1, FCVSR_SURFACE_NV12 = 2, FCVSR_SURFACE_P010LE = 3 };
+int fcvsr_surface_unpack(const void* raw, int fmt, int n, int H, int W, const int* slots, int R, int Hp, int Wp, void* ring_y,
+                         void* ring_u, void* ring_v, void* stream);
+int fcvsr_surface_pack(const void* y, const void* u, const void* v, long long y_stride, long long u_stride, long long v_stride,
+                       int fmt, int b, int H, int W, void* out, void* stream);
 #ifdef __cplusplus
 }
 #endif
