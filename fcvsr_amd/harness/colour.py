@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from .surfaces import _check_size
 
 MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 CHROMA_LOCS = {"left": hip.CHROMA_LEFT, "center": hip.CHROMA_CENTER}
@@ -91,11 +92,6 @@ def coefficients(spec: ColourSpec) -> Dict[str, int]:
     return c
 
 
-def _check_size(H: int, W: int):
-    if H <= 0 or W <= 0 or H % 2 or W % 2:
-        raise ValueError(f"4:2:0 frames need an even, positive width and height, got {W}x{H}")
-
-
 def _host_planes(spec: ColourSpec, *arrays):
     out = []
     for a in arrays:
@@ -129,7 +125,7 @@ def yuv420_to_rgb_host(y, u, v, spec: ColourSpec = ColourSpec()) -> np.ndarray:
     if y.ndim != 3 or u.ndim != 3 or u.shape != v.shape:
         raise ValueError(f"expected Y (N,H,W), U and V (N,H/2,W/2), got {y.shape}, {u.shape}, {v.shape}")
     N, H, W = y.shape
-    _check_size(H, W)
+    _check_size(W, H)
     if u.shape != (N, H // 2, W // 2):
         raise ValueError(f"chroma planes must be (N,H/2,W/2) = {(N, H // 2, W // 2)}, got {u.shape}")
     k, P = coefficients(spec), spec.peak
@@ -146,7 +142,7 @@ def rgb_to_yuv420_host(rgb, spec: ColourSpec = ColourSpec()) -> Tuple[np.ndarray
     if rgb.ndim != 4 or rgb.shape[1] != 3:
         raise ValueError(f"expected (N,3,H,W) frames, got {rgb.shape}")
     N, _, H, W = rgb.shape
-    _check_size(H, W)
+    _check_size(W, H)
     k, P = coefficients(spec), spec.peak
     dt = np.uint8 if spec.bit_depth == 8 else np.uint16
     R, G, B = rgb[:, 0], rgb[:, 1], rgb[:, 2]
@@ -191,7 +187,7 @@ def _frame_strided(t: torch.Tensor) -> torch.Tensor:
 
 
 def i420_frame_samples(H: int, W: int) -> int:
-    _check_size(H, W)
+    _check_size(W, H)
     return H * W * 3 // 2
 
 
@@ -213,7 +209,7 @@ def yuv420_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, spec: Colou
     if y.dim() != 3 or u.dim() != 3 or u.shape != v.shape:
         raise ValueError(f"expected Y (N,H,W), U and V (N,H/2,W/2), got {tuple(y.shape)}, {tuple(u.shape)}, {tuple(v.shape)}")
     N, H, W = y.shape
-    _check_size(H, W)
+    _check_size(W, H)
     if tuple(u.shape) != (N, H // 2, W // 2):
         raise ValueError(f"chroma planes must be (N,H/2,W/2) = {(N, H // 2, W // 2)}, got {tuple(u.shape)}")
     rgb = torch.empty((N, 3, H, W), dtype=spec.dtype, device=y.device)

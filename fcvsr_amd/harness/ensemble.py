@@ -40,6 +40,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from .steps import Resolver
 
 MODES = (None, "spatial", "spatial+temporal")
 
@@ -120,13 +121,13 @@ def ensemble_host(win: torch.Tensor, fn: Callable, temporal: bool = False, multi
     return out
 
 
-class SelfEnsemble:
+class SelfEnsemble(Resolver):
     """x8 (x16 with ``temporal``) self-ensemble around a model of this package; see the module docstring for the semantics.
 
     ``ens = SelfEnsemble(model)``; ``ens(win)`` takes a (B,T,C,H,W) f32, uint8 or uint16 window on the model's device (any H, W:
     the variants are padded to multiples of 4 inside) and returns the f32 (B,C,4H,4W) mean; `super_resolve_u8` /
     `super_resolve_u16` return it quantised as ``model.super_resolve_u8`` / ``_u16`` quantise; `sequence` takes the resident
-    sequence and window index rows instead of windows."""
+    sequence and window index rows instead of windows (`steps.Resolver`)."""
 
     def __init__(self, model, temporal: bool = False):
         self.model, self.temporal = model, bool(temporal)
@@ -139,16 +140,8 @@ class SelfEnsemble:
         (`harness.windows.window_indices`).  Returns (b,C,4h,4w): the f32 mean, or - `dtype` uint8 / uint16 with `quantise` - its
         quantised frames.  The model always runs without autograd (with gradients enabled its ``forward`` is the training graph),
         through its float ``forward``, on the two batches of 4b windows the gather kernel made."""
-        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
-            raise ValueError(f"expected (N,C,h,w) frames, got {tuple(getattr(frames, 'shape', ()))}")
-        if not frames.is_cuda:
-            raise RuntimeError("SelfEnsemble runs on the HIP device only (there is no CPU fallback)")
-        if dtype in (torch.uint8, torch.uint16) and quantise not in hip.QUANTISE:
-            raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
-        rows = [[int(j) for j in r] for r in idx]
-        N, _, h, w = frames.shape
-        if not rows or any(len(r) != len(rows[0]) or not r for r in rows) or any(not 0 <= j < N for r in rows for j in r):
-            raise ValueError(f"idx: rows of equal length with frame numbers in 0..{N - 1}, got {rows}")
+        rows = self._rows(frames, idx, dtype, quantise)
+        h, w = frames.shape[-2:]
         if frames.dtype not in (torch.uint8, torch.uint16):
             frames = frames.float()
         table = torch.tensor(rows, dtype=torch.int32).to(frames.device)
@@ -158,28 +151,6 @@ class SelfEnsemble:
             outs += [self.model(v.flatten(0, 1)).unflatten(0, (4, len(rows))) for v in (va, vt)]
         return hip.ensemble_merge(outs[0], outs[1], h, w, ra=outs[2] if self.temporal else None,
                                   rat=outs[3] if self.temporal else None, dtype=dtype, quantise=quantise)
-
-    def _window(self, win: torch.Tensor, **kw) -> torch.Tensor:
-        if not isinstance(win, torch.Tensor) or win.dim() != 5:
-            raise ValueError(f"expected a (B,T,C,H,W) window, got {tuple(getattr(win, 'shape', ()))}")
-        B, T = win.shape[:2]
-        frames = hip.bits16(win).reshape(B * T, *win.shape[2:]).view(win.dtype)
-        return self.sequence(frames, np.arange(B * T).reshape(B, T).tolist(), **kw)
-
-    def __call__(self, win: torch.Tensor) -> torch.Tensor:
-        return self._window(win)
-
-    def super_resolve_u8(self, win: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
-        """uint8 (B,T,C,H,W) window -> uint8 (B,C,4H,4W): ``q(clamp(self(win), 0, 1) * 255)``, q as ``model.super_resolve_u8``."""
-        if not isinstance(win, torch.Tensor) or win.dtype != torch.uint8:
-            raise ValueError(f"expected a uint8 tensor, got {getattr(win, 'dtype', type(win))}")
-        return self._window(win, dtype=torch.uint8, quantise=quantise)
-
-    def super_resolve_u16(self, win: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
-        """uint16 (B,T,C,H,W) window of 10-bit samples -> uint16 (B,C,4H,4W) in [0, 1023], as ``model.super_resolve_u16``."""
-        if not isinstance(win, torch.Tensor) or win.dtype != torch.uint16:
-            raise ValueError(f"expected a uint16 tensor, got {getattr(win, 'dtype', type(win))}")
-        return self._window(win, dtype=torch.uint16, quantise=quantise)
 
 
 def for_mode(model, ensemble: Optional[str]) -> Optional[SelfEnsemble]:

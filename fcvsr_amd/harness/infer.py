@@ -21,58 +21,27 @@ import numpy as np
 import torch
 
 from ..hip import bits16, frames_to_numpy
-from .ensemble import check_mode
 from .metrics import psnr
-from .shots import check_auto, cuts_from_sad, device_pair_sad, resolve_cuts, shot_ranges, windows_for
-from .tiles import check_tile, resolver_for
-
-
-def pad_to_multiple(frames: torch.Tensor, mult: int = 4) -> torch.Tensor:
-    """(N,C,H,W) -> zero-padded at the bottom/right so that H, W are multiples of `mult`."""
-    H, W = frames.shape[-2:]
-    ph, pw = (-H) % mult, (-W) % mult
-    if ph == 0 and pw == 0:
-        return frames
-    return torch.nn.functional.pad(frames, (0, pw, 0, ph))
-
-
-_INT_FRAMES = (torch.uint8, torch.uint16)
+from .shots import cuts_from_sad, device_pair_sad, resolve_cuts, shot_ranges, windows_for
+from .steps import INT_FRAMES as _INT_FRAMES
+from .steps import ScoreCollector, check_keywords, check_scores, pad_to_multiple, run_window, super_resolve_int  # noqa: F401
 
 
 def _int_kind(t: torch.Tensor):
     return t.dtype if t.dtype in _INT_FRAMES else None
 
 
-def _lr_frames(lr: torch.Tensor, dev) -> torch.Tensor:
-    """The padded LR sequence on the device: uint8 / uint16 frames keep their dtype (the model's integer paths), anything else
-    becomes f32."""
-    if lr.dtype in _INT_FRAMES:
-        return pad_to_multiple(bits16(lr), 4).to(dev).view(lr.dtype)
-    return pad_to_multiple(lr.float(), 4).to(dev)
-
-
-def _lr_frames_dense(lr: torch.Tensor, dev) -> torch.Tensor:
-    """The UNPADDED LR sequence on the device (the self-ensemble pads every variant itself), dtypes as `_lr_frames`."""
-    if lr.dtype in _INT_FRAMES:
-        return bits16(lr).to(dev).contiguous().view(lr.dtype)
-    return lr.float().to(dev).contiguous()
+def _lr_frames(lr: torch.Tensor, dev, multiple: int) -> torch.Tensor:
+    """The resident LR sequence of a resolver (`steps.Resolver.multiple`) on the device, dense, zero-padded on the host before the
+    one upload: uint8 / uint16 frames keep their dtype (the integer paths), anything else becomes f32."""
+    x = bits16(lr) if lr.dtype in _INT_FRAMES else lr.float()
+    return pad_to_multiple(x, multiple).to(dev).contiguous().view(lr.dtype if lr.dtype in _INT_FRAMES else torch.float32)
 
 
 def _auto_cuts(x: torch.Tensor, count: int, threshold: float):
     """`shots.detect_cuts` of the resident integer sequence x on the device.  x may carry the zero padding of `_lr_frames`, which adds
     nothing to the sums: `count` is C*H*W of the unpadded frames."""
     return lambda: cuts_from_sad(device_pair_sad(x), count, 8 if x.dtype == torch.uint8 else 10, threshold)
-
-
-def _windows(x: torch.Tensor, idx) -> torch.Tensor:
-    """(b, T, C, Hp, Wp) windows of the device sequence x, in x's dtype."""
-    xb = bits16(x)
-    return torch.stack([xb[j] for j in idx], 0).view(x.dtype)
-
-
-def super_resolve_int(model, win: torch.Tensor, quantise: str) -> torch.Tensor:
-    """The model's integer path for a uint8 or uint16 window."""
-    return model.super_resolve_u16(win, quantise) if win.dtype == torch.uint16 else model.super_resolve_u8(win, quantise)
 
 
 def _quantised_dev(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> torch.Tensor:
@@ -114,38 +83,21 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
     output_shape=..., out="int")` bit for bit and only (Ho, Wo) frames cross to the host.  Ho / 4H and Wo / 4W must lie in
     [1/8, 8] (ValueError before any model pass).  Orthogonal to ``ensemble``, ``cuts`` and ``tile``: it acts on the final frames."""
     from .resize import check_output_shape, imresize
-    check_mode(ensemble)
-    check_auto(cuts, lr.dtype)
-    check_tile(tile, tile_overlap)
+    resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
+                              cuts=cuts, frame_dtype=lr.dtype)
     N, C, H, W = lr.shape
     shape = check_output_shape(output_shape, 4 * H, 4 * W)
-
-    def deliver(sr: torch.Tensor) -> np.ndarray:
-        """Quantised frames on the device -> host, through the resize when one was asked for."""
-        return frames_to_numpy(sr if shape is None else imresize(sr, output_shape=shape, out="int"))
     dev = next(model.parameters()).device
     centres = list(range(N)) if centres is None else list(centres)
-    out: List[np.ndarray] = []
-    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
-    if ens is not None:
-        x = _lr_frames_dense(lr, dev)
-        cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
-        for s in range(0, len(centres), batch):
-            idx = windows_for(centres[s:s + batch], num_frames, N, padding, cuts)
-            if x.dtype in _INT_FRAMES:                                # quantised by the merge kernel
-                out.append(deliver(ens.sequence(x, idx, dtype=x.dtype, quantise=quantise)))
-            else:
-                out.append(deliver(_quantised_dev(ens.sequence(x, idx), quantise)))
-        return np.concatenate(out, 0)
-    x = _lr_frames(lr, dev)
+    x = _lr_frames(lr, dev, resolver.multiple)
     cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
+    out: List[np.ndarray] = []
     for s in range(0, len(centres), batch):
         idx = windows_for(centres[s:s + batch], num_frames, N, padding, cuts)
-        win = _windows(x, idx)                                    # (b, 7, C, Hp, Wp)
-        if win.dtype in _INT_FRAMES:                              # quantised by the model's last kernel
-            out.append(deliver(super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]))
-        else:
-            out.append(deliver(_quantised_dev(model(win)[:, :, :4 * H, :4 * W], quantise)))   # the integer cast truncates
+        sr = resolver.frames(x, idx, quantise, H, W)                  # integer frames: quantised by the last / the merge kernel
+        if sr.dtype not in _INT_FRAMES:
+            sr = _quantised_dev(sr, quantise)                         # the integer cast truncates
+        out.append(frames_to_numpy(sr if shape is None else imresize(sr, output_shape=shape, out="int")))
     return np.concatenate(out, 0)
 
 
@@ -223,11 +175,9 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     centre frames straight to (Ho, Wo) - a true 3x bicubic row for 3x delivery -, out="int" for integer lr, f32 frames quantised by
     the metric kernel for float lr.  Ho / 4H, Wo / 4W (and Ho / H, Wo / W with the baseline) must lie in [1/8, 8]."""
     from .device_metrics import frame_metrics
-    from . import brisque as brisque_mod
-    from . import niqe as niqe_mod
     from .resize import bicubic_upscale, check_output_shape, imresize
-    check_mode(ensemble)
-    check_auto(cuts, lr.dtype)
+    resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
+                              cuts=cuts, frame_dtype=lr.dtype)
     if baseline not in (None, "bicubic"):
         raise ValueError(f'baseline must be "bicubic" or None, got {baseline!r}')
     N, C, H, W = lr.shape
@@ -235,16 +185,7 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     if shape is not None and baseline is not None:
         check_output_shape(shape, H, W)
     Ho, Wo = (4 * H, 4 * W) if shape is None else shape
-    if niqe is not None:
-        if hr.dtype == torch.uint16:
-            raise ValueError("NIQE is defined on 8-bit frames: niqe= cannot be used with uint16 (10-bit) hr")
-        niqe_mod.crop_geometry(Ho, Wo, 0)                            # ValueError up front when the SR frame holds < 2 blocks
-    if brisque is not None:
-        brisque = brisque_mod._check_model(brisque)
-        if hr.dtype == torch.uint16:
-            raise ValueError("BRISQUE is defined on 8-bit frames: brisque= cannot be used with uint16 (10-bit) hr")
-        brisque_mod._check_size(Ho, Wo)
-    niqe_y = "Y" if C == 3 else None
+    brisque = check_scores(niqe, brisque, 10 if hr.dtype == torch.uint16 else 8, Ho, Wo)     # ValueError up front
     if tuple(hr.shape) != (N, C, Ho, Wo):
         raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, Ho, Wo)}, got {tuple(hr.shape)}" if shape is None else
                          f"hr must be (N,C,Ho,Wo) = {(N, C, Ho, Wo)}, got {tuple(hr.shape)}")
@@ -253,79 +194,50 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     if lr.dtype in _INT_FRAMES and lr.dtype != hr.dtype:
         raise ValueError(f"{lr.dtype} lr needs {lr.dtype} hr, got {hr.dtype}")
     peak = 255.0 if hr.dtype == torch.uint8 else 1023.0
-    if quantise not in ("truncate", "round"):
-        raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
-    check_tile(tile, tile_overlap)
     dev = next(model.parameters()).device
-    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
-    x = _lr_frames(lr, dev) if ens is None else _lr_frames_dense(lr, dev)
+    x = _lr_frames(lr, dev, resolver.multiple)
     cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
-    p_dev, s_dev, n_dev, frames = [], [], [], []                  # per-batch device results, fetched once at the end
-    bp_dev, bs_dev, bn_dev = [], [], []                           # the same for the bicubic baseline
-    q_dev, bq_dev = [], []                                        # BRISQUE features of the SR frames and of the baseline
+
+    def scorer(keep: bool):
+        """(score, result) of one row of the table.  score(f, hr_b, q): a batch of frames against its HR frames - q None for integer
+        frames, else the rule f32 frames are quantised by in the kernels; everything stays on the device.  result(): the row's
+        `SequenceScores` entries, fetched once, and the frames that were kept."""
+        col, p_dev, s_dev, kept = ScoreCollector(niqe, brisque, "Y" if C == 3 else None), [], [], []
+
+        def score(f, hr_b, q):
+            p, s = frame_metrics(f, hr_b, crop_border=crop_border, quantise=q, convert_to=convert_to)
+            p_dev.append(p)
+            s_dev.append(s)
+            col.add(col.features(f, q))
+            if keep:
+                kept.append(frames_to_numpy(f) if q is None else _quantised(f, q, peak))
+
+        def result():
+            p, s = torch.cat(p_dev).cpu().numpy(), torch.cat(s_dev).cpu().numpy()
+            return {"psnr": p, "ssim": s, "psnr_mean": float(np.mean(p)), "ssim_mean": float(np.mean(s)), **col.stats()}, kept
+        return score, result
+    score_sr, result_sr = scorer(return_frames)
+    score_base, result_base = scorer(False)
+    fq = None if x.dtype in _INT_FRAMES else quantise                # f32 frames are quantised where they are scored
     for s in range(0, N, batch):
         idx = windows_for(range(s, min(N, s + batch)), num_frames, N, padding, cuts)
-        win = _windows(x, idx) if ens is None else None           # (b, 7, C, Hp, Wp)
         hr_b = bits16(hr[s:s + len(idx)]).to(dev).view(hr.dtype)
         if baseline is not None:
             lr_b = bits16(x)[s:s + len(idx), :, :H, :W].view(x.dtype)     # the unpadded centre frames
-            as_int = x.dtype in _INT_FRAMES
-            up = (bicubic_upscale(lr_b, 4, out="int" if as_int else "f32") if shape is None else
-                  imresize(lr_b, output_shape=shape, out="int" if as_int else "f32"))
-            p, q = frame_metrics(up, hr_b, crop_border=crop_border, quantise=None if as_int else quantise, convert_to=convert_to)
-            bp_dev.append(p)
-            bs_dev.append(q)
-            if niqe is not None:
-                bn_dev.append(niqe_mod.frame_niqe_features(up, niqe, quantise=None if as_int else quantise, convert_to=niqe_y))
-            if brisque is not None:
-                bq_dev.append(brisque_mod.frame_brisque_features(up, quantise=None if as_int else quantise, convert_to=niqe_y))
-        if x.dtype in _INT_FRAMES or shape is not None:
-            if x.dtype in _INT_FRAMES:
-                sr8 = (super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W] if ens is None else
-                       ens.sequence(x, idx, dtype=x.dtype, quantise=quantise))
-            else:                                                     # float lr: quantised first, then resized
-                sr8 = _quantised_dev(model(win)[:, :, :4 * H, :4 * W] if ens is None else ens.sequence(x, idx), quantise, peak)
-            if shape is not None:
-                sr8 = imresize(sr8, output_shape=shape, out="int")
-            p, q = frame_metrics(sr8, hr_b, crop_border=crop_border, quantise=None, convert_to=convert_to)
-            p_dev.append(p)
-            s_dev.append(q)
-            if niqe is not None:
-                n_dev.append(niqe_mod.frame_niqe_features(sr8, niqe, convert_to=niqe_y))
-            if brisque is not None:
-                q_dev.append(brisque_mod.frame_brisque_features(sr8, convert_to=niqe_y))
-            if return_frames:
-                frames.append(frames_to_numpy(sr8))
-            continue
-        sr = model(win)[:, :, :4 * H, :4 * W] if ens is None else ens.sequence(x, idx)
-        p, q = frame_metrics(sr, hr_b, crop_border=crop_border, quantise=quantise, convert_to=convert_to)
-        p_dev.append(p)
-        s_dev.append(q)
-        if niqe is not None:
-            n_dev.append(niqe_mod.frame_niqe_features(sr, niqe, quantise=quantise, convert_to=niqe_y))
-        if brisque is not None:
-            q_dev.append(brisque_mod.frame_brisque_features(sr, quantise=quantise, convert_to=niqe_y))
-        if return_frames:
-            frames.append(_quantised(sr, quantise, peak))
-    psnr_np, ssim_np = torch.cat(p_dev).cpu().numpy(), torch.cat(s_dev).cpu().numpy()
-    niqe_np = niqe_mod.scores_from_features(torch.cat(n_dev).cpu().numpy(), niqe) if niqe is not None else None
-    scores = SequenceScores(psnr_np, ssim_np, float(np.mean(psnr_np)), float(np.mean(ssim_np)),
-                            np.concatenate(frames, 0) if return_frames else None, niqe_np,
-                            float(np.mean(niqe_np)) if niqe is not None else None)
+            out = "int" if fq is None else "f32"
+            score_base(bicubic_upscale(lr_b, 4, out=out) if shape is None else imresize(lr_b, output_shape=shape, out=out), hr_b, fq)
+        sr, q = resolver.frames(x, idx, quantise, H, W), fq
+        if shape is not None:                                         # float lr: quantised first, then resized
+            sr, q = imresize(sr if q is None else _quantised_dev(sr, q, peak), output_shape=shape, out="int"), None
+        score_sr(sr, hr_b, q)
+    row, frames = result_sr()
+    scores = SequenceScores(row.pop("psnr"), row.pop("ssim"), row.pop("psnr_mean"), row.pop("ssim_mean"),
+                            np.concatenate(frames, 0) if return_frames else None, row.pop("niqe", None), row.pop("niqe_mean", None))
+    vars(scores).update(row)                                          # brisque, brisque_mean: plain attributes
     if cuts is not None:
         scores.cuts = cuts
-    if brisque is not None:
-        scores.brisque = brisque_mod.scores_from_features(torch.cat(q_dev).cpu().numpy(), brisque)
-        scores.brisque_mean = float(np.mean(scores.brisque))
     if baseline is not None:
-        scores.baseline_psnr, scores.baseline_ssim = torch.cat(bp_dev).cpu().numpy(), torch.cat(bs_dev).cpu().numpy()
-        scores.baseline_psnr_mean, scores.baseline_ssim_mean = float(np.mean(scores.baseline_psnr)), float(np.mean(scores.baseline_ssim))
-        if niqe is not None:
-            scores.baseline_niqe = niqe_mod.scores_from_features(torch.cat(bn_dev).cpu().numpy(), niqe)
-            scores.baseline_niqe_mean = float(np.mean(scores.baseline_niqe))
-        if brisque is not None:
-            scores.baseline_brisque = brisque_mod.scores_from_features(torch.cat(bq_dev).cpu().numpy(), brisque)
-            scores.baseline_brisque_mean = float(np.mean(scores.baseline_brisque))
+        vars(scores).update({"baseline_" + k: v for k, v in result_base()[0].items()})
     return scores
 
 
@@ -497,14 +409,10 @@ class StreamedSuperResolver:
                     ready[(bi + 1) & 1].synchronize()                     # staging buffers of batch bi-1 have been consumed
                 fill(bi + 1)                                              # host work + upload overlap the model call below
             n = len(items)
-            if idt is not None:                                       # quantised by the model's last kernel
-                sr = super_resolve_int(self.model, win.view(idt), self.quantise)[:, :, :4 * H, :4 * W]
-                out_host[pos:pos + n].copy_(bits16(sr[:n]), non_blocking=on_gpu)
-            else:
-                sr = self.model(win)[:, :, :4 * H, :4 * W]
-                sr = sr.clamp(0, 1) * 255.0
-                sr = sr.round() if self.quantise == "round" else sr
-                out_host[pos:pos + n].copy_(sr[:n].to(torch.uint8), non_blocking=on_gpu)
+            sr = run_window(self.model, win if idt is None else win.view(idt), self.quantise)[:n, :, :4 * H, :4 * W]
+            if idt is None:                                           # integer frames: quantised by the model's last kernel
+                sr = _quantised_dev(sr, self.quantise)
+            out_host[pos:pos + n].copy_(bits16(sr), non_blocking=on_gpu)
             pos += n
         if on_gpu:
             torch.cuda.synchronize(self.device)

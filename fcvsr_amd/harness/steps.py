@@ -1,0 +1,219 @@
+"""The steps every harness entry point shares, each written once: `check_keywords` (the keyword prologue; it returns the resolver),
+`Resolver` (what a batch of windows runs through: `PlainResolver` here, `ensemble.SelfEnsemble`, `tiles.TiledSuperResolver`),
+`check_scores` / `ScoreCollector` (``niqe=`` / ``brisque=``), `deliver_luma` / `deliver_rgb` (SR frames to the planes a file holds)
+and `run_stats`.  `harness.infer`, `harness.yuv` and `harness.stream` are loops around them; a new keyword goes into the step it
+belongs to, not into the loops.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import hip
+from . import brisque as brisque_mod
+from . import niqe as niqe_mod
+from .shots import check_auto
+
+INT_FRAMES = (torch.uint8, torch.uint16)
+
+
+def pad_to_multiple(frames: torch.Tensor, mult: int = 4) -> torch.Tensor:
+    """(N,C,H,W) -> zero-padded at the bottom/right so that H, W are multiples of `mult`."""
+    H, W = frames.shape[-2:]
+    ph, pw = (-H) % mult, (-W) % mult
+    if ph == 0 and pw == 0:
+        return frames
+    return torch.nn.functional.pad(frames, (0, pw, 0, ph))
+
+
+def to_device(a, bit_depth: int, dev) -> torch.Tensor:
+    """Samples of a file (any array of them; a copy is made, a file map is read-only) on the device as uint8 / uint16: uint16
+    samples travel as int16 bits (`hip.bits16`)."""
+    host_dt, sdt = (np.uint8, torch.uint8) if bit_depth == 8 else (np.uint16, torch.uint16)
+    return hip.bits16(torch.from_numpy(np.array(a, dtype=host_dt))).to(dev).view(sdt)
+
+
+# ---- resolvers -----------------------------------------------------------------------------------------------------------------
+
+class Resolver:
+    """What the harness runs a batch of windows through.  The contract is ``sequence(frames, idx, *, dtype=torch.float32,
+    quantise=None)``: `frames` the resident sequence (N,C,h,w) on the model's device - f32 in [0,1], uint8 or uint16 (10-bit
+    samples), zero-padded once at the bottom / right to a multiple of `multiple` (`pad_to_multiple`) -, `idx` b rows of T frame
+    numbers; it returns (b,C,>=4h,>=4w): f32, or - `dtype` uint8 / uint16 with `quantise` - quantised as
+    ``model.super_resolve_u8`` / ``_u16`` quantise.  `frames` is the group step of the entry points around it; the window forms
+    (`__call__`, `super_resolve_u8`, `super_resolve_u16`) are for direct users."""
+    multiple = 1
+
+    def frames(self, x: torch.Tensor, idx, quantise: str, H: int, W: int) -> torch.Tensor:
+        """One group of windows of the resident x, cropped (a view) to the 4H x 4W of the unpadded frame: integer x gives quantised
+        frames of its dtype, float x the f32 frames (the caller quantises them: `infer._quantised_dev`, or the metric kernels)."""
+        sr = self.sequence(x, idx, dtype=x.dtype, quantise=quantise) if x.dtype in INT_FRAMES else self.sequence(x, idx)
+        return sr[..., :4 * H, :4 * W]
+
+    def _rows(self, frames, idx, dtype, quantise):
+        """The `frames` / `idx` / `quantise` checks of the resolvers that run kernels on them; the index rows as lists."""
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+            raise ValueError(f"expected (N,C,h,w) frames, got {tuple(getattr(frames, 'shape', ()))}")
+        if not frames.is_cuda:
+            raise RuntimeError(f"{type(self).__name__} runs on the HIP device only (there is no CPU fallback)")
+        if dtype in INT_FRAMES and quantise not in hip.QUANTISE:
+            raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+        rows = [[int(j) for j in r] for r in idx]
+        N = frames.shape[0]
+        if not rows or any(len(r) != len(rows[0]) or not r for r in rows) or any(not 0 <= j < N for r in rows for j in r):
+            raise ValueError(f"idx: rows of equal length with frame numbers in 0..{N - 1}, got {rows}")
+        return rows
+
+    def _window(self, win: torch.Tensor, **kw) -> torch.Tensor:
+        if not isinstance(win, torch.Tensor) or win.dim() != 5:
+            raise ValueError(f"expected a (B,T,C,H,W) window, got {tuple(getattr(win, 'shape', ()))}")
+        B, T = win.shape[:2]
+        frames = hip.bits16(win).reshape(B * T, *win.shape[2:]).view(win.dtype)
+        return self.sequence(frames, np.arange(B * T).reshape(B, T).tolist(), **kw)
+
+    def __call__(self, win: torch.Tensor, **kw) -> torch.Tensor:
+        return self._window(win, **kw)
+
+    def super_resolve_u8(self, win: torch.Tensor, quantise: str = "truncate", **kw) -> torch.Tensor:
+        """uint8 (B,T,C,H,W) window -> uint8 (B,C,4H,4W): ``q(clamp(self(win), 0, 1) * 255)``, q as ``model.super_resolve_u8``."""
+        if not isinstance(win, torch.Tensor) or win.dtype != torch.uint8:
+            raise ValueError(f"expected a uint8 tensor, got {getattr(win, 'dtype', type(win))}")
+        return self._window(win, dtype=torch.uint8, quantise=quantise, **kw)
+
+    def super_resolve_u16(self, win: torch.Tensor, quantise: str = "truncate", **kw) -> torch.Tensor:
+        """uint16 (B,T,C,H,W) window of 10-bit samples -> uint16 (B,C,4H,4W) in [0, 1023], as ``model.super_resolve_u16``."""
+        if not isinstance(win, torch.Tensor) or win.dtype != torch.uint16:
+            raise ValueError(f"expected a uint16 tensor, got {getattr(win, 'dtype', type(win))}")
+        return self._window(win, dtype=torch.uint16, quantise=quantise, **kw)
+
+
+def super_resolve_int(model, win: torch.Tensor, quantise: str) -> torch.Tensor:
+    """The model's integer path for a uint8 or uint16 window."""
+    return model.super_resolve_u16(win, quantise) if win.dtype == torch.uint16 else model.super_resolve_u8(win, quantise)
+
+
+def run_window(model, win: torch.Tensor, quantise: Optional[str] = None) -> torch.Tensor:
+    """The model on a (b,T,C,Hp,Wp) window that exists: integer windows take its integer path (quantised by the last kernel), float
+    windows its ``forward``."""
+    return super_resolve_int(model, win, quantise) if win.dtype in INT_FRAMES else model(win)
+
+
+class PlainResolver(Resolver):
+    """The model itself: whole frames, one pass.  The resident frames carry the zero padding to a multiple of 4 (the reference
+    pads 270 -> 272), so a window is a stack of rows and nothing is padded per batch; the output keeps the padding (4x), which
+    `Resolver.frames` crops by view.  Integer frames take ``model.super_resolve_u8`` / ``_u16`` - the last kernel quantises -, float
+    frames ``model(win)``; it runs wherever the model runs.  Index rows are used as ``x[j]`` uses them: a number below 0 counts from
+    the end (a sequence shorter than its window)."""
+    multiple = 4
+
+    def __init__(self, model):
+        self.model = model
+
+    def sequence(self, frames: torch.Tensor, idx: Sequence[Sequence[int]], *, dtype: torch.dtype = torch.float32,
+                 quantise: Optional[str] = None) -> torch.Tensor:
+        xb = hip.bits16(frames)                                                   # no checks: negative numbers are meant
+        return run_window(self.model, torch.stack([xb[j] for j in idx], 0).view(frames.dtype), quantise)   # (b, T, C, Hp, Wp)
+
+    def _window(self, win: torch.Tensor, dtype=None, quantise: Optional[str] = None) -> torch.Tensor:
+        return run_window(self.model, win, quantise)
+
+
+# ---- the keyword prologue ------------------------------------------------------------------------------------------------------
+
+_CHANNELS = {1: "one-channel (Y)", 3: "three-channel (RGB)"}
+
+
+def check_keywords(model, *, ensemble, tile, tile_overlap, batch, quantise, cuts, frame_dtype, channels=None, who="") -> Resolver:
+    """What every entry point validates before any device or file work - ``ensemble``, ``cuts`` ("auto" needs integer frames:
+    `frame_dtype`), the model's channel count where the entry point `who` needs one of `channels`, ``quantise``, ``batch``,
+    ``tile`` / ``tile_overlap`` - and the resolver of these values (`tiles.resolver_for`).  ValueError names the keyword."""
+    from .ensemble import check_mode
+    from .tiles import resolver_for
+    check_mode(ensemble)
+    check_auto(cuts, frame_dtype)
+    if channels is not None and getattr(model, "_img_ch", None) not in channels:
+        raise ValueError(f"{who} needs a {' or '.join(_CHANNELS[c] for c in channels)} model, got C={getattr(model, '_img_ch', None)}")
+    if quantise not in hip.QUANTISE:
+        raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    return resolver_for(model, ensemble, tile, tile_overlap, batch)
+
+
+def check_scores(niqe, brisque, bit_depth: int, height: int, width: int):
+    """The ``niqe=`` / ``brisque=`` keywords against the bit depth of the run and the height x width of the scored frames, before
+    anything is read: both scores are 8-bit only, NIQE needs >= 2 blocks, BRISQUE a `BrisqueModel` and even sides >= 16.  Returns
+    the validated BRISQUE model (None for None)."""
+    if niqe is not None:
+        if bit_depth != 8:
+            raise ValueError("NIQE is defined on 8-bit frames: niqe= cannot be used with 10-bit (uint16) frames")
+        niqe_mod.crop_geometry(height, width, 0)
+    if brisque is not None:
+        brisque = brisque_mod._check_model(brisque)
+        if bit_depth != 8:
+            raise ValueError("BRISQUE is defined on 8-bit frames: brisque= cannot be used with 10-bit (uint16) frames")
+        brisque_mod._check_size(height, width)
+    return brisque
+
+
+# ---- scores --------------------------------------------------------------------------------------------------------------------
+
+class ScoreCollector:
+    """The no-reference scores of a run: `features` computes a batch's NIQE / BRISQUE feature tensors on the device (no host
+    sync), `add` holds what it is given - the device tensors, or their host copies where the caller downloads per group -, and
+    `stats` turns all of it into the scores, one download and one ``scores_from_features`` per score."""
+
+    def __init__(self, niqe=None, brisque=None, convert_to: Optional[str] = None):
+        self.niqe, self.brisque, self.convert_to = niqe, brisque, convert_to
+        self.held = []
+
+    def features(self, frames: torch.Tensor, quantise: Optional[str] = None):
+        """(NIQE features, BRISQUE features) of (b,C,H,W) frames, None for a score that was not asked for.  `quantise`: None for
+        integer frames, the rule of the run for f32 frames (quantised in the kernels)."""
+        kw = dict(quantise=quantise, convert_to=self.convert_to)
+        return (None if self.niqe is None else niqe_mod.frame_niqe_features(frames, self.niqe, **kw),
+                None if self.brisque is None else brisque_mod.frame_brisque_features(frames, **kw))
+
+    def add(self, feats) -> None:
+        self.held.append(feats)
+
+    def stats(self) -> dict:
+        """{"niqe", "niqe_mean", "brisque", "brisque_mean"}: per-frame f64 scores and their means; absent scores, absent keys."""
+        out = {}
+        for k, (name, mod, model) in enumerate((("niqe", niqe_mod, self.niqe), ("brisque", brisque_mod, self.brisque))):
+            if model is not None:
+                f = [h[k] for h in self.held]
+                f = torch.cat(f).cpu().numpy() if isinstance(f[0], torch.Tensor) else np.concatenate(f, 0)
+                out[name] = mod.scores_from_features(f, model)
+                out[name + "_mean"] = float(np.mean(out[name]))
+        return out
+
+
+# ---- delivery ------------------------------------------------------------------------------------------------------------------
+
+def deliver_luma(ysr: torch.Tensor, uv: torch.Tensor, shape):
+    """The Y path's planes as they are written: `ysr` (b,4H,4W) SR luma and `uv` (2b,H/2,W/2) LR chroma, U planes then V planes ->
+    (Y (b,Ho,Wo), U then V (2b,Ho/2,Wo/2)).  `shape` None: the 4x frame, chroma by ``hip.chroma_up4``; (Ho, Wo): luma resized from
+    the 4x frame and chroma ONCE from the LR planes, by `hip.imresize`."""
+    if shape is None:
+        return ysr, hip.chroma_up4(uv)
+    return (hip.imresize(ysr, output_shape=shape, out="int"),
+            hip.imresize(uv, output_shape=(shape[0] // 2, shape[1] // 2), out="int"))
+
+
+def deliver_rgb(sr: torch.Tensor, colour, shape) -> torch.Tensor:
+    """The RGB path's frames as they are written: (b,3,4H,4W) SR frames -> (b, Ho*Wo*3/2) I420 frames, resized plane by plane
+    before the encode when `shape` = (Ho, Wo) is given."""
+    from .colour import rgb_to_i420
+    if shape is not None:
+        sr = hip.imresize(sr, output_shape=shape, out="int")
+    return rgb_to_i420(sr, colour)
+
+
+def run_stats(frames: int, seconds: float, bytes_read: int, bytes_written: int, out_size, scores=(), cuts=None) -> dict:
+    """The stats every file / stream entry point returns: `out_size` is (width, height); `scores` (`ScoreCollector.stats`) and
+    ``"cuts"`` are there when the keywords were."""
+    return {"frames": frames, "seconds": seconds, "fps": frames / seconds if seconds > 0 else float("inf"), "bytes_read": bytes_read,
+            "bytes_written": bytes_written, "out_size": out_size, **dict(scores), **({} if cuts is None else {"cuts": cuts})}

@@ -3,8 +3,8 @@ device) and the entry point `stream_yuv420` around it.
 
 `harness.yuv.super_resolve_yuv420*` map a whole file and upload every frame before the first model pass; here the frames arrive in
 chunks of at most `batch`, are taken apart on the device into a ring of frame slots (`hip.surface_unpack`), and leave as soon as
-their window is complete.  Everything the harness runs on a ``(frames, idx)`` pair - the plain stack of ``x[j]``, `SelfEnsemble`,
-`TiledSuperResolver` - takes the ring as `frames` and rows of slot numbers as `idx`, unchanged.
+their window is complete.  Every resolver (`steps.Resolver`: `PlainResolver`, `SelfEnsemble`,
+`TiledSuperResolver`) takes the ring as `frames` and rows of slot numbers as `idx`, unchanged.
 
 The windows are those of the finished stream, ``shots.windows_for(range(N), num_frames, N, padding, cuts)``, although N is not known
 while they are made.  Before the end a centre c is released when frame ``c + num_frames // 2`` has arrived (`window_indices` then no
@@ -216,14 +216,10 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     import torch
 
     from .. import hip
-    from . import brisque as brisque_mod
     from . import surfaces
-    from .colour import i420_planes, rgb_to_i420, yuv420_to_rgb
-    from .ensemble import check_mode
-    from .infer import super_resolve_int
-    from .niqe import frame_niqe_features, scores_from_features
-    from .tiles import check_tile, resolver_for
-    from .yuv import _check_brisque, _check_niqe, _check_output_shape_420
+    from .colour import i420_planes, yuv420_to_rgb
+    from .steps import ScoreCollector, check_keywords, check_scores, deliver_luma, deliver_rgb, run_stats
+    from .yuv import _check_output_shape_420
 
     surfaces.check_fmt(pix_fmt)
     out_pix_fmt = pix_fmt if out_pix_fmt is None else surfaces.check_fmt(out_pix_fmt)
@@ -234,24 +230,18 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     W, H = int(width), int(height)
     fb_in = surfaces.frame_bytes(pix_fmt, W, H)
     C = getattr(model, "_img_ch", None)
-    if C not in (1, 3):
-        raise ValueError(f"stream_yuv420 needs a one-channel (Y) or three-channel (RGB) model, got C={C}")
     if C == 3:
         if not isinstance(colour, ColourSpec):
             raise ValueError(f"colour must be a ColourSpec, got {type(colour).__name__}")
         if colour.bit_depth != bits:
             raise ValueError(f"colour is {colour.bit_depth}-bit, pix_fmt {pix_fmt!r} {bits}-bit")
     shape = _check_output_shape_420(output_shape, W, H, chroma=C == 1)
-    check_mode(ensemble)
-    _check_niqe(niqe, bits, W, H)
-    brisque = _check_brisque(brisque, bits, W, H)
-    if quantise not in hip.QUANTISE:
-        raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+    brisque = check_scores(niqe, brisque, bits, 4 * H, 4 * W)
+    resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
+                              cuts=cuts, frame_dtype="uint8", channels=(1, 3), who="stream_yuv420")
     if max_frames is not None and max_frames < 0:
         raise ValueError(f"max_frames must be >= 0, got {max_frames}")
-    check_tile(tile, tile_overlap)
     plan = StreamPlan(num_frames, padding, batch, cuts)
-    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("stream_yuv420 runs on the HIP device only (there is no CPU fallback)")
@@ -260,7 +250,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     sdt, bdt = (torch.uint8, torch.uint8) if bits == 8 else (torch.uint16, torch.int16)       # frames travel as `hip.bits16`
     B, T, h2, w2 = plan.batch, plan.num_frames, H // 2, W // 2
     R = 2 * B + 2 * (T - 1)
-    Hp, Wp = (H + (-H) % 4, W + (-W) % 4) if ens is None else (H, W)     # the padding `pad_to_multiple` adds; zero for ever
+    Hp, Wp = (n + (-n) % resolver.multiple for n in (H, W))              # the padding `pad_to_multiple` adds; zero for ever
     auto = AutoCuts(H * W, bits, cut_threshold) if plan.auto else None
 
     with contextlib.ExitStack() as stack, torch.no_grad(), torch.cuda.device(dev):
@@ -287,7 +277,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
         where, resident, free = {}, deque(), list(range(R - 1, -1, -1))   # frame -> slot; resident frames in order; free slots
         prev_y = None                                                     # RGB path, cuts="auto": the luma of the last frame
         written, groups_run, pending, last_up = 0, 0, None, 0
-        niqe_feats, brisque_feats = [], []
+        scores = ScoreCollector(niqe, brisque, None if C == 1 else "Y")
 
         def upload(k: int, n: int, first: int) -> None:
             """Chunk k = frames first .. first + n - 1, staged in stage[k & 1]: into free slots on the side stream."""
@@ -333,30 +323,17 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
             main.wait_event(uploaded[last_up & 1])                         # the side stream is in order: every chunk so far
             # a frame number below 0 (a sequence shorter than the window, after its end) counts from the end, as ``x[j]`` does
             idx = [[where[f if f >= 0 else plan.frames + f] for f in row] for row in rows]
-            if ens is None:
-                win = torch.stack([ring[j] for j in idx], 0).view(sdt)                    # (b, T, C, Hp, Wp)
-                sr = super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]
-            else:
-                sr = ens.sequence(ring.view(sdt), idx, dtype=sdt, quantise=quantise)
+            sr = resolver.frames(ring.view(sdt), idx, quantise, H, W)
             if C == 1:
                 cs = torch.tensor([where[c] for c in centres], dtype=torch.int64).to(dev)
                 uv = torch.cat([ring_u[cs], ring_v[cs]], 0).view(sdt)                      # (2b, H/2, W/2)
             gathered.record(main)
-            feats = (frame_niqe_features(sr, niqe, **({} if C == 1 else {"convert_to": "Y"})) if niqe is not None else None,
-                     brisque_mod.frame_brisque_features(sr, **({} if C == 1 else {"convert_to": "Y"})) if brisque is not None
-                     else None)
+            feats = scores.features(sr)
             if C == 1:
-                ysr = sr[:, 0]
-                if shape is None:
-                    uvsr = hip.chroma_up4(uv)
-                else:
-                    ysr = hip.imresize(ysr, output_shape=shape, out="int")
-                    uvsr = hip.imresize(uv, output_shape=(shape[0] // 2, shape[1] // 2), out="int")
+                ysr, uvsr = deliver_luma(sr[:, 0], uv, shape)
                 planes = (ysr, uvsr[:b], uvsr[b:])
             else:
-                if shape is not None:
-                    sr = hip.imresize(sr, output_shape=shape, out="int")
-                planes = i420_planes(rgb_to_i420(sr, colour), Ho, Wo)
+                planes = i420_planes(deliver_rgb(sr, colour, shape), Ho, Wo)
             out_pin[g & 1][:b].copy_(hip.surface_pack(*planes, out_pix_fmt), non_blocking=True)
             done[g & 1].record(main)
             groups_run += 1
@@ -369,10 +346,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
             done[g & 1].synchronize()
             _write_all(fout, memoryview(out_pin[g & 1][:b].numpy()).cast("B"))
             written += b * fb_out
-            if feats[0] is not None:
-                niqe_feats.append(feats[0].cpu().numpy())
-            if feats[1] is not None:
-                brisque_feats.append(feats[1].cpu().numpy())
+            scores.add(tuple(f if f is None else f.cpu().numpy() for f in feats))      # after `done`: it waits for nothing newer
 
         k, stray, eof = 0, 0, False
         while not eof:
@@ -404,15 +378,6 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     if stray:
         raise ValueError(f"the stream ends with {stray} stray bytes after {N} whole {W}x{H} {pix_fmt} frames ({fb_in} bytes each)")
     used = plan.finish()                                                  # ValueError: an explicit cut at or beyond the end
-    stats = {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"), "bytes_read": N * fb_in,
-             "bytes_written": written, "out_size": (Wo, Ho)}
-    if niqe is not None:
-        scores = scores_from_features(np.concatenate(niqe_feats, 0), niqe)
-        stats.update(niqe=scores, niqe_mean=float(np.mean(scores)))
-    if brisque is not None:
-        scores = brisque_mod.scores_from_features(np.concatenate(brisque_feats, 0), brisque)
-        stats.update(brisque=scores, brisque_mean=float(np.mean(scores)))
-    if used is not None:
-        stats["cuts"] = used
+    stats = run_stats(N, dt, N * fb_in, written, (Wo, Ho), scores.stats(), used)
     stats.update(ring_frames=R, frames_uploaded=N, h2d_bytes=N * fb_in, d2h_bytes=written)
     return stats

@@ -63,6 +63,7 @@ import torch
 
 from .. import hip
 from .ensemble import SelfEnsemble, check_mode
+from .steps import PlainResolver, Resolver
 
 SCALE = 4
 
@@ -226,21 +227,22 @@ def tiled_host(win: torch.Tensor, fn: Callable, plan: TilePlan, idx: Optional[Se
     return blend_host(torch.stack(rows, 1), plan)
 
 
-class TiledSuperResolver:
+class TiledSuperResolver(Resolver):
     """Tiled inference around a model of this package; see the module docstring for the semantics.
 
-    ``tsr = TiledSuperResolver(model, tile, tile_overlap=16, ensemble=None)``; ``tsr(win)`` takes a (B,T,C,H,W) f32, uint8 or uint16
-    window on the model's device (any H, W) and returns the f32 (B,C,4H,4W) blend; `super_resolve_u8` / `super_resolve_u16` return
-    it quantised as ``model.super_resolve_u8`` / ``_u16`` quantise; `sequence` takes the resident sequence and window index rows
-    instead of windows, as `SelfEnsemble.sequence` does.  ``ensemble``: None, "spatial" or "spatial+temporal" - every tile window
-    then goes through the `SelfEnsemble` of the model."""
+    ``tsr = TiledSuperResolver(model, tile, tile_overlap=16, ensemble=None, batch=8)``; ``tsr(win)`` takes a (B,T,C,H,W) f32, uint8
+    or uint16 window on the model's device (any H, W) and returns the f32 (B,C,4H,4W) blend; `super_resolve_u8` /
+    `super_resolve_u16` return it quantised as ``model.super_resolve_u8`` / ``_u16`` quantise; `sequence` takes the resident
+    sequence and window index rows instead of windows (`steps.Resolver`).  ``ensemble``: None, "spatial" or "spatial+temporal" -
+    every tile window then goes through the `SelfEnsemble` of the model.  ``batch``: the most tile windows of one model pass; every
+    call takes ``batch=`` to override it."""
 
-    def __init__(self, model, tile, tile_overlap=16, ensemble: Optional[str] = None):
+    def __init__(self, model, tile, tile_overlap=16, ensemble: Optional[str] = None, batch: int = 8):
         chk = check_tile(tile, tile_overlap)
         if chk is None:
             raise ValueError("TiledSuperResolver needs a tile size, got tile=None")
         self.tile, self.tile_overlap = chk
-        self.model = model
+        self.model, self.batch = model, batch
         self.ensemble = check_mode(ensemble)
         self._fn = model if ensemble is None else SelfEnsemble(model, temporal=ensemble == "spatial+temporal")
 
@@ -249,24 +251,17 @@ class TiledSuperResolver:
 
     @torch.no_grad()
     def sequence(self, frames: torch.Tensor, idx: Sequence[Sequence[int]], *, dtype: torch.dtype = torch.float32,
-                 quantise: Optional[str] = None, batch: int = 8) -> torch.Tensor:
+                 quantise: Optional[str] = None, batch: Optional[int] = None) -> torch.Tensor:
         """`frames`: the dense UNPADDED sequence (N,C,h,w) on the model's device, f32 in [0,1], uint8, or uint16 (10-bit samples;
         integer samples enter as the floats of ``hip.u8_table`` / ``hip.u16_table``).  `idx`: b rows of T frame numbers
         (`harness.windows.window_indices`).  Returns (b,C,4h,4w): the f32 blend, or - `dtype` uint8 / uint16 with `quantise` - its
         quantised frames.  The ``b * ny * nx`` tile windows go through the model's float ``forward`` (or its `SelfEnsemble`),
-        without autograd, in chunks of at most `batch` windows."""
-        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
-            raise ValueError(f"expected (N,C,h,w) frames, got {tuple(getattr(frames, 'shape', ()))}")
-        if not frames.is_cuda:
-            raise RuntimeError("TiledSuperResolver runs on the HIP device only (there is no CPU fallback)")
-        if dtype in (torch.uint8, torch.uint16) and quantise not in hip.QUANTISE:
-            raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
+        without autograd, in chunks of at most `batch` windows (default: the constructor's)."""
+        rows = self._rows(frames, idx, dtype, quantise)
+        batch = self.batch if batch is None else batch
         if batch < 1:
             raise ValueError(f"batch must be >= 1, got {batch}")
-        rows = [[int(j) for j in r] for r in idx]
-        N, C, h, w = frames.shape
-        if not rows or any(len(r) != len(rows[0]) or not r for r in rows) or any(not 0 <= j < N for r in rows for j in r):
-            raise ValueError(f"idx: rows of equal length with frame numbers in 0..{N - 1}, got {rows}")
+        C, h, w = frames.shape[1:]
         if frames.dtype not in (torch.uint8, torch.uint16):
             frames = frames.float()
         plan = self.plan(h, w)
@@ -278,47 +273,13 @@ class TiledSuperResolver:
             outs[s:s + batch] = self._fn(wins[s:s + batch])
         return hip.tile_merge(outs.unflatten(0, (len(rows), plan.ny, plan.nx)), plan, h, w, dtype=dtype, quantise=quantise)
 
-    def _window(self, win: torch.Tensor, **kw) -> torch.Tensor:
-        if not isinstance(win, torch.Tensor) or win.dim() != 5:
-            raise ValueError(f"expected a (B,T,C,H,W) window, got {tuple(getattr(win, 'shape', ()))}")
-        B, T = win.shape[:2]
-        frames = hip.bits16(win).reshape(B * T, *win.shape[2:]).view(win.dtype)
-        return self.sequence(frames, np.arange(B * T).reshape(B, T).tolist(), **kw)
 
-    def __call__(self, win: torch.Tensor, batch: int = 8) -> torch.Tensor:
-        return self._window(win, batch=batch)
-
-    def super_resolve_u8(self, win: torch.Tensor, quantise: str = "truncate", batch: int = 8) -> torch.Tensor:
-        """uint8 (B,T,C,H,W) window -> uint8 (B,C,4H,4W): ``q(clamp(self(win), 0, 1) * 255)``, q as ``model.super_resolve_u8``."""
-        if not isinstance(win, torch.Tensor) or win.dtype != torch.uint8:
-            raise ValueError(f"expected a uint8 tensor, got {getattr(win, 'dtype', type(win))}")
-        return self._window(win, dtype=torch.uint8, quantise=quantise, batch=batch)
-
-    def super_resolve_u16(self, win: torch.Tensor, quantise: str = "truncate", batch: int = 8) -> torch.Tensor:
-        """uint16 (B,T,C,H,W) window of 10-bit samples -> uint16 (B,C,4H,4W) in [0, 1023], as ``model.super_resolve_u16``."""
-        if not isinstance(win, torch.Tensor) or win.dtype != torch.uint16:
-            raise ValueError(f"expected a uint16 tensor, got {getattr(win, 'dtype', type(win))}")
-        return self._window(win, dtype=torch.uint16, quantise=quantise, batch=batch)
-
-
-class _Batched:
-    """A `TiledSuperResolver` with the harness's `batch` bound into `sequence`, so that the harness calls it as it calls a
-    `SelfEnsemble`: ``.sequence(frames, idx, dtype=..., quantise=...)``."""
-
-    def __init__(self, tsr: TiledSuperResolver, batch: int):
-        self._tsr, self._batch = tsr, int(batch)
-
-    def sequence(self, frames, idx, **kw):
-        return self._tsr.sequence(frames, idx, batch=self._batch, **kw)
-
-
-def resolver_for(model, ensemble: Optional[str], tile, tile_overlap=16, batch: int = 8):
+def resolver_for(model, ensemble: Optional[str], tile, tile_overlap=16, batch: int = 8) -> Resolver:
     """What the harness entry points run a batch of windows through, from their ``ensemble=`` / ``tile=`` / ``tile_overlap=``
-    values (validated here, before any device work): None (the plain model), the `SelfEnsemble` of ``ensemble`` without tiles, or a
-    `TiledSuperResolver` whose model passes take at most `batch` windows.  Whatever is returned has the `SelfEnsemble.sequence`
-    contract."""
+    values (validated here, before any device work): the `PlainResolver` of the model, the `SelfEnsemble` of ``ensemble`` without
+    tiles, or a `TiledSuperResolver` whose model passes take at most `batch` windows.  Always a `steps.Resolver`."""
     from .ensemble import for_mode
     check_mode(ensemble)
     if check_tile(tile, tile_overlap) is None:
-        return for_mode(model, ensemble)
-    return _Batched(TiledSuperResolver(model, tile, tile_overlap, ensemble), batch)
+        return PlainResolver(model) if ensemble is None else for_mode(model, ensemble)
+    return TiledSuperResolver(model, tile, tile_overlap, ensemble, batch)

@@ -18,13 +18,11 @@ import numpy as np
 import torch
 
 from .. import hip
-from .colour import ColourSpec, i420_planes, rgb_to_i420, yuv420_to_rgb
-from .ensemble import check_mode
-from .infer import pad_to_multiple, super_resolve_int
-from . import brisque as brisque_mod
-from .niqe import crop_geometry, frame_niqe_features, scores_from_features
-from .shots import check_auto, detect_cuts, resolve_cuts, windows_for
-from .tiles import check_tile, resolver_for
+from .colour import ColourSpec, i420_planes, yuv420_to_rgb
+from .shots import detect_cuts, resolve_cuts, windows_for
+from .steps import (ScoreCollector, check_keywords, check_scores, deliver_luma, deliver_rgb, pad_to_multiple, run_stats,
+                    to_device)
+from .surfaces import _check_size
 
 
 class YuvName(NamedTuple):
@@ -48,11 +46,6 @@ def parse_yuv_name(path: str) -> YuvName:
         raise ValueError(f"{base!r}: no _WxH size token (expected Name_WxH_NF.yuv)")
     f = _FRAMES.search(stem, m.end())
     return YuvName(stem[:m.start()], int(m.group(1)), int(m.group(2)), int(f.group(1)) if f else None)
-
-
-def _check_size(width: int, height: int):
-    if width <= 0 or height <= 0 or width % 2 or height % 2:
-        raise ValueError(f"4:2:0 frames need an even, positive width and height, got {width}x{height}")
 
 
 _BIT10 = re.compile(r"_10bit(?=_|\.|$)", re.IGNORECASE)
@@ -137,40 +130,8 @@ def write_yuv420(path: str, y: np.ndarray, u: np.ndarray, v: np.ndarray) -> None
 
 
 def _check_niqe(niqe, bit_depth: int, width: int, height: int):
-    """The `niqe=` keyword of the file-to-file paths, checked before anything is read: 8-bit only, and an SR frame of >= 2 blocks."""
-    if niqe is None:
-        return
-    if bit_depth != 8:
-        raise ValueError("NIQE is defined on 8-bit frames: niqe= cannot be used with a 10-bit run")
-    crop_geometry(4 * height, 4 * width, 0)
-
-
-def _check_brisque(brisque, bit_depth: int, width: int, height: int):
-    """The `brisque=` keyword of the file-to-file paths, checked before anything is read: a BrisqueModel, 8-bit only, and an SR
-    frame of even sides >= 16."""
-    if brisque is None:
-        return None
-    brisque = brisque_mod._check_model(brisque)
-    if bit_depth != 8:
-        raise ValueError("BRISQUE is defined on 8-bit frames: brisque= cannot be used with a 10-bit run")
-    brisque_mod._check_size(4 * height, 4 * width)
-    return brisque
-
-
-def _brisque_stats(feats, brisque) -> dict:
-    """One download of the per-batch device features, then the host's range scaling and RBF regressor per frame."""
-    if brisque is None:
-        return {}
-    scores = brisque_mod.scores_from_features(torch.cat(feats).cpu().numpy(), brisque)
-    return {"brisque": scores, "brisque_mean": float(np.mean(scores))}
-
-
-def _niqe_stats(feats, niqe) -> dict:
-    """One download of the per-batch device features, then the host's 36 x 36 Gaussian distance per frame."""
-    if niqe is None:
-        return {}
-    scores = scores_from_features(torch.cat(feats).cpu().numpy(), niqe)
-    return {"niqe": scores, "niqe_mean": float(np.mean(scores))}
+    """`steps.check_scores` of the `niqe=` keyword for width x height LR frames: the 4x frame is what is scored."""
+    check_scores(niqe, None, bit_depth, 4 * height, 4 * width)
 
 
 @torch.no_grad()
@@ -204,59 +165,29 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     [1/8, 8] as well, so at most 2x beyond the 4x frame (ValueError before any model pass).  ``niqe`` / ``brisque`` score the 4x
     luma the model made, as without the keyword.  ``"out_size"`` is (Wo, Ho)."""
     shape = _check_output_shape_420(output_shape, width, height)
-    check_mode(ensemble)
-    check_auto(cuts, "uint8")
-    _check_niqe(niqe, bit_depth, width, height)
-    brisque = _check_brisque(brisque, bit_depth, width, height)
-    if getattr(model, "_img_ch", None) != 1:
-        raise ValueError(f"super_resolve_yuv420 needs a one-channel (Y) model, got C={getattr(model, '_img_ch', None)}")
-    if quantise not in hip.QUANTISE:
-        raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
-    if batch < 1:
-        raise ValueError(f"batch must be >= 1, got {batch}")
-    check_tile(tile, tile_overlap)
-    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
+    brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
+    resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
+                              cuts=cuts, frame_dtype="uint8", channels=(1,), who="super_resolve_yuv420")
     y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
     N, H, W = y.shape
-    sdt, host_dt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.uint16, np.uint16)
-
-    def to_dev(a):
-        """Planes of the file on the device; uint16 samples as int16 bits (hip.bits16), viewed back for the kernels."""
-        return hip.bits16(torch.from_numpy(np.ascontiguousarray(a).astype(host_dt, copy=False))).to(dev)
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
-    x = to_dev(y)[:, None]                                                                # (N,1,H,W)
-    cuts = resolve_cuts(cuts, N, lambda: detect_cuts(x.view(sdt), threshold=cut_threshold))
-    x = pad_to_multiple(x, 4) if ens is None else x.contiguous().view(sdt)                # zero padded to (N,1,Hp,Wp); unpadded
-    written, niqe_feats, brisque_feats = 0, [], []
+    x = to_device(y, bit_depth, dev)[:, None]                                             # (N,1,H,W)
+    cuts = resolve_cuts(cuts, N, lambda: detect_cuts(x, threshold=cut_threshold))
+    x = pad_to_multiple(hip.bits16(x), resolver.multiple).view(x.dtype)                   # the resident frames, zero padded
+    written, scores = 0, ScoreCollector(niqe, brisque)
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             e = min(N, s + batch)
-            idx = windows_for(range(s, e), num_frames, N, padding, cuts)
-            if ens is None:
-                win = torch.stack([x[j] for j in idx], 0).view(sdt)                       # (b, 7, 1, Hp, Wp)
-                ysr = super_resolve_int(model, win, quantise)[:, 0, :4 * H, :4 * W]
-            else:
-                ysr = ens.sequence(x, idx, dtype=sdt, quantise=quantise)[:, 0]
-            if niqe is not None:
-                niqe_feats.append(frame_niqe_features(ysr[:, None], niqe))
-            if brisque is not None:
-                brisque_feats.append(brisque_mod.frame_brisque_features(ysr[:, None]))
-            uv = to_dev(np.concatenate([u[s:e], v[s:e]], 0)).view(sdt)                    # (2b, H/2, W/2)
-            if shape is None:
-                uvsr = hip.chroma_up4(uv)
-            else:                                                                         # resized on the device, then downloaded
-                ysr = hip.imresize(ysr, output_shape=shape, out="int")
-                uvsr = hip.imresize(uv, output_shape=(shape[0] // 2, shape[1] // 2), out="int")
-            ysr, uvsr = hip.frames_to_numpy(ysr), hip.frames_to_numpy(uvsr)
+            sr = resolver.frames(x, windows_for(range(s, e), num_frames, N, padding, cuts), quantise, H, W)   # (b,1,4H,4W)
+            scores.add(scores.features(sr))
+            uv = to_device(np.concatenate([u[s:e], v[s:e]], 0), bit_depth, dev)           # (2b, H/2, W/2)
+            ysr, uvsr = (hip.frames_to_numpy(t) for t in deliver_luma(sr[:, 0], uv, shape))   # resized on the device, then downloaded
             _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
             written += ysr.nbytes + uvsr.nbytes
-    niqe_stats = {**_niqe_stats(niqe_feats, niqe), **_brisque_stats(brisque_feats, brisque)}
-    dt = time.perf_counter() - t0
-    return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
-            "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
-            "bytes_written": written, "out_size": (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), **niqe_stats,
-            **({} if cuts is None else {"cuts": cuts})}
+    stats = scores.stats()
+    return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
+                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts)
 
 
 def _check_output_shape_420(output_shape, width: int, height: int, chroma: bool = True):
@@ -295,55 +226,32 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     plane by plane on the device (`resize.imresize`, out="int") before the encode, and the file is written at Wo x Ho.  ``niqe`` /
     ``brisque`` score the 4x frames, as without the keyword."""
     shape = _check_output_shape_420(output_shape, width, height, chroma=False)
-    check_mode(ensemble)
-    check_auto(cuts, "uint8")
-    _check_niqe(niqe, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
-    brisque = _check_brisque(brisque, colour.bit_depth if isinstance(colour, ColourSpec) else 8, width, height)
-    if getattr(model, "_img_ch", None) != 3:
-        raise ValueError(f"super_resolve_yuv420_rgb needs a three-channel (RGB) model, got C={getattr(model, '_img_ch', None)}")
+    bit_depth = colour.bit_depth if isinstance(colour, ColourSpec) else 8
+    brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
+    resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
+                              cuts=cuts, frame_dtype="uint8", channels=(3,), who="super_resolve_yuv420_rgb")
     if not isinstance(colour, ColourSpec):
         raise ValueError(f"colour must be a ColourSpec, got {type(colour).__name__}")
-    if quantise not in hip.QUANTISE:
-        raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
-    if batch < 1:
-        raise ValueError(f"batch must be >= 1, got {batch}")
-    check_tile(tile, tile_overlap)
-    ens = resolver_for(model, ensemble, tile, tile_overlap, batch)
-    bit_depth = colour.bit_depth
     mm = _map_frames(src, width, height, bit_depth=bit_depth)
     N, H, W = mm.shape[0], height, width
-    sdt, host_dt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.uint16, np.uint16)
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
-    frames = hip.bits16(torch.from_numpy(np.array(mm, dtype=host_dt))).to(dev).view(sdt)      # one host copy of the mapped file
-    cuts = resolve_cuts(cuts, N, lambda: detect_cuts(hip.bits16(frames)[:, :H * W].reshape(N, 1, H, W).view(sdt),
+    frames = to_device(mm, bit_depth, dev)                                                    # one host copy of the mapped file
+    cuts = resolve_cuts(cuts, N, lambda: detect_cuts(hip.bits16(frames)[:, :H * W].reshape(N, 1, H, W).view(frames.dtype),
                                                      threshold=cut_threshold))    # the file's luma plane, made dense
     x = yuv420_to_rgb(*i420_planes(frames, H, W), colour)                                     # (N,3,H,W)
-    x = pad_to_multiple(hip.bits16(x), 4) if ens is None else x.contiguous()                  # zero padded to (N,3,Hp,Wp); unpadded
-    written, niqe_feats, brisque_feats = 0, [], []
+    x = pad_to_multiple(hip.bits16(x), resolver.multiple).view(x.dtype)                       # the resident frames, zero padded
+    written, scores = 0, ScoreCollector(niqe, brisque, "Y")
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
-            idx = windows_for(range(s, min(N, s + batch)), num_frames, N, padding, cuts)
-            if ens is None:
-                win = torch.stack([x[j] for j in idx], 0).view(sdt)                       # (b, 7, 3, Hp, Wp)
-                sr = super_resolve_int(model, win, quantise)[:, :, :4 * H, :4 * W]
-            else:
-                sr = ens.sequence(x, idx, dtype=sdt, quantise=quantise)
-            if niqe is not None:
-                niqe_feats.append(frame_niqe_features(sr, niqe, convert_to="Y"))
-            if brisque is not None:
-                brisque_feats.append(brisque_mod.frame_brisque_features(sr, convert_to="Y"))
-            if shape is not None:
-                sr = hip.imresize(sr, output_shape=shape, out="int")
-            out = hip.frames_to_numpy(rgb_to_i420(sr, colour))                            # (b, 16 W H 3/2)
+            sr = resolver.frames(x, windows_for(range(s, min(N, s + batch)), num_frames, N, padding, cuts), quantise, H, W)
+            scores.add(scores.features(sr))
+            out = hip.frames_to_numpy(deliver_rgb(sr, colour, shape))                     # (b, Ho Wo 3/2)
             fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())
             written += out.nbytes
-    niqe_stats = {**_niqe_stats(niqe_feats, niqe), **_brisque_stats(brisque_feats, brisque)}
-    dt = time.perf_counter() - t0
-    return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
-            "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
-            "bytes_written": written, "out_size": (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), **niqe_stats,
-            **({} if cuts is None else {"cuts": cuts})}
+    stats = scores.stats()
+    return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
+                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts)
 
 
 @torch.no_grad()
@@ -368,12 +276,11 @@ def upscale_yuv420(src: str, dst: str, width: int, height: int, *, factor: int =
         raise ValueError(f"batch must be >= 1, got {batch}")
     y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
     N, H, W = y.shape
-    sdt, host_dt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.uint16, np.uint16)
     dev = torch.device("cuda" if device is None else device)
 
     def up(a, div=1):
-        """Planes of the file through the kernel and back; uint16 samples travel as int16 bits (hip.bits16)."""
-        t = hip.bits16(torch.from_numpy(np.array(a, dtype=host_dt))).to(dev).view(sdt)    # a copy: the file map is read-only
+        """Planes of the file through the kernel and back."""
+        t = to_device(a, bit_depth, dev)
         if shape is not None:
             return hip.frames_to_numpy(imresize(t, output_shape=(shape[0] // div, shape[1] // div), out="int"))
         return hip.frames_to_numpy(bicubic_upscale(t, factor, out="int"))
@@ -385,7 +292,5 @@ def upscale_yuv420(src: str, dst: str, width: int, height: int, *, factor: int =
             ysr, uvsr = up(y[s:e]), up(np.concatenate([u[s:e], v[s:e]], 0), 2)           # (b, fH, fW), (2b, fH/2, fW/2)
             _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
             written += ysr.nbytes + uvsr.nbytes
-    dt = time.perf_counter() - t0
-    return {"frames": N, "seconds": dt, "fps": N / dt if dt > 0 else float("inf"),
-            "bytes_read": N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2),
-            "bytes_written": written, "out_size": (factor * W, factor * H) if shape is None else (shape[1], shape[0])}
+    return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
+                     (factor * W, factor * H) if shape is None else (shape[1], shape[0]))
