@@ -1,0 +1,345 @@
+// Letterbox-aware SR, the two device ends (the contract is fcvsr_amd/harness/active.py: line_sums_host, compose_host).
+//
+// fcvsr_frame_line_sums: the sum of every row and of every column of every frame, over all channels, in exact integers.  One pass
+// that reads every sample once, integer arithmetic only, no atomics: a workgroup writes its own u32 partial sums and a second launch
+// adds them in a fixed order, as shots.hip does.
+//   A workgroup is four waves and owns, of one frame, a tile of kRows rows x a span of kSpanBytes bytes of every row (16 bytes per
+//   lane: one global_load_dwordx4), over all channels.  Wave w takes the rows w, w + 4, .. of the tile in kIters batches of kBatch
+//   rows: the loads of a batch and channel are issued together.  A row's sum is a wave reduction, written once per (row, span); a
+//   lane keeps the column sums of its own 16 (uint8: as packed 16-bit sums that are emptied into u32 every kFlush batches) or 8
+//   (uint16) columns in registers over all its rows and channels, the four waves meet in LDS, and the workgroup writes one partial
+//   per (row tile, column): with 128 rows per tile the partials are 1/32 of the frame bytes at uint8.  DESIGN.md section 4 has the arithmetic behind the shape.
+//
+// fcvsr_active_compose: the 4x frame of a group whose model pass saw the active box only.  Inside the box (4t .. 4b x 4l .. 4r) the
+// resolver's frames are copied; outside it every sample is the MATLAB-style bicubic up-scale of the LR centre frame, computed by the
+// device code upscale_kernel (resize.hip) is made of (bicubic_up.h): the same taps, products added in tap order, borders reflected at
+// the true H, W, the same rounding.  The thread layout is upscale_kernel's at 4x: a thread owns the output columns 4q .. 4q + 3 of
+// the four output rows 4n + 2 .. 4n + 5, which share their source rows n - 1 .. n + 2.  The box's edges are multiples of 4 in the
+// output, so a store of four samples is inside or outside as a whole, and a thread whose outputs all lie inside loads no LR sample.
+#include "bicubic_up.h"
+
+namespace fcvsr {
+namespace {
+
+using namespace bicubic_up;
+
+constexpr int kLanes = 64;
+constexpr int kWaves = 4;
+constexpr int kThreads = kLanes * kWaves;
+constexpr int kChunk = 16;                      // bytes per lane and row
+constexpr int kSpanBytes = kLanes * kChunk;     // bytes of a row per workgroup
+constexpr int kBatch = 8;                       // rows of a wave whose loads are in flight together
+constexpr int kIters = 4;                       // batches per wave
+constexpr int kRows = kWaves * kBatch * kIters; // rows of a tile
+constexpr int kMaxC = 4096;
+constexpr int kFlush = 32;                      // uint8: batches between two flushes of the packed 16-bit column sums
+
+static_assert(kSpanBytes == FCVSR_LINE_SUMS_SPAN_BYTES && kRows == FCVSR_LINE_SUMS_ROWS, "the header's tile sizes the caller's scratch");
+// A lane adds at most 16 samples of 255 (8 of 1023) per row and channel and a wave 64 such sums, over kMaxC channels at the most; a
+// column sum holds kRows rows of kMaxC channels of at most 1023: all below 2^32.  A 16-bit byte sum holds kFlush batches of 255.
+static_assert(16ull * 255 * kLanes * kMaxC <= 0xffffffffull && 1023ull * kRows * kMaxC <= 0xffffffffull, "u32 partial sums");
+static_assert(kFlush * kBatch * 255 <= 0xffff, "the 16-bit byte sums of kFlush batches must not overflow");
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+// uint16 samples are read as min(k, 1023), both halves of a word at once (v_pk_min_u16)
+__device__ __forceinline__ unsigned clamp10(unsigned w) {
+  u16x2 v;
+  __builtin_memcpy(&v, &w, 4);
+  v = __builtin_elementwise_min(v, u16x2{1023, 1023});
+  __builtin_memcpy(&w, &v, 4);
+  return w;
+}
+
+// The lane's 16 bytes of one row.  left: bytes of the row from p on - a whole chunk (>= kChunk), a tail that is read byte by byte
+// and zero-filled, or nothing (<= 0: p is never dereferenced).  A16: every chunk address is a multiple of 16; otherwise the load
+// carries the sample's alignment only.
+template <int E, bool A16>
+__device__ __forceinline__ u32x4 load_chunk(const unsigned char* p, long long left) {
+  u32x4 v = {0u, 0u, 0u, 0u};
+  if (left >= kChunk) {
+    if (A16) v = *reinterpret_cast<const u32x4*>(p);
+    else __builtin_memcpy(&v, __builtin_assume_aligned(p, E), kChunk);
+  } else if (left > 0) {
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < kChunk; ++j)
+      if (j < left) w[j / 4] |= (unsigned)p[j] << (8 * (j % 4));
+    v = u32x4{w[0], w[1], w[2], w[3]};
+  }
+  if (E == 2) v = u32x4{clamp10(v.x), clamp10(v.y), clamp10(v.z), clamp10(v.w)};
+  return v;
+}
+
+// One word of a row into the row's sum and the lane's column sums.  uint16: acc is the two u32 column sums of the word.  uint8:
+// acc is two words of 16-bit sums, bytes 0 and 2 in the first and bytes 1 and 3 in the second (two masks and two adds for four
+// columns); flush_bytes empties them into the u32 column sums before a 16-bit sum can overflow.
+template <int E>
+__device__ __forceinline__ void add_word(unsigned w, unsigned& row, unsigned* acc) {
+  if (E == 1) {
+    row = __builtin_amdgcn_sad_u8(w, 0u, row);
+    acc[0] += w & 0x00ff00ffu;
+    acc[1] += (w >> 8) & 0x00ff00ffu;
+  } else {
+    row = __builtin_amdgcn_sad_u16(w, 0u, row);
+    acc[0] += w & 0xffffu;
+    acc[1] += w >> 16;
+  }
+}
+
+__device__ __forceinline__ void flush_bytes(unsigned* pk, unsigned* col) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    col[4 * i + 0] += pk[2 * i] & 0xffffu;
+    col[4 * i + 2] += pk[2 * i] >> 16;
+    col[4 * i + 1] += pk[2 * i + 1] & 0xffffu;
+    col[4 * i + 3] += pk[2 * i + 1] >> 16;
+    pk[2 * i] = pk[2 * i + 1] = 0u;
+  }
+}
+
+// grid (column spans, row tiles, frames).  rowpart[n][span][h], colpart[n][tile][w].
+template <int E, bool A16>
+__global__ __launch_bounds__(kThreads) void line_sums_kernel(const unsigned char* __restrict__ frames, int C, int H, int W,
+                                                            unsigned* __restrict__ rowpart, unsigned* __restrict__ colpart) {
+  constexpr int V = kChunk / E;                                    // columns per lane
+  __shared__ unsigned sm[kWaves][kLanes * V];
+  const int lane = threadIdx.x % kLanes, wave = threadIdx.x / kLanes;
+  const int cs = blockIdx.x, rt = blockIdx.y, ncs = gridDim.x, nrt = gridDim.y;
+  const long long n = blockIdx.z;
+  const long long rowbytes = (long long)W * E;
+  const long long off = (long long)cs * kSpanBytes + lane * kChunk;
+  const long long left = rowbytes - off;
+  unsigned col[V], pk[8];
+#pragma unroll
+  for (int j = 0; j < V; ++j) col[j] = 0u;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pk[j] = 0u;
+  unsigned* acc = E == 1 ? pk : col;                                // two words of sums per word of a row, either way
+  int held = 0;                                                     // batches in the 16-bit sums
+  for (int it = 0; it < kIters; ++it) {
+    const int r0 = rt * kRows + it * (kWaves * kBatch) + wave;      // the batch: rows r0, r0 + 4, ..
+    if (r0 >= H) break;                                             // the same in the whole wave; the barrier comes after the loop
+    unsigned row[kBatch];
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k) row[k] = 0u;
+    for (int c = 0; c < C; ++c) {
+      const unsigned char* p = frames + ((n * C + c) * H + r0) * rowbytes + off;
+      u32x4 f[kBatch];
+#pragma unroll
+      for (int k = 0; k < kBatch; ++k)                              // a row below the frame is not read: left 0
+        f[k] = load_chunk<E, A16>(p + (long long)k * kWaves * rowbytes, r0 + k * kWaves < H ? left : 0);
+#pragma unroll
+      for (int k = 0; k < kBatch; ++k) {
+        add_word<E>(f[k].x, row[k], acc + 0);
+        add_word<E>(f[k].y, row[k], acc + 2);
+        add_word<E>(f[k].z, row[k], acc + 4);
+        add_word<E>(f[k].w, row[k], acc + 6);
+      }
+      if (E == 1 && ++held == kFlush) {
+        flush_bytes(pk, col);
+        held = 0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k) {
+      unsigned v = row[k];
+      for (int o = kLanes / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      const int r = r0 + k * kWaves;
+      if (lane == 0 && r < H) rowpart[(n * ncs + cs) * H + r] = v;
+    }
+  }
+  if (E == 1) flush_bytes(pk, col);
+#pragma unroll
+  for (int j = 0; j < V; ++j) sm[wave][lane * V + j] = col[j];
+  __syncthreads();
+  for (int q = threadIdx.x; q < kLanes * V; q += kThreads) {
+    const long long w = (long long)cs * (kLanes * V) + q;
+    if (w < W) {
+      unsigned s = 0u;
+#pragma unroll
+      for (int k = 0; k < kWaves; ++k) s += sm[k][q];
+      colpart[(n * nrt + rt) * W + w] = s;
+    }
+  }
+}
+
+// One thread per output: rows[n][h] = sum over spans of rowpart, cols[n][w] = sum over row tiles of colpart.
+__global__ __launch_bounds__(kThreads) void line_sums_sum_kernel(const unsigned* __restrict__ rowpart, const unsigned* __restrict__ colpart,
+                                                                long long N, int H, int W, int ncs, int nrt,
+                                                                long long* __restrict__ rows, long long* __restrict__ cols) {
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i < N * H) {
+    const long long n = i / H, h = i % H;
+    unsigned long long s = 0;
+    for (int k = 0; k < ncs; ++k) s += rowpart[(n * ncs + k) * H + h];
+    rows[i] = (long long)s;
+  } else if (i < N * (H + W)) {
+    const long long j = i - N * H, n = j / W, w = j % W;
+    unsigned long long s = 0;
+    for (int k = 0; k < nrt; ++k) s += colpart[(n * nrt + k) * W + w];
+    cols[j] = (long long)s;
+  }
+}
+
+template <int E>
+void launch_line_sums(const void* frames, int N, int C, int H, int W, int ncs, int nrt, unsigned* rowpart, unsigned* colpart,
+                      hipStream_t st) {
+  const dim3 grid((unsigned)ncs, (unsigned)nrt, (unsigned)N);
+  const unsigned char* f = (const unsigned char*)frames;
+  if ((uintptr_t)frames % kChunk == 0 && ((long long)W * E) % kChunk == 0)
+    hipLaunchKernelGGL((line_sums_kernel<E, true>), grid, dim3(kThreads), 0, st, f, C, H, W, rowpart, colpart);
+  else
+    hipLaunchKernelGGL((line_sums_kernel<E, false>), grid, dim3(kThreads), 0, st, f, C, H, W, rowpart, colpart);
+}
+
+// ---- compose ---------------------------------------------------------------------------------------------------------------------
+
+struct ComposeArgs {
+  long long sb, sc, sy, sx;      // strides of the resolver's frames, in samples
+  long long fb, fc, fy;          // frame, plane and row pitch of the resident LR frames, in samples
+  int C, H, W, t, b, l, r;
+};
+
+__device__ inline void load4(const float* p, float o[4]) {
+  const float4 v = *reinterpret_cast<const float4*>(p);
+  o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+}
+__device__ inline void load4(const unsigned char* p, unsigned char o[4]) {
+  const uchar4 v = *reinterpret_cast<const uchar4*>(p);
+  o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+}
+__device__ inline void load4(const unsigned short* p, unsigned short o[4]) {
+  const ushort4 v = *reinterpret_cast<const ushort4*>(p);
+  o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+}
+
+// (H + 1) * W threads per plane (blockIdx.y = frame of the group * C + channel): thread (n + 1, q) makes the output rows
+// 4 n + 2 + j (j < 4) x output columns 4q .. 4q + 3.  VEC: the resolver's rows can be read four samples at a time.
+template <class T, bool VEC>
+__global__ __launch_bounds__(256) void active_compose_kernel(const T* __restrict__ sr, const T* __restrict__ lr,
+                                                             const int* __restrict__ centres, ComposeArgs a, T* __restrict__ dst) {
+  constexpr int F = 4, NC = 5;
+  const int H = a.H, W = a.W, Ho = F * H, Wo = F * W;
+  const unsigned t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= (unsigned)(H + 1) * (unsigned)W) return;
+  const int q = (int)(t % (unsigned)W);
+  const int n = (int)(t / (unsigned)W) - 1;
+  const long long p = blockIdx.y;
+  const int k = (int)(p / a.C), c = (int)(p % a.C);
+  const bool incol = q >= a.l && q < a.r;
+  const bool in0 = incol && n >= a.t && n < a.b, in1 = incol && n + 1 >= a.t && n + 1 < a.b;   // output rows of LR row n, n + 1
+  const bool need = (n >= 0 && !in0) || (n + 1 < H && !in1);
+  float v[4][NC];
+  if (need) {
+    const T* sp = lr + (long long)centres[k] * a.fb + (long long)c * a.fc;
+    int cx[NC];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) cx[i] = reflect(q - 2 + i, W);
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const long long row = (long long)reflect(n - 1 + rr, H) * a.fy;
+#pragma unroll
+      for (int i = 0; i < NC; ++i) v[rr][i] = up_sample(sp, row + cx[i]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < F; ++j) {
+    const int oy = F * n + F / 2 + j, py = (F / 2 + j) % F;
+    if (oy < 0 || oy >= Ho) continue;
+    T o[4];
+    if (j < F / 2 ? in0 : in1) {
+      const T* s = sr + (long long)k * a.sb + (long long)c * a.sc + (long long)(oy - F * a.t) * a.sy + (long long)(F * (q - a.l)) * a.sx;
+      if (VEC) {
+        load4(s, o);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = s[i * a.sx];
+      }
+    } else {
+      float s[NC];                                          // the row pass of the contract at output row oy, per source column
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        float acc = UpTaps<F>::w(py, 0) * v[0][i];
+#pragma unroll
+        for (int rr = 1; rr < 4; ++rr) acc = acc + UpTaps<F>::w(py, rr) * v[rr][i];
+        s[i] = acc;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int k0 = i >= F / 2 ? 1 : 0;                  // output 4q + i reads s[k0 .. k0 + 3]
+        float acc = UpTaps<F>::w(i, 0) * s[k0];
+#pragma unroll
+        for (int kk = 1; kk < 4; ++kk) acc = acc + UpTaps<F>::w(i, kk) * s[k0 + kk];
+        up_result(acc, o[i]);
+      }
+    }
+    up_store4(dst + p * Ho * Wo + (long long)oy * Wo + 4 * q, o);
+  }
+}
+
+template <class T>
+void launch_compose(const void* sr, const void* lr, const int* centres, const ComposeArgs& a, int B, void* out, hipStream_t st) {
+  const long long per_plane = (long long)(a.H + 1) * a.W;
+  const dim3 grid((unsigned)((per_plane + 255) / 256), (unsigned)(B * a.C));
+  const long long q4 = 4 * (long long)sizeof(T);
+  const bool vec = a.sx == 1 && (uintptr_t)sr % q4 == 0 && a.sy % 4 == 0 && a.sc % 4 == 0 && a.sb % 4 == 0;
+  if (vec) hipLaunchKernelGGL((active_compose_kernel<T, true>), grid, dim3(256), 0, st, (const T*)sr, (const T*)lr, centres, a, (T*)out);
+  else hipLaunchKernelGGL((active_compose_kernel<T, false>), grid, dim3(256), 0, st, (const T*)sr, (const T*)lr, centres, a, (T*)out);
+}
+
+}  // namespace
+}  // namespace fcvsr
+
+extern "C" int fcvsr_frame_line_sums(const void* frames, int elem_size, int N, int C, int H, int W, void* scratch,
+                                     long long scratch_bytes, long long* rows, long long* cols, void* stream) {
+  using namespace fcvsr;
+  FCVSR_CHECK_ARG(elem_size == 1 || elem_size == 2, "elem_size: 1 (uint8) or 2 (uint16)");
+  FCVSR_CHECK_ARG(N >= 1 && C >= 1 && H >= 1 && W >= 1, "N, C, H and W: at least 1");
+  FCVSR_CHECK_ARG(N <= 65535 && C <= kMaxC && H <= (1 << 20) && W <= (1 << 20), "N <= 65535, C <= 4096, H and W <= 2^20");
+  FCVSR_CHECK_ARG(frames && rows && cols && scratch, "null device pointer");
+  FCVSR_CHECK_ARG(((uintptr_t)frames % elem_size) == 0, "frames: aligned to its sample size");
+  FCVSR_CHECK_ARG(((uintptr_t)scratch % 4) == 0 && ((uintptr_t)rows % 8) == 0 && ((uintptr_t)cols % 8) == 0,
+                  "scratch 4-byte, rows and cols 8-byte aligned");
+  const int ncs = cdiv((long long)W * elem_size, kSpanBytes), nrt = cdiv(H, kRows);
+  FCVSR_CHECK_ARG(nrt <= 65535, "too many row tiles");
+  const long long nrow = (long long)N * ncs * H, ncol = (long long)N * nrt * W;
+  FCVSR_CHECK_ARG(scratch_bytes >= (nrow + ncol) * 4,
+                  "scratch: N * (ceil(W * elem_size / FCVSR_LINE_SUMS_SPAN_BYTES) * H + ceil(H / FCVSR_LINE_SUMS_ROWS) * W) * 4 bytes");
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* rowpart = (unsigned*)scratch;
+  unsigned* colpart = rowpart + nrow;
+  if (elem_size == 1) launch_line_sums<1>(frames, N, C, H, W, ncs, nrt, rowpart, colpart, st);
+  else launch_line_sums<2>(frames, N, C, H, W, ncs, nrt, rowpart, colpart, st);
+  FCVSR_LAUNCH_CHECK();
+  const long long total = (long long)N * (H + W);
+  hipLaunchKernelGGL(line_sums_sum_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, rowpart, colpart,
+                     (long long)N, H, W, ncs, nrt, rows, cols);
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fcvsr_active_compose(const void* sr, long long sr_sb, long long sr_sc, long long sr_sy, long long sr_sx,
+                                    const void* frames, const int* centres, long long f_sb, long long f_sc, long long f_sy, int dtype,
+                                    int B, int C, int H, int W, int top, int bottom, int left, int right, void* out, void* stream) {
+  using namespace fcvsr;
+  FCVSR_CHECK_ARG(dtype == FCVSR_U8 || dtype == FCVSR_U16 || dtype == FCVSR_F32, "dtype: FCVSR_U8, FCVSR_U16 or FCVSR_F32");
+  FCVSR_CHECK_ARG(sr && frames && centres && out, "null device pointer");
+  FCVSR_CHECK_ARG(B >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)B * C <= 65535, "B, C, H and W: at least 1; B * C <= 65535");
+  FCVSR_CHECK_ARG(H <= (1 << 20) && W <= (1 << 20) && (long long)(H + 1) * W < (1ll << 31), "plane too large");
+  FCVSR_CHECK_ARG(0 <= top && top < bottom && bottom <= H && 0 <= left && left < right && right <= W,
+                  "box: 0 <= top < bottom <= H, 0 <= left < right <= W");
+  FCVSR_CHECK_ARG(sr_sb >= 0 && sr_sc >= 0 && sr_sy >= 0 && sr_sx >= 0 && f_sb >= 0 && f_sc >= 0 && f_sy >= W, "strides: not negative, row pitch >= W");
+  const int elem = dtype == FCVSR_U8 ? 1 : dtype == FCVSR_U16 ? 2 : 4;
+  FCVSR_CHECK_ARG(((uintptr_t)sr % elem) == 0 && ((uintptr_t)frames % elem) == 0, "sr and frames: aligned to their sample size");
+  FCVSR_CHECK_ARG(((uintptr_t)out % (4 * elem)) == 0 && ((uintptr_t)centres % 4) == 0, "out: aligned to four samples; centres: to 4 bytes");
+  const ComposeArgs a{sr_sb, sr_sc, sr_sy, sr_sx, f_sb, f_sc, f_sy, C, H, W, top, bottom, left, right};
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == FCVSR_U8) launch_compose<unsigned char>(sr, frames, centres, a, B, out, st);
+  else if (dtype == FCVSR_U16) launch_compose<unsigned short>(sr, frames, centres, a, B, out, st);
+  else launch_compose<float>(sr, frames, centres, a, B, out, st);
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}

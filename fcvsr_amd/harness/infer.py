@@ -24,7 +24,8 @@ from ..hip import bits16, frames_to_numpy
 from .metrics import psnr
 from .shots import cuts_from_sad, device_pair_sad, resolve_cuts, shot_ranges, windows_for
 from .steps import INT_FRAMES as _INT_FRAMES
-from .steps import ScoreCollector, check_keywords, check_scores, pad_to_multiple, run_window, super_resolve_int  # noqa: F401
+from .steps import (ScoreCollector, check_keywords, check_scores, group_boxes, pad_to_multiple, push_line_sums,  # noqa: F401
+                    run_window, super_resolve_int)
 
 
 def _int_kind(t: torch.Tensor):
@@ -62,7 +63,7 @@ def _quantised(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> np.ndarr
 def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                            centres: Optional[Iterable[int]] = None, quantise: str = "truncate",
                            ensemble: Optional[str] = None, cuts=None, cut_threshold: float = 10.0,
-                           tile=None, tile_overlap=16, output_shape=None) -> np.ndarray:
+                           tile=None, tile_overlap=16, output_shape=None, active=None) -> np.ndarray:
     """lr: (N,C,H,W) float in [0,1], uint8, or uint16 (10-bit samples; host or device).  Returns uint8 (len(centres),C,4H,4W) SR
     frames, uint16 for uint16 lr.  ``ensemble``: None, "spatial" (x8 self-ensemble, `harness.ensemble`) or "spatial+temporal"
     (x16); the windows are then built as variants straight from the resident sequence and never materialised.
@@ -81,20 +82,29 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
     ``output_shape``: None (the 4x frames), or (Ho, Wo): every quantised SR frame is resized on the device by `resize.imresize`
     (MATLAB `imresize`, out="int") before it is downloaded, so the result is `resize.imresize_host(frames without the keyword,
     output_shape=..., out="int")` bit for bit and only (Ho, Wo) frames cross to the host.  Ho / 4H and Wo / 4W must lie in
-    [1/8, 8] (ValueError before any model pass).  Orthogonal to ``ensemble``, ``cuts`` and ``tile``: it acts on the final frames."""
+    [1/8, 8] (ValueError before any model pass).  Orthogonal to ``ensemble``, ``cuts`` and ``tile``: it acts on the final frames.
+
+    ``active``: None (the model sees whole frames), a box (top, bottom, left, right) in LR samples, half-open, "auto" or a
+    `harness.active.ActiveSpec` (letterbox / pillarbox detection on the resident integer frames, `harness.active`; "auto" with float
+    lr raises ValueError before any model pass).  The model - or the resolver ``ensemble`` / ``tile`` select - then sees the active
+    box of every window only, and the 4x frame outside the box is the MATLAB-style bicubic up-scale of the LR centre frame
+    (`active.compose_host` is the contract).  An explicit box is used as it is given; a detected one is aligned and checked by
+    `active.used_box`.  ``output_shape`` acts on the composed frame."""
     from .resize import check_output_shape, imresize
-    resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
-                              cuts=cuts, frame_dtype=lr.dtype)
     N, C, H, W = lr.shape
+    resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
+                              cuts=cuts, frame_dtype=lr.dtype, active=active, frame_shape=(C, H, W))
     shape = check_output_shape(output_shape, 4 * H, 4 * W)
     dev = next(model.parameters()).device
     centres = list(range(N)) if centres is None else list(centres)
     x = _lr_frames(lr, dev, resolver.multiple)
     cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
+    push_line_sums(resolver, x)                                       # active="auto": x carries no padding then
     out: List[np.ndarray] = []
     for s in range(0, len(centres), batch):
         idx = windows_for(centres[s:s + batch], num_frames, N, padding, cuts)
-        sr = resolver.frames(x, idx, quantise, H, W)                  # integer frames: quantised by the last / the merge kernel
+        # integer frames: quantised by the last / the merge kernel
+        sr = resolver.frames(x, idx, quantise, H, W, group_boxes(resolver, centres[s:s + batch], idx, N))
         if sr.dtype not in _INT_FRAMES:
             sr = _quantised_dev(sr, quantise)                         # the integer cast truncates
         out.append(frames_to_numpy(sr if shape is None else imresize(sr, output_shape=shape, out="int")))
@@ -129,13 +139,16 @@ class SequenceScores:
     baseline_brisque_mean = None
     # the scene cuts that were used (cuts=): a list of frame numbers, None without the keyword; a plain attribute as well
     cuts = None
+    # the (first frame, box) changes of the active box (active=): None without the keyword; a plain attribute as well
+    active = None
 
 
 @torch.no_grad()
 def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
                       ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None, brisque=None,
-                      cuts=None, cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None) -> SequenceScores:
+                      cuts=None, cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None,
+                      active=None) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -173,14 +186,17 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     device, resized there (`resize.imresize`, out="int") and scored as integer frames; ``niqe``, ``brisque`` and their size checks
     see (Ho, Wo), and ``return_frames`` gives the resized frames.  ``baseline="bicubic"`` becomes `resize.imresize` of the unpadded LR
     centre frames straight to (Ho, Wo) - a true 3x bicubic row for 3x delivery -, out="int" for integer lr, f32 frames quantised by
-    the metric kernel for float lr.  Ho / 4H, Wo / 4W (and Ho / H, Wo / W with the baseline) must lie in [1/8, 8]."""
+    the metric kernel for float lr.  Ho / 4H, Wo / 4W (and Ho / H, Wo / W with the baseline) must lie in [1/8, 8].
+
+    ``active`` as in `super_resolve_sequence`: the composed frames are what is scored, resized and returned; the (first frame, box)
+    changes of the run come back as `SequenceScores.active` (None without the keyword)."""
     from .device_metrics import frame_metrics
     from .resize import bicubic_upscale, check_output_shape, imresize
+    N, C, H, W = lr.shape
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
-                              cuts=cuts, frame_dtype=lr.dtype)
+                              cuts=cuts, frame_dtype=lr.dtype, active=active, frame_shape=(C, H, W))
     if baseline not in (None, "bicubic"):
         raise ValueError(f'baseline must be "bicubic" or None, got {baseline!r}')
-    N, C, H, W = lr.shape
     shape = check_output_shape(output_shape, 4 * H, 4 * W)
     if shape is not None and baseline is not None:
         check_output_shape(shape, H, W)
@@ -197,6 +213,7 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     dev = next(model.parameters()).device
     x = _lr_frames(lr, dev, resolver.multiple)
     cuts = resolve_cuts(cuts, N, _auto_cuts(x, C * H * W, cut_threshold))
+    push_line_sums(resolver, x)                                       # active="auto": x carries no padding then
 
     def scorer(keep: bool):
         """(score, result) of one row of the table.  score(f, hr_b, q): a batch of frames against its HR frames - q None for integer
@@ -226,7 +243,7 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
             lr_b = bits16(x)[s:s + len(idx), :, :H, :W].view(x.dtype)     # the unpadded centre frames
             out = "int" if fq is None else "f32"
             score_base(bicubic_upscale(lr_b, 4, out=out) if shape is None else imresize(lr_b, output_shape=shape, out=out), hr_b, fq)
-        sr, q = resolver.frames(x, idx, quantise, H, W), fq
+        sr, q = resolver.frames(x, idx, quantise, H, W, group_boxes(resolver, range(s, s + len(idx)), idx, N)), fq
         if shape is not None:                                         # float lr: quantised first, then resized
             sr, q = imresize(sr if q is None else _quantised_dev(sr, q, peak), output_shape=shape, out="int"), None
         score_sr(sr, hr_b, q)
@@ -236,6 +253,8 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     vars(scores).update(row)                                          # brisque, brisque_mean: plain attributes
     if cuts is not None:
         scores.cuts = cuts
+    if resolver.boxes is not None:
+        scores.active = list(resolver.boxes.changes)
     if baseline is not None:
         vars(scores).update({"baseline_" + k: v for k, v in result_base()[0].items()})
     return scores

@@ -1,5 +1,6 @@
 """The steps every harness entry point shares, each written once: `check_keywords` (the keyword prologue; it returns the resolver),
-`Resolver` (what a batch of windows runs through: `PlainResolver` here, `ensemble.SelfEnsemble`, `tiles.TiledSuperResolver`),
+`Resolver` (what a batch of windows runs through: `PlainResolver` here, `ensemble.SelfEnsemble`, `tiles.TiledSuperResolver`, and
+`ActiveResolver`, which wraps one of them for ``active=``),
 `check_scores` / `ScoreCollector` (``niqe=`` / ``brisque=``), `deliver_luma` / `deliver_rgb` (SR frames to the planes a file holds)
 and `run_stats`.  `harness.infer`, `harness.yuv` and `harness.stream` are loops around them; a new keyword goes into the step it
 belongs to, not into the loops.
@@ -45,10 +46,12 @@ class Resolver:
     ``model.super_resolve_u8`` / ``_u16`` quantise.  `frames` is the group step of the entry points around it; the window forms
     (`__call__`, `super_resolve_u8`, `super_resolve_u16`) are for direct users."""
     multiple = 1
+    boxes = None                               # the `active.ActivePlan` of an `ActiveResolver`; None: the model sees whole frames
 
-    def frames(self, x: torch.Tensor, idx, quantise: str, H: int, W: int) -> torch.Tensor:
+    def frames(self, x: torch.Tensor, idx, quantise: str, H: int, W: int, boxes=None) -> torch.Tensor:
         """One group of windows of the resident x, cropped (a view) to the 4H x 4W of the unpadded frame: integer x gives quantised
-        frames of its dtype, float x the f32 frames (the caller quantises them: `infer._quantised_dev`, or the metric kernels)."""
+        frames of its dtype, float x the f32 frames (the caller quantises them: `infer._quantised_dev`, or the metric kernels).
+        `boxes`: the active box of every row, for an `ActiveResolver` only (`group_boxes`)."""
         sr = self.sequence(x, idx, dtype=x.dtype, quantise=quantise) if x.dtype in INT_FRAMES else self.sequence(x, idx)
         return sr[..., :4 * H, :4 * W]
 
@@ -120,15 +123,78 @@ class PlainResolver(Resolver):
         return run_window(self.model, win, quantise)
 
 
+class ActiveResolver(Resolver):
+    """Another resolver on the active box of every window (``active=``, `harness.active`): a resolver that wraps a resolver.  Per
+    run of rows with one box it takes the box out of the resident frames - of the frames the rows name, nothing else -, pads it to
+    `inner.multiple` as `pad_to_multiple` pads a frame, runs `inner.frames` at the box size and composes the 4x frames
+    (`hip.active_compose`): the inner result inside the box, the MATLAB-style bicubic up-scale of the LR centre frame (the middle of
+    a row) outside it.  The resident frames carry no padding (`multiple` 1).  A box equal to the whole frame gives what `inner`
+    gives on the whole frame, bit for bit.  `boxes`: the `active.ActivePlan` of the run; the caller asks it for the boxes of a
+    group's rows (`group_boxes`) - the rows themselves may be ring slots - and hands them to `frames`."""
+    multiple = 1
+
+    def __init__(self, inner: Resolver, boxes):
+        self.inner, self.boxes = inner, boxes
+
+    def frames(self, x: torch.Tensor, idx, quantise: str, H: int, W: int, boxes=None) -> torch.Tensor:
+        from .active import split_runs
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or not x.is_cuda:
+            raise RuntimeError("ActiveResolver runs on (N,C,H,W) frames on the HIP device only (there is no CPU fallback)")
+        rows = [[int(j) for j in r] for r in idx]                     # a number below 0 counts from the end, as ``x[j]`` reads it
+        if boxes is None or len(boxes) != len(rows):
+            raise ValueError(f"ActiveResolver.frames needs the box of each of its {len(rows)} rows, got {boxes!r}")
+        xb, N = hip.bits16(x), x.shape[0]
+        out = []
+        for s, e, box in split_runs(boxes):
+            t, b, l, r = box
+            run = [[j % N for j in row] for row in rows[s:e]]
+            named = sorted({j for row in run for j in row})
+            pos = {j: k for k, j in enumerate(named)}
+            crop = xb[:, :, t:b, l:r].index_select(0, torch.tensor(named, dtype=torch.int64).to(x.device))    # dense: the box only
+            crop = pad_to_multiple(crop, self.inner.multiple).view(x.dtype)
+            sr = self.inner.frames(crop, [[pos[j] for j in row] for row in run], quantise, b - t, r - l)
+            if (t, b, l, r) == (0, H, 0, W):
+                out.append(sr)                                        # nothing lies outside the box
+            else:
+                out.append(hip.active_compose(sr, x, [row[len(row) // 2] for row in run], box, H, W))
+        return out[0] if len(out) == 1 else torch.cat([hip.bits16(o) for o in out], 0).view(out[0].dtype)
+
+    def sequence(self, frames: torch.Tensor, idx, *, dtype: torch.dtype = torch.float32, quantise: Optional[str] = None,
+                 boxes=None) -> torch.Tensor:
+        """The `Resolver` contract on unpadded frames; `boxes` may be left out where the run has one explicit box."""
+        rows = self._rows(frames, idx, dtype, quantise)
+        if boxes is None and self.boxes is not None and not self.boxes.auto:
+            boxes = [self.boxes.box] * len(rows)
+        return self.frames(frames, rows, quantise, *frames.shape[-2:], boxes=boxes)
+
+
+def group_boxes(resolver: Resolver, centres, windows, seq_len=None):
+    """The ``boxes=`` of `Resolver.frames` for one group: the active box of every row from the frame numbers of its window
+    (`active.ActivePlan.group`; a number below 0 counts from the end of `seq_len` frames), None without ``active=``."""
+    return None if resolver.boxes is None else resolver.boxes.group(centres, windows, seq_len)
+
+
+def push_line_sums(resolver: Resolver, frames: torch.Tensor) -> None:
+    """``active="auto"``: the line sums of the integer (n,C,H,W) device frames (`hip.frame_line_sums`, one small download) into the
+    run's `active.ActivePlan`.  Nothing happens without the keyword or with an explicit box."""
+    if resolver.boxes is not None and resolver.boxes.auto:
+        rows, cols = hip.frame_line_sums(frames)
+        resolver.boxes.push(rows.cpu().numpy(), cols.cpu().numpy())
+
+
 # ---- the keyword prologue ------------------------------------------------------------------------------------------------------
 
 _CHANNELS = {1: "one-channel (Y)", 3: "three-channel (RGB)"}
 
 
-def check_keywords(model, *, ensemble, tile, tile_overlap, batch, quantise, cuts, frame_dtype, channels=None, who="") -> Resolver:
+def check_keywords(model, *, ensemble, tile, tile_overlap, batch, quantise, cuts, frame_dtype, channels=None, who="",
+                   active=None, frame_shape=None, bit_depth=None) -> Resolver:
     """What every entry point validates before any device or file work - ``ensemble``, ``cuts`` ("auto" needs integer frames:
     `frame_dtype`), the model's channel count where the entry point `who` needs one of `channels`, ``quantise``, ``batch``,
-    ``tile`` / ``tile_overlap`` - and the resolver of these values (`tiles.resolver_for`).  ValueError names the keyword."""
+    ``tile`` / ``tile_overlap``, ``active`` (against `frame_dtype` and `frame_shape` = (C, H, W) of the planes "auto" detects on,
+    of `bit_depth` bits where the dtype does not say it) - and the resolver of these values (`tiles.resolver_for`, inside an
+    `ActiveResolver` with ``active``).  ValueError names the keyword."""
+    from .active import ActivePlan, check_active
     from .ensemble import check_mode
     from .tiles import resolver_for
     check_mode(ensemble)
@@ -139,7 +205,15 @@ def check_keywords(model, *, ensemble, tile, tile_overlap, batch, quantise, cuts
         raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
     if batch < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
-    return resolver_for(model, ensemble, tile, tile_overlap, batch)
+    if active is not None:
+        C, H, W = frame_shape
+        active = check_active(active, frame_dtype, H, W)
+    resolver = resolver_for(model, ensemble, tile, tile_overlap, batch)
+    if active is None:
+        return resolver
+    if bit_depth is None:
+        bit_depth = 10 if str(frame_dtype).replace("torch.", "") == "uint16" else 8
+    return ActiveResolver(resolver, ActivePlan(active, C, H, W, bit_depth))
 
 
 def check_scores(niqe, brisque, bit_depth: int, height: int, width: int):
@@ -212,8 +286,10 @@ def deliver_rgb(sr: torch.Tensor, colour, shape) -> torch.Tensor:
     return rgb_to_i420(sr, colour)
 
 
-def run_stats(frames: int, seconds: float, bytes_read: int, bytes_written: int, out_size, scores=(), cuts=None) -> dict:
-    """The stats every file / stream entry point returns: `out_size` is (width, height); `scores` (`ScoreCollector.stats`) and
-    ``"cuts"`` are there when the keywords were."""
+def run_stats(frames: int, seconds: float, bytes_read: int, bytes_written: int, out_size, scores=(), cuts=None, active=None) -> dict:
+    """The stats every file / stream entry point returns: `out_size` is (width, height); `scores` (`ScoreCollector.stats`),
+    ``"cuts"`` and ``"active"`` (`active`: the run's `active.ActivePlan`; the list of (first frame, box) changes) are there when the
+    keywords were."""
     return {"frames": frames, "seconds": seconds, "fps": frames / seconds if seconds > 0 else float("inf"), "bytes_read": bytes_read,
-            "bytes_written": bytes_written, "out_size": out_size, **dict(scores), **({} if cuts is None else {"cuts": cuts})}
+            "bytes_written": bytes_written, "out_size": out_size, **dict(scores), **({} if cuts is None else {"cuts": cuts}),
+            **({} if active is None else {"active": list(active.changes)})}

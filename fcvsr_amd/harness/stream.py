@@ -190,7 +190,7 @@ def _write_all(fh, view: memoryview) -> None:
 def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "yuv420p", out_pix_fmt: Optional[str] = None,
                   colour: ColourSpec = ColourSpec(), batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
                   ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0, tile=None,
-                  tile_overlap=16, output_shape=None, max_frames: Optional[int] = None) -> dict:
+                  tile_overlap=16, output_shape=None, max_frames: Optional[int] = None, active=None) -> dict:
     """Super-resolve raw 4:2:0 video of any length from `src` to `dst` 4x, a chunk of frames at a time.
 
     `src`: a path, or any binary object with ``readinto`` (``sys.stdin.buffer``, a pipe, a socket file); it is never seeked or
@@ -198,9 +198,11 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     the same bit depth): ``harness.surfaces.PIX_FMTS``.  A one-channel model runs as `harness.yuv.super_resolve_yuv420` (Y through
     the model, U and V through ``hip.chroma_up4`` or `imresize`), a three-channel model as `super_resolve_yuv420_rgb` with `colour`
     (its bit depth must be the format's; a one-channel model ignores it).  Every other keyword means what it
-    means there, and for yuv420p / yuv420p10le the bytes written and the stats entries ``frames``, ``out_size``, ``cuts``, ``niqe``,
-    ``niqe_mean``, ``brisque``, ``brisque_mean``, ``bytes_written`` are those of the whole-file function on a file of the same
-    frames; for nv12 / p010le they are `surfaces.pack_host` of that result on `surfaces.unpack_host` of the source.
+    means there, and for yuv420p / yuv420p10le the bytes written and the stats entries ``frames``, ``out_size``, ``cuts``, ``active``,
+    ``niqe``, ``niqe_mean``, ``brisque``, ``brisque_mean``, ``bytes_written`` are those of the whole-file function on a file of the
+    same frames (``active="auto"``: one `hip.frame_line_sums` of the luma planes of every chunk and its small download; the box of a
+    window is that of the last frame it names, which has arrived when the window runs); for nv12 / p010le they are
+    `surfaces.pack_host` of that result on `surfaces.unpack_host` of the source.
 
     Frames are read in chunks of at most `batch` into two pinned staging buffers and uploaded on a side stream while the previous
     group is in the model; `hip.surface_unpack` puts them into a ring of ``2 batch + 2 (num_frames - 1)`` frame slots (`StreamPlan`
@@ -218,7 +220,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     from .. import hip
     from . import surfaces
     from .colour import i420_planes, yuv420_to_rgb
-    from .steps import ScoreCollector, check_keywords, check_scores, deliver_luma, deliver_rgb, run_stats
+    from .steps import ScoreCollector, check_keywords, check_scores, deliver_luma, deliver_rgb, group_boxes, run_stats
     from .yuv import _check_output_shape_420
 
     surfaces.check_fmt(pix_fmt)
@@ -238,7 +240,9 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     shape = _check_output_shape_420(output_shape, W, H, chroma=C == 1)
     brisque = check_scores(niqe, brisque, bits, 4 * H, 4 * W)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
-                              cuts=cuts, frame_dtype="uint8", channels=(1, 3), who="stream_yuv420")
+                              cuts=cuts, frame_dtype="uint8", channels=(1, 3), who="stream_yuv420", active=active,
+                              frame_shape=(1, H, W), bit_depth=bits)
+    act = resolver.boxes if resolver.boxes is not None and resolver.boxes.auto else None      # active="auto": fed per chunk
     if max_frames is not None and max_frames < 0:
         raise ValueError(f"max_frames must be >= 0, got {max_frames}")
     plan = StreamPlan(num_frames, padding, batch, cuts)
@@ -304,6 +308,8 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
                     if auto is not None:
                         idx = ([where[first - 1]] if first else []) + slots
                         luma = ring[torch.tensor(idx, dtype=torch.int64).to(dev)]
+                    if act is not None:                                   # the chunk's luma planes, without the padding
+                        lines = hip.frame_line_sums(ring[torch.tensor(slots, dtype=torch.int64).to(dev)][:, :, :H, :W].view(sdt))
                 else:
                     hip.surface_unpack(raw, pix_fmt, W, H, chunk_slots[:n], ring_y.view(sdt), ring_u.view(sdt), ring_v.view(sdt))
                     rgb = yuv420_to_rgb(ring_y[:n, 0].view(sdt), ring_u[:n].view(sdt), ring_v[:n].view(sdt), colour)
@@ -311,9 +317,13 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
                     if auto is not None:
                         luma = ring_y[:n] if prev_y is None else torch.cat([prev_y, ring_y[:n]], 0)
                         prev_y = ring_y[n - 1:n].clone()
+                    if act is not None:
+                        lines = hip.frame_line_sums(ring_y[:n].view(sdt))
                 if auto is not None:                                      # one small download per chunk; waits for this upload only
                     sad = hip.frame_pair_sad(luma.view(sdt)).cpu().numpy()
                     plan.cuts_known(auto.push(sad), auto.known_upto)
+                if act is not None:                                       # the same: one small download per chunk
+                    act.push(lines[0].cpu().numpy(), lines[1].cpu().numpy())
                 uploaded[k & 1].record(side)
 
         def launch(centres, rows):
@@ -323,7 +333,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
             main.wait_event(uploaded[last_up & 1])                         # the side stream is in order: every chunk so far
             # a frame number below 0 (a sequence shorter than the window, after its end) counts from the end, as ``x[j]`` does
             idx = [[where[f if f >= 0 else plan.frames + f] for f in row] for row in rows]
-            sr = resolver.frames(ring.view(sdt), idx, quantise, H, W)
+            sr = resolver.frames(ring.view(sdt), idx, quantise, H, W, group_boxes(resolver, centres, rows, plan.frames))
             if C == 1:
                 cs = torch.tensor([where[c] for c in centres], dtype=torch.int64).to(dev)
                 uv = torch.cat([ring_u[cs], ring_v[cs]], 0).view(sdt)                      # (2b, H/2, W/2)
@@ -378,6 +388,6 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     if stray:
         raise ValueError(f"the stream ends with {stray} stray bytes after {N} whole {W}x{H} {pix_fmt} frames ({fb_in} bytes each)")
     used = plan.finish()                                                  # ValueError: an explicit cut at or beyond the end
-    stats = run_stats(N, dt, N * fb_in, written, (Wo, Ho), scores.stats(), used)
+    stats = run_stats(N, dt, N * fb_in, written, (Wo, Ho), scores.stats(), used, resolver.boxes)
     stats.update(ring_frames=R, frames_uploaded=N, h2d_bytes=N * fb_in, d2h_bytes=written)
     return stats

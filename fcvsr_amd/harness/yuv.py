@@ -20,8 +20,8 @@ import torch
 from .. import hip
 from .colour import ColourSpec, i420_planes, yuv420_to_rgb
 from .shots import detect_cuts, resolve_cuts, windows_for
-from .steps import (ScoreCollector, check_keywords, check_scores, deliver_luma, deliver_rgb, pad_to_multiple, run_stats,
-                    to_device)
+from .steps import (ScoreCollector, check_keywords, check_scores, deliver_luma, deliver_rgb, group_boxes, pad_to_multiple,
+                    push_line_sums, run_stats, to_device)
 from .surfaces import _check_size
 
 
@@ -138,7 +138,7 @@ def _check_niqe(niqe, bit_depth: int, width: int, height: int):
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
                          quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
                          ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0,
-                         tile=None, tile_overlap=16, output_shape=None) -> dict:
+                         tile=None, tile_overlap=16, output_shape=None, active=None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -163,23 +163,32 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     `super_resolve_sequence`; U and V go ONCE from the LR chroma planes to (Ho/2, Wo/2) by the same function, in place of
     ``hip.chroma_up4``.  Ho / (4 height), Wo / (4 width) must lie in [1/8, 8] and the chroma step Ho / height, Wo / width in
     [1/8, 8] as well, so at most 2x beyond the 4x frame (ValueError before any model pass).  ``niqe`` / ``brisque`` score the 4x
-    luma the model made, as without the keyword.  ``"out_size"`` is (Wo, Ho)."""
+    luma the model made, as without the keyword.  ``"out_size"`` is (Wo, Ho).
+
+    ``active`` as in `super_resolve_sequence` (`harness.active`): None, a box (top, bottom, left, right) in luma samples, "auto" or
+    an `ActiveSpec` (detection on the file's luma plane, on the device).  The model sees the active box of every window only; the
+    luma outside it is the MATLAB-style bicubic up-scale of the LR frame, and ``niqe`` / ``brisque`` / ``output_shape`` act on the
+    composed frame.  Chroma does not depend on it.  The (first frame, box) changes of the run are added to the stats as
+    ``"active"``."""
     shape = _check_output_shape_420(output_shape, width, height)
     brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
-                              cuts=cuts, frame_dtype="uint8", channels=(1,), who="super_resolve_yuv420")
+                              cuts=cuts, frame_dtype="uint8", channels=(1,), who="super_resolve_yuv420", active=active,
+                              frame_shape=(1, height, width), bit_depth=bit_depth)
     y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
     N, H, W = y.shape
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
     x = to_device(y, bit_depth, dev)[:, None]                                             # (N,1,H,W)
     cuts = resolve_cuts(cuts, N, lambda: detect_cuts(x, threshold=cut_threshold))
+    push_line_sums(resolver, x)
     x = pad_to_multiple(hip.bits16(x), resolver.multiple).view(x.dtype)                   # the resident frames, zero padded
     written, scores = 0, ScoreCollector(niqe, brisque)
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
             e = min(N, s + batch)
-            sr = resolver.frames(x, windows_for(range(s, e), num_frames, N, padding, cuts), quantise, H, W)   # (b,1,4H,4W)
+            idx = windows_for(range(s, e), num_frames, N, padding, cuts)
+            sr = resolver.frames(x, idx, quantise, H, W, group_boxes(resolver, range(s, e), idx, N))          # (b,1,4H,4W)
             scores.add(scores.features(sr))
             uv = to_device(np.concatenate([u[s:e], v[s:e]], 0), bit_depth, dev)           # (2b, H/2, W/2)
             ysr, uvsr = (hip.frames_to_numpy(t) for t in deliver_luma(sr[:, 0], uv, shape))   # resized on the device, then downloaded
@@ -187,7 +196,7 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
             written += ysr.nbytes + uvsr.nbytes
     stats = scores.stats()
     return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
-                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts)
+                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts, resolver.boxes)
 
 
 def _check_output_shape_420(output_shape, width: int, height: int, chroma: bool = True):
@@ -204,7 +213,7 @@ def _check_output_shape_420(output_shape, width: int, height: int, chroma: bool 
 def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int, *, colour: ColourSpec = ColourSpec(),
                              batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
                              ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None,
-                             cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None) -> dict:
+                             cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None, active=None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -224,12 +233,16 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
 
     ``output_shape``: None, or (Ho, Wo), both even, Ho / (4 height) and Wo / (4 width) in [1/8, 8]: the SR RGB frames are resized
     plane by plane on the device (`resize.imresize`, out="int") before the encode, and the file is written at Wo x Ho.  ``niqe`` /
-    ``brisque`` score the 4x frames, as without the keyword."""
+    ``brisque`` score the 4x frames, as without the keyword.
+
+    ``active`` as in `super_resolve_yuv420`: "auto" detects on the luma plane of the file, before the colour conversion, and the
+    same box is applied to the decoded RGB frames; outside it the frame is the bicubic up-scale of the decoded LR frame."""
     shape = _check_output_shape_420(output_shape, width, height, chroma=False)
     bit_depth = colour.bit_depth if isinstance(colour, ColourSpec) else 8
     brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
-                              cuts=cuts, frame_dtype="uint8", channels=(3,), who="super_resolve_yuv420_rgb")
+                              cuts=cuts, frame_dtype="uint8", channels=(3,), who="super_resolve_yuv420_rgb", active=active,
+                              frame_shape=(1, height, width), bit_depth=bit_depth)
     if not isinstance(colour, ColourSpec):
         raise ValueError(f"colour must be a ColourSpec, got {type(colour).__name__}")
     mm = _map_frames(src, width, height, bit_depth=bit_depth)
@@ -237,21 +250,24 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
     frames = to_device(mm, bit_depth, dev)                                                    # one host copy of the mapped file
-    cuts = resolve_cuts(cuts, N, lambda: detect_cuts(hip.bits16(frames)[:, :H * W].reshape(N, 1, H, W).view(frames.dtype),
-                                                     threshold=cut_threshold))    # the file's luma plane, made dense
+    luma = lambda: hip.bits16(frames)[:, :H * W].reshape(N, 1, H, W).view(frames.dtype)       # the file's luma plane, made dense
+    cuts = resolve_cuts(cuts, N, lambda: detect_cuts(luma(), threshold=cut_threshold))
+    if resolver.boxes is not None and resolver.boxes.auto:
+        push_line_sums(resolver, luma())
     x = yuv420_to_rgb(*i420_planes(frames, H, W), colour)                                     # (N,3,H,W)
     x = pad_to_multiple(hip.bits16(x), resolver.multiple).view(x.dtype)                       # the resident frames, zero padded
     written, scores = 0, ScoreCollector(niqe, brisque, "Y")
     with open(dst, "wb") as fh:
         for s in range(0, N, batch):
-            sr = resolver.frames(x, windows_for(range(s, min(N, s + batch)), num_frames, N, padding, cuts), quantise, H, W)
+            idx = windows_for(range(s, min(N, s + batch)), num_frames, N, padding, cuts)
+            sr = resolver.frames(x, idx, quantise, H, W, group_boxes(resolver, range(s, s + len(idx)), idx, N))
             scores.add(scores.features(sr))
             out = hip.frames_to_numpy(deliver_rgb(sr, colour, shape))                     # (b, Ho Wo 3/2)
             fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())
             written += out.nbytes
     stats = scores.stats()
     return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
-                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts)
+                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts, resolver.boxes)
 
 
 @torch.no_grad()

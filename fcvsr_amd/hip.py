@@ -239,6 +239,8 @@ SIGNATURES = {
     "fcvsr_bicubic_upscale": [_VP, _I, C.c_longlong, _I, _I, _I, _VP, _I, _VP],
     "fcvsr_imresize": [_VP, _I, C.c_longlong, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _I, _VP],
     "fcvsr_frame_pair_sad": [_VP, _I, _I, C.c_longlong, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_frame_line_sums": [_VP, _I, _I, _I, _I, _I, _VP, C.c_longlong, _VP, _VP, _VP],
+    "fcvsr_active_compose": [_VP] + [C.c_longlong] * 4 + [_VP, _VP] + [C.c_longlong] * 3 + [_I] * 9 + [_VP, _VP],
     "fcvsr_surface_unpack": [_VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],
     "fcvsr_surface_pack": [_VP, _VP, _VP, C.c_longlong, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _VP, _VP],
 }
@@ -655,6 +657,75 @@ def frame_pair_sad(frames: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(frames.device):
         check(lib().fcvsr_frame_pair_sad(src.data_ptr(), elem, N, samples, scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(),
                                          stream_ptr()), "fcvsr_frame_pair_sad")
+    return out
+
+
+LINE_SUMS_SPAN_BYTES, LINE_SUMS_ROWS = 1024, 128      # FCVSR_LINE_SUMS_* of include/fcvsr_hip.h: a workgroup's tile, sizes the scratch
+
+
+def frame_line_sums(frames: torch.Tensor):
+    """fcvsr_frame_line_sums: frames (N,C,H,W) uint8, or uint16 (10-bit samples; int16 views of the same bits, `bits16`, are taken
+    as uint16) on the HIP device -> (rows (N,H), cols (N,W)) int64 on the device: the sums of every row and every column over all
+    channels in exact integers, uint16 samples read as min(k, 1023) (`harness.active.line_sums_host` is the contract).  Two
+    launches, every sample read once, no host sync.  Any N, C, H, W >= 1 and any start address a sample can have; non-contiguous
+    frames are made dense first."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, torch.uint16, torch.int16) or frames.dim() != 4:
+        raise ValueError(f"expected uint8 or uint16 (N,C,H,W) frames, got {getattr(frames, 'dtype', type(frames))} "
+                         f"{tuple(getattr(frames, 'shape', ()))}")
+    if not frames.is_cuda:
+        raise RuntimeError("frame_line_sums runs on the HIP device only (the host path is harness.active.line_sums_host)")
+    N, Cn, H, W = frames.shape
+    if min(N, Cn, H, W) < 1:
+        raise ValueError(f"frames must hold at least one frame of at least one sample, got {tuple(frames.shape)}")
+    src = bits16(frames).contiguous()
+    elem = src.element_size()
+    rows = torch.empty((N, H), dtype=torch.int64, device=frames.device)
+    cols = torch.empty((N, W), dtype=torch.int64, device=frames.device)
+    spans, tiles = -(-W * elem // LINE_SUMS_SPAN_BYTES), -(-H // LINE_SUMS_ROWS)
+    scratch = torch.empty((N * (spans * H + tiles * W),), dtype=torch.int32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        check(lib().fcvsr_frame_line_sums(src.data_ptr(), elem, N, Cn, H, W, scratch.data_ptr(), scratch.numel() * 4, rows.data_ptr(),
+                                          cols.data_ptr(), stream_ptr()), "fcvsr_frame_line_sums")
+    return rows, cols
+
+
+def active_compose(sr_box: torch.Tensor, frames: torch.Tensor, centres, box, H: int, W: int) -> torch.Tensor:
+    """fcvsr_active_compose: the (b,C,4H,4W) frames of a group whose resolver saw the box (top, bottom, left, right) only, one launch
+    (`harness.active.compose_host` is the contract, bit for bit).  `sr_box`: (b,C,4(bottom-top),4(right-left)) uint8, uint16 or f32
+    on the HIP device, any strides (a view is read in place); `frames`: the resident LR frames (N,C,>=H,>=W) of the same dtype, dense
+    rows (the last stride 1), of which H x W is the true frame; `centres`: b frame numbers in [0, N), the LR centre frame of every
+    `sr_box` frame (a list, uploaded here, or a device int32 tensor the caller has checked).  Inside the box the result is `sr_box`,
+    outside it `bicubic_upscale(frames[centres, :, :H, :W], 4)` - out="int" for integer frames, the f32 sums for f32."""
+    if not isinstance(sr_box, torch.Tensor) or not isinstance(frames, torch.Tensor) or sr_box.dim() != 4 or frames.dim() != 4:
+        raise ValueError("expected (b,C,4hb,4wb) sr_box and (N,C,h,w) frames")
+    if not (sr_box.is_cuda and frames.is_cuda):
+        raise RuntimeError("active_compose runs on the HIP device only (the host path is harness.active.compose_host)")
+    if frames.dtype not in (torch.uint8, torch.uint16, torch.float32) or sr_box.dtype != frames.dtype:
+        raise ValueError(f"sr_box and frames must share one dtype of uint8, uint16, f32, got {sr_box.dtype} and {frames.dtype}")
+    t, b, l, r = (int(v) for v in box)
+    N, Cn = frames.shape[:2]
+    H, W = int(H), int(W)
+    if not (1 <= H <= frames.shape[2] and 1 <= W <= frames.shape[3] and 0 <= t < b <= H and 0 <= l < r <= W):
+        raise ValueError(f"box {(t, b, l, r)} must lie in the {H}x{W} frame, and that in the resident {tuple(frames.shape[2:])} frames")
+    B = sr_box.shape[0]
+    if tuple(sr_box.shape) != (B, Cn, 4 * (b - t), 4 * (r - l)) or B < 1:
+        raise ValueError(f"sr_box must be (b,{Cn},{4 * (b - t)},{4 * (r - l)}), got {tuple(sr_box.shape)}")
+    if frames.stride(3) != 1:
+        frames = bits16(frames).contiguous().view(frames.dtype)
+    if isinstance(centres, torch.Tensor):
+        if centres.dtype != torch.int32 or tuple(centres.shape) != (B,) or centres.device != frames.device:
+            raise ValueError("centres: a device int32 tensor of b frame numbers")
+        cdev = centres.contiguous()
+    else:
+        centres = [int(c) for c in centres]
+        if len(centres) != B or any(not 0 <= c < N for c in centres):
+            raise ValueError(f"centres: {B} frame numbers in 0..{N - 1}, got {centres}")
+        cdev = torch.tensor(centres, dtype=torch.int32).to(frames.device)
+    out = torch.empty((B, Cn, 4 * H, 4 * W), dtype=frames.dtype, device=frames.device)
+    with torch.cuda.device(frames.device):
+        check(lib().fcvsr_active_compose(bits16(sr_box).data_ptr(), *sr_box.stride(), bits16(frames).data_ptr(), cdev.data_ptr(),
+                                         *frames.stride()[:3], _DT[frames.dtype], B, Cn, H, W, t, b, l, r, bits16(out).data_ptr(),
+                                         stream_ptr()), "fcvsr_active_compose")
     return out
 
 

@@ -29,6 +29,16 @@ def _cuts(text: str):
     return "auto" if text == "auto" else [int(v) for v in text.split(",") if v]
 
 
+def _active(text: str):
+    if text == "auto":
+        return "auto"
+    try:
+        t, b, l, r = (int(v) for v in text.split(":"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected auto or T:B:L:R, got {text!r}")
+    return t, b, l, r
+
+
 def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m fcvsr_amd.sr", description="4x video super-resolution of raw YUV 4:2:0, "
                                 "streamed: SRC and DST are files, or - for stdin / stdout.")
@@ -45,6 +55,10 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--tile-overlap", type=int, default=16)
     p.add_argument("--cuts", type=_cuts, default=None, metavar="auto|N,N,...", help="scene cuts: detect them, or frame numbers")
     p.add_argument("--cut-threshold", type=float, default=10.0)
+    p.add_argument("--active", type=_active, default=None, metavar="auto|T:B:L:R", help="run the model on the picture only: detect "
+                   "letterbox / pillarbox bars, or the box top:bottom:left:right in source samples (half-open)")
+    p.add_argument("--active-limit", type=float, default=24.0, help="--active auto: a row or column is picture when its mean "
+                   "sample lies above this (8-bit scale)")
     p.add_argument("--output-size", type=_size, default=None, metavar="WxH", help="deliver this size in place of 4x")
     p.add_argument("--matrix", default="bt709", choices=("bt601", "bt709"), help="RGB models: the stream's matrix")
     p.add_argument("--full-range", action="store_true", help="RGB models: full-range code values")
@@ -69,13 +83,17 @@ def main(argv=None) -> int:
     model.load_state_dict({k[len("generator."):] if k.startswith("generator.") else k: v for k, v in sd.items()})
     model = model.to(a.device)
     bits = 10 if a.pix_fmt in ("yuv420p10le", "p010le") else 8
+    active = a.active
+    if active == "auto":
+        from .harness.active import ActiveSpec
+        active = ActiveSpec(limit=a.active_limit)
     stats = stream_yuv420(model, sys.stdin.buffer if a.src == "-" else a.src, sys.stdout.buffer if a.dst == "-" else a.dst,
                           a.size[0], a.size[1], pix_fmt=a.pix_fmt, out_pix_fmt=a.out_pix_fmt,
                           colour=ColourSpec(a.matrix, a.full_range, a.chroma_loc, bits), batch=a.batch, padding=a.padding,
                           quantise=a.quantise, ensemble=a.ensemble, tile=None if a.tile is None else (a.tile[1], a.tile[0]),
                           tile_overlap=a.tile_overlap, cuts=a.cuts, cut_threshold=a.cut_threshold,
                           output_shape=None if a.output_size is None else (a.output_size[1], a.output_size[0]),
-                          max_frames=a.max_frames)
+                          max_frames=a.max_frames, active=active)
     if a.dst == "-":
         sys.stdout.buffer.flush()
     print(json.dumps({k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in stats.items()}), file=sys.stderr)

@@ -838,6 +838,29 @@ int fcvsr_imresize(const void* src, int src_dtype, long long planes, int H, int 
 #define FCVSR_PAIR_SAD_TILE_BYTES 1024
 int fcvsr_frame_pair_sad(const void* frames, int elem_size, int N, long long samples, void* scratch, long long scratch_bytes,
                          long long* out, void* stream);
+/* ---- letterbox-aware SR (no counterpart in the reference, whose clips carry no bars; the contract is
+ * fcvsr_amd/harness/active.py, line_sums_host / compose_host) ------------------------------------------------------------------------
+ * Line sums.  frames: N dense frames of C planes of H x W samples, elem_size 1 (uint8) or 2 (uint16, a sample above 1023 reads as
+ * 1023); aligned to elem_size, nothing more.  rows: DEVICE (N, H) int64, rows[n][h] = sum over all channels and columns of row h;
+ * cols: DEVICE (N, W) int64, the same over all channels and rows, in exact integers: every sample is read once, a workgroup writes
+ * u32 partial sums and a second launch adds them in a fixed order, no atomics.  scratch: DEVICE, 4-byte aligned, at least
+ * N * (ceil(W * elem_size / FCVSR_LINE_SUMS_SPAN_BYTES) * H + ceil(H / FCVSR_LINE_SUMS_ROWS) * W) * 4 bytes.  No host sync.
+ * FCVSR_E_ARG: a null pointer, another elem_size, a size < 1, N > 65535, C > 4096, a scratch that is too small. */
+#define FCVSR_LINE_SUMS_SPAN_BYTES 1024
+#define FCVSR_LINE_SUMS_ROWS 128
+int fcvsr_frame_line_sums(const void* frames, int elem_size, int N, int C, int H, int W, void* scratch, long long scratch_bytes,
+                          long long* rows, long long* cols, void* stream);
+/* Compose.  out: dense (B, C, 4H, 4W) frames of `dtype` (FCVSR_U8, FCVSR_U16 or FCVSR_F32), every sample written once, one launch.
+ * Rows 4 top .. 4 bottom x columns 4 left .. 4 right are copied from `sr`, the (B, C, 4 (bottom - top), 4 (right - left)) frames of a
+ * resolver that saw the box only, with the strides sr_s* (in samples; a view is fine).  Everything else is fcvsr_bicubic_upscale at
+ * factor 4 of the LR centre frames, bit for bit (integer dtypes: clipped and rounded half to even; FCVSR_F32: the f32 sums): frame
+ * k of the group is frame centres[k] (DEVICE int32, B of them, each a valid frame number of `frames`: the caller checks) of the
+ * resident frames, whose frame, plane and row pitch are f_sb, f_sc, f_sy samples; H, W are the true frame size, at which the border
+ * is reflected.  FCVSR_E_ARG: a null pointer, another dtype, a size < 1, B * C > 65535, a box outside the frame, a negative stride,
+ * a misaligned pointer (out: four samples). */
+int fcvsr_active_compose(const void* sr, long long sr_sb, long long sr_sc, long long sr_sy, long long sr_sx, const void* frames,
+                         const int* centres, long long f_sb, long long f_sc, long long f_sy, int dtype, int B, int C, int H, int W,
+                         int top, int bottom, int left, int right, void* out, void* stream);
 /* ---- raw 4:2:0 surfaces <-> plane rings: the two ends of the streamed YUV path (no counterpart in the reference; the contract is
  * fcvsr_amd/harness/surfaces.py, unpack_host / pack_host) -------------------------------------------------------------------------
  * The formats carry ffmpeg's names: planar I420 in 8 bits and in little-endian 16-bit words (10-bit value in the low bits), NV12
