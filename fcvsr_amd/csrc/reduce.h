@@ -9,6 +9,9 @@ constexpr int kRedPix = 256;   // pixels per stage-1 block (enough blocks to fil
 
 inline int red_blocks(long long npix) { return cdiv(npix, kRedPix); }
 
+// The OR of a predicate over the workgroup, the same value in every thread (one barrier; every thread of the workgroup calls it).
+__device__ __forceinline__ bool block_or(bool v) { return __syncthreads_or(v ? 1 : 0) != 0; }
+
 // Stage 1: partial[k][b][blk][c] = sum over this block's pixels of f(b, pix, c)[k].
 // Thread (sub, c): sub = tid / C strides over pixels; lanes with consecutive tid read consecutive channels.
 template <int K, class F>

@@ -24,21 +24,29 @@
 // quantised (u8.h) as 4 uint16 (8 bytes) / 4 uint8 (4 bytes), as ensemble_merge_kernel's does.  No LDS.
 #include "common.h"
 #include "u8.h"
+#include "reduce.h"
 #include "window_load.h"
 
 namespace fcvsr {
 
 __device__ __forceinline__ int tile_start(const int32_t* starts, int k, int last) { return min(max(starts[k], 0), last); }
 
-template <int SRC>
+// SEL: the output holds the tile windows the DEVICE table sel names, row k = (bi, ky, kx), each clamped into its range
+template <int SRC, bool SEL>
 __global__ __launch_bounds__(EN_THREADS) void tile_windows_kernel(const void* src, const float* tab, const int32_t* idx, int N, int C,
                                                                   int h, int w, int T, const int32_t* ys, int ny, const int32_t* xs,
-                                                                  int nx, int th, int tw, int blocks_x, int blocks, float* out) {
-  // plane p of the output: ((bi * ny + ky) * nx + kx) * T + ti) * C + c
+                                                                  int nx, int th, int tw, int blocks_x, int blocks, const int32_t* sel,
+                                                                  int b, float* out) {
+  // plane p of the output: ((bi * ny + ky) * nx + kx) * T + ti) * C + c; with SEL (k * T + ti) * C + c
   const int p = blockIdx.x / blocks, t = blockIdx.x % blocks;
   const int c = p % C, ti = (p / C) % T;
-  const int k = p / (C * T);                                                // (bi * ny + ky) * nx + kx
-  const int kx = k % nx, ky = (k / nx) % ny, bi = k / (nx * ny);
+  const int k = p / (C * T);                                                // (bi * ny + ky) * nx + kx, or the row of sel
+  int kx = k % nx, ky = (k / nx) % ny, bi = k / (nx * ny);
+  if constexpr (SEL) {
+    bi = min(max(sel[3 * k], 0), b - 1);
+    ky = min(max(sel[3 * k + 1], 0), ny - 1);
+    kx = min(max(sel[3 * k + 2], 0), nx - 1);
+  }
   const int ay = tile_start(ys, ky, ceil4(h) - th), ax = tile_start(xs, kx, ceil4(w) - tw);
   const int n = min(max(idx[bi * T + ti], 0), N - 1);
   const long long plane = ((long long)n * C + c) * h * w;
@@ -66,10 +74,11 @@ __global__ __launch_bounds__(EN_THREADS) void tile_windows_kernel(const void* sr
 }
 
 // O = float: the f32 blend; uint8_t / uint16_t: quantised with mode Q at peak PEAK
-template <class O, int PEAK, int Q>
+// SEL: tiles is a pool (n,C,4th,4tw) and tile (bi,ky,kx) is its slot slots[bi][ky][kx] (a DEVICE table, clamped into 0..n-1)
+template <class O, int PEAK, int Q, bool SEL>
 __global__ __launch_bounds__(EN_THREADS) void tile_merge_kernel(const float* tiles, const int32_t* ys, int ny, const int32_t* xs, int nx,
                                                                 int th, int tw, const float* wy, const float* wx, int C, int h, int w,
-                                                                int blocks_x, int blocks, O* out) {
+                                                                int blocks_x, int blocks, const int32_t* slots, int n, O* out) {
   const int H4 = 4 * h, W4 = 4 * w;
   const int Hp = ceil4(h), Wp = ceil4(w);
   const int TH = 4 * th, TW = 4 * tw;                                       // a tile output plane
@@ -101,7 +110,9 @@ __global__ __launch_bounds__(EN_THREADS) void tile_merge_kernel(const float* til
         const int ax = 4 * tile_start(xs, kx, Wp - tw);
         if (X < ax || X >= ax + TW) continue;                               // X and ax are multiples of 4: all 4 pixels or none
         const float4 gx = *reinterpret_cast<const float4*>(wx + (long long)kx * 4 * Wp + X);
-        const float* src = tiles + ((((long long)bi * ny + ky) * nx + kx) * C + c) * TH * TW + (X - ax);
+        long long tile = ((long long)bi * ny + ky) * nx + kx;
+        if constexpr (SEL) tile = min(max(slots[tile], 0), n - 1);
+        const float* src = tiles + (tile * C + c) * TH * TW + (X - ax);
         float4 v[EN_PASSES];
         float gy[EN_PASSES];
         bool on[EN_PASSES];
@@ -143,6 +154,85 @@ __global__ __launch_bounds__(EN_THREADS) void tile_merge_kernel(const float* til
   }
 }
 
+// ---- static tiles: which tile rectangles of two frames hold the same bits ------------------------------------------------------
+// tile_pairs_equal_kernel compares, for pair p = (fa, fb) of the DEVICE table pairs (P,2; numbers clamped into 0..N-1) and tile
+// (ky, kx), the rectangle [ay, min(ay + th, h)) x [ax, min(ax + tw, w)) of all C planes of the two frames as raw bits: bytes, 16-bit
+// words or 32-bit patterns, whatever the sample format means by them.  A rectangle row is cut into chunks of kEqChunk bytes from its
+// first byte; the chunks of a tile (C planes, th rows, ceil(tw E / 16) chunks a row) are numbered plane by plane, row by row, and
+// segment s of a tile - one workgroup - takes kEqItems consecutive chunks, consecutive threads consecutive chunks.  A whole chunk is one
+// 16-byte load that carries the sample's alignment only (a row starts at any sample); the last chunk of a row is read sample bytes
+// one by one and zero-filled, alike for both frames.  Every load lies inside the rectangle, so none touches the multiple-of-4
+// padding (which is not in memory), another frame or memory beyond the sequence.  All 2 kEqLoads loads of a thread are issued
+// before the first comparison.  The OR over the workgroup is reduce.h's block_or; the workgroup writes its own flag
+// partial[(p ny nx + ky nx + kx) segs + s] (1: no difference), and tile_pairs_combine_kernel ANDs the segs flags of a tile in
+// ascending order: no atomics, no flag with two writers.
+constexpr int kEqThreads = 256;
+constexpr int kEqChunk = 16;
+constexpr int kEqLoads = 4;                                                  // chunks per thread and frame
+constexpr int kEqItems = kEqThreads * kEqLoads;
+static_assert(kEqItems == FCVSR_TILE_EQ_SEG_CHUNKS, "the header's segment size sizes the caller's scratch array");
+
+typedef unsigned int eq_u32x4 __attribute__((ext_vector_type(4)));
+
+// the chunk at p: left >= kEqChunk bytes of the row remain (one load), fewer (byte by byte, zero-filled) or none (p is not read)
+template <int E>
+__device__ __forceinline__ eq_u32x4 eq_load(const unsigned char* p, int left) {
+  eq_u32x4 v = {0u, 0u, 0u, 0u};
+  if (left >= kEqChunk) {
+    __builtin_memcpy(&v, __builtin_assume_aligned(p, E), kEqChunk);
+  } else if (left > 0) {
+    unsigned q[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < kEqChunk - 1; ++j)
+      if (j < left) q[j / 4] |= (unsigned)p[j] << (8 * (j % 4));
+    v = eq_u32x4{q[0], q[1], q[2], q[3]};
+  }
+  return v;
+}
+
+template <int E>
+__global__ __launch_bounds__(kEqThreads) void tile_pairs_equal_kernel(const unsigned char* frames, const int32_t* pairs, int N, int C,
+                                                                      int h, int w, const int32_t* ys, int ny, const int32_t* xs, int nx,
+                                                                      int th, int tw, int segs, uint8_t* partial) {
+  const int s = blockIdx.x % segs, k = blockIdx.x / segs;                   // k = (p * ny + ky) * nx + kx
+  const int kx = k % nx, ky = (k / nx) % ny, p = k / (nx * ny);
+  const int ay = tile_start(ys, ky, ceil4(h) - th), ax = tile_start(xs, kx, ceil4(w) - tw);   // ay < h, ax < w: th, tw >= 4
+  const int fa = min(max(pairs[2 * p], 0), N - 1), fb = min(max(pairs[2 * p + 1], 0), N - 1);
+  const int rows = min(th, h - ay);                                         // rows and bytes a row of the clipped rectangle
+  const int rb = min(tw, w - ax) * E;
+  const int cpr = (tw * E + kEqChunk - 1) / kEqChunk;                       // chunks of an unclipped row, as the host counts them
+  const long long fbytes = (long long)C * h * w * E;
+  const unsigned char* pa = frames + fa * fbytes;
+  const unsigned char* pb = frames + fb * fbytes;
+  eq_u32x4 a[kEqLoads], b[kEqLoads];
+#pragma unroll
+  for (int u = 0; u < kEqLoads; ++u) {                                      // all loads of the thread in flight before the first use
+    const int item = (s * kEqLoads + u) * kEqThreads + threadIdx.x;
+    const int j = item % cpr, y = (item / cpr) % th, c = item / (cpr * th);
+    const bool live = c < C && y < rows;
+    const int left = live ? rb - j * kEqChunk : 0;
+    const long long off = live ? (((long long)c * h + ay + y) * w + ax) * E + (long long)j * kEqChunk : 0;
+    a[u] = eq_load<E>(pa + off, left);
+    b[u] = eq_load<E>(pb + off, left);
+  }
+  unsigned d = 0u;
+#pragma unroll
+  for (int u = 0; u < kEqLoads; ++u) {
+    const eq_u32x4 x = a[u] ^ b[u];
+    d |= x.x | x.y | x.z | x.w;
+  }
+  const bool differ = block_or(d != 0u);
+  if (threadIdx.x == 0) partial[blockIdx.x] = differ ? 0 : 1;
+}
+
+__global__ __launch_bounds__(kEqThreads) void tile_pairs_combine_kernel(const uint8_t* partial, int segs, int n, uint8_t* out) {
+  const int i = blockIdx.x * kEqThreads + threadIdx.x;
+  if (i >= n) return;
+  unsigned v = 1u;
+  for (int s = 0; s < segs; ++s) v &= partial[(long long)i * segs + s];
+  out[i] = (uint8_t)v;
+}
+
 }  // namespace fcvsr
 
 using namespace fcvsr;
@@ -156,25 +246,94 @@ constexpr int kTileMaxSide = 1 << 24;                                        // 
   FCVSR_CHECK_ARG(th <= ceil4(h) && tw <= ceil4(w), "th, tw: at most the padded frame");                                   \
   FCVSR_CHECK_ARG(ys && xs && ((uintptr_t)ys % 4) == 0 && ((uintptr_t)xs % 4) == 0, "ys, xs: non-null, 4-byte aligned")
 
-template <int SRC>
+// SEL: the n tile windows the device table sel (n,3) names; otherwise all b * ny * nx (sel and n are not looked at)
+template <int SRC, bool SEL = false>
 static int tile_windows_launch(const void* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b, int T,
-                               const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, float* out, void* stream) {
+                               const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, float* out, void* stream,
+                               const int32_t* sel = nullptr, int n = 0) {
   FCVSR_CHECK_ARG(src && idx && out && (SRC == kSrcF32 || tab), "null pointer");
   FCVSR_CHECK_ARG(N > 0 && C > 0 && b > 0 && T > 0, "sizes: all positive");
+  if (SEL) {
+    FCVSR_CHECK_ARG(sel && ((uintptr_t)sel % 4) == 0, "sel: non-null, 4-byte aligned");
+    FCVSR_CHECK_ARG(n > 0, "n: at least one selected tile window");
+  }
   FCVSR_TILE_GRID_CHECKS();
   FCVSR_CHECK_ARG(((uintptr_t)src % (SRC == kSrcF32 ? 4 : SRC == kSrcU16 ? 2 : 1)) == 0, "src: aligned to its sample size");
   FCVSR_CHECK_ARG(((uintptr_t)idx % 4) == 0, "idx: 4-byte aligned");
   FCVSR_CHECK_ARG(((uintptr_t)out % 16) == 0, "out: 16-byte aligned");
   const int blocks_x = cdiv(tw, EN_TILE);
   const long long blocks = (long long)blocks_x * cdiv(th, EN_TILE);
-  const long long planes = (long long)b * ny * nx * T * C;
+  const long long wins = SEL ? (long long)n : (long long)b * ny * nx;
+  const long long planes = wins * T * C;
   FCVSR_CHECK_ARG((long long)b * ny * nx < (1ll << 31) && (long long)T * C < (1ll << 31) && planes < (1ll << 31) &&
                       planes * blocks < (1ll << 31),
                   "too many blocks for one launch");
-  hipLaunchKernelGGL((tile_windows_kernel<SRC>), dim3((unsigned)(planes * blocks)), dim3(EN_THREADS), 0, (hipStream_t)stream, src, tab,
-                     idx, N, C, h, w, T, ys, ny, xs, nx, th, tw, blocks_x, (int)blocks, out);
+  hipLaunchKernelGGL((tile_windows_kernel<SRC, SEL>), dim3((unsigned)(planes * blocks)), dim3(EN_THREADS), 0, (hipStream_t)stream, src,
+                     tab, idx, N, C, h, w, T, ys, ny, xs, nx, th, tw, blocks_x, (int)blocks, sel, b, out);
   FCVSR_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fcvsr_tile_windows_sel(const float* src, int N, int C, int h, int w, const int32_t* idx, int b, int T, const int32_t* ys,
+                                      int ny, const int32_t* xs, int nx, int th, int tw, const int32_t* sel, int n, float* out,
+                                      void* stream) {
+  return tile_windows_launch<kSrcF32, true>(src, nullptr, N, C, h, w, idx, b, T, ys, ny, xs, nx, th, tw, out, stream, sel, n);
+}
+
+extern "C" int fcvsr_tile_windows_sel_u8(const uint8_t* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b,
+                                         int T, const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, const int32_t* sel,
+                                         int n, float* out, void* stream) {
+  return tile_windows_launch<kSrcU8, true>(src, tab, N, C, h, w, idx, b, T, ys, ny, xs, nx, th, tw, out, stream, sel, n);
+}
+
+extern "C" int fcvsr_tile_windows_sel_u16(const uint16_t* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b,
+                                          int T, const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw,
+                                          const int32_t* sel, int n, float* out, void* stream) {
+  return tile_windows_launch<kSrcU16, true>(src, tab, N, C, h, w, idx, b, T, ys, ny, xs, nx, th, tw, out, stream, sel, n);
+}
+
+template <int E>
+static int tile_pairs_equal_launch(const void* src, int N, int C, int h, int w, const int32_t* pairs, int P, const int32_t* ys, int ny,
+                                   const int32_t* xs, int nx, int th, int tw, uint8_t* scratch, long long scratch_bytes, uint8_t* out,
+                                   void* stream) {
+  FCVSR_CHECK_ARG(src && pairs && scratch && out, "null pointer");
+  FCVSR_CHECK_ARG(N > 0 && C > 0 && P > 0, "sizes: all positive");
+  FCVSR_TILE_GRID_CHECKS();
+  FCVSR_CHECK_ARG(((uintptr_t)src % E) == 0, "src: aligned to its sample size");
+  FCVSR_CHECK_ARG(((uintptr_t)pairs % 4) == 0, "pairs: 4-byte aligned");
+  const long long chunks = (long long)C * th * cdiv((long long)tw * E, kEqChunk);          // of one tile, unclipped
+  FCVSR_CHECK_ARG(chunks < (1ll << 30), "tile too large");
+  const long long segs = cdiv(chunks, kEqItems);
+  const long long tiles = (long long)P * ny * nx;
+  FCVSR_CHECK_ARG(tiles < (1ll << 31) && tiles * segs < (1ll << 31), "too many blocks for one launch");
+  FCVSR_CHECK_ARG(scratch_bytes >= tiles * segs, "scratch: P * ny * nx * ceil(C * th * ceil(tw * sample bytes / 16) / "
+                                                 "FCVSR_TILE_EQ_SEG_CHUNKS) bytes");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((tile_pairs_equal_kernel<E>), dim3((unsigned)(tiles * segs)), dim3(kEqThreads), 0, st, (const unsigned char*)src,
+                     pairs, N, C, h, w, ys, ny, xs, nx, th, tw, (int)segs, scratch);
+  FCVSR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tile_pairs_combine_kernel, dim3((unsigned)cdiv(tiles, kEqThreads)), dim3(kEqThreads), 0, st, scratch, (int)segs,
+                     (int)tiles, out);
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fcvsr_tile_pairs_equal(const float* src, int N, int C, int h, int w, const int32_t* pairs, int P, const int32_t* ys,
+                                      int ny, const int32_t* xs, int nx, int th, int tw, uint8_t* scratch, long long scratch_bytes,
+                                      uint8_t* out, void* stream) {
+  return tile_pairs_equal_launch<4>(src, N, C, h, w, pairs, P, ys, ny, xs, nx, th, tw, scratch, scratch_bytes, out, stream);
+}
+
+extern "C" int fcvsr_tile_pairs_equal_u8(const uint8_t* src, int N, int C, int h, int w, const int32_t* pairs, int P, const int32_t* ys,
+                                         int ny, const int32_t* xs, int nx, int th, int tw, uint8_t* scratch, long long scratch_bytes,
+                                         uint8_t* out, void* stream) {
+  return tile_pairs_equal_launch<1>(src, N, C, h, w, pairs, P, ys, ny, xs, nx, th, tw, scratch, scratch_bytes, out, stream);
+}
+
+extern "C" int fcvsr_tile_pairs_equal_u16(const uint16_t* src, int N, int C, int h, int w, const int32_t* pairs, int P,
+                                          const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, uint8_t* scratch,
+                                          long long scratch_bytes, uint8_t* out, void* stream) {
+  return tile_pairs_equal_launch<2>(src, N, C, h, w, pairs, P, ys, ny, xs, nx, th, tw, scratch, scratch_bytes, out, stream);
 }
 
 extern "C" int fcvsr_tile_windows(const float* src, int N, int C, int h, int w, const int32_t* idx, int b, int T, const int32_t* ys,
@@ -195,13 +354,21 @@ extern "C" int fcvsr_tile_windows_u16(const uint16_t* src, const float* tab, int
 
 template <class O, int PEAK, int Q>
 static void tile_merge_go(const float* tiles, const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, const float* wy,
-                          const float* wx, int planes, int C, int h, int w, int blocks_x, int blocks, void* out, void* stream) {
-  hipLaunchKernelGGL((tile_merge_kernel<O, PEAK, Q>), dim3((unsigned)((long long)planes * blocks)), dim3(EN_THREADS), 0,
-                     (hipStream_t)stream, tiles, ys, ny, xs, nx, th, tw, wy, wx, C, h, w, blocks_x, blocks, reinterpret_cast<O*>(out));
+                          const float* wx, int planes, int C, int h, int w, int blocks_x, int blocks, const int32_t* slots, int n,
+                          void* out, void* stream) {
+  const dim3 grid((unsigned)((long long)planes * blocks));
+  if (slots)
+    hipLaunchKernelGGL((tile_merge_kernel<O, PEAK, Q, true>), grid, dim3(EN_THREADS), 0, (hipStream_t)stream, tiles, ys, ny, xs, nx, th,
+                       tw, wy, wx, C, h, w, blocks_x, blocks, slots, n, reinterpret_cast<O*>(out));
+  else
+    hipLaunchKernelGGL((tile_merge_kernel<O, PEAK, Q, false>), grid, dim3(EN_THREADS), 0, (hipStream_t)stream, tiles, ys, ny, xs, nx, th,
+                       tw, wy, wx, C, h, w, blocks_x, blocks, slots, n, reinterpret_cast<O*>(out));
 }
 
-extern "C" int fcvsr_tile_merge(const float* tiles, const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, const float* wy,
-                                const float* wx, int b, int C, int h, int w, int out_dtype, int quantise, void* out, void* stream) {
+// slots: null - tiles is (b,ny,nx,C,4th,4tw); else tiles is the pool (n,C,4th,4tw) and slots the device table (b,ny,nx)
+static int tile_merge_launch(const float* tiles, const int32_t* slots, int n, const int32_t* ys, int ny, const int32_t* xs, int nx, int th,
+                             int tw, const float* wy, const float* wx, int b, int C, int h, int w, int out_dtype, int quantise, void* out,
+                             void* stream) {
   FCVSR_CHECK_ARG(tiles && wy && wx && out, "null pointer");
   FCVSR_CHECK_ARG(b > 0 && C > 0, "sizes: all positive");
   FCVSR_TILE_GRID_CHECKS();
@@ -219,15 +386,32 @@ extern "C" int fcvsr_tile_merge(const float* tiles, const int32_t* ys, int ny, c
   FCVSR_CHECK_ARG((long long)b * ny * nx < (1ll << 31), "too many tiles");
   const int pl = (int)planes, bl = (int)blocks;
   if (out_dtype == FCVSR_F32)
-    tile_merge_go<float, 0, FCVSR_QUANT_TRUNCATE>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, out, stream);
+    tile_merge_go<float, 0, FCVSR_QUANT_TRUNCATE>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, slots, n, out, stream);
   else if (out_dtype == FCVSR_U8 && quantise == FCVSR_QUANT_TRUNCATE)
-    tile_merge_go<uint8_t, kPeak8, FCVSR_QUANT_TRUNCATE>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, out, stream);
+    tile_merge_go<uint8_t, kPeak8, FCVSR_QUANT_TRUNCATE>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, slots, n, out,
+                                                        stream);
   else if (out_dtype == FCVSR_U8)
-    tile_merge_go<uint8_t, kPeak8, FCVSR_QUANT_ROUND>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, out, stream);
+    tile_merge_go<uint8_t, kPeak8, FCVSR_QUANT_ROUND>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, slots, n, out,
+                                                     stream);
   else if (quantise == FCVSR_QUANT_TRUNCATE)
-    tile_merge_go<uint16_t, kPeak10, FCVSR_QUANT_TRUNCATE>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, out, stream);
+    tile_merge_go<uint16_t, kPeak10, FCVSR_QUANT_TRUNCATE>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, slots, n, out,
+                                                          stream);
   else
-    tile_merge_go<uint16_t, kPeak10, FCVSR_QUANT_ROUND>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, out, stream);
+    tile_merge_go<uint16_t, kPeak10, FCVSR_QUANT_ROUND>(tiles, ys, ny, xs, nx, th, tw, wy, wx, pl, C, h, w, blocks_x, bl, slots, n, out,
+                                                       stream);
   FCVSR_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fcvsr_tile_merge(const float* tiles, const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, const float* wy,
+                                const float* wx, int b, int C, int h, int w, int out_dtype, int quantise, void* out, void* stream) {
+  return tile_merge_launch(tiles, nullptr, 0, ys, ny, xs, nx, th, tw, wy, wx, b, C, h, w, out_dtype, quantise, out, stream);
+}
+
+extern "C" int fcvsr_tile_merge_sel(const float* pool, int n, const int32_t* slots, const int32_t* ys, int ny, const int32_t* xs, int nx,
+                                    int th, int tw, const float* wy, const float* wx, int b, int C, int h, int w, int out_dtype,
+                                    int quantise, void* out, void* stream) {
+  FCVSR_CHECK_ARG(slots && ((uintptr_t)slots % 4) == 0, "slots: non-null, 4-byte aligned");
+  FCVSR_CHECK_ARG(n > 0, "n: at least one tile output in the pool");
+  return tile_merge_launch(pool, slots, n, ys, ny, xs, nx, th, tw, wy, wx, b, C, h, w, out_dtype, quantise, out, stream);
 }

@@ -63,7 +63,8 @@ def _quantised(sr: torch.Tensor, quantise: str, peak: float = 255.0) -> np.ndarr
 def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padding: str = "replicate", batch: int = 8,
                            centres: Optional[Iterable[int]] = None, quantise: str = "truncate",
                            ensemble: Optional[str] = None, cuts=None, cut_threshold: float = 10.0,
-                           tile=None, tile_overlap=16, output_shape=None, active=None) -> np.ndarray:
+                           tile=None, tile_overlap=16, output_shape=None, active=None,
+                           static_tiles: bool = False) -> np.ndarray:
     """lr: (N,C,H,W) float in [0,1], uint8, or uint16 (10-bit samples; host or device).  Returns uint8 (len(centres),C,4H,4W) SR
     frames, uint16 for uint16 lr.  ``ensemble``: None, "spatial" (x8 self-ensemble, `harness.ensemble`) or "spatial+temporal"
     (x16); the windows are then built as variants straight from the resident sequence and never materialised.
@@ -89,11 +90,16 @@ def super_resolve_sequence(model, lr: torch.Tensor, *, num_frames: int = 7, padd
     lr raises ValueError before any model pass).  The model - or the resolver ``ensemble`` / ``tile`` select - then sees the active
     box of every window only, and the 4x frame outside the box is the MATLAB-style bicubic up-scale of the LR centre frame
     (`active.compose_host` is the contract).  An explicit box is used as it is given; a detected one is aligned and checked by
-    `active.used_box`.  ``output_shape`` acts on the composed frame."""
+    `active.used_box`.  ``output_shape`` acts on the composed frame.
+
+    ``static_tiles``: False, or True together with ``tile`` (`harness.tiles`): inside every group of `batch` windows, a tile window
+    whose seven LR patches hold the same bits as those of the previous window of the group is not run through the model again; its
+    tile output is reused.  The frames are, bit for bit, those of ``static_tiles=False``; at most a factor `batch` of the model
+    passes is saved.  True without ``tile`` raises ValueError before any model pass."""
     from .resize import check_output_shape, imresize
     N, C, H, W = lr.shape
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
-                              cuts=cuts, frame_dtype=lr.dtype, active=active, frame_shape=(C, H, W))
+                              cuts=cuts, frame_dtype=lr.dtype, active=active, frame_shape=(C, H, W), static_tiles=static_tiles)
     shape = check_output_shape(output_shape, 4 * H, 4 * W)
     dev = next(model.parameters()).device
     centres = list(range(N)) if centres is None else list(centres)
@@ -148,7 +154,7 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
                       ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None, brisque=None,
                       cuts=None, cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None,
-                      active=None) -> SequenceScores:
+                      active=None, static_tiles: bool = False) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -189,12 +195,14 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     the metric kernel for float lr.  Ho / 4H, Wo / 4W (and Ho / H, Wo / W with the baseline) must lie in [1/8, 8].
 
     ``active`` as in `super_resolve_sequence`: the composed frames are what is scored, resized and returned; the (first frame, box)
-    changes of the run come back as `SequenceScores.active` (None without the keyword)."""
+    changes of the run come back as `SequenceScores.active` (None without the keyword).
+
+    ``static_tiles`` as in `super_resolve_sequence`: the scores and frames are those of ``static_tiles=False``."""
     from .device_metrics import frame_metrics
     from .resize import bicubic_upscale, check_output_shape, imresize
     N, C, H, W = lr.shape
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
-                              cuts=cuts, frame_dtype=lr.dtype, active=active, frame_shape=(C, H, W))
+                              cuts=cuts, frame_dtype=lr.dtype, active=active, frame_shape=(C, H, W), static_tiles=static_tiles)
     if baseline not in (None, "bicubic"):
         raise ValueError(f'baseline must be "bicubic" or None, got {baseline!r}')
     shape = check_output_shape(output_shape, 4 * H, 4 * W)

@@ -188,11 +188,11 @@ _CHANNELS = {1: "one-channel (Y)", 3: "three-channel (RGB)"}
 
 
 def check_keywords(model, *, ensemble, tile, tile_overlap, batch, quantise, cuts, frame_dtype, channels=None, who="",
-                   active=None, frame_shape=None, bit_depth=None) -> Resolver:
+                   active=None, frame_shape=None, bit_depth=None, static_tiles=False) -> Resolver:
     """What every entry point validates before any device or file work - ``ensemble``, ``cuts`` ("auto" needs integer frames:
     `frame_dtype`), the model's channel count where the entry point `who` needs one of `channels`, ``quantise``, ``batch``,
-    ``tile`` / ``tile_overlap``, ``active`` (against `frame_dtype` and `frame_shape` = (C, H, W) of the planes "auto" detects on,
-    of `bit_depth` bits where the dtype does not say it) - and the resolver of these values (`tiles.resolver_for`, inside an
+    ``tile`` / ``tile_overlap`` / ``static_tiles`` (True needs ``tile``), ``active`` (against `frame_dtype` and `frame_shape` =
+    (C, H, W) of the planes "auto" detects on, of `bit_depth` bits where the dtype does not say it) - and the resolver of these values (`tiles.resolver_for`, inside an
     `ActiveResolver` with ``active``).  ValueError names the keyword."""
     from .active import ActivePlan, check_active
     from .ensemble import check_mode
@@ -208,7 +208,7 @@ def check_keywords(model, *, ensemble, tile, tile_overlap, batch, quantise, cuts
     if active is not None:
         C, H, W = frame_shape
         active = check_active(active, frame_dtype, H, W)
-    resolver = resolver_for(model, ensemble, tile, tile_overlap, batch)
+    resolver = resolver_for(model, ensemble, tile, tile_overlap, batch, static_tiles)
     if active is None:
         return resolver
     if bit_depth is None:
@@ -286,10 +286,13 @@ def deliver_rgb(sr: torch.Tensor, colour, shape) -> torch.Tensor:
     return rgb_to_i420(sr, colour)
 
 
-def run_stats(frames: int, seconds: float, bytes_read: int, bytes_written: int, out_size, scores=(), cuts=None, active=None) -> dict:
+def run_stats(frames: int, seconds: float, bytes_read: int, bytes_written: int, out_size, scores=(), cuts=None, active=None,
+              tiles=None) -> dict:
     """The stats every file / stream entry point returns: `out_size` is (width, height); `scores` (`ScoreCollector.stats`),
     ``"cuts"`` and ``"active"`` (`active`: the run's `active.ActivePlan`; the list of (first frame, box) changes) are there when the
-    keywords were."""
+    keywords were; `tiles`: the run's resolver, whose ``"tiles_total"`` / ``"tiles_run"`` are added with ``static_tiles=True``
+    (`tiles.tile_counts`)."""
+    from .tiles import tile_counts
     return {"frames": frames, "seconds": seconds, "fps": frames / seconds if seconds > 0 else float("inf"), "bytes_read": bytes_read,
             "bytes_written": bytes_written, "out_size": out_size, **dict(scores), **({} if cuts is None else {"cuts": cuts}),
-            **({} if active is None else {"active": list(active.changes)})}
+            **({} if active is None else {"active": list(active.changes)}), **({} if tiles is None else tile_counts(tiles))}

@@ -190,7 +190,8 @@ def _write_all(fh, view: memoryview) -> None:
 def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "yuv420p", out_pix_fmt: Optional[str] = None,
                   colour: ColourSpec = ColourSpec(), batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
                   ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0, tile=None,
-                  tile_overlap=16, output_shape=None, max_frames: Optional[int] = None, active=None) -> dict:
+                  tile_overlap=16, output_shape=None, max_frames: Optional[int] = None, active=None,
+                  static_tiles: bool = False) -> dict:
     """Super-resolve raw 4:2:0 video of any length from `src` to `dst` 4x, a chunk of frames at a time.
 
     `src`: a path, or any binary object with ``readinto`` (``sys.stdin.buffer``, a pipe, a socket file); it is never seeked or
@@ -214,7 +215,13 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     end, when the length is known and the frames have been written.  A trailing partial frame: all whole frames are written, then
     ValueError names the stray bytes.  An empty stream raises ValueError.  ``max_frames=n`` stops after n frames and leaves the rest
     of a pipe unread.  Extra stats: ``ring_frames``, ``frames_uploaded`` (= frames), ``h2d_bytes``, ``d2h_bytes``, ``seconds``,
-    ``fps``."""
+    ``fps``.
+
+    ``static_tiles`` as in `super_resolve_sequence` (True needs ``tile``; stats ``"tiles_total"`` / ``"tiles_run"``).  Reuse stays
+    inside a group: the ring slots of the previous group's oldest frames may already hold newer frames.  The comparison runs on
+    the main stream at the head of the group's step, after the wait for the chunk's upload, and its small download is the one
+    host synchronisation of the group.  Running the comparison and its download on the side stream instead, so that they do not
+    wait behind the previous group's model pass, was measured against this placement and made no difference (profiles/NOTES.md)."""
     import torch
 
     from .. import hip
@@ -241,7 +248,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     brisque = check_scores(niqe, brisque, bits, 4 * H, 4 * W)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
                               cuts=cuts, frame_dtype="uint8", channels=(1, 3), who="stream_yuv420", active=active,
-                              frame_shape=(1, H, W), bit_depth=bits)
+                              frame_shape=(1, H, W), bit_depth=bits, static_tiles=static_tiles)
     act = resolver.boxes if resolver.boxes is not None and resolver.boxes.auto else None      # active="auto": fed per chunk
     if max_frames is not None and max_frames < 0:
         raise ValueError(f"max_frames must be >= 0, got {max_frames}")
@@ -388,6 +395,6 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     if stray:
         raise ValueError(f"the stream ends with {stray} stray bytes after {N} whole {W}x{H} {pix_fmt} frames ({fb_in} bytes each)")
     used = plan.finish()                                                  # ValueError: an explicit cut at or beyond the end
-    stats = run_stats(N, dt, N * fb_in, written, (Wo, Ho), scores.stats(), used, resolver.boxes)
+    stats = run_stats(N, dt, N * fb_in, written, (Wo, Ho), scores.stats(), used, resolver.boxes, resolver)
     stats.update(ring_frames=R, frames_uploaded=N, h2d_bytes=N * fb_in, d2h_bytes=written)
     return stats

@@ -48,8 +48,31 @@ tile windows of a batch straight from the resident sequence through the index ta
 materialised) and ``hip.tile_merge`` crops, blends in the fixed order and quantises.  The results equal the specification bit for
 bit.
 
+Static tiles (``static_tiles=True``, only together with ``tile=``).  The model is a pure function of a tile window, and the
+engine's output does not depend on the batch a window sits in, so a tile window that holds the same bits as an earlier one has the
+same output, and that output can be reused: the delivered frames are exactly those of ``static_tiles=False``.  Reuse is WITHIN one
+call of `Resolver.sequence`, i.e. within one group of b index rows:
+
+- row 0 of a group computes all its tiles;
+- for r >= 1, tile (ky,kx) of row r is static iff for every i in 0..T-1 the frames ``rows[r][i]`` and ``rows[r-1][i]`` are the same
+  frame number, or are bit-identical AS STORED, over all channels, on the tile's rectangle clipped to the frame,
+  ``[ay, min(ay + th, h)) x [ax, min(ax + tw, w))``: bytes for uint8, the raw 16-bit words for uint16 (not ``min(k, 1023)``: two
+  words above 1023 that differ count as different although the model reads both as 1023), the 32-bit patterns for f32 (``+0.0`` and
+  ``-0.0`` differ; equal NaN patterns agree).  Raw comparison can only miss reuse, it can never reuse wrongly;
+- a static tile takes the tile output of row r-1, which may itself be reused: chains end at a computed tile of the same group.
+
+Reuse is not carried across groups: the `Resolver` contract is stateless, and in `stream_yuv420` the ring slots of the previous
+group's oldest frames may already be overwritten.  So at least ``ny * nx`` tile windows run per group and the saving is capped at a
+factor b (the `batch` of the entry points): the cost per group falls from ``b ny nx`` windows to no less than ``ny nx``, 1/b of it.
+`static_pairs`, `static_sources` and `static_map_host` are this specification on the host.  On the device
+(`TiledSuperResolver._sequence_static`): ``hip.tile_pairs_equal`` compares the pairs, one small download of its (P,ny,nx) flags is the
+one host synchronisation of the group, ``hip.tile_windows(sel=)`` gathers only the computed windows in row-major (row, ky, kx)
+order, the model passes fill a pool of tile outputs, and ``hip.tile_merge(src=)`` blends through the slot table.  The resolver
+counts ``tiles_total`` and ``tiles_run``.  Not claimed: a speed-up on any real sequence - how many tiles of compressed footage are
+bit-identical over 8 consecutive frames has not been measured; the claim is the mechanism and its exactness.
+
 Out of scope: `StreamedSuperResolver` and ``fit(..., val_sequences=...)`` take no tile option; there is no temporal tiling and no
-automatic choice of the tile size.
+automatic choice of the tile size; no reuse across groups or calls, and no tolerance-based ("nearly static") reuse.
 """
 from __future__ import annotations
 
@@ -227,6 +250,81 @@ def tiled_host(win: torch.Tensor, fn: Callable, plan: TilePlan, idx: Optional[Se
     return blend_host(torch.stack(rows, 1), plan)
 
 
+# ---- static tiles: the specification --------------------------------------------------------------------------------------------
+
+def _index_rows(rows) -> List[List[int]]:
+    rows = [[int(j) for j in r] for r in rows]
+    if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError(f"rows: b >= 1 rows of equal length T >= 1, got {rows}")
+    return rows
+
+
+def static_pairs(rows) -> List[Tuple[int, int]]:
+    """The frame pairs ``static_tiles`` has to compare for a group of index rows (b rows of T frame numbers): the unique unordered
+    pairs ``(fa, fb)``, ``fa < fb``, of ``rows[r][i]`` and ``rows[r - 1][i]`` for r >= 1 that are different numbers, sorted.  The
+    same number on both sides is the same frame and is not compared."""
+    rows = _index_rows(rows)
+    return sorted({(min(a, b), max(a, b)) for prev, row in zip(rows, rows[1:]) for a, b in zip(prev, row) if a != b})
+
+
+def static_sources(E, pairs, rows) -> np.ndarray:
+    """``src`` (b,ny,nx) int32: the row whose COMPUTED tile output tile (ky,kx) of row r uses.  `E` (P,ny,nx): nonzero where the
+    two frames of ``pairs[p]`` (`static_pairs` of `rows`) are bit-identical on the tile's rectangle.  Row 0 computes everything
+    (``src[0] = 0``); tile (ky,kx) of row r >= 1 is static iff for every i the frames ``rows[r][i]`` and ``rows[r - 1][i]`` are the
+    same number or an equal pair on that tile, and then ``src[r] = src[r - 1]`` - a chain ends at a computed tile -, else
+    ``src[r] = r``."""
+    rows = _index_rows(rows)
+    E = np.asarray(E).astype(bool)
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    if E.ndim != 3 or E.shape[0] != len(pairs):
+        raise ValueError(f"E: expected ({len(pairs)},ny,nx), got {E.shape}")
+    where = {p: k for k, p in enumerate(pairs)}
+    src = np.zeros((len(rows),) + E.shape[1:], dtype=np.int32)
+    for r in range(1, len(rows)):
+        static = np.ones(E.shape[1:], dtype=bool)
+        for a, b in zip(rows[r - 1], rows[r]):
+            if a != b:
+                static &= E[where[(min(a, b), max(a, b))]]
+        src[r] = np.where(static, src[r - 1], r)
+    return src
+
+
+def _raw_bytes(frames) -> np.ndarray:
+    """(N,C,h,w) frames as stored -> (N,C,h,w,itemsize) uint8."""
+    if isinstance(frames, torch.Tensor):
+        frames = hip.bits16(frames.detach().cpu()).contiguous().numpy()
+    a = np.ascontiguousarray(frames)
+    if a.ndim != 4:
+        raise ValueError(f"expected (N,C,h,w) frames, got {a.shape}")
+    return a.view(np.uint8).reshape(*a.shape, a.dtype.itemsize)
+
+
+def static_map_host(frames, rows, plan: TilePlan) -> np.ndarray:
+    """The whole specification of ``static_tiles`` on CPU frames: `frames` (N,C,h,w) - a CPU tensor or numpy array, uint8, uint16 or
+    f32 -, `rows` the b index rows of one group, `plan` the `TilePlan` of h x w.  Returns `static_sources` of the exact comparison:
+    a pair is equal on tile (ky,kx) iff the two frames hold the same bits - bytes, raw 16-bit words, 32-bit patterns - in all
+    channels on ``[ay, min(ay + th, h)) x [ax, min(ax + tw, w))``.  ``(src == arange(b)[:, None, None])`` marks the tiles that run."""
+    raw = _raw_bytes(frames)
+    if raw.shape[2:4] != (plan.h, plan.w):
+        raise ValueError(f"frames {raw.shape[:4]} do not fit the plan ({plan.h} x {plan.w})")
+    rows = _index_rows(rows)
+    if any(not 0 <= j < raw.shape[0] for r in rows for j in r):
+        raise ValueError(f"rows: frame numbers in 0..{raw.shape[0] - 1}, got {rows}")
+    pairs = static_pairs(rows)
+    E = np.zeros((len(pairs), plan.ny, plan.nx), dtype=bool)
+    for p, (fa, fb) in enumerate(pairs):
+        for ky, ay in enumerate(plan.ys):
+            for kx, ax in enumerate(plan.xs):
+                y1, x1 = min(ay + plan.th, plan.h), min(ax + plan.tw, plan.w)
+                E[p, ky, kx] = np.array_equal(raw[fa, :, ay:y1, ax:x1], raw[fb, :, ay:y1, ax:x1])
+    return static_sources(E, pairs, rows)
+
+
+def _graph_chunk(n: int, batch: int) -> int:
+    """The pass size for a last chunk of n < batch windows under ``use_graph``: the next power of two, at most `batch`."""
+    return min(1 << (n - 1).bit_length(), batch)
+
+
 class TiledSuperResolver(Resolver):
     """Tiled inference around a model of this package; see the module docstring for the semantics.
 
@@ -235,15 +333,20 @@ class TiledSuperResolver(Resolver):
     `super_resolve_u16` return it quantised as ``model.super_resolve_u8`` / ``_u16`` quantise; `sequence` takes the resident
     sequence and window index rows instead of windows (`steps.Resolver`).  ``ensemble``: None, "spatial" or "spatial+temporal" -
     every tile window then goes through the `SelfEnsemble` of the model.  ``batch``: the most tile windows of one model pass; every
-    call takes ``batch=`` to override it."""
+    call takes ``batch=`` to override it.  ``static_tiles=True``: inside a `sequence` call of b > 1 rows, a tile window whose frames
+    hold the same bits as those of the previous row's is not run again (module docstring: exact, and capped at a factor b because
+    nothing is carried from one call to the next).  ``tiles_total`` / ``tiles_run`` count the tile windows delivered / run through
+    the per-window function since the caller last reset them."""
 
-    def __init__(self, model, tile, tile_overlap=16, ensemble: Optional[str] = None, batch: int = 8):
+    def __init__(self, model, tile, tile_overlap=16, ensemble: Optional[str] = None, batch: int = 8, static_tiles: bool = False):
         chk = check_tile(tile, tile_overlap)
         if chk is None:
             raise ValueError("TiledSuperResolver needs a tile size, got tile=None")
         self.tile, self.tile_overlap = chk
         self.model, self.batch = model, batch
         self.ensemble = check_mode(ensemble)
+        self.static_tiles = bool(static_tiles)
+        self.tiles_total = self.tiles_run = 0          # tile windows delivered / run through the model; the caller resets them
         self._fn = model if ensemble is None else SelfEnsemble(model, temporal=ensemble == "spatial+temporal")
 
     def plan(self, h: int, w: int) -> TilePlan:
@@ -266,20 +369,75 @@ class TiledSuperResolver(Resolver):
             frames = frames.float()
         plan = self.plan(h, w)
         table = torch.tensor(rows, dtype=torch.int32).to(frames.device)
+        self.tiles_total += len(rows) * plan.ny * plan.nx
+        if self.static_tiles and len(rows) > 1:
+            return self._sequence_static(frames, rows, table, plan, batch, dtype, quantise)
         wins = hip.tile_windows(frames, table, plan).flatten(0, 2)            # (b ny nx, T, C, th, tw)
         n = wins.shape[0]
+        self.tiles_run += n
         outs = torch.empty((n, C, SCALE * plan.th, SCALE * plan.tw), dtype=torch.float32, device=frames.device)
         for s in range(0, n, batch):
             outs[s:s + batch] = self._fn(wins[s:s + batch])
         return hip.tile_merge(outs.unflatten(0, (len(rows), plan.ny, plan.nx)), plan, h, w, dtype=dtype, quantise=quantise)
 
+    def _sequence_static(self, frames, rows, table, plan: TilePlan, batch: int, dtype, quantise) -> torch.Tensor:
+        """`sequence` with ``static_tiles`` for b > 1 rows: compare (`hip.tile_pairs_equal`), one small download - the one host
+        synchronisation of the group -, `static_sources`, then only the computed tile windows, in row-major (row, ky, kx) order,
+        are gathered and run, and the merge reads every tile through the slot table.  Under ``model.use_graph`` the passes are
+        full chunks of `batch` and a last chunk padded to the next power of two by repeating its last window, so at most
+        ``1 + log2(batch)`` pass sizes are ever captured; eager runs use the exact remainder."""
+        dev, b, C = frames.device, len(rows), frames.shape[1]
+        pairs = static_pairs(rows)
+        if pairs:
+            E = hip.tile_pairs_equal(frames, torch.tensor(pairs, dtype=torch.int32).to(dev), plan).cpu().numpy()
+        else:
+            E = np.zeros((0, plan.ny, plan.nx), dtype=np.uint8)
+        src = static_sources(E, pairs, rows)
+        run = src == np.arange(b, dtype=np.int32)[:, None, None]
+        sel = np.argwhere(run).astype(np.int32)                               # (n,3) rows (r, ky, kx), row-major
+        n = sel.shape[0]
+        slot = np.zeros(src.shape, dtype=np.int32)
+        slot[run] = np.arange(n, dtype=np.int32)
+        slots = np.take_along_axis(slot, src, 0)                              # the slot of the computed tile each tile uses
+        wins = hip.tile_windows(frames, table, plan, sel=torch.from_numpy(sel).to(dev))      # (n, T, C, th, tw)
+        pool = torch.empty((n, C, SCALE * plan.th, SCALE * plan.tw), dtype=torch.float32, device=dev)
+        graph = bool(getattr(self.model, "use_graph", False))
+        for s in range(0, n, batch):
+            chunk = wins[s:s + batch]
+            m = chunk.shape[0]
+            if graph and m < batch and _graph_chunk(m, batch) > m:
+                chunk = torch.cat([chunk, chunk[-1:].expand(_graph_chunk(m, batch) - m, *chunk.shape[1:])], 0)
+            pool[s:s + m] = self._fn(chunk)[:m]
+        self.tiles_run += n
+        return hip.tile_merge(pool, plan, h=plan.h, w=plan.w, dtype=dtype, quantise=quantise, src=torch.from_numpy(slots).to(dev))
 
-def resolver_for(model, ensemble: Optional[str], tile, tile_overlap=16, batch: int = 8) -> Resolver:
-    """What the harness entry points run a batch of windows through, from their ``ensemble=`` / ``tile=`` / ``tile_overlap=``
-    values (validated here, before any device work): the `PlainResolver` of the model, the `SelfEnsemble` of ``ensemble`` without
-    tiles, or a `TiledSuperResolver` whose model passes take at most `batch` windows.  Always a `steps.Resolver`."""
+
+def check_static_tiles(static_tiles, tile) -> bool:
+    """The ``static_tiles=`` keyword: a bool, and True only together with ``tile=``; anything else is a ValueError."""
+    if not isinstance(static_tiles, (bool, np.bool_)):
+        raise ValueError(f"static_tiles must be True or False, got {static_tiles!r}")
+    if static_tiles and tile is None:
+        raise ValueError("static_tiles=True needs tile=: reuse is per tile window")
+    return bool(static_tiles)
+
+
+def resolver_for(model, ensemble: Optional[str], tile, tile_overlap=16, batch: int = 8, static_tiles: bool = False) -> Resolver:
+    """What the harness entry points run a batch of windows through, from their ``ensemble=`` / ``tile=`` / ``tile_overlap=`` /
+    ``static_tiles=`` values (validated here, before any device work): the `PlainResolver` of the model, the `SelfEnsemble` of
+    ``ensemble`` without tiles, or a `TiledSuperResolver` whose model passes take at most `batch` windows.  Always a
+    `steps.Resolver`."""
     from .ensemble import for_mode
     check_mode(ensemble)
+    static_tiles = check_static_tiles(static_tiles, tile)
     if check_tile(tile, tile_overlap) is None:
         return PlainResolver(model) if ensemble is None else for_mode(model, ensemble)
-    return TiledSuperResolver(model, tile, tile_overlap, ensemble, batch)
+    return TiledSuperResolver(model, tile, tile_overlap, ensemble, batch, static_tiles)
+
+
+def tile_counts(resolver: Resolver) -> dict:
+    """``{"tiles_total", "tiles_run"}`` of the `TiledSuperResolver` a harness run used with ``static_tiles=True`` - the resolver
+    itself or the one inside an `ActiveResolver` -, {} for any other run."""
+    inner = getattr(resolver, "inner", resolver)
+    if isinstance(inner, TiledSuperResolver) and inner.static_tiles:
+        return {"tiles_total": inner.tiles_total, "tiles_run": inner.tiles_run}
+    return {}

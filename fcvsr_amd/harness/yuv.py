@@ -138,7 +138,7 @@ def _check_niqe(niqe, bit_depth: int, width: int, height: int):
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
                          quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
                          ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0,
-                         tile=None, tile_overlap=16, output_shape=None, active=None) -> dict:
+                         tile=None, tile_overlap=16, output_shape=None, active=None, static_tiles: bool = False) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -169,12 +169,16 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     an `ActiveSpec` (detection on the file's luma plane, on the device).  The model sees the active box of every window only; the
     luma outside it is the MATLAB-style bicubic up-scale of the LR frame, and ``niqe`` / ``brisque`` / ``output_shape`` act on the
     composed frame.  Chroma does not depend on it.  The (first frame, box) changes of the run are added to the stats as
-    ``"active"``."""
+    ``"active"``.
+
+    ``static_tiles`` as in `super_resolve_sequence` (True needs ``tile``): tile windows that did not change inside a group are not
+    run again; the file written is the same, and the stats gain ``"tiles_total"`` and ``"tiles_run"`` (tile windows delivered and
+    run through the model)."""
     shape = _check_output_shape_420(output_shape, width, height)
     brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
                               cuts=cuts, frame_dtype="uint8", channels=(1,), who="super_resolve_yuv420", active=active,
-                              frame_shape=(1, height, width), bit_depth=bit_depth)
+                              frame_shape=(1, height, width), bit_depth=bit_depth, static_tiles=static_tiles)
     y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
     N, H, W = y.shape
     dev = next(model.parameters()).device
@@ -196,7 +200,7 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
             written += ysr.nbytes + uvsr.nbytes
     stats = scores.stats()
     return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
-                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts, resolver.boxes)
+                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts, resolver.boxes, resolver)
 
 
 def _check_output_shape_420(output_shape, width: int, height: int, chroma: bool = True):
@@ -213,7 +217,8 @@ def _check_output_shape_420(output_shape, width: int, height: int, chroma: bool 
 def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int, *, colour: ColourSpec = ColourSpec(),
                              batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
                              ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None,
-                             cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None, active=None) -> dict:
+                             cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None, active=None,
+                             static_tiles: bool = False) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -236,13 +241,17 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     ``brisque`` score the 4x frames, as without the keyword.
 
     ``active`` as in `super_resolve_yuv420`: "auto" detects on the luma plane of the file, before the colour conversion, and the
-    same box is applied to the decoded RGB frames; outside it the frame is the bicubic up-scale of the decoded LR frame."""
+    same box is applied to the decoded RGB frames; outside it the frame is the bicubic up-scale of the decoded LR frame.
+
+    ``static_tiles`` as in `super_resolve_sequence` (True needs ``tile``): tile windows that did not change inside a group are not
+    run again; the file written is the same, and the stats gain ``"tiles_total"`` and ``"tiles_run"`` (tile windows delivered and
+    run through the model)."""
     shape = _check_output_shape_420(output_shape, width, height, chroma=False)
     bit_depth = colour.bit_depth if isinstance(colour, ColourSpec) else 8
     brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
                               cuts=cuts, frame_dtype="uint8", channels=(3,), who="super_resolve_yuv420_rgb", active=active,
-                              frame_shape=(1, height, width), bit_depth=bit_depth)
+                              frame_shape=(1, height, width), bit_depth=bit_depth, static_tiles=static_tiles)
     if not isinstance(colour, ColourSpec):
         raise ValueError(f"colour must be a ColourSpec, got {type(colour).__name__}")
     mm = _map_frames(src, width, height, bit_depth=bit_depth)
@@ -267,7 +276,7 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
             written += out.nbytes
     stats = scores.stats()
     return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
-                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts, resolver.boxes)
+                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts, resolver.boxes, resolver)
 
 
 @torch.no_grad()

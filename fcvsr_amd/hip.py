@@ -229,6 +229,13 @@ SIGNATURES = {
     "fcvsr_tile_windows_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP],
     "fcvsr_tile_windows_u16": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP],
     "fcvsr_tile_merge": [_VP, _VP, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP],
+    "fcvsr_tile_pairs_equal": [_VP, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_tile_pairs_equal_u8": [_VP, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_tile_pairs_equal_u16": [_VP, _I, _I, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_tile_windows_sel": [_VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _I, _VP, _VP],
+    "fcvsr_tile_windows_sel_u8": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _I, _VP, _VP],
+    "fcvsr_tile_windows_sel_u16": [_VP, _VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _I, _VP, _VP],
+    "fcvsr_tile_merge_sel": [_VP, _I, _VP, _VP, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP],
     "fcvsr_niqe_scratch_bytes": [_I] * 4,
     "fcvsr_niqe_features": [_VP, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _VP, _VP, _VP, C.c_longlong,
                             _VP],
@@ -1000,17 +1007,24 @@ def ensemble_merge(a: torch.Tensor, at: torch.Tensor, h: int, w: int, *, ra: Opt
     return out
 
 
+TILE_EQ_SEG_CHUNKS = 1024                       # FCVSR_TILE_EQ_SEG_CHUNKS
+
+
 def _tile_plan_for(plan, h: int, w: int, what: str):
     if (plan.h, plan.w) != (h, w):
         raise ValueError(f"{what}: the plan is for {plan.h} x {plan.w} frames, got {h} x {w}")
 
 
-def tile_windows(frames: torch.Tensor, idx: torch.Tensor, plan) -> torch.Tensor:
+def tile_windows(frames: torch.Tensor, idx: torch.Tensor, plan, sel: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fcvsr_tile_windows / _u8 / _u16: the tile windows (`harness.tiles`) of b windows, one launch.  `frames` is the dense UNPADDED
     sequence (N,C,h,w) on the HIP device, f32, uint8 or uint16 (integer samples enter as ``u8_table`` / ``u16_table[min(k, 1023)]``);
     `idx` an int32 (b,T) tensor on the same device, row i the frame numbers of window i; `plan` the `harness.tiles.TilePlan` of
     h x w frames.  Returns f32 ``(b,ny,nx,T,C,th,tw)``: tile (ky,kx) is the window cut at ``(plan.ys[ky], plan.xs[kx])`` out of the
-    frames zero-padded at the bottom / right to multiples of 4."""
+    frames zero-padded at the bottom / right to multiples of 4.
+
+    `sel` (fcvsr_tile_windows_sel / _u8 / _u16): an int32 (n,3) tensor on the same device, rows ``(bi, ky, kx)`` in any order,
+    repeats allowed.  Returns f32 ``(n,T,C,th,tw)``, row k the bits of ``tile_windows(frames, idx, plan)[bi, ky, kx]``; the other
+    tile windows are not made."""
     if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype not in (torch.float32, torch.uint8, torch.uint16):
         raise ValueError(f"frames: expected an f32, uint8 or uint16 (N,C,h,w) tensor, got {getattr(frames, 'dtype', type(frames))} "
                          f"{tuple(getattr(frames, 'shape', ()))}")
@@ -1022,38 +1036,109 @@ def tile_windows(frames: torch.Tensor, idx: torch.Tensor, plan) -> torch.Tensor:
         raise ValueError(f"frames on {frames.device}, idx on {idx.device}")
     if min(frames.shape) == 0 or idx.numel() == 0:
         raise ValueError(f"empty input: frames {tuple(frames.shape)}, idx {tuple(idx.shape)}")
+    if sel is not None:
+        if not isinstance(sel, torch.Tensor) or sel.dtype != torch.int32 or sel.dim() != 2 or sel.shape[1] != 3 or sel.shape[0] < 1:
+            raise ValueError(f"sel: expected an int32 (n,3) tensor with n >= 1, got {getattr(sel, 'dtype', type(sel))} "
+                             f"{tuple(getattr(sel, 'shape', ()))}")
+        if sel.device != frames.device:
+            raise ValueError(f"frames on {frames.device}, sel on {sel.device}")
     N, Cc, h, w = frames.shape
     _tile_plan_for(plan, h, w, "tile_windows")
     (b, T), dev = idx.shape, frames.device
     src, idx = bits16(frames).contiguous(), idx.contiguous()
     ys, xs, _, _ = plan.device_tables(dev)
-    out = torch.empty((b, plan.ny, plan.nx, T, Cc, plan.th, plan.tw), dtype=torch.float32, device=dev)
-    tail = (N, Cc, h, w, idx.data_ptr(), b, T, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx, plan.th, plan.tw, out.data_ptr())
+    if sel is None:
+        suffix, extra = "", ()
+        out = torch.empty((b, plan.ny, plan.nx, T, Cc, plan.th, plan.tw), dtype=torch.float32, device=dev)
+    else:
+        sel = sel.contiguous()
+        suffix, extra = "_sel", (sel.data_ptr(), sel.shape[0])
+        out = torch.empty((sel.shape[0], T, Cc, plan.th, plan.tw), dtype=torch.float32, device=dev)
+    tail = (N, Cc, h, w, idx.data_ptr(), b, T, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx, plan.th, plan.tw, *extra, out.data_ptr())
     with torch.cuda.device(dev):
         if frames.dtype == torch.float32:
-            check(lib().fcvsr_tile_windows(src.data_ptr(), *tail, stream_ptr()), "fcvsr_tile_windows")
+            name = "fcvsr_tile_windows" + suffix
+            check(getattr(lib(), name)(src.data_ptr(), *tail, stream_ptr()), name)
         elif frames.dtype == torch.uint8:
-            check(lib().fcvsr_tile_windows_u8(src.data_ptr(), u8_table(dev).data_ptr(), *tail, stream_ptr()), "fcvsr_tile_windows_u8")
+            name = "fcvsr_tile_windows" + suffix + "_u8"
+            check(getattr(lib(), name)(src.data_ptr(), u8_table(dev).data_ptr(), *tail, stream_ptr()), name)
         else:
-            check(lib().fcvsr_tile_windows_u16(src.data_ptr(), u16_table(dev).data_ptr(), *tail, stream_ptr()),
-                  "fcvsr_tile_windows_u16")
+            name = "fcvsr_tile_windows" + suffix + "_u16"
+            check(getattr(lib(), name)(src.data_ptr(), u16_table(dev).data_ptr(), *tail, stream_ptr()), name)
+    return out
+
+
+def tile_eq_segments(Cc: int, th: int, tw: int, elem_size: int) -> int:
+    """The flags per tile fcvsr_tile_pairs_equal writes into its scratch array (FCVSR_TILE_EQ_SEG_CHUNKS chunks of 16 bytes each)."""
+    return -(-(Cc * th * -(-(tw * elem_size) // 16)) // TILE_EQ_SEG_CHUNKS)
+
+
+def tile_pairs_equal(frames: torch.Tensor, pairs: torch.Tensor, plan) -> torch.Tensor:
+    """fcvsr_tile_pairs_equal / _u8 / _u16: `frames` the dense UNPADDED sequence (N,C,h,w) on the HIP device, f32, uint8 or uint16;
+    `pairs` an int32 (P,2) tensor of frame numbers on the same device; `plan` the `harness.tiles.TilePlan` of h x w frames.  Returns
+    uint8 ``(P,ny,nx)``: 1 where the two frames of the pair hold the same bits (bytes, raw 16-bit words, 32-bit patterns) in every
+    sample of every channel on the tile's rectangle clipped to the frame, 0 otherwise (`harness.tiles.static_map_host` is the
+    specification).  Two launches, no host synchronisation."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype not in (torch.float32, torch.uint8, torch.uint16):
+        raise ValueError(f"frames: expected an f32, uint8 or uint16 (N,C,h,w) tensor, got {getattr(frames, 'dtype', type(frames))} "
+                         f"{tuple(getattr(frames, 'shape', ()))}")
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+        raise ValueError(f"pairs: expected an int32 (P,2) tensor with P >= 1, got {getattr(pairs, 'dtype', type(pairs))} "
+                         f"{tuple(getattr(pairs, 'shape', ()))}")
+    if not frames.is_cuda or not pairs.is_cuda:
+        raise RuntimeError("tile_pairs_equal runs on the HIP device only (there is no CPU fallback)")
+    if frames.device != pairs.device:
+        raise ValueError(f"frames on {frames.device}, pairs on {pairs.device}")
+    if min(frames.shape) == 0:
+        raise ValueError(f"empty input: frames {tuple(frames.shape)}")
+    N, Cc, h, w = frames.shape
+    _tile_plan_for(plan, h, w, "tile_pairs_equal")
+    dev, P = frames.device, pairs.shape[0]
+    src, pairs = bits16(frames).contiguous(), pairs.contiguous()
+    ys, xs, _, _ = plan.device_tables(dev)
+    nbytes = P * plan.ny * plan.nx * tile_eq_segments(Cc, plan.th, plan.tw, frames.element_size())
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out = torch.empty((P, plan.ny, plan.nx), dtype=torch.uint8, device=dev)
+    name = "fcvsr_tile_pairs_equal" + {torch.float32: "", torch.uint8: "_u8", torch.uint16: "_u16"}[frames.dtype]
+    with torch.cuda.device(dev):
+        check(getattr(lib(), name)(src.data_ptr(), N, Cc, h, w, pairs.data_ptr(), P, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx,
+                                   plan.th, plan.tw, scratch.data_ptr(), nbytes, out.data_ptr(), stream_ptr()), name)
     return out
 
 
 def tile_merge(tiles: torch.Tensor, plan, h: int, w: int, *, dtype: torch.dtype = torch.float32,
-               quantise: Optional[str] = None) -> torch.Tensor:
+               quantise: Optional[str] = None, src: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fcvsr_tile_merge: `tiles` (b,ny,nx,C,4th,4tw), f32 on the HIP device, are the model's outputs for the tile windows of b
     windows of h x w frames (`plan`: their `harness.tiles.TilePlan`).  Returns the dense (b,C,4h,4w) blend (`harness.tiles.blend_host`:
     crop, the normalised feathered weights, the fixed-order f32 sum): f32, or - `dtype` uint8 / uint16 with `quantise` "truncate" /
-    "round" - quantised as the model's integer paths quantise.  One launch."""
-    if not isinstance(tiles, torch.Tensor) or tiles.dtype != torch.float32 or tiles.dim() != 6:
-        raise ValueError(f"tiles: expected an f32 (b,ny,nx,C,4th,4tw) tensor, got {getattr(tiles, 'dtype', type(tiles))} "
-                         f"{tuple(getattr(tiles, 'shape', ()))}")
+    "round" - quantised as the model's integer paths quantise.  One launch.
+
+    `src` (fcvsr_tile_merge_sel): an int32 (b,ny,nx) tensor of slots on the same device; `tiles` is then a pool (n,C,4th,4tw) and
+    the result is, bit for bit, ``tile_merge(tiles[src.long()], ...)`` without that tensor being made."""
+    if src is None:
+        if not isinstance(tiles, torch.Tensor) or tiles.dtype != torch.float32 or tiles.dim() != 6:
+            raise ValueError(f"tiles: expected an f32 (b,ny,nx,C,4th,4tw) tensor, got {getattr(tiles, 'dtype', type(tiles))} "
+                             f"{tuple(getattr(tiles, 'shape', ()))}")
+    else:
+        if not isinstance(tiles, torch.Tensor) or tiles.dtype != torch.float32 or tiles.dim() != 4 or tiles.shape[0] < 1:
+            raise ValueError(f"tiles: with src expected an f32 pool (n,C,4th,4tw), got {getattr(tiles, 'dtype', type(tiles))} "
+                             f"{tuple(getattr(tiles, 'shape', ()))}")
+        if not isinstance(src, torch.Tensor) or src.dtype != torch.int32 or src.dim() != 3:
+            raise ValueError(f"src: expected an int32 (b,ny,nx) tensor, got {getattr(src, 'dtype', type(src))} "
+                             f"{tuple(getattr(src, 'shape', ()))}")
+        if src.device != tiles.device:
+            raise ValueError(f"tiles on {tiles.device}, src on {src.device}")
     if not tiles.is_cuda:
         raise RuntimeError("tile_merge runs on the HIP device only (there is no CPU fallback)")
     _tile_plan_for(plan, h, w, "tile_merge")
-    b, Cc = tiles.shape[0], tiles.shape[3]
-    want = (b, plan.ny, plan.nx, Cc, 4 * plan.th, 4 * plan.tw)
+    if src is None:
+        b, Cc = tiles.shape[0], tiles.shape[3]
+        want = (b, plan.ny, plan.nx, Cc, 4 * plan.th, 4 * plan.tw)
+    else:
+        b, Cc = src.shape[0], tiles.shape[1]
+        want = (tiles.shape[0], Cc, 4 * plan.th, 4 * plan.tw)
+        if tuple(src.shape) != (b, plan.ny, plan.nx):
+            raise ValueError(f"src: expected (b,{plan.ny},{plan.nx}), got {tuple(src.shape)}")
     if tuple(tiles.shape) != want:
         raise ValueError(f"tiles: expected {want}, got {tuple(tiles.shape)}")
     if b == 0 or Cc == 0:
@@ -1071,7 +1156,13 @@ def tile_merge(tiles: torch.Tensor, plan, h: int, w: int, *, dtype: torch.dtype 
     tiles = tiles.contiguous()
     ys, xs, wy, wx = plan.device_tables(tiles.device)
     out = torch.empty((b, Cc, 4 * h, 4 * w), dtype=dtype, device=tiles.device)
+    grid = (ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx, plan.th, plan.tw, wy.data_ptr(), wx.data_ptr(), b, Cc, h, w, code, q,
+            out.data_ptr())
     with torch.cuda.device(tiles.device):
-        check(lib().fcvsr_tile_merge(tiles.data_ptr(), ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx, plan.th, plan.tw, wy.data_ptr(),
-                                     wx.data_ptr(), b, Cc, h, w, code, q, out.data_ptr(), stream_ptr()), "fcvsr_tile_merge")
+        if src is None:
+            check(lib().fcvsr_tile_merge(tiles.data_ptr(), *grid, stream_ptr()), "fcvsr_tile_merge")
+        else:
+            src = src.contiguous()
+            check(lib().fcvsr_tile_merge_sel(tiles.data_ptr(), tiles.shape[0], src.data_ptr(), *grid, stream_ptr()),
+                  "fcvsr_tile_merge_sel")
     return out

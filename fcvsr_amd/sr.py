@@ -53,6 +53,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--ensemble", default=None, choices=("spatial", "spatial+temporal"))
     p.add_argument("--tile", type=_size, default=None, metavar="WxH", help="run the model on overlapping tiles of this size")
     p.add_argument("--tile-overlap", type=int, default=16)
+    p.add_argument("--static-tiles", action="store_true", help="with --tile: do not run a tile window again whose frames did not "
+                   "change since the previous frame of its group; the bytes written are the same")
     p.add_argument("--cuts", type=_cuts, default=None, metavar="auto|N,N,...", help="scene cuts: detect them, or frame numbers")
     p.add_argument("--cut-threshold", type=float, default=10.0)
     p.add_argument("--active", type=_active, default=None, metavar="auto|T:B:L:R", help="run the model on the picture only: detect "
@@ -93,7 +95,7 @@ def main(argv=None) -> int:
                           quantise=a.quantise, ensemble=a.ensemble, tile=None if a.tile is None else (a.tile[1], a.tile[0]),
                           tile_overlap=a.tile_overlap, cuts=a.cuts, cut_threshold=a.cut_threshold,
                           output_shape=None if a.output_size is None else (a.output_size[1], a.output_size[0]),
-                          max_frames=a.max_frames, active=active)
+                          max_frames=a.max_frames, active=active, static_tiles=a.static_tiles)
     if a.dst == "-":
         sys.stdout.buffer.flush()
     print(json.dumps({k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in stats.items()}), file=sys.stderr)

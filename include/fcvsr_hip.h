@@ -755,6 +755,39 @@ int fcvsr_tile_windows_u16(const uint16_t* src, const float* tab, int N, int C, 
  * out: dense (b,C,4h,4w) (the crop of the padded frame), out_dtype / quantise / alignment as fcvsr_ensemble_merge. */
 int fcvsr_tile_merge(const float* tiles, const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, const float* wy,
                      const float* wx, int b, int C, int h, int w, int out_dtype, int quantise, void* out, void* stream);
+/* ---- static tiles (harness/tiles.py, static_map_host): tile windows that did not change are not run again ----------------------
+ * fcvsr_tile_pairs_equal: pairs is a DEVICE table (P,2) of frame numbers (clamped into 0..N-1).  out (P,ny,nx) uint8: 1 where the
+ * two frames of the pair hold the same bits - bytes, 16-bit words (the raw word, not min(k, 1023)) or 32-bit patterns (+0.0 and
+ * -0.0 differ, equal NaN patterns agree) - in every sample of all C planes on the tile's rectangle clipped to the frame,
+ * [ys[ky], min(ys[ky] + th, h)) x [xs[kx], min(xs[kx] + tw, w)); 0 otherwise.  No load leaves that rectangle.  Two launches, no
+ * atomics: scratch (device, any alignment) takes one flag per tile segment, scratch_bytes >=
+ * P * ny * nx * ceil(C * th * ceil(tw * sample bytes / 16) / FCVSR_TILE_EQ_SEG_CHUNKS). */
+#define FCVSR_TILE_EQ_SEG_CHUNKS 1024
+int fcvsr_tile_pairs_equal(const float* src, int N, int C, int h, int w, const int32_t* pairs, int P, const int32_t* ys, int ny,
+                           const int32_t* xs, int nx, int th, int tw, uint8_t* scratch, long long scratch_bytes, uint8_t* out,
+                           void* stream);
+int fcvsr_tile_pairs_equal_u8(const uint8_t* src, int N, int C, int h, int w, const int32_t* pairs, int P, const int32_t* ys, int ny,
+                              const int32_t* xs, int nx, int th, int tw, uint8_t* scratch, long long scratch_bytes, uint8_t* out,
+                              void* stream);
+int fcvsr_tile_pairs_equal_u16(const uint16_t* src, int N, int C, int h, int w, const int32_t* pairs, int P, const int32_t* ys, int ny,
+                               const int32_t* xs, int nx, int th, int tw, uint8_t* scratch, long long scratch_bytes, uint8_t* out,
+                               void* stream);
+/* fcvsr_tile_windows_sel: the tile windows a DEVICE table sel (n,3) of int32 rows (bi, ky, kx) names, each entry clamped into its
+ * range; rows may repeat and come in any order.  out (n,T,C,th,tw) f32, 16-byte aligned: out[k] holds the bits of
+ * fcvsr_tile_windows' out[bi][ky][kx].  Everything else as fcvsr_tile_windows. */
+int fcvsr_tile_windows_sel(const float* src, int N, int C, int h, int w, const int32_t* idx, int b, int T, const int32_t* ys, int ny,
+                           const int32_t* xs, int nx, int th, int tw, const int32_t* sel, int n, float* out, void* stream);
+int fcvsr_tile_windows_sel_u8(const uint8_t* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b, int T,
+                              const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, const int32_t* sel, int n,
+                              float* out, void* stream);
+int fcvsr_tile_windows_sel_u16(const uint16_t* src, const float* tab, int N, int C, int h, int w, const int32_t* idx, int b, int T,
+                               const int32_t* ys, int ny, const int32_t* xs, int nx, int th, int tw, const int32_t* sel, int n,
+                               float* out, void* stream);
+/* fcvsr_tile_merge_sel: fcvsr_tile_merge on tiles[bi][ky][kx] = pool[slots[bi][ky][kx]] without that tensor: pool (n,C,4th,4tw)
+ * dense f32, 16-byte aligned; slots a DEVICE table (b,ny,nx) of int32 (clamped into 0..n-1).  The same blend, order, quantisers. */
+int fcvsr_tile_merge_sel(const float* pool, int n, const int32_t* slots, const int32_t* ys, int ny, const int32_t* xs, int nx, int th,
+                         int tw, const float* wy, const float* wx, int b, int C, int h, int w, int out_dtype, int quantise, void* out,
+                         void* stream);
 /* ---- NIQE block features and the MATLAB-style bicubic down-scale (reference mmedit/core/evaluation/metrics.py:398-590
  * estimate_aggd_param / compute_feature / niqe_core / niqe, used by CVSR_train/metric/cal_VideoLQ.py; the down-scale is
  * mmedit/datasets/pipelines/matlab_like_resize.py; the contract is fcvsr_amd/harness/niqe.py) ------------------------------------
