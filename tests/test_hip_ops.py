@@ -93,7 +93,8 @@ def test_conv_mfma_stride2_and_planar_source():
 
 def test_conv_mfma_fused_context_block_partials():
     """ContextBlock pooling (softmax over H*W of <r, wmask>, :657-701) from the conv epilogue's per-wave partials ==
-    the stand-alone two-stage kernel == the torch formula, all evaluated on the conv's own output r."""
+    the stand-alone two-stage kernel == the torch formula, all evaluated on the conv's own output r.
+    The f64 pin of fcvsr_gc_context / fcvsr_gc_finish at the block edges is tests/test_freq_kernels_gpu.py."""
     from fcvsr_amd import hip
     L = hip.lib()
     B, Cc, H, W = 2, 64, 22, 70                        # partial tiles: 22 = 5*4+2 rows, 70 = 2*32+6 cols
@@ -196,6 +197,7 @@ def test_fft_roundtrip_full_size():
 
 
 def test_corr_warp_sac_vs_oracle():
+    """The f64 pin of fcvsr_corr_lookup (shapes, strip, strided destination) is tests/test_freq_kernels_gpu.py."""
     from fcvsr_amd import hip
     from oracle import fcvsr_oracle as O
     L = hip.lib()
@@ -429,7 +431,8 @@ def test_freq_mlp3_matches_three_1x1_launches():
 
 @pytest.mark.parametrize("k", [1, 3, 5, 7])
 def test_convblk_fused_head_matches_separate_launches(k):
-    """fcvsr_convblk (conv1 + PReLU + conv2 + channel sums | gate + tail) against the six stand-alone launches it replaces."""
+    """fcvsr_convblk (conv1 + PReLU + conv2 + channel sums | gate + tail) against the six stand-alone launches it replaces.
+    The f64 pin of both sides (fcvsr_channel_sum, fcvsr_ca_gate, fcvsr_convblk_tail, fcvsr_convblk) is tests/test_freq_kernels_gpu.py."""
     from fcvsr_amd import hip
     L = hip.lib()
     st = hip.stream_ptr()
@@ -565,7 +568,8 @@ def test_conv_f32_matrix_core_pixel_shuffle_and_skinny_outputs():
 
 def test_gc_partials_from_stored_r_match_the_reference_formula():
     """fcvsr_gc_partial_levels: per 4 x 32 tile, (sum_p exp(l_p - m) r_p, m, sum exp) of a stored bf16 r over three levels with
-    partial tiles; combined by fcvsr_gc_finish_levels they must give the ContextBlock vector of the f64 formula (:657-701)."""
+    partial tiles; combined by fcvsr_gc_finish_levels they must give the ContextBlock vector of the f64 formula (:657-701).
+    The f64 pin with a per-case bound (bf16 and f16, tile edges, stress inputs) is tests/test_freq_kernels_gpu.py."""
     from fcvsr_amd import hip
     L = hip.lib()
     g0 = torch.Generator().manual_seed(3)
