@@ -1,0 +1,203 @@
+// Full-reference scoring, the device end: the sum of squared sample differences of P pairs of planes inside a crop border, in exact
+// integers (the contract is fcvsr_amd/harness/reference.py, plane_sse_host).  Integer arithmetic only, no atomics: every workgroup
+// writes its own u64 partial sum and a second launch adds them in a fixed order, as shots.hip and active.hip do.  Per-frame and
+// whole-video PSNR then do not depend on how the frames fall into groups.
+//
+// A workgroup is four waves and owns, of one pair of planes, a tile of kRows rows x a span of kSpanBytes bytes of the cropped row
+// (16 bytes per lane and plane: one global_load_dwordx4 each).  Wave w takes the rows w, w + 4, .. of the tile in kIters batches of
+// kBatch rows; the 2 kBatch loads of a batch are issued together.  A chunk starts at the first cropped sample of its row, so the
+// loads carry the sample's alignment only (the two planes of a pair, views of an I420 buffer or of a ring, rarely share a 16-byte
+// phase anyway).  A row's tail shorter than a chunk is read as the last 16 bytes of the cropped row, with the bytes that the chunk
+// before has counted zeroed on both sides; only rows shorter than one chunk are read sample by sample (zero-filled, which adds
+// nothing).  Nothing outside [crop, h - crop) x [crop, w - crop) is read.
+//
+// (a - b)^2 summed over a word is a.a + b.b - 2 a.b, three dot instructions per word (v_dot4_u32_u8 / v_dot2_u32_u16) in place of an
+// unpack, a subtract and a multiply-add per sample.  The u32 arithmetic wraps in between and is exact at the end: the true sum of a
+// lane, and of a wave, is bounded below 2^32 by the static_assert.
+#include "common.h"
+
+namespace fcvsr {
+namespace {
+
+constexpr int kLanes = 64;
+constexpr int kWaves = 4;
+constexpr int kThreads = kLanes * kWaves;
+constexpr int kChunk = 16;                      // bytes per lane, row and plane
+constexpr int kSpanBytes = kLanes * kChunk;     // bytes of a cropped row per workgroup
+constexpr int kBatch = 4;                       // rows of a wave whose loads are in flight together (two planes: 8 loads)
+constexpr int kIters = 2;                       // batches per wave
+constexpr int kRows = kWaves * kBatch * kIters; // rows of a tile
+constexpr int kSumThreads = 256;
+
+static_assert(kSpanBytes == FCVSR_PLANE_SSE_SPAN_BYTES && kRows == FCVSR_PLANE_SSE_ROWS, "the header's tile sizes the caller's scratch");
+// A squared difference is at most 255^2 (uint8) or 1023^2 < 2^20 (uint16, samples clamped to 1023).  A lane adds kChunk (kChunk / 2)
+// of them per row over kBatch * kIters rows, and the wave reduction adds kLanes such sums in u32.
+constexpr unsigned long long kChunkMax = (kChunk * 255ull * 255ull > (kChunk / 2) * 1023ull * 1023ull) ? kChunk * 255ull * 255ull
+                                                                                                       : (kChunk / 2) * 1023ull * 1023ull;
+static_assert(kChunkMax * kBatch * kIters * kLanes <= 0xffffffffull, "a wave's sum of its rows must fit in 32 bits");
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ u16x2 halves(unsigned w) {
+  u16x2 v;
+  __builtin_memcpy(&v, &w, 4);
+  return v;
+}
+
+// uint16 samples are read as min(k, 1023), both halves of a word at once (v_pk_min_u16)
+__device__ __forceinline__ unsigned clamp10(unsigned w) {
+  u16x2 v = __builtin_elementwise_min(halves(w), u16x2{1023, 1023});
+  __builtin_memcpy(&w, &v, 4);
+  return w;
+}
+
+// Bytes z .. 15 of a chunk, the bytes below z zeroed (0 <= z < 16): the word that starts at byte first_byte
+__device__ __forceinline__ unsigned keep_from(unsigned w, int first_byte, int z) {
+  const int k = z - first_byte;                 // bytes of this word to zero
+  return k <= 0 ? w : k >= 4 ? 0u : w & (0xffffffffu << (8 * k));
+}
+
+// The lane's 16 bytes of one cropped row.  left: bytes of the cropped row from p on - a whole chunk (>= kChunk), a tail, or nothing
+// (<= 0: p is never dereferenced).  BACK: the cropped row holds at least one chunk, and a tail is the last 16 bytes of the row with
+// the bytes the lane before has already counted zeroed, on both sides alike: one load, still inside the crop.  Otherwise (rows shorter
+// than a chunk) the tail is read byte by byte and zero-filled.
+template <int E, bool BACK>
+__device__ __forceinline__ u32x4 load_chunk(const unsigned char* p, long long left) {
+  u32x4 v = {0u, 0u, 0u, 0u};
+  if (BACK) {                                   // one load path for whole chunks (z = 0 keeps every byte) and tails
+    if (left > 0) {
+      const int z = left >= kChunk ? 0 : kChunk - (int)left;
+      __builtin_memcpy(&v, __builtin_assume_aligned(p - z, E), kChunk);
+      v = u32x4{keep_from(v.x, 0, z), keep_from(v.y, 4, z), keep_from(v.z, 8, z), keep_from(v.w, 12, z)};
+    }
+  } else if (left >= kChunk) {
+    __builtin_memcpy(&v, __builtin_assume_aligned(p, E), kChunk);
+  } else if (left > 0) {
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < kChunk; ++j)
+      if (j < left) w[j / 4] |= (unsigned)p[j] << (8 * (j % 4));
+    v = u32x4{w[0], w[1], w[2], w[3]};
+  }
+  if (E == 2) v = u32x4{clamp10(v.x), clamp10(v.y), clamp10(v.z), clamp10(v.w)};
+  return v;
+}
+
+// acc + the sum of the squared differences of the samples of one word, modulo 2^32
+template <int E>
+__device__ __forceinline__ unsigned sq_word(unsigned a, unsigned b, unsigned acc) {
+  if (E == 1) {
+    acc = __builtin_amdgcn_udot4(a, a, acc, false);
+    acc = __builtin_amdgcn_udot4(b, b, acc, false);
+    return acc - 2u * __builtin_amdgcn_udot4(a, b, 0u, false);
+  }
+  acc = __builtin_amdgcn_udot2(halves(a), halves(a), acc, false);
+  acc = __builtin_amdgcn_udot2(halves(b), halves(b), acc, false);
+  return acc - 2u * __builtin_amdgcn_udot2(halves(a), halves(b), 0u, false);
+}
+
+template <int E>
+__device__ __forceinline__ unsigned sq_chunk(u32x4 a, u32x4 b, unsigned acc) {
+  return sq_word<E>(a.w, b.w, sq_word<E>(a.z, b.z, sq_word<E>(a.y, b.y, sq_word<E>(a.x, b.x, acc))));
+}
+
+struct SseArgs {
+  const unsigned char* a;        // the first cropped sample of plane 0
+  const unsigned char* b;
+  long long sa, sb;              // plane pitch, in bytes
+  long long rowbytes, cropbytes; // bytes of a whole row and of its cropped part
+  int hc;                        // cropped rows
+};
+
+// grid (spans, row tiles, planes).  partial[plane][tile][span] = this tile's sum.
+template <int E, bool BACK>
+__global__ __launch_bounds__(kThreads) void plane_sse_kernel(SseArgs g, unsigned long long* __restrict__ partial) {
+  __shared__ unsigned sm[kWaves];
+  const int lane = threadIdx.x % kLanes, wave = threadIdx.x / kLanes;
+  const int span = blockIdx.x, tile = blockIdx.y;
+  const long long p = blockIdx.z;
+  const long long off = (long long)span * kSpanBytes + lane * kChunk;
+  const long long left = g.cropbytes - off;
+  const unsigned char* pa = g.a + p * g.sa + off;
+  const unsigned char* pb = g.b + p * g.sb + off;
+  unsigned acc = 0u;
+  for (int it = 0; it < kIters; ++it) {
+    const int r0 = tile * kRows + it * (kWaves * kBatch) + wave;    // the batch: rows r0, r0 + 4, ..
+    if (r0 >= g.hc) break;                                          // the same in the whole wave; the barrier comes after the loop
+    u32x4 fa[kBatch], fb[kBatch];
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k) {                              // a row below the crop is not read: left 0
+      const long long r = r0 + k * kWaves;
+      const long long l = r < g.hc ? left : 0;
+      fa[k] = load_chunk<E, BACK>(pa + r * g.rowbytes, l);
+      fb[k] = load_chunk<E, BACK>(pb + r * g.rowbytes, l);
+    }
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k) acc = sq_chunk<E>(fa[k], fb[k], acc);
+  }
+  for (int o = kLanes / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if (lane == 0) sm[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) t += sm[w];
+    partial[(p * gridDim.y + tile) * gridDim.x + span] = t;
+  }
+}
+
+// grid (planes).  out[plane] = sum of the plane's nparts partials: strided per thread, then the wave, then the four waves.
+__global__ __launch_bounds__(kSumThreads) void plane_sse_sum_kernel(const unsigned long long* __restrict__ partial, int nparts,
+                                                                    long long* __restrict__ out) {
+  __shared__ unsigned long long sm[kSumThreads / kLanes];
+  const unsigned long long* pp = partial + (long long)blockIdx.x * nparts;
+  unsigned long long s = 0;
+  for (int t = threadIdx.x; t < nparts; t += kSumThreads) s += pp[t];
+  for (int o = kLanes / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (threadIdx.x % kLanes == 0) sm[threadIdx.x / kLanes] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < kSumThreads / kLanes; ++w) t += sm[w];
+    out[blockIdx.x] = (long long)t;
+  }
+}
+
+}  // namespace
+}  // namespace fcvsr
+
+extern "C" int fcvsr_plane_sse(const void* a, const void* b, int elem_size, int P, int h, int w, long long a_stride, long long b_stride,
+                               int crop, void* scratch, long long scratch_bytes, long long* out, void* stream) {
+  using namespace fcvsr;
+  FCVSR_CHECK_ARG(elem_size == 1 || elem_size == 2, "elem_size: 1 (uint8) or 2 (uint16)");
+  FCVSR_CHECK_ARG(P >= 0 && P <= 65535, "P: 0 .. 65535 planes");
+  FCVSR_CHECK_ARG(h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 20), "h and w: 1 .. 2^20");
+  FCVSR_CHECK_ARG(crop >= 0 && 2ll * crop < (h < w ? h : w), "crop: 0 <= 2 crop < min(h, w)");
+  FCVSR_CHECK_ARG(a_stride >= 0 && b_stride >= 0 && a_stride <= (1ll << 40) && b_stride <= (1ll << 40), "strides: 0 .. 2^40 samples");
+  if (P == 0) return 0;                                            // nothing to read, nothing to write
+  FCVSR_CHECK_ARG(a && b && out && scratch, "null device pointer");
+  FCVSR_CHECK_ARG(((uintptr_t)a % elem_size) == 0 && ((uintptr_t)b % elem_size) == 0, "a and b: aligned to their sample size");
+  FCVSR_CHECK_ARG(((uintptr_t)scratch % 8) == 0 && ((uintptr_t)out % 8) == 0, "scratch and out: 8-byte aligned");
+  const int hc = h - 2 * crop, wc = w - 2 * crop;
+  const int spans = cdiv((long long)wc * elem_size, kSpanBytes), tiles = cdiv(hc, kRows);
+  const long long nparts = (long long)spans * tiles;
+  FCVSR_CHECK_ARG(scratch_bytes >= (long long)P * nparts * 8,
+                  "scratch: P * ceil((w - 2 crop) * elem_size / FCVSR_PLANE_SSE_SPAN_BYTES) * ceil((h - 2 crop) / FCVSR_PLANE_SSE_ROWS) * 8 bytes");
+  const long long first = ((long long)crop * w + crop) * elem_size;
+  const SseArgs g{(const unsigned char*)a + first, (const unsigned char*)b + first, a_stride * elem_size, b_stride * elem_size,
+                  (long long)w * elem_size, (long long)wc * elem_size, hc};
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)spans, (unsigned)tiles, (unsigned)P);
+  unsigned long long* partial = (unsigned long long*)scratch;
+  const bool back = g.cropbytes >= kChunk;                          // a row's tail can be read as the row's last whole chunk
+  if (elem_size == 1 && back) hipLaunchKernelGGL((plane_sse_kernel<1, true>), grid, dim3(kThreads), 0, st, g, partial);
+  else if (elem_size == 1) hipLaunchKernelGGL((plane_sse_kernel<1, false>), grid, dim3(kThreads), 0, st, g, partial);
+  else if (back) hipLaunchKernelGGL((plane_sse_kernel<2, true>), grid, dim3(kThreads), 0, st, g, partial);
+  else hipLaunchKernelGGL((plane_sse_kernel<2, false>), grid, dim3(kThreads), 0, st, g, partial);
+  FCVSR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(plane_sse_sum_kernel, dim3((unsigned)P), dim3(kSumThreads), 0, st, (const unsigned long long*)scratch, (int)nparts,
+                     out);
+  FCVSR_LAUNCH_CHECK();
+  return 0;
+}

@@ -1,8 +1,8 @@
 """The steps every harness entry point shares, each written once: `check_keywords` (the keyword prologue; it returns the resolver),
 `Resolver` (what a batch of windows runs through: `PlainResolver` here, `ensemble.SelfEnsemble`, `tiles.TiledSuperResolver`, and
 `ActiveResolver`, which wraps one of them for ``active=``),
-`check_scores` / `ScoreCollector` (``niqe=`` / ``brisque=``), `deliver_luma` / `deliver_rgb` (SR frames to the planes a file holds)
-and `run_stats`.  `harness.infer`, `harness.yuv` and `harness.stream` are loops around them; a new keyword goes into the step it
+`check_scores` / `ScoreCollector` (``niqe=`` / ``brisque=``), `check_reference` / `ReferenceCollector` (``reference=``),
+`deliver_luma` / `deliver_rgb` (SR frames to the planes a file holds) and `run_stats`.  `harness.infer`, `harness.yuv` and `harness.stream` are loops around them; a new keyword goes into the step it
 belongs to, not into the loops.
 """
 from __future__ import annotations
@@ -265,6 +265,93 @@ class ScoreCollector:
         return out
 
 
+def check_reference(reference, dst, *, crop_border, baseline, bit_depth: int, height: int, width: int, out_shape=None,
+                    reference_pix_fmt=None) -> Optional["ReferenceCollector"]:
+    """The ``reference=`` keyword and its companions (``crop_border``, ``baseline``, ``reference_pix_fmt``, and ``dst=None``, which
+    needs it) of a run on `width` x `height` LR frames of `bit_depth` bits that delivers `out_shape` (None: the 4x frame), before
+    any device or file work (`reference.check_reference` has the rules).  Returns the run's `ReferenceCollector`, None without the
+    keyword."""
+    from . import reference as reference_mod
+    from .resize import check_output_shape
+    Ho, Wo = (4 * height, 4 * width) if out_shape is None else out_shape
+    crop = reference_mod.check_reference(reference, dst is not None, crop_border, baseline, bit_depth, Ho, Wo, reference_pix_fmt)
+    if crop is None:
+        return None
+    if baseline is not None and out_shape is not None:
+        check_output_shape(out_shape, height, width)                  # the baseline goes from the LR frame straight to (Ho, Wo)
+    return ReferenceCollector(crop, bit_depth, Ho, Wo, baseline)
+
+
+# ---- full-reference scores -----------------------------------------------------------------------------------------------------
+
+def _as_samples(t: torch.Tensor) -> torch.Tensor:
+    """int16 views of uint16 planes (`hip.bits16`) back as uint16; everything else as it is."""
+    return t.view(torch.uint16) if t.dtype == torch.int16 else t
+
+
+def baseline_luma(lr: torch.Tensor, shape, colour=None) -> torch.Tensor:
+    """The luma (b,Ho,Wo) of the bicubic baseline of a group (``baseline="bicubic"``), no model pass.  `lr`: the unpadded integer LR
+    centre frames, (b,1,H,W) luma of the Y path - `resize.bicubic_upscale(., 4, out="int")`, or `imresize` straight to `shape` =
+    (Ho, Wo): the baseline of `evaluate_sequence` - or, with `colour`, the decoded (b,3,H,W) RGB frames of the RGB path: the luma of
+    ``rgb_to_i420(imresize(lr, out="int"), colour)``."""
+    from .colour import i420_planes, rgb_to_i420
+    from .resize import bicubic_upscale, imresize
+    H, W = lr.shape[-2:]
+    if colour is None:
+        return (bicubic_upscale(lr, 4, out="int") if shape is None else imresize(lr, output_shape=shape, out="int"))[:, 0]
+    Ho, Wo = (4 * H, 4 * W) if shape is None else shape
+    return i420_planes(rgb_to_i420(imresize(lr, output_shape=(Ho, Wo), out="int"), colour), Ho, Wo)[0]
+
+
+class ReferenceCollector:
+    """The full-reference scores of a run (``reference=``; `harness.reference` is the contract).  `score` computes a group's numbers
+    on the device with no host sync - the exact squared-error sums of the luma planes and of U and V together (`hip.plane_sse`, two
+    calls), the luma SSIM (`device_metrics.frame_metrics`) and, with ``baseline``, the PSNR / SSIM of the baseline luma - and packs
+    them into one int64 tensor of `words` rows of b (f64 values as their bits); `add` holds what it is given, that tensor or its
+    host copy where the caller downloads per group; `stats` makes the scores, one ``scores_from_sse`` for the run."""
+
+    def __init__(self, crop_border: int, bit_depth: int, height: int, width: int, baseline=None):
+        self.crop, self.bit_depth, self.height, self.width, self.baseline = int(crop_border), int(bit_depth), height, width, baseline
+        self.words = 4 if baseline is None else 6                     # sse_y, sse_u, sse_v, ssim_y (, baseline psnr_y, ssim_y)
+        self.held = []
+
+    def _read10(self, g: torch.Tensor) -> torch.Tensor:
+        """Ground-truth samples of a 10-bit run as min(k, 1023) (the delivered ones never exceed it), on the int16 bits."""
+        if self.bit_depth == 8:
+            return g
+        b = hip.bits16(g)
+        return torch.where((b < 0) | (b > 1023), torch.full_like(b, 1023), b).view(torch.uint16)
+
+    def score(self, y: torch.Tensor, uv: torch.Tensor, gy: torch.Tensor, guv: torch.Tensor, base=None) -> torch.Tensor:
+        """y (b,Ho,Wo), uv (2b,Ho/2,Wo/2: U planes, then V planes): the delivered planes; gy, guv: the ground truth's, laid out
+        alike; base: the baseline luma (b,Ho,Wo) with ``baseline``.  Returns the packed (words * b,) int64 device tensor."""
+        from .device_metrics import frame_metrics
+        y, gy = _as_samples(y), self._read10(_as_samples(gy))
+        parts = [hip.plane_sse(y, gy, self.crop), hip.plane_sse(uv, guv, self.crop // 2)]
+        parts.append(frame_metrics(y[:, None], gy[:, None], crop_border=self.crop, quantise=None)[1].view(torch.int64))
+        if self.baseline is not None:
+            parts += [m.view(torch.int64) for m in frame_metrics(_as_samples(base)[:, None], gy[:, None], crop_border=self.crop,
+                                                                 quantise=None)]
+        return torch.cat(parts)
+
+    def add(self, packed) -> None:
+        self.held.append(packed)
+
+    def stats(self) -> dict:
+        """The keys of `reference.sequence_scores`, and ``baseline_psnr_y`` / ``baseline_ssim_y`` with their means."""
+        from . import reference as reference_mod
+        rows = [(h.cpu().numpy() if isinstance(h, torch.Tensor) else np.asarray(h)).reshape(self.words, -1) for h in self.held]
+        a = np.concatenate(rows, 1) if rows else np.zeros((self.words, 0), dtype=np.int64)
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        out = reference_mod.sequence_scores(a[:3].T, a[3].view(np.float64), reference_mod.plane_sizes(self.height, self.width, self.crop),
+                                            reference_mod.PEAKS[self.bit_depth])
+        if self.baseline is not None:
+            for k, name in ((4, "baseline_psnr_y"), (5, "baseline_ssim_y")):
+                out[name] = a[k].view(np.float64).copy()
+                out[name + "_mean"] = float(np.mean(out[name])) if out[name].size else float("nan")
+        return out
+
+
 # ---- delivery ------------------------------------------------------------------------------------------------------------------
 
 def deliver_luma(ysr: torch.Tensor, uv: torch.Tensor, shape):
@@ -287,12 +374,13 @@ def deliver_rgb(sr: torch.Tensor, colour, shape) -> torch.Tensor:
 
 
 def run_stats(frames: int, seconds: float, bytes_read: int, bytes_written: int, out_size, scores=(), cuts=None, active=None,
-              tiles=None) -> dict:
+              tiles=None, reference=None) -> dict:
     """The stats every file / stream entry point returns: `out_size` is (width, height); `scores` (`ScoreCollector.stats`),
     ``"cuts"`` and ``"active"`` (`active`: the run's `active.ActivePlan`; the list of (first frame, box) changes) are there when the
     keywords were; `tiles`: the run's resolver, whose ``"tiles_total"`` / ``"tiles_run"`` are added with ``static_tiles=True``
-    (`tiles.tile_counts`)."""
+    (`tiles.tile_counts`); `reference`: the run's `ReferenceCollector`, whose scores are added with ``reference=`` only."""
     from .tiles import tile_counts
     return {"frames": frames, "seconds": seconds, "fps": frames / seconds if seconds > 0 else float("inf"), "bytes_read": bytes_read,
             "bytes_written": bytes_written, "out_size": out_size, **dict(scores), **({} if cuts is None else {"cuts": cuts}),
-            **({} if active is None else {"active": list(active.changes)}), **({} if tiles is None else tile_counts(tiles))}
+            **({} if active is None else {"active": list(active.changes)}), **({} if tiles is None else tile_counts(tiles)),
+            **({} if reference is None else reference.stats())}

@@ -191,7 +191,8 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
                   colour: ColourSpec = ColourSpec(), batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
                   ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0, tile=None,
                   tile_overlap=16, output_shape=None, max_frames: Optional[int] = None, active=None,
-                  static_tiles: bool = False) -> dict:
+                  static_tiles: bool = False, reference=None, reference_pix_fmt: Optional[str] = None, crop_border: int = 4,
+                  baseline: Optional[str] = None) -> dict:
     """Super-resolve raw 4:2:0 video of any length from `src` to `dst` 4x, a chunk of frames at a time.
 
     `src`: a path, or any binary object with ``readinto`` (``sys.stdin.buffer``, a pipe, a socket file); it is never seeked or
@@ -221,13 +222,29 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     inside a group: the ring slots of the previous group's oldest frames may already hold newer frames.  The comparison runs on
     the main stream at the head of the group's step, after the wait for the chunk's upload, and its small download is the one
     host synchronisation of the group.  Running the comparison and its download on the side stream instead, so that they do not
-    wait behind the previous group's model pass, was measured against this placement and made no difference (profiles/NOTES.md)."""
+    wait behind the previous group's model pass, was measured against this placement and made no difference (profiles/NOTES.md).
+
+    ``reference`` / ``crop_border`` as in `harness.yuv.super_resolve_yuv420`, with the same stats keys and values.
+    ``baseline="bicubic"`` (needs ``reference``) adds ``"baseline_psnr_y"`` / ``"baseline_ssim_y"`` and their means, without a
+    model pass: `device_metrics.frame_metrics` of the bicubic luma against the ground truth's - for a one-channel model the
+    unpadded LR luma through `resize.bicubic_upscale(., 4, out="int")` (`imresize` straight to ``output_shape``), exactly the
+    baseline of `evaluate_sequence`; for a three-channel model as in `super_resolve_yuv420_rgb`.  Chroma is not part of it.
+    `reference` is a path, or any object with ``readinto`` (never seeked), whose frames have the delivered size in
+    `reference_pix_fmt` (default `out_pix_fmt`; it must have the run's bit depth).  After every chunk of n source frames exactly n
+    ground-truth frames are read into a second pair of pinned staging buffers, uploaded on the side stream and taken apart by
+    `hip.surface_unpack` into a ring of their own with the slots and the bookkeeping of the frame ring: a frame's slot is free once
+    its group has been scored, so device and pinned memory stay independent of the length.  A group's scores reach the host after
+    its ``done`` event, one small pinned copy.  The ground truth must hold at least as many whole frames as the source: if it ends
+    early every source frame is still written, and ValueError names both counts at the end; bytes beyond the last frame needed are
+    left unread.  ``dst=None`` (needs ``reference``): no pack, no download, no write, ``bytes_written`` 0 - a pure evaluation
+    run."""
     import torch
 
     from .. import hip
     from . import surfaces
     from .colour import i420_planes, yuv420_to_rgb
-    from .steps import ScoreCollector, check_keywords, check_scores, deliver_luma, deliver_rgb, group_boxes, run_stats
+    from .steps import (ScoreCollector, baseline_luma, check_keywords, check_reference, check_scores, deliver_luma, deliver_rgb,
+                        group_boxes, run_stats)
     from .yuv import _check_output_shape_420
 
     surfaces.check_fmt(pix_fmt)
@@ -245,6 +262,9 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
         if colour.bit_depth != bits:
             raise ValueError(f"colour is {colour.bit_depth}-bit, pix_fmt {pix_fmt!r} {bits}-bit")
     shape = _check_output_shape_420(output_shape, W, H, chroma=C == 1)
+    ref = check_reference(reference, dst, crop_border=crop_border, baseline=baseline, bit_depth=bits, height=H, width=W,
+                          out_shape=shape, reference_pix_fmt=reference_pix_fmt)
+    ref_fmt = out_pix_fmt if reference_pix_fmt is None else reference_pix_fmt
     brisque = check_scores(niqe, brisque, bits, 4 * H, 4 * W)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
                               cuts=cuts, frame_dtype="uint8", channels=(1, 3), who="stream_yuv420", active=active,
@@ -267,6 +287,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     with contextlib.ExitStack() as stack, torch.no_grad(), torch.cuda.device(dev):
         fin = stack.enter_context(open(src, "rb", buffering=0)) if isinstance(src, (str, bytes, os.PathLike)) else src
         fout = stack.enter_context(open(dst, "wb")) if isinstance(dst, (str, bytes, os.PathLike)) else dst
+        gin = stack.enter_context(open(reference, "rb", buffering=0)) if isinstance(reference, (str, bytes, os.PathLike)) else reference
         t0 = time.perf_counter()
         main, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
         # the ring the resolvers read (Y, or decoded RGB), the chroma rings of the Y path, the planes of one chunk for the RGB path
@@ -280,7 +301,19 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
         slots_dev = torch.zeros((B,), dtype=torch.int32, device=dev)
         stage = [torch.empty((B * fb_in,), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         slots_pin = [torch.zeros((B,), dtype=torch.int32, pin_memory=True) for _ in range(2)]
-        out_pin = [torch.empty((B, fb_out), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        out_pin = [torch.empty((B, fb_out), dtype=torch.uint8, pin_memory=True) for _ in range(2)] if fout is not None else None
+        if ref is not None:
+            # the ground truth's own ring (U and V in the two halves of one tensor: a group's chroma is one gather), staging and slots
+            fb_ref, ho2, wo2 = surfaces.frame_bytes(ref_fmt, Wo, Ho), Ho // 2, Wo // 2
+            gring_y = torch.zeros((R, 1, Ho, Wo), dtype=bdt, device=dev)
+            gring_uv = torch.zeros((2 * R, ho2, wo2), dtype=bdt, device=dev)
+            graw_dev = torch.empty((B * fb_ref,), dtype=torch.uint8, device=dev)
+            gslots_dev = torch.zeros((B,), dtype=torch.int32, device=dev)
+            gstage = [torch.empty((B * fb_ref,), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            gslots_pin = [torch.zeros((B,), dtype=torch.int32, pin_memory=True) for _ in range(2)]
+            score_pin = [torch.zeros((ref.words * B,), dtype=torch.int64, pin_memory=True) for _ in range(2)]
+            gwhere, gresident, gfree = {}, deque(), list(range(R - 1, -1, -1))
+        gt_frames, gt_short = 0, False
         uploaded = [torch.cuda.Event() for _ in range(2)]
         done = [torch.cuda.Event() for _ in range(2)]
         gathered = torch.cuda.Event()
@@ -290,8 +323,9 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
         written, groups_run, pending, last_up = 0, 0, None, 0
         scores = ScoreCollector(niqe, brisque, None if C == 1 else "Y")
 
-        def upload(k: int, n: int, first: int) -> None:
-            """Chunk k = frames first .. first + n - 1, staged in stage[k & 1]: into free slots on the side stream."""
+        def upload(k: int, n: int, first: int, ng: int = 0) -> None:
+            """Chunk k = frames first .. first + n - 1, staged in stage[k & 1]: into free slots on the side stream; with it the
+            ground-truth frames first .. first + ng - 1, staged in gstage[k & 1]."""
             nonlocal prev_y, last_up
             last_up = k
             keep = plan.keep_from()
@@ -304,6 +338,14 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
                 where[first + i] = s
                 resident.append(first + i)
                 slots_pin[k & 1][i] = s
+            if ng:                                                        # a ground-truth frame stays until its group has been scored
+                while gresident and gresident[0] < plan.next:
+                    gfree.append(gwhere.pop(gresident.popleft()))
+                if len(gfree) < ng:
+                    raise RuntimeError(f"reference ring of {R} slots is full: {len(gresident)} frames held from {plan.next}")
+                for i in range(ng):
+                    gwhere[first + i] = gslots_pin[k & 1][i] = gfree.pop()
+                    gresident.append(first + i)
             with torch.cuda.stream(side):
                 side.wait_event(gathered)                                 # the gathers launched so far read the slots first
                 raw = raw_dev[:n * fb_in]
@@ -331,6 +373,12 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
                     plan.cuts_known(auto.push(sad), auto.known_upto)
                 if act is not None:                                       # the same: one small download per chunk
                     act.push(lines[0].cpu().numpy(), lines[1].cpu().numpy())
+                if ng:
+                    graw = graw_dev[:ng * fb_ref]
+                    graw.copy_(gstage[k & 1][:ng * fb_ref], non_blocking=True)
+                    gsl = gslots_dev[:ng]
+                    gsl.copy_(gslots_pin[k & 1][:ng], non_blocking=True)
+                    hip.surface_unpack(graw, ref_fmt, Wo, Ho, gsl, gring_y.view(sdt), gring_uv[:R].view(sdt), gring_uv[R:].view(sdt))
                 uploaded[k & 1].record(side)
 
         def launch(centres, rows):
@@ -341,9 +389,15 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
             # a frame number below 0 (a sequence shorter than the window, after its end) counts from the end, as ``x[j]`` does
             idx = [[where[f if f >= 0 else plan.frames + f] for f in row] for row in rows]
             sr = resolver.frames(ring.view(sdt), idx, quantise, H, W, group_boxes(resolver, centres, rows, plan.frames))
-            if C == 1:
+            scored = ref is not None and all(c in gwhere for c in centres)                 # not beyond the end of a short reference
+            if C == 1 or (scored and baseline is not None):
                 cs = torch.tensor([where[c] for c in centres], dtype=torch.int64).to(dev)
+            if C == 1:
                 uv = torch.cat([ring_u[cs], ring_v[cs]], 0).view(sdt)                      # (2b, H/2, W/2)
+            if scored:                                                                    # the group's ground truth, out of its ring
+                gs = torch.tensor([gwhere[c] for c in centres], dtype=torch.int64).to(dev)
+                gy, guv = gring_y[gs][:, 0], gring_uv[torch.cat([gs, gs + R])]
+                lrc = ring[cs][:, :, :H, :W].view(sdt) if baseline is not None else None   # the unpadded LR centre frames
             gathered.record(main)
             feats = scores.features(sr)
             if C == 1:
@@ -351,18 +405,30 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
                 planes = (ysr, uvsr[:b], uvsr[b:])
             else:
                 planes = i420_planes(deliver_rgb(sr, colour, shape), Ho, Wo)
-            out_pin[g & 1][:b].copy_(hip.surface_pack(*planes, out_pix_fmt), non_blocking=True)
+                if scored:
+                    ysr, uvsr = planes[0], torch.cat([hip.bits16(planes[1]), hip.bits16(planes[2])], 0)
+            words = 0
+            if scored:                                                                    # its host copy is read after `done`
+                base = None if baseline is None else baseline_luma(lrc, shape, None if C == 1 else colour)
+                packed = ref.score(ysr, uvsr, gy, guv, base)
+                words = packed.numel()
+                score_pin[g & 1][:words].copy_(packed, non_blocking=True)
+            if fout is not None:
+                out_pin[g & 1][:b].copy_(hip.surface_pack(*planes, out_pix_fmt), non_blocking=True)
             done[g & 1].record(main)
             groups_run += 1
-            return g, b, feats
+            return g, b, feats, words
 
         def deliver(group) -> None:
             """The write of a launched group, and its scores' features to the host."""
             nonlocal written
-            g, b, feats = group
+            g, b, feats, words = group
             done[g & 1].synchronize()
-            _write_all(fout, memoryview(out_pin[g & 1][:b].numpy()).cast("B"))
-            written += b * fb_out
+            if fout is not None:
+                _write_all(fout, memoryview(out_pin[g & 1][:b].numpy()).cast("B"))
+                written += b * fb_out
+            if words:
+                ref.add(score_pin[g & 1][:words].numpy().copy())
             scores.add(tuple(f if f is None else f.cpu().numpy() for f in feats))      # after `done`: it waits for nothing newer
 
         k, stray, eof = 0, 0, False
@@ -374,8 +440,12 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
             n, rest = divmod(got, fb_in)
             eof = got < want * fb_in or (max_frames is not None and plan.frames + n >= max_frames)
             stray = rest
+            ng = 0
+            if ref is not None and n and not gt_short:                    # exactly n ground-truth frames, as long as there are any
+                ng = _read_into(gin, memoryview(gstage[k & 1].numpy())[:n * fb_ref]) // fb_ref
+                gt_frames, gt_short = gt_frames + ng, ng < n
             if n:
-                upload(k, n, plan.frames)
+                upload(k, n, plan.frames, ng)
             if eof and auto is not None:
                 plan.cuts_known(auto.end(), FAR)
             plan.arrived(n, eof)
@@ -394,7 +464,11 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
         raise ValueError("the stream holds no frames")
     if stray:
         raise ValueError(f"the stream ends with {stray} stray bytes after {N} whole {W}x{H} {pix_fmt} frames ({fb_in} bytes each)")
+    if ref is not None and gt_frames < N:
+        raise ValueError(f"the reference ends after {gt_frames} whole {Wo}x{Ho} {ref_fmt} frames, the source holds {N}: "
+                         f"{N} frames were super-resolved, none of the scores is returned")
     used = plan.finish()                                                  # ValueError: an explicit cut at or beyond the end
-    stats = run_stats(N, dt, N * fb_in, written, (Wo, Ho), scores.stats(), used, resolver.boxes, resolver)
-    stats.update(ring_frames=R, frames_uploaded=N, h2d_bytes=N * fb_in, d2h_bytes=written)
+    stats = run_stats(N, dt, N * fb_in, written, (Wo, Ho), scores.stats(), used, resolver.boxes, resolver, ref)
+    stats.update(ring_frames=R, frames_uploaded=N, h2d_bytes=N * fb_in + (0 if ref is None else gt_frames * fb_ref),
+                 d2h_bytes=written)                                       # the ground-truth frames are uploaded too
     return stats

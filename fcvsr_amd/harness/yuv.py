@@ -9,6 +9,7 @@ up-sampled 4x by the bicubic chroma kernel (``hip.chroma_up4``).  `upscale_yuv42
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import re
 import time
@@ -20,8 +21,8 @@ import torch
 from .. import hip
 from .colour import ColourSpec, i420_planes, yuv420_to_rgb
 from .shots import detect_cuts, resolve_cuts, windows_for
-from .steps import (ScoreCollector, check_keywords, check_scores, deliver_luma, deliver_rgb, group_boxes, pad_to_multiple,
-                    push_line_sums, run_stats, to_device)
+from .steps import (ScoreCollector, baseline_luma, check_keywords, check_reference, check_scores, deliver_luma, deliver_rgb,
+                    group_boxes, pad_to_multiple, push_line_sums, run_stats, to_device)
 from .surfaces import _check_size
 
 
@@ -129,6 +130,31 @@ def write_yuv420(path: str, y: np.ndarray, u: np.ndarray, v: np.ndarray) -> None
         _write_frames(fh, y, u, v)
 
 
+def _map_reference(path: str, width: int, height: int, frames: int, bit_depth: int) -> np.ndarray:
+    """The first `frames` frames of the ground-truth I420 file of ``reference=``, (frames, W*H*3/2) samples as a read-only memory
+    map; ValueError when the file holds fewer whole frames (what follows them is never read)."""
+    dt = _sample_dtype(bit_depth)
+    fs = frame_bytes(width, height)
+    have = os.path.getsize(path) // (fs * dt.itemsize)
+    if have < frames:
+        raise ValueError(f"{path}: the reference holds {have} whole {width}x{height} {bit_depth}-bit 4:2:0 frames, the source {frames}")
+    return np.memmap(path, dtype=dt, mode="r", shape=(frames, fs))
+
+
+def _reference_planes(g: np.ndarray, width: int, height: int, bit_depth: int, dev):
+    """A group of mapped ground-truth frames on the device, laid out as `ReferenceCollector.score` takes them: Y (b,H,W) and the U
+    planes followed by the V planes (2b,H/2,W/2)."""
+    b, ys, cs = g.shape[0], width * height, (width // 2) * (height // 2)
+    gy = to_device(g[:, :ys].reshape(b, height, width), bit_depth, dev)
+    guv = to_device(np.concatenate([g[:, ys:ys + cs], g[:, ys + cs:]], 0).reshape(2 * b, height // 2, width // 2), bit_depth, dev)
+    return gy, guv
+
+
+def _open_dst(dst):
+    """The destination file, or nothing to write to (``dst=None``: a scores-only run)."""
+    return contextlib.nullcontext() if dst is None else open(dst, "wb")
+
+
 def _check_niqe(niqe, bit_depth: int, width: int, height: int):
     """`steps.check_scores` of the `niqe=` keyword for width x height LR frames: the 4x frame is what is scored."""
     check_scores(niqe, None, bit_depth, 4 * height, 4 * width)
@@ -138,7 +164,8 @@ def _check_niqe(niqe, bit_depth: int, width: int, height: int):
 def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, batch: int = 8, padding: str = "replicate",
                          quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
                          ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0,
-                         tile=None, tile_overlap=16, output_shape=None, active=None, static_tiles: bool = False) -> dict:
+                         tile=None, tile_overlap=16, output_shape=None, active=None, static_tiles: bool = False,
+                         reference: Optional[str] = None, crop_border: int = 4) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -173,14 +200,27 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
 
     ``static_tiles`` as in `super_resolve_sequence` (True needs ``tile``): tile windows that did not change inside a group are not
     run again; the file written is the same, and the stats gain ``"tiles_total"`` and ``"tiles_run"`` (tile windows delivered and
-    run through the model)."""
+    run through the model).
+
+    ``reference``: None, or the path of the ground-truth I420 file, of `bit_depth` and of the size that is written, with at least
+    as many frames as `src` (ValueError before any model pass otherwise); it is mapped and uploaded group by group.  The planes
+    that are written - Y, U and V after every other keyword - are scored against it on the device (`harness.reference` is the
+    contract): the stats gain ``"sse"`` (int64 (N,3), exact), ``"psnr_y"``, ``"psnr_u"``, ``"psnr_v"``, ``"psnr_yuv"``, ``"ssim_y"``
+    (f64 (N,)), their ``*_mean``, ``"psnr_{y,u,v,yuv}_global"`` and ``"reference_frames"``; the file written is the same.  Luma is
+    cropped by ``crop_border`` (even; the reference's 4), chroma by half of it.  ``dst=None`` (needs ``reference``): nothing is
+    downloaded or written, ``"bytes_written"`` is 0.  This function takes no ``baseline=`` (the "Bicubic" video of a file is
+    `upscale_yuv420`'s); `harness.stream.stream_yuv420` scores the bicubic baseline next to the same numbers."""
     shape = _check_output_shape_420(output_shape, width, height)
+    ref = check_reference(reference, dst, crop_border=crop_border, baseline=None, bit_depth=bit_depth, height=height,
+                          width=width, out_shape=shape)
     brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
                               cuts=cuts, frame_dtype="uint8", channels=(1,), who="super_resolve_yuv420", active=active,
                               frame_shape=(1, height, width), bit_depth=bit_depth, static_tiles=static_tiles)
     y, u, v = read_yuv420(src, width, height, bit_depth=bit_depth)
     N, H, W = y.shape
+    Ho, Wo = (4 * H, 4 * W) if shape is None else shape
+    gt = None if ref is None else _map_reference(reference, Wo, Ho, N, bit_depth)
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
     x = to_device(y, bit_depth, dev)[:, None]                                             # (N,1,H,W)
@@ -188,19 +228,23 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     push_line_sums(resolver, x)
     x = pad_to_multiple(hip.bits16(x), resolver.multiple).view(x.dtype)                   # the resident frames, zero padded
     written, scores = 0, ScoreCollector(niqe, brisque)
-    with open(dst, "wb") as fh:
+    with _open_dst(dst) as fh:
         for s in range(0, N, batch):
             e = min(N, s + batch)
             idx = windows_for(range(s, e), num_frames, N, padding, cuts)
             sr = resolver.frames(x, idx, quantise, H, W, group_boxes(resolver, range(s, e), idx, N))          # (b,1,4H,4W)
             scores.add(scores.features(sr))
             uv = to_device(np.concatenate([u[s:e], v[s:e]], 0), bit_depth, dev)           # (2b, H/2, W/2)
-            ysr, uvsr = (hip.frames_to_numpy(t) for t in deliver_luma(sr[:, 0], uv, shape))   # resized on the device, then downloaded
-            _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
-            written += ysr.nbytes + uvsr.nbytes
+            planes = deliver_luma(sr[:, 0], uv, shape)                                    # resized on the device
+            if ref is not None:
+                ref.add(ref.score(*planes, *_reference_planes(gt[s:e], Wo, Ho, bit_depth, dev)))
+            if fh is not None:
+                ysr, uvsr = (hip.frames_to_numpy(t) for t in planes)                      # downloaded
+                _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
+                written += ysr.nbytes + uvsr.nbytes
     stats = scores.stats()
-    return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
-                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts, resolver.boxes, resolver)
+    return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written, (Wo, Ho), stats,
+                     cuts, resolver.boxes, resolver, ref)
 
 
 def _check_output_shape_420(output_shape, width: int, height: int, chroma: bool = True):
@@ -218,7 +262,8 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
                              batch: int = 8, padding: str = "replicate", quantise: str = "truncate", num_frames: int = 7,
                              ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None,
                              cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None, active=None,
-                             static_tiles: bool = False) -> dict:
+                             static_tiles: bool = False, reference: Optional[str] = None, crop_border: int = 4,
+                             baseline: Optional[str] = None) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -245,9 +290,16 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
 
     ``static_tiles`` as in `super_resolve_sequence` (True needs ``tile``): tile windows that did not change inside a group are not
     run again; the file written is the same, and the stats gain ``"tiles_total"`` and ``"tiles_run"`` (tile windows delivered and
-    run through the model)."""
+    run through the model).
+
+    ``reference`` / ``crop_border`` / ``dst=None`` as in `super_resolve_yuv420`: the Y, U and V planes of the encoded frames are what
+    is scored.  ``baseline="bicubic"`` (needs ``reference``) adds ``"baseline_psnr_y"`` / ``"baseline_ssim_y"`` and their means,
+    without a model pass: `device_metrics.frame_metrics` of the luma of ``rgb_to_i420(imresize(decoded RGB LR frame, out="int"),
+    colour)`` against the ground truth's."""
     shape = _check_output_shape_420(output_shape, width, height, chroma=False)
     bit_depth = colour.bit_depth if isinstance(colour, ColourSpec) else 8
+    ref = check_reference(reference, dst, crop_border=crop_border, baseline=baseline, bit_depth=bit_depth, height=height,
+                          width=width, out_shape=shape)
     brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
                               cuts=cuts, frame_dtype="uint8", channels=(3,), who="super_resolve_yuv420_rgb", active=active,
@@ -256,6 +308,8 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
         raise ValueError(f"colour must be a ColourSpec, got {type(colour).__name__}")
     mm = _map_frames(src, width, height, bit_depth=bit_depth)
     N, H, W = mm.shape[0], height, width
+    Ho, Wo = (4 * H, 4 * W) if shape is None else shape
+    gt = None if ref is None else _map_reference(reference, Wo, Ho, N, bit_depth)
     dev = next(model.parameters()).device
     t0 = time.perf_counter()
     frames = to_device(mm, bit_depth, dev)                                                    # one host copy of the mapped file
@@ -266,17 +320,25 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     x = yuv420_to_rgb(*i420_planes(frames, H, W), colour)                                     # (N,3,H,W)
     x = pad_to_multiple(hip.bits16(x), resolver.multiple).view(x.dtype)                       # the resident frames, zero padded
     written, scores = 0, ScoreCollector(niqe, brisque, "Y")
-    with open(dst, "wb") as fh:
+    with _open_dst(dst) as fh:
         for s in range(0, N, batch):
             idx = windows_for(range(s, min(N, s + batch)), num_frames, N, padding, cuts)
-            sr = resolver.frames(x, idx, quantise, H, W, group_boxes(resolver, range(s, s + len(idx)), idx, N))
+            e = s + len(idx)
+            sr = resolver.frames(x, idx, quantise, H, W, group_boxes(resolver, range(s, e), idx, N))
             scores.add(scores.features(sr))
-            out = hip.frames_to_numpy(deliver_rgb(sr, colour, shape))                     # (b, Ho Wo 3/2)
-            fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())
-            written += out.nbytes
+            out = deliver_rgb(sr, colour, shape)                                          # (b, Ho Wo 3/2)
+            if ref is not None:
+                ysr, usr, vsr = i420_planes(out, Ho, Wo)
+                base = None if baseline is None else baseline_luma(hip.bits16(x)[s:e, :, :H, :W].view(x.dtype), shape, colour)
+                ref.add(ref.score(ysr, torch.cat([hip.bits16(usr), hip.bits16(vsr)], 0),
+                                  *_reference_planes(gt[s:e], Wo, Ho, bit_depth, dev), base))
+            if fh is not None:
+                out = hip.frames_to_numpy(out)
+                fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())
+                written += out.nbytes
     stats = scores.stats()
-    return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written,
-                     (4 * W, 4 * H) if shape is None else (shape[1], shape[0]), stats, cuts, resolver.boxes, resolver)
+    return run_stats(N, time.perf_counter() - t0, N * frame_bytes(W, H) * (1 if bit_depth == 8 else 2), written, (Wo, Ho), stats,
+                     cuts, resolver.boxes, resolver, ref)
 
 
 @torch.no_grad()

@@ -250,6 +250,7 @@ SIGNATURES = {
     "fcvsr_active_compose": [_VP] + [C.c_longlong] * 4 + [_VP, _VP] + [C.c_longlong] * 3 + [_I] * 9 + [_VP, _VP],
     "fcvsr_surface_unpack": [_VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],
     "fcvsr_surface_pack": [_VP, _VP, _VP, C.c_longlong, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _VP, _VP],
+    "fcvsr_plane_sse": [_VP, _VP, _I, _I, _I, _I, C.c_longlong, C.c_longlong, _I, _VP, C.c_longlong, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
@@ -894,6 +895,43 @@ def surface_pack(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, fmt: str) ->
     with torch.cuda.device(y.device):
         check(lib().fcvsr_surface_pack(y.data_ptr(), u.data_ptr(), v.data_ptr(), y.stride(0), u.stride(0), v.stride(0), code, b, H,
                                        W, out.data_ptr(), stream_ptr()), "fcvsr_surface_pack")
+    return out
+
+
+PLANE_SSE_SPAN_BYTES, PLANE_SSE_ROWS = 1024, 32       # FCVSR_PLANE_SSE_* of include/fcvsr_hip.h: a workgroup's tile, sizes the scratch
+
+
+def plane_sse(a: torch.Tensor, b: torch.Tensor, crop: int = 0) -> torch.Tensor:
+    """fcvsr_plane_sse: `a` and `b` (P,h,w) uint8, or uint16 (10-bit samples; int16 views of the same bits, `bits16`, are taken as
+    uint16) planes of one dtype on the HIP device -> (P,) int64 on the device, element p the sum of ``(a[p] - b[p]) ** 2`` over
+    ``[crop:h-crop, crop:w-crop]`` in exact integers, uint16 samples read as min(k, 1023) (`harness.reference.plane_sse_host` is the
+    contract).  Two launches, no host sync.  Planes whose rows are dense are read where they lie at any plane stride and any
+    sample-aligned address (three tensors, slices of a ring, the Y / U / V views `harness.colour.i420_planes` gives); anything else
+    is made dense first.  P = 0 gives an empty result; ``2 * crop < min(h, w)``."""
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.uint16, torch.int16) or t.dim() != 3:
+            raise ValueError(f"expected uint8 or uint16 (P,h,w) planes, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError("plane_sse runs on the HIP device only (the host path is harness.reference.plane_sse_host)")
+    a, b = bits16(a), bits16(b)
+    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"a and b must share dtype, shape and device, got {a.dtype} {tuple(a.shape)} on {a.device} and "
+                         f"{b.dtype} {tuple(b.shape)} on {b.device}")
+    P, h, w = a.shape
+    crop = int(crop)
+    if P > 65535 or h < 1 or w < 1 or crop < 0 or 2 * crop >= min(h, w):
+        raise ValueError(f"plane_sse: at most 65535 planes of at least 1x1 and 0 <= 2 crop < min(h, w), got {tuple(a.shape)}, crop {crop}")
+    out = torch.empty((P,), dtype=torch.int64, device=a.device)
+    if P == 0:
+        return out
+    a, b = _dense_frames(a), _dense_frames(b)
+    elem = a.element_size()
+    parts = -(-(w - 2 * crop) * elem // PLANE_SSE_SPAN_BYTES) * -(-(h - 2 * crop) // PLANE_SSE_ROWS)
+    scratch = torch.empty((P * parts,), dtype=torch.int64, device=a.device)
+    with torch.cuda.device(a.device):
+        check(lib().fcvsr_plane_sse(a.data_ptr(), b.data_ptr(), elem, P, h, w, a.stride(0), b.stride(0), crop, scratch.data_ptr(),
+                                    scratch.numel() * 8, out.data_ptr(), stream_ptr()), "fcvsr_plane_sse")
     return out
 
 

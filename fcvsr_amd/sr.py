@@ -5,7 +5,9 @@
         ffmpeg -f rawvideo -pix_fmt nv12 -s 1920x1080 -r 24 -i - out.mkv
 
 Nothing but the model and `harness.stream.stream_yuv420` (its docstring says what every option means); the stats go to stderr as
-one JSON line.
+one JSON line.  With ``--reference GT.yuv`` the frames that are written are scored against a ground-truth video of the delivered
+size (PSNR of Y, U, V and all three, SSIM of Y; ``inf`` prints as ``Infinity``), ``--scores-log`` writes them per frame as CSV, and
+``--scores-only`` evaluates without writing DST.
 """
 from __future__ import annotations
 
@@ -66,6 +68,14 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--full-range", action="store_true", help="RGB models: full-range code values")
     p.add_argument("--chroma-loc", default="left", choices=("left", "center"), help="RGB models: chroma siting")
     p.add_argument("--max-frames", type=int, default=None)
+    p.add_argument("--reference", default=None, metavar="PATH", help="ground-truth raw video of the delivered size (- is not taken: "
+                   "stdin is SRC's): PSNR per plane and luma SSIM of the frames that are written go into the stats")
+    p.add_argument("--reference-pix-fmt", choices=PIX_FMTS, default=None, help="default: the output format (same bit depth)")
+    p.add_argument("--crop-border", type=int, default=4, help="--reference: luma border left out of the scores (even; chroma half)")
+    p.add_argument("--baseline", default=None, choices=("bicubic",), help="--reference: also score the bicubic up-scale of the luma")
+    p.add_argument("--scores-only", action="store_true", help="--reference: evaluate only; DST is neither opened nor written")
+    p.add_argument("--scores-log", default=None, metavar="FILE", help="--reference: one CSV line per frame, "
+                   "frame,psnr_y,psnr_u,psnr_v,psnr_yuv,ssim_y, written at the end")
     p.add_argument("--device", default="cuda")
     p.add_argument("src", metavar="SRC")
     p.add_argument("dst", metavar="DST")
@@ -73,7 +83,11 @@ def parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None) -> int:
-    a = parser().parse_args(argv)
+    p = parser()
+    a = p.parse_args(argv)
+    if a.reference is None and (a.scores_only or a.scores_log is not None or a.baseline is not None
+                                or a.reference_pix_fmt is not None):
+        p.error("--scores-only, --scores-log, --baseline and --reference-pix-fmt need --reference")
     import torch
 
     from .arch import CVSR_freq, fcvsr_rgb
@@ -89,15 +103,20 @@ def main(argv=None) -> int:
     if active == "auto":
         from .harness.active import ActiveSpec
         active = ActiveSpec(limit=a.active_limit)
-    stats = stream_yuv420(model, sys.stdin.buffer if a.src == "-" else a.src, sys.stdout.buffer if a.dst == "-" else a.dst,
-                          a.size[0], a.size[1], pix_fmt=a.pix_fmt, out_pix_fmt=a.out_pix_fmt,
+    dst = None if a.scores_only else sys.stdout.buffer if a.dst == "-" else a.dst
+    stats = stream_yuv420(model, sys.stdin.buffer if a.src == "-" else a.src, dst, a.size[0], a.size[1], pix_fmt=a.pix_fmt, out_pix_fmt=a.out_pix_fmt,
                           colour=ColourSpec(a.matrix, a.full_range, a.chroma_loc, bits), batch=a.batch, padding=a.padding,
                           quantise=a.quantise, ensemble=a.ensemble, tile=None if a.tile is None else (a.tile[1], a.tile[0]),
                           tile_overlap=a.tile_overlap, cuts=a.cuts, cut_threshold=a.cut_threshold,
                           output_shape=None if a.output_size is None else (a.output_size[1], a.output_size[0]),
-                          max_frames=a.max_frames, active=active, static_tiles=a.static_tiles)
-    if a.dst == "-":
+                          max_frames=a.max_frames, active=active, static_tiles=a.static_tiles, reference=a.reference,
+                          reference_pix_fmt=a.reference_pix_fmt, crop_border=a.crop_border, baseline=a.baseline)
+    if a.dst == "-" and dst is not None:
         sys.stdout.buffer.flush()
+    if a.scores_log is not None:
+        from .harness.reference import scores_csv
+        with open(a.scores_log, "w") as f:
+            f.write(scores_csv(stats))
     print(json.dumps({k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in stats.items()}), file=sys.stderr)
     return 0
 

@@ -914,6 +914,20 @@ int fcvsr_surface_unpack(const void* raw, int fmt, int n, int H, int W, const in
                          void* ring_u, void* ring_v, void* stream);
 int fcvsr_surface_pack(const void* y, const void* u, const void* v, long long y_stride, long long u_stride, long long v_stride,
                        int fmt, int b, int H, int W, void* out, void* stream);
+/* ---- full-reference scoring of delivered planes (the reference's cal_psnr_ssim works on files on the host; the contract is
+ * fcvsr_amd/harness/reference.py, plane_sse_host) ----------------------------------------------------------------------------------
+ * a, b: P planes each of h x w samples with dense rows, whose planes are a_stride / b_stride SAMPLES apart (three tensors, the Y, U
+ * or V planes of a batch of I420 frames, slices of a ring: read where they lie); elem_size 1 (uint8) or 2 (uint16, a sample above
+ * 1023 reads as 1023); aligned to elem_size, nothing more.  out: DEVICE (P) int64, out[p] = sum of (a - b)^2 over the rows
+ * [crop, h - crop) and columns [crop, w - crop) of plane p, in exact integers: two launches, u64 partial sums per workgroup added in
+ * a fixed order, no atomics, no float.  Nothing outside the cropped region is read.  P = 0 writes nothing.  scratch: DEVICE, 8-byte
+ * aligned, at least P * ceil((w - 2 crop) * elem_size / FCVSR_PLANE_SSE_SPAN_BYTES) * ceil((h - 2 crop) / FCVSR_PLANE_SSE_ROWS) * 8
+ * bytes.  No host sync.  FCVSR_E_ARG before any device call: another elem_size, P outside 0 .. 65535, h or w outside 1 .. 2^20,
+ * crop < 0 or 2 crop >= min(h, w), a negative stride, a null or misaligned pointer, a scratch that is too small. */
+#define FCVSR_PLANE_SSE_SPAN_BYTES 1024
+#define FCVSR_PLANE_SSE_ROWS 32
+int fcvsr_plane_sse(const void* a, const void* b, int elem_size, int P, int h, int w, long long a_stride, long long b_stride, int crop,
+                    void* scratch, long long scratch_bytes, long long* out, void* stream);
 #ifdef __cplusplus
 }
 #endif
