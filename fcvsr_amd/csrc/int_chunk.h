@@ -1,5 +1,5 @@
-// What the exact-integer statistics over resident uint8 / uint16 frames share (active.hip, plane_sse.hip and the tile comparison
-// of tiles.hip; shots.hip, the oldest of them, still has its own copy): a lane takes kChunk bytes of a row in one
+// What the exact-integer statistics over resident uint8 / uint16 frames share (shots.hip, active.hip, plane_sse.hip and the tile
+// comparison of tiles.hip): a lane takes kChunk bytes of a row in one
 // global_load_dwordx4 from an address that carries the sample's alignment only, a tail shorter than a chunk is read byte by byte
 // and zero-filled, uint16 samples are read as min(k, 1023), and u64 partial sums are added by a second launch in a fixed order:
 // integer arithmetic only, no atomics.  A wave sum is the one-line

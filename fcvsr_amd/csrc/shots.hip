@@ -7,51 +7,26 @@
 // it belongs to, and the first frame of a run a second time by the run before it (1 / kRun more traffic, and that line is usually
 // still in L2).  DESIGN.md section 4 has the arithmetic behind kRun and the one-wave workgroup.
 #include "common.h"
+#include "int_chunk.h"
 
 namespace fcvsr {
 namespace {
 
-constexpr int kLanes = 64;                      // one wave per workgroup: no LDS, no barrier
-constexpr int kChunk = 16;                      // bytes per lane and frame
+using int_chunk::kChunk;                        // bytes per lane and frame
+using int_chunk::kLanes;                        // one wave per workgroup: no LDS, no barrier
+using int_chunk::kSumThreads;
+using int_chunk::u32x4;
+// load_chunk<E, A16, WHOLE>: the lane's 16 bytes of one frame, uint16 samples as min(k, 1023).  WHOLE: the tile lies inside the frame.
+// A16 fails where the frame size is no multiple of 16 bytes: every second frame is then off the 16-byte grid.
+using int_chunk::load_chunk;
 constexpr int kTile = kLanes * kChunk;          // bytes of a frame per workgroup
 constexpr int kRun = 8;                         // pairs per workgroup (kRun + 1 frames read)
-constexpr int kSumThreads = 256;
 
 static_assert(kTile == FCVSR_PAIR_SAD_TILE_BYTES, "the header's tile size sizes the caller's scratch array");
 // Per pair a lane adds kChunk differences of at most 255 (uint8) or kChunk / 2 of at most 1023 (uint16, samples clamped to 1023) into
 // a u32, and the wave reduction adds kLanes such sums in u32: both stay far below 2^32.
 constexpr unsigned long long kLaneMax = (kChunk * 255ull > (kChunk / 2) * 1023ull) ? kChunk * 255ull : (kChunk / 2) * 1023ull;
 static_assert(kLaneMax * kLanes <= 0xffffffffull, "a wave's sum of one pair must fit in 32 bits");
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// uint16 samples are read as min(k, 1023), both halves of a word
-__device__ __forceinline__ unsigned clamp10(unsigned w) {
-  const unsigned lo = w & 0xffffu, hi = w >> 16;
-  return (lo < 1023u ? lo : 1023u) | ((hi < 1023u ? hi : 1023u) << 16);
-}
-
-// The lane's 16 bytes of one frame.  left: bytes of the frame from p on - a whole chunk (>= kChunk), a tail that is read byte by
-// byte and zero-filled (two frames agree in the fill, it adds nothing), or nothing (<= 0: p is never dereferenced).
-// WHOLE: the tile lies inside the frame, every lane has a whole chunk and the load is unconditional.
-// A16: every chunk address is a multiple of 16; otherwise the 16-byte load carries the sample's alignment only (frame sizes that
-// are no multiple of 16 bytes shift every second frame off the 16-byte grid).
-template <int E, bool A16, bool WHOLE>
-__device__ __forceinline__ u32x4 load_chunk(const unsigned char* p, long long left) {
-  u32x4 v = {0u, 0u, 0u, 0u};
-  if (WHOLE || left >= kChunk) {
-    if (A16) v = *reinterpret_cast<const u32x4*>(p);
-    else __builtin_memcpy(&v, __builtin_assume_aligned(p, E), kChunk);
-  } else if (left > 0) {
-    unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < kChunk; ++j)
-      if (j < left) w[j / 4] |= (unsigned)p[j] << (8 * (j % 4));
-    v = u32x4{w[0], w[1], w[2], w[3]};
-  }
-  if (E == 2) v = u32x4{clamp10(v.x), clamp10(v.y), clamp10(v.z), clamp10(v.w)};
-  return v;
-}
 
 template <int E>
 __device__ __forceinline__ unsigned sad_word(unsigned a, unsigned b, unsigned acc) {
@@ -109,23 +84,6 @@ __global__ __launch_bounds__(kLanes) void pair_sad_kernel(const unsigned char* _
   else pair_sad_run<E, A16, false>(p, fbytes, left, n, out, tiles);
 }
 
-// grid (npairs).  out[pair] = sum over tiles of partial[pair][tile]: strided per thread, then the wave, then the four waves.
-__global__ __launch_bounds__(kSumThreads) void pair_sad_sum_kernel(const unsigned long long* __restrict__ partial, int tiles,
-                                                                   long long* __restrict__ out) {
-  __shared__ unsigned long long sm[kSumThreads / kLanes];
-  const unsigned long long* pp = partial + (long long)blockIdx.x * tiles;
-  unsigned long long s = 0;
-  for (int t = threadIdx.x; t < tiles; t += kSumThreads) s += pp[t];
-  for (int o = kLanes / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if (threadIdx.x % kLanes == 0) sm[threadIdx.x / kLanes] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < kSumThreads / kLanes; ++w) t += sm[w];
-    out[blockIdx.x] = (long long)t;
-  }
-}
-
 template <int E>
 void launch_pair_sad(const void* frames, long long fbytes, int npairs, int tiles, unsigned long long* partial, hipStream_t st) {
   const dim3 grid((unsigned)tiles, (unsigned)cdiv(npairs, kRun));
@@ -159,8 +117,9 @@ extern "C" int fcvsr_frame_pair_sad(const void* frames, int elem_size, int N, lo
   if (elem_size == 1) launch_pair_sad<1>(frames, fbytes, npairs, (int)tiles, (unsigned long long*)scratch, st);
   else launch_pair_sad<2>(frames, fbytes, npairs, (int)tiles, (unsigned long long*)scratch, st);
   FCVSR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pair_sad_sum_kernel, dim3((unsigned)npairs), dim3(kSumThreads), 0, st, (const unsigned long long*)scratch,
-                     (int)tiles, out);
+  // out[pair] = the sum over tiles of partial[pair][tile]
+  hipLaunchKernelGGL(int_chunk::partial_sum_kernel<kSumThreads>, dim3((unsigned)npairs), dim3(kSumThreads), 0, st,
+                     (const unsigned long long*)scratch, (int)tiles, out);
   FCVSR_LAUNCH_CHECK();
   return 0;
 }

@@ -55,10 +55,6 @@ def band_masks_half(Q: int, H: int, W: int) -> torch.Tensor:
     return _MASKS[key]
 
 
-# integer frame formats of forward_u8 / forward_u16: the suffix of their entry points and the table their samples are read through
-_INT_IO = {torch.uint8: ("u8", hip.u8_table), torch.uint16: ("u16", hip.u16_table)}
-
-
 class Engine:
     def __init__(self, model):
         self._model = weakref.ref(model)
@@ -747,23 +743,20 @@ class Engine:
         ("truncate", the reference's ``.astype(np.uint8)``) or rounding half to even ("round").  The first kernels read the
         uint8 window (pixel k through the table of ``hip.u8_table``) and the last one quantises its f32 result; configurations
         whose first or last layer has no uint8 variant convert in one small kernel on that side."""
-        if quantise not in hip.QUANTISE:
-            raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
-            raise ValueError(f"expected a uint8 tensor, got {getattr(x, 'dtype', type(x))}")
-        m = self._model()
-        with torch.no_grad():
-            return self._forward_checked(x, m, hip.QUANTISE[quantise])
+        return self._forward_int(x, quantise, torch.uint8, "uint8")
 
     def forward_u16(self, x: torch.Tensor, quantise: str = "truncate") -> torch.Tensor:
         """10-bit frames in, 10-bit SR frames out: x (B,T,C,H,W) uint16 (10-bit samples in 16-bit containers) -> (B,C,4H,4W)
         uint16, the samples of ``q(clamp(forward(x_f32), 0, 1) * 1023)`` with x_f32 = ``x.clamp(max=1023).float() / 1023`` computed
         on the host and q as in `forward_u8`.  The divisor is full scale (2^10 - 1); a sample above 1023 is read as 1023.  The same
         kernels as the uint8 path, instantiated for 2-byte samples and the 1024-entry table of ``hip.u16_table``."""
+        return self._forward_int(x, quantise, torch.uint16, "uint16")
+
+    def _forward_int(self, x, quantise, dtype, word):
         if quantise not in hip.QUANTISE:
             raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint16:
-            raise ValueError(f"expected a uint16 tensor, got {getattr(x, 'dtype', type(x))}")
+        if not isinstance(x, torch.Tensor) or x.dtype != dtype:
+            raise ValueError(f"expected a {word} tensor, got {getattr(x, 'dtype', type(x))}")
         m = self._model()
         with torch.no_grad():
             return self._forward_checked(x, m, hip.QUANTISE[quantise])
@@ -791,7 +784,7 @@ class Engine:
             x = self._copy_of(x, contiguous_only=True) if quant is not None else x.contiguous().float()
             self._refresh(dev)
             if quant is not None:
-                _INT_IO[x.dtype][1](dev)            # the table: built once, on the caller's stream and outside any capture
+                hip.sample_table(x.dtype, dev)      # the table: built once, on the caller's stream and outside any capture
             ns = max(1, min(int(getattr(m, "streams", 1)), B))
             flags = (bool(m.trunk16), bool(m.fold_f1), bool(m.fuse_tail), bool(m.fuse_rcb_l0))
             # the input dtype and the quantise mode are part of every key: a uint8 or uint16 call never replays an f32 call's graph,
@@ -862,12 +855,8 @@ class Engine:
         n = m.n_feats
         L = lib()
         st = stream_ptr()
-        int_in = x.dtype in _INT_IO                              # integer frames: read through the table of their format
+        int_in = x.dtype != torch.float32                        # integer frames: read through the table of their format
         odt = x.dtype if quant is not None else torch.float32
-        if int_in:
-            sfx, table = _INT_IO[x.dtype]
-            tab = table(dev)
-            entry = lambda name: (getattr(L, f"{name}_{sfx}"), f"{name}_{sfx}")
         a_t = m.lrelu.weight
         # 16-bit activation storage with trunk16 (feat_extract multiplies in f16 - 8-bit pixels stay exact - and stores its
         # output in the mode's activation dtype)
@@ -879,8 +868,7 @@ class Engine:
         if int_in and not fe_dedicated:
             # the generic feat_extract reads f32: the window is converted once (the same floats as a host-side conversion)
             xf = self._new(dev, *x.shape)
-            fn, what = (L.fcvsr_u8_to_f32, "fcvsr_u8_to_f32") if sfx == "u8" else (L.fcvsr_u16_to_f32, "fcvsr_u16_to_f32")
-            check(fn(x.data_ptr(), tab.data_ptr(), x.numel(), xf.data_ptr(), st), what)
+            hip.samples_to_f32(x, xf)
             x = xf
             int_in = False
         xin = x.view(B, T * Cimg, H, W).permute(0, 2, 3, 1)      # (b,y,x,c) strided view of the NCHW frames
@@ -892,18 +880,8 @@ class Engine:
             # then streams whole DRAM pages instead of a third of each.
             p13 = self._new(dev, 3, 2 * B, H, W, n, dtype=adt)
             wf, bf = self._feat_weights()
-            xv = view(xin)
-            nb = 7 * n // 64
-            P = C.c_void_p * nb
-            ptrs = [p13[k, :B].data_ptr() for k in range(3)] + [f2.data_ptr()] + [p13[k, B:].data_ptr() for k in range(3)]
-            if int_in:
-                fn, what = entry("fcvsr_feat_extract")
-                check(fn(C.byref(xv), tab.data_ptr(), B, H, W, wf.data_ptr(), ptr(bf), nb, P(*ptrs), (C.c_int64 * nb)(*([n] * nb)),
-                         (C.c_int32 * nb)(*([0] * nb)), self._code(adt), st), what)
-            else:
-                check(L.fcvsr_feat_extract(C.byref(xv), B, H, W, wf.data_ptr(), ptr(bf), nb, P(*ptrs),
-                                           (C.c_int64 * nb)(*([n] * nb)), (C.c_int32 * nb)(*([0] * nb)), self._code(adt), st),
-                      "fcvsr_feat_extract")
+            dsts = [p13[k, :B] for k in range(3)] + [f2] + [p13[k, B:] for k in range(3)]
+            hip.feat_extract(xin, B, H, W, wf, bf, dsts, n, self._code(adt))
             x1s, x2s, x3s = p13[0], p13[1], p13[2]
         else:
             f13 = self._new(dev, 2 * B, H, W, 3 * n, dtype=adt)  # [f1 of every clip | f3 of every clip]
@@ -971,57 +949,28 @@ class Engine:
         res = out if (quant is None or base_in_tail) else self._new(dev, B, Cimg, 4 * H, 4 * W)
         out_v = res.permute(0, 2, 3, 1)
         centre = x[:, T // 2].permute(0, 2, 3, 1)                 # (B,H,W,Cimg) view of the centre LR frame
-        cv, ov = view(centre), view(out_v)
-        qv = view(out.permute(0, 2, 3, 1)) if quant is not None else None
-        if quant is not None:                                     # the last kernel's variant follows the result's dtype
-            osfx = _INT_IO[odt][0]
-            out_entry = lambda name: (getattr(L, f"{name}_{osfx}"), f"{name}_{osfx}")
+        q_v = out.permute(0, 2, 3, 1)                             # the last kernel's variant follows the result's dtype
         if not base_in_tail:
-            if int_in:
-                fn, what = entry("fcvsr_bilinear_up4")
-                check(fn(C.byref(cv), tab.data_ptr(), B, H, W, C.byref(ov), st), what)
-            else:
-                check(L.fcvsr_bilinear_up4(C.byref(cv), B, H, W, C.byref(ov), st), "fcvsr_bilinear_up4")
+            hip.bilinear_up4(centre, out_v)
         if fuse_tail:
             # upconv2 (1x1) + PixelShuffle + PReLU + conv_last0 in one kernel: the 64-channel tensor at 4H x 4W is never stored
             dt = self._adt()
             w2, b2, _, _ = self._weights("upconv2", dt, True)
             wl = self._tap_weights("conv_last0", dt)
             bl = self._par.get("conv_last0.bias")
-            u1v = view(u1)
-            if base_in_tail and quant is None:
-                check(L.fcvsr_tail_fused_base(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl),
-                                              C.byref(cv), B, 2 * H, 2 * W, C.byref(ov), st), "fcvsr_tail_fused_base")
-            elif base_in_tail:
-                fn, what = entry("fcvsr_tail_fused_base")
-                check(fn(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), C.byref(cv), tab.data_ptr(),
-                         B, 2 * H, 2 * W, C.byref(qv), quant, st), what)
-            elif quant is None:
-                check(L.fcvsr_tail_fused(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B,
-                                         2 * H, 2 * W, C.byref(ov), st), "fcvsr_tail_fused")
-            else:
-                fn, what = out_entry("fcvsr_tail_fused")
-                check(fn(C.byref(u1v), w2.data_ptr(), ptr(b2), a_t.data_ptr(), wl.data_ptr(), ptr(bl), B, 2 * H, 2 * W, C.byref(ov),
-                         C.byref(qv), quant, st), what)
+            hip.tail_fused(u1, w2, b2, a_t, wl, bl, B, 2 * H, 2 * W, q_v, quant=quant,
+                           centre=centre if base_in_tail else None, base=None if base_in_tail else out_v)
         else:
             u2 = self._new(dev, B, 4 * H, 4 * W, n, dtype=self._adt())
             self._conv("upconv2", [u1], u2, act=ACT_PRELU, slope_t=a_t, ps=True)
             if self.precision != "f32" and n == 64 and Cimg <= 3:
                 # 3x3 up-convs (full / RGB models): conv_last0 as a memory-bound "taps are MFMA columns" pass over u2
                 wl = self._last_weights("conv_last0", self._adt(), Cimg)
-                u2v = view(u2)
-                if quant is None:
-                    check(L.fcvsr_conv_last(C.byref(u2v), wl.data_ptr(), ptr(self._par.get("conv_last0.bias")), B, 4 * H, 4 * W,
-                                            Cimg, C.byref(ov), st), "fcvsr_conv_last")
-                else:
-                    fn, what = out_entry("fcvsr_conv_last")
-                    check(fn(C.byref(u2v), wl.data_ptr(), ptr(self._par.get("conv_last0.bias")), B, 4 * H, 4 * W, Cimg,
-                             C.byref(ov), C.byref(qv), quant, st), what)
+                hip.conv_last(u2, wl, self._par.get("conv_last0.bias"), B, 4 * H, 4 * W, Cimg, out_v, q_v, quant)
             else:
                 self._conv("conv_last0", [u2], out_v, res=[out_v])
                 if quant is not None:
-                    fn, what = out_entry("fcvsr_quantise")
-                    check(fn(res.data_ptr(), res.numel(), quant, out.data_ptr(), st), what)
+                    hip.quantise(res, out, quant)
         if self.taps is not None:
             self.taps["out"] = self._copy_of(out)
         return out

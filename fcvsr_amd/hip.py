@@ -485,13 +485,11 @@ def frame_metric_sums(sr: torch.Tensor, hr: torch.Tensor, quantise: int, crop_bo
     out = torch.empty((N, 2), dtype=torch.float64, device=sr.device)
     s_st, h_st = (C.c_int64 * 4)(*sr.stride()), (C.c_int64 * 4)(*hr.stride())
     win = (C.c_double * 11)(*[float(v) for v in window])
-    if hr.dtype == torch.uint16:
-        check(lib().fcvsr_frame_metrics_u16(sr.data_ptr(), s_st, quantise, hr.data_ptr(), h_st, N, Cc, H, W, crop_border, to_y, win,
-                                            float(PEAK10 if peak is None else peak), out.data_ptr(), scratch.data_ptr(),
-                                            scratch.numel() * 8, stream_ptr()), "fcvsr_frame_metrics_u16")
-        return out
-    check(lib().fcvsr_frame_metrics(sr.data_ptr(), s_st, quantise, hr.data_ptr(), h_st, N, Cc, H, W, crop_border, to_y, win,
-                                    out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, stream_ptr()), "fcvsr_frame_metrics")
+    fmt = hr.dtype if hr.dtype in _INT_FORMATS else torch.uint8        # an hr of any other dtype: the uint8 form's check refuses it
+    fn, name, _ = _entry("frame_metrics", fmt)
+    pk = (float(PEAK10 if peak is None else peak),) if fmt == torch.uint16 else ()      # the SSIM peak: the uint8 form fixes it at 255
+    check(fn(sr.data_ptr(), s_st, quantise, hr.data_ptr(), h_st, N, Cc, H, W, crop_border, to_y, win, *pk, out.data_ptr(),
+             scratch.data_ptr(), scratch.numel() * 8, stream_ptr()), name)
     return out
 
 
@@ -660,11 +658,7 @@ def frame_pair_sad(frames: torch.Tensor) -> torch.Tensor:
     |frames[i+1] - frames[i]| in exact integers, uint16 samples read as min(k, 1023) (`harness.shots.pair_sad_host` is the
     contract).  Two launches, no host sync.  Any C, H, W >= 1; N = 1 gives an empty result; non-contiguous frames are made dense
     first."""
-    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, torch.uint16, torch.int16) or frames.dim() != 4:
-        raise ValueError(f"expected uint8 or uint16 (N,C,H,W) frames, got {getattr(frames, 'dtype', type(frames))} "
-                         f"{tuple(getattr(frames, 'shape', ()))}")
-    if not frames.is_cuda:
-        raise RuntimeError("frame_pair_sad runs on the HIP device only (the host path is harness.shots.pair_sad_host)")
+    _int_samples("frame_pair_sad", "the host path is harness.shots.pair_sad_host", "(N,C,H,W) frames", frames)
     N, samples = frames.shape[0], frames.shape[1] * frames.shape[2] * frames.shape[3]
     if N < 1 or samples < 1:
         raise ValueError(f"frames must hold at least one frame of at least one sample, got {tuple(frames.shape)}")
@@ -747,48 +741,71 @@ def active_compose(sr_box: torch.Tensor, frames: torch.Tensor, centres, box, H: 
 
 
 QUANTISE = {"truncate": QUANT_TRUNCATE, "round": QUANT_ROUND}
-_U8_TABLES = {}
+
+# the integer sample formats, the only description of them: dtype code, peak, and the host expression of table entry k
+_INT_FORMATS = {torch.uint8: (U8, 255, lambda: torch.arange(256, dtype=torch.uint8).float() / 255),
+                torch.uint16: (U16, PEAK10, lambda: torch.arange(PEAK10 + 1, dtype=torch.int32).float() / PEAK10)}
+_SAMPLE_TABLES = {}
+
+
+def sample_table(dtype: torch.dtype, device) -> torch.Tensor:
+    """The f32 table the entry points of integer format `dtype` read their samples through, on `device` (`u8_table` / `u16_table`
+    describe the two).  Built once per format and device, synchronised; create it outside stream fan-out and graph capture."""
+    key = (dtype, str(torch.device(device)))
+    t = _SAMPLE_TABLES.get(key)
+    if t is None:
+        t = _INT_FORMATS[dtype][2]().to(device)
+        torch.cuda.synchronize(device)          # readers on any stream find it complete
+        _SAMPLE_TABLES[key] = t
+    return t
 
 
 def u8_table(device) -> torch.Tensor:
     """The 256-entry f32 table of the uint8 entry points on `device`: entry k is the f32 that ``uint8 -> .float() / 255`` gives on
     the host, so a kernel fed uint8 frames sees the floats of a caller that converts its frames on the host.  Built once per device
     (create it outside stream fan-out and graph capture: Engine.forward_u8's first pass does)."""
-    key = str(torch.device(device))
-    t = _U8_TABLES.get(key)
-    if t is None:
-        t = (torch.arange(256, dtype=torch.uint8).float() / 255).to(device)
-        torch.cuda.synchronize(device)          # readers on any stream find it complete
-        _U8_TABLES[key] = t
-    return t
-
-
-_U16_TABLES = {}
+    return sample_table(torch.uint8, device)
 
 
 def u16_table(device) -> torch.Tensor:
     """The 1024-entry f32 table of the uint16 (10-bit) entry points on `device`: entry k is the f32 that ``k.float() / 1023`` gives
     on the host.  The kernels clamp the index to 1023, so a sample above 1023 in its 16-bit container reads the last entry (the
     float path's ``x.clamp(max=1023)``).  Built once per device, outside stream fan-out and graph capture, as `u8_table`."""
-    key = str(torch.device(device))
-    t = _U16_TABLES.get(key)
-    if t is None:
-        t = (torch.arange(PEAK10 + 1, dtype=torch.int32).float() / PEAK10).to(device)
-        torch.cuda.synchronize(device)          # readers on any stream find it complete
-        _U16_TABLES[key] = t
-    return t
+    return sample_table(torch.uint16, device)
 
 
-# the integer sample formats: the suffix of their entry points (fcvsr_<name>_u8 / _u16) and the table their samples are read through
-_INT_FORMATS = {torch.uint8: ("_u8", u8_table), torch.uint16: ("_u16", u16_table)}
+def _family(name: str, f32: bool = True):
+    """{dtype: symbol} of a kernel family with regular names: fcvsr_<name>_u8 / _u16 and, where there is one, fcvsr_<name> for f32."""
+    d = {torch.uint8: f"fcvsr_{name}_u8", torch.uint16: f"fcvsr_{name}_u16"}
+    return {torch.float32: f"fcvsr_{name}", **d} if f32 else d
 
 
-def _format_args(dtype: torch.dtype, device):
-    """(entry-point suffix, leading table arguments) for frames of `dtype`: f32 frames have neither."""
-    if dtype == torch.float32:
-        return "", ()
-    suffix, table = _INT_FORMATS[dtype]
-    return suffix, (table(device).data_ptr(),)
+# the entry point of every kernel family that has integer forms, by the dtype of the samples it reads (or, for the last kernels
+# of the model, writes).  The names are stated here and nowhere else; `_entry` picks one.
+_ENTRIES = {
+    "samples_to_f32": {torch.uint8: "fcvsr_u8_to_f32", torch.uint16: "fcvsr_u16_to_f32"},        # the format is a prefix
+    "chroma_up4": {torch.uint8: "fcvsr_chroma_up4", torch.uint16: "fcvsr_chroma_up4_u16"},       # the uint8 form has no suffix
+    "frame_metrics": {torch.uint8: "fcvsr_frame_metrics", torch.uint16: "fcvsr_frame_metrics_u16"},      # by the dtype of hr
+    "feat_extract": _family("feat_extract"),
+    "bilinear_up4": _family("bilinear_up4"),
+    "tail_fused": _family("tail_fused"),
+    "tail_fused_base": _family("tail_fused_base"),
+    "conv_last": _family("conv_last"),
+    "quantise": _family("quantise", f32=False),
+    "clip_batch": _family("clip_batch", f32=False),
+    "ensemble_windows": _family("ensemble_windows"),
+    "tile_windows": _family("tile_windows"),
+    "tile_windows_sel": _family("tile_windows_sel"),
+    "tile_pairs_equal": _family("tile_pairs_equal"),
+}
+
+
+def _entry(family: str, dtype: torch.dtype, table_on=None):
+    """(function, its name, leading table arguments) of `family` for samples of `dtype`.  A family whose integer forms read through
+    the sample table names the device in `table_on`; f32 forms, and families without a table, get no table argument."""
+    name = _ENTRIES[family][dtype]
+    tab = () if table_on is None or dtype == torch.float32 else (sample_table(dtype, table_on).data_ptr(),)
+    return getattr(lib(), name), name, tab
 
 
 def _out_format(dtype: torch.dtype, quantise: Optional[str]):
@@ -797,10 +814,10 @@ def _out_format(dtype: torch.dtype, quantise: Optional[str]):
         if quantise is not None:
             raise ValueError("quantise applies to uint8 / uint16 results only")
         return F32, QUANT_NONE
-    if dtype in tuple(_INT_FORMATS):
+    if dtype in _INT_FORMATS:
         if quantise not in QUANTISE:
             raise ValueError(f'quantise must be "truncate" or "round", got {quantise!r}')
-        return _DT[dtype], QUANTISE[quantise]
+        return _INT_FORMATS[dtype][0], QUANTISE[quantise]
     raise ValueError(f"dtype: torch.float32, torch.uint8 or torch.uint16, got {dtype!r}")
 
 
@@ -848,11 +865,75 @@ def chroma_up4(planes: torch.Tensor) -> torch.Tensor:
     out = torch.empty((P, 4 * h, 4 * w), dtype=planes.dtype, device=planes.device)
     if out.numel() == 0:
         return out
-    suffix, table = _INT_FORMATS[planes.dtype]
-    name = "fcvsr_chroma_up4" + ("" if planes.dtype == torch.uint8 else suffix)      # the uint8 entry point carries no suffix
     with torch.cuda.device(planes.device):
-        check(getattr(lib(), name)(src.data_ptr(), table(planes.device).data_ptr(), P, h, w, out.data_ptr(), stream_ptr()), name)
+        fn, name, tab = _entry("chroma_up4", planes.dtype, planes.device)
+        check(fn(src.data_ptr(), *tab, P, h, w, out.data_ptr(), stream_ptr()), name)
     return out
+
+
+# The model's first and last kernels (`Engine._forward`).  They run inside graph capture and stream fan-out: nothing here allocates
+# or synchronises (the table is a cache hit, `Engine._forward_checked` built it), and the library checks the arguments.  A tensor's
+# dtype selects the entry point and the table together; image tensors come as (b,y,x,c) views of any strides.
+
+def samples_to_f32(x: torch.Tensor, out: torch.Tensor) -> None:
+    """fcvsr_u8_to_f32 / fcvsr_u16_to_f32: the dense uint8 / uint16 samples of `x` through their table into the dense f32 `out`."""
+    fn, name, tab = _entry("samples_to_f32", x.dtype, x.device)
+    check(fn(x.data_ptr(), *tab, x.numel(), out.data_ptr(), stream_ptr()), name)
+
+
+def feat_extract(src: torch.Tensor, B: int, H: int, W: int, wf: torch.Tensor, bf: Optional[torch.Tensor], dsts, n: int,
+                 code: int) -> None:
+    """fcvsr_feat_extract / _u8 / _u16: the dedicated first convolution on the window `src` (B,H,W,7), f32, uint8 or uint16.  Output
+    block k goes to the dense tensor ``dsts[k]`` of `n` channels per pixel, stored as dtype code `code`."""
+    fn, name, tab = _entry("feat_extract", src.dtype, src.device)
+    xv, nb = view(src), len(dsts)
+    check(fn(C.byref(xv), *tab, B, H, W, wf.data_ptr(), ptr(bf), nb, (C.c_void_p * nb)(*[d.data_ptr() for d in dsts]),
+             (C.c_int64 * nb)(*([n] * nb)), (C.c_int32 * nb)(*([0] * nb)), code, stream_ptr()), name)
+
+
+def bilinear_up4(centre: torch.Tensor, out: torch.Tensor) -> None:
+    """fcvsr_bilinear_up4 / _u8 / _u16: the bilinear x4 base skip of `centre` (B,H,W,c), f32, uint8 or uint16, into the f32 `out`
+    (B,4H,4W,c)."""
+    fn, name, tab = _entry("bilinear_up4", centre.dtype, centre.device)
+    cv, ov = view(centre), view(out)
+    check(fn(C.byref(cv), *tab, *centre.shape[:3], C.byref(ov), stream_ptr()), name)
+
+
+def tail_fused(u1: torch.Tensor, w2: torch.Tensor, b2: Optional[torch.Tensor], slope: torch.Tensor, wl: torch.Tensor,
+               bl: Optional[torch.Tensor], B: int, H2: int, W2: int, out: torch.Tensor, *, base: Optional[torch.Tensor] = None,
+               centre: Optional[torch.Tensor] = None, quant: Optional[int] = None) -> None:
+    """fcvsr_tail_fused[_base][_u8|_u16]: the fused end of the S-model up-sampler into `out` (B,2 H2,2 W2,1), f32, or uint8 / uint16
+    quantised by `quant`.  Exactly one of `base` and `centre`: `base` is the f32 tensor that holds the base skip (an f32 `out`
+    accumulates in place, so `base` is then `out` itself; an integer `out` only reads it); `centre` is the LR centre frame
+    (B,H2/2,W2/2,1) of `out`'s dtype, from which the kernel evaluates the base itself."""
+    if (base is None) == (centre is None):
+        raise ValueError("tail_fused takes exactly one of base and centre")
+    integer = out.dtype != torch.float32
+    if base is None:
+        fn, name, tab = _entry("tail_fused_base", out.dtype, out.device)
+    else:
+        fn, name, tab = _entry("tail_fused", out.dtype)
+    u1v, sv, ov = view(u1), view(centre if base is None else base), view(out)
+    lead = (C.byref(sv), *tab) if base is None else ()                      # the centre frame and its table stand before the sizes,
+    dst = (C.byref(sv), C.byref(ov)) if integer and base is not None else (C.byref(ov),)      # a base that is only read before out
+    check(fn(C.byref(u1v), w2.data_ptr(), ptr(b2), slope.data_ptr(), wl.data_ptr(), ptr(bl), *lead, B, H2, W2, *dst,
+             *((quant,) if integer else ()), stream_ptr()), name)
+
+
+def conv_last(u2: torch.Tensor, wl: torch.Tensor, bias: Optional[torch.Tensor], B: int, H4: int, W4: int, Cimg: int,
+              base: torch.Tensor, out: torch.Tensor, quant: Optional[int] = None) -> None:
+    """fcvsr_conv_last / _u8 / _u16: conv_last0 over `u2` (B,H4,W4,64) on top of the f32 base skip `base` into `out` (B,H4,W4,Cimg):
+    f32 (accumulated in place: `base` is `out` itself), or uint8 / uint16 quantised by `quant` (`base` is only read)."""
+    fn, name, _ = _entry("conv_last", out.dtype)
+    u2v, bv, ov = view(u2), view(base), view(out)
+    tail = (C.byref(ov),) if out.dtype == torch.float32 else (C.byref(bv), C.byref(ov), quant)
+    check(fn(C.byref(u2v), wl.data_ptr(), ptr(bias), B, H4, W4, Cimg, *tail, stream_ptr()), name)
+
+
+def quantise(src: torch.Tensor, out: torch.Tensor, quant: int) -> None:
+    """fcvsr_quantise_u8 / _u16: the dense f32 `src` into the dense uint8 / uint16 `out`, quantised by `quant`."""
+    fn, name, _ = _entry("quantise", out.dtype)
+    check(fn(src.data_ptr(), src.numel(), quant, out.data_ptr(), stream_ptr()), name)
 
 
 SURFACE_FMTS = {"yuv420p": 0, "yuv420p10le": 1, "nv12": 2, "p010le": 3}      # enum fcvsr_surface of include/fcvsr_hip.h
@@ -1000,10 +1081,9 @@ def clip_batch(desc: torch.Tensor, s: int, out: torch.Tensor, dtype: torch.dtype
     P, rem = divmod(desc.numel(), C.sizeof(CropDesc))
     if rem or P == 0 or out.numel() != P * s * s:
         raise ValueError(f"{desc.numel()} descriptor bytes / {out.numel()} output elements do not make whole {s} x {s} planes")
-    suffix, table = _INT_FORMATS[dtype]
-    entry = "fcvsr_clip_batch" + suffix
     with torch.cuda.device(out.device):
-        check(getattr(lib(), entry)(desc.data_ptr(), table(out.device).data_ptr(), P, s, out.data_ptr(), stream_ptr()), entry)
+        fn, name, tab = _entry("clip_batch", dtype, out.device)
+        check(fn(desc.data_ptr(), *tab, P, s, out.data_ptr(), stream_ptr()), name)
     return out
 
 
@@ -1025,9 +1105,8 @@ def ensemble_windows(frames: torch.Tensor, idx: torch.Tensor, reverse: bool = Fa
     out_t = torch.empty((4, b, T, Cc, _ceil4(w), _ceil4(h)), dtype=torch.float32, device=dev)
     tail = (N, Cc, h, w, idx.data_ptr(), b, T, int(bool(reverse)), out_a.data_ptr(), out_t.data_ptr())
     with torch.cuda.device(dev):
-        suffix, table = _format_args(frames.dtype, dev)
-        name = "fcvsr_ensemble_windows" + suffix
-        check(getattr(lib(), name)(src.data_ptr(), *table, *tail, stream_ptr()), name)
+        fn, name, tab = _entry("ensemble_windows", frames.dtype, dev)
+        check(fn(src.data_ptr(), *tab, *tail, stream_ptr()), name)
     return out_a, out_t
 
 
@@ -1095,17 +1174,16 @@ def tile_windows(frames: torch.Tensor, idx: torch.Tensor, plan, sel: Optional[to
     src, idx = bits16(frames).contiguous(), idx.contiguous()
     ys, xs, _, _ = plan.device_tables(dev)
     if sel is None:
-        suffix, extra = "", ()
+        family, extra = "tile_windows", ()
         out = torch.empty((b, plan.ny, plan.nx, T, Cc, plan.th, plan.tw), dtype=torch.float32, device=dev)
     else:
         sel = sel.contiguous()
-        suffix, extra = "_sel", (sel.data_ptr(), sel.shape[0])
+        family, extra = "tile_windows_sel", (sel.data_ptr(), sel.shape[0])
         out = torch.empty((sel.shape[0], T, Cc, plan.th, plan.tw), dtype=torch.float32, device=dev)
     tail = (N, Cc, h, w, idx.data_ptr(), b, T, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx, plan.th, plan.tw, *extra, out.data_ptr())
     with torch.cuda.device(dev):
-        fmt, table = _format_args(frames.dtype, dev)
-        name = "fcvsr_tile_windows" + suffix + fmt
-        check(getattr(lib(), name)(src.data_ptr(), *table, *tail, stream_ptr()), name)
+        fn, name, tab = _entry(family, frames.dtype, dev)
+        check(fn(src.data_ptr(), *tab, *tail, stream_ptr()), name)
     return out
 
 
@@ -1138,9 +1216,9 @@ def tile_pairs_equal(frames: torch.Tensor, pairs: torch.Tensor, plan) -> torch.T
     nbytes = P * plan.ny * plan.nx * tile_eq_segments(Cc, plan.th, plan.tw, frames.element_size())
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     out = torch.empty((P, plan.ny, plan.nx), dtype=torch.uint8, device=dev)
-    name = "fcvsr_tile_pairs_equal" + ("" if frames.dtype == torch.float32 else _INT_FORMATS[frames.dtype][0])
     with torch.cuda.device(dev):
-        check(getattr(lib(), name)(src.data_ptr(), N, Cc, h, w, pairs.data_ptr(), P, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx,
+        fn, name, _ = _entry("tile_pairs_equal", frames.dtype)      # compares bits: no table
+        check(fn(src.data_ptr(), N, Cc, h, w, pairs.data_ptr(), P, ys.data_ptr(), plan.ny, xs.data_ptr(), plan.nx,
                                    plan.th, plan.tw, scratch.data_ptr(), nbytes, out.data_ptr(), stream_ptr()), name)
     return out
 

@@ -232,7 +232,7 @@ class DeviceClipSampler:
         self._lr_ptr = np.array([lr.data_ptr() for lr, _ in self.sequences], dtype=np.uint64)
         self._hr_ptr = np.array([hr.data_ptr() for _, hr in self.sequences], dtype=np.uint64)
         self._N, self._H, self._W = (np.array(v, dtype=np.int64) for v in zip(*self.shapes))
-        (hip.u8_table if self.dtype == torch.uint8 else hip.u16_table)(self.device)     # built here, outside any capture
+        hip.sample_table(self.dtype, self.device)                                       # built here, outside any capture
         # Descriptor lifetime: a ring of _RING (pinned host buffer, device buffer, event) slots per batch size.  A slot's event is
         # recorded behind the two launches that read its device buffer (and so behind the upload that read its host buffer);
         # build() waits for that event before it writes the slot again, so neither buffer changes under queued work, however

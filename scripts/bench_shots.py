@@ -99,7 +99,7 @@ def main():
                     "call_gbps": round(nbytes / k_ms[0] / 1e6, 1), "torch_gbps": round(nbytes / t_ms[0] / 1e6, 1)}
             try:
                 by_kernel = kernel_ms(lambda: hip.frame_pair_sad(x), args.iters)
-                mine = {k: v for k, v in by_kernel.items() if "pair_sad" in k}
+                mine = {k: v for k, v in by_kernel.items() if "pair_sad" in k or "partial_sum_kernel" in k}      # both launches
                 case["kernel_ms"] = {k: round(v, 5) for k, v in sorted(mine.items())}
                 case["kernels_gbps"] = round(nbytes / sum(mine.values()) / 1e6, 1) if mine else None
                 case["torch_kernels_ms"] = round(sum(kernel_ms(lambda: torch_sad(x), args.iters).values()), 5)

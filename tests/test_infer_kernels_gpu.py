@@ -121,6 +121,31 @@ def test_bilinear_up4_u16_equals_f32_kernel_on_table_values():
     assert set(range(1024)) <= seen and max(seen) == 65535 and sum(v > 1023 for v in seen) >= 8
 
 
+# ---- samples_to_f32 -------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dt", [torch.uint8, torch.uint16], ids=["u8", "u16"])
+def test_samples_to_f32_reads_every_sample_value_through_the_table_of_its_dtype(dt):
+    """hip.samples_to_f32 == tab[min(k, peak)], bit for bit, on every sample value (uint16: 0..1023 and container values above 1023)
+    at numel 1027 (more than one block, no multiple of it) and, value by value, at numel 1; nothing past numel is written."""
+    from fcvsr_amd import hip
+    if dt == torch.uint8:
+        k = np.arange(1027) % 256
+        src, tab, peak = torch.from_numpy(k.astype(np.uint8)).cuda(), hip.u8_table("cuda"), 255
+    else:
+        k = np.concatenate([np.arange(1024), [1024, 4095, 65535]])
+        src, tab, peak = dev16(k.astype(np.uint16)), hip.u16_table("cuda"), 1023
+    assert tab.numel() == peak + 1 and src.numel() == 1027 and src.dtype == dt
+    want = tab[torch.from_numpy(np.minimum(k, peak)).cuda()]
+    whole = torch.full((1027 + 5,), NAN, device="cuda")
+    hip.samples_to_f32(src, whole[:1027])
+    single = torch.full((1027, 2), NAN, device="cuda")
+    for i in range(1027):
+        hip.samples_to_f32(src[i:i + 1], single[i, :1])
+    torch.cuda.synchronize()
+    assert torch.equal(whole[:1027], want) and bool(torch.isnan(whole[1027:]).all())
+    assert torch.equal(single[:, 0], want) and bool(torch.isnan(single[:, 1]).all())
+
+
 # ---- the fused tail -------------------------------------------------------------------------------------------------------------------
 
 def _tail_dev(p):
