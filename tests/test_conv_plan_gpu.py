@@ -1,4 +1,5 @@
-"""GPU: hip.conv_plan names the kernel that fcvsr_conv2d_mfma really launches, one small problem per non-generic path."""
+"""GPU: hip.conv_plan names the kernel that fcvsr_conv2d_mfma really launches, one small problem per non-generic path.
+What those kernels compute is pinned per element by tests/test_infer_conv_gpu.py (rounded-operand f64 reference, every kernel string)."""
 import pytest
 import torch
 

@@ -23,6 +23,7 @@ def _rand(*s, seed=0):
 
 @pytest.mark.parametrize("cin,cout,k,stride", [(7, 448, 3, 1), (64, 64, 3, 2), (4, 4, 7, 1), (64, 1, 3, 1), (84, 64, 3, 1)])
 def test_conv_direct_vs_torch(cin, cout, k, stride):
+    """The per-element f64 pin of fcvsr_conv2d (all four CO_T, k 1..7, stride 2, views) is tests/test_infer_conv_gpu.py."""
     from fcvsr_amd import hip
     x, w, b = _rand(2, cin, 20, 28), _rand(cout, cin, k, k, seed=1) * 0.1, _rand(cout, seed=2)
     ref = F.leaky_relu(F.conv2d(x, w, b, stride=stride, padding=k // 2), 0.1)
@@ -39,7 +40,8 @@ def test_conv_direct_vs_torch(cin, cout, k, stride):
                                             ([64], 256, 1, True), ([64], 256, 3, True), ([128, 84], 64, 1, False),
                                             ([64], 1, 3, False), ([64], 576, 1, False)])
 def test_conv_mfma_vs_torch(dt, cins, cout, k, ps):
-    """Reference = fp32 conv of the operands rounded to the MFMA dtype (exactly what the kernel multiplies)."""
+    """Reference = fp32 conv of the operands rounded to the MFMA dtype (exactly what the kernel multiplies).
+    The per-element f64 pin of every fcvsr_conv2d_mfma kernel string (derived bound, tile edges) is tests/test_infer_conv_gpu.py."""
     from fcvsr_amd import hip
     tdt = torch.bfloat16 if dt == "bf16" else torch.float16
     B, H, W = 2, 20, 44            # partial tiles in both directions; for 1x1 a flat tail (2*20*44 % 256 != 0)
@@ -629,7 +631,8 @@ def test_conv_resident_weights_pixel_shuffle_matches_generic(monkeypatch):
 @pytest.mark.parametrize("cimg", [1, 3])
 def test_conv_last_kernel_vs_f32_reference(cimg):
     """fcvsr_conv_last (3x3, 64 -> 1 or 3 channels, taps as MFMA columns, read-modify-write of the NCHW result) against torch's f32
-    convolution of the same bf16-rounded operands: bf16 products are exact in f32, only the summation order differs."""
+    convolution of the same bf16-rounded operands: bf16 products are exact in f32, only the summation order differs.
+    The per-element f64 pin (bf16 and f16 tables, 1 x 1 to 21 x 45, the integer forms) is tests/test_infer_conv_gpu.py."""
     import ctypes as C
     from fcvsr_amd import hip
     g0 = torch.Generator().manual_seed(40 + cimg)
