@@ -2,10 +2,15 @@
 //     out += conv_last0( PReLU( PixelShuffle2( upconv2(u1) ) ) )          upconv2: 1x1, 64 -> 256; conv_last0: 3x3, 64 -> 1
 // The 64-channel tensor at the output resolution (B x 4H x 4W x 64: the largest activation of the whole path, 118 MB per
 // clip in 16-bit) is never written.  One workgroup produces an 8 x 32 tile of output pixels:
-//   1. GEMM 1 (v_mfma 32x32x16): the 6 x 18 pixels of u1 under the tile's 10 x 34 halo times the 256 x 64 weight block.  Wave
-//      w owns sub-pixel w (rows w*64 .. w*64+63 of the sub-pixel-major packing), so PixelShuffle is just the LDS address
-//      the result is written to; bias, PReLU, zero padding outside the image and the rounding to the MFMA dtype (what
-//      the stand-alone layer would have stored) happen on the way.
+//   1. GEMM 1 (v_mfma 32x32x16): wave w owns sub-pixel (sy, sx) = (w >> 1, w & 1), i.e. rows w*64 .. w*64+63 of the
+//      sub-pixel-major packing, so PixelShuffle is just the LDS address the result is written to.  Of the 6 x 18 pixels of u1
+//      under the tile's 10 x 34 halo a sub-pixel lands inside the halo for 5 x 17 only (sy = 0 misses it from u1 row 0, sy = 1
+//      from row 5; columns 0 / 17 likewise with sx), so each wave multiplies its own 5 x 17 = 85 live pixels (three 32-pixel
+//      fragments; 4 x 85 = 340: every halo position is produced exactly once) by its 64 x 64 weight block.  Bias, PReLU, zero
+//      padding outside the image and the rounding to the MFMA dtype (what the stand-alone layer would have stored) happen on
+//      the way.  A u2 value is the chain of the same four MFMAs over the same 16-channel steps for the same weight rows and
+//      the same pixel, whichever column of whichever fragment the pixel sits in, and bias, PReLU and rounding are per value:
+//      the result has the bits of a GEMM over all 108 pixels.
 //   2. GEMM 2 (v_mfma 16x16x32): conv_last0 as "taps are output columns": P[pixel][tap] = sum_c u2[pixel][c] * w[tap][c] for
 //      the 340 halo pixels - 44 small MFMAs instead of 576 multiply-adds per output pixel on the vector ALU.
 //   3. out[y][x] += bias + sum_tap P[y+dy][x+dx][tap]   (out holds the bilinear x4 base skip).
@@ -29,8 +34,10 @@ constexpr int kTfTH = 8, kTfTW = 32;                       // output tile: one t
 constexpr int kTfHH = kTfTH + 2, kTfHW = kTfTW + 2;        // halo of the 3x3 convolution (output resolution)
 constexpr int kTfNHP = kTfHH * kTfHW;                      // 340
 constexpr int kTfUH = kTfTH / 2 + 2, kTfUW = kTfTW / 2 + 2;   // 6 x 18 pixels of u1
-constexpr int kTfNU = kTfUH * kTfUW;                       // 108
-constexpr int kTfNF = (kTfNU + 31) / 32;                   // 32-pixel fragments of GEMM 1 (the last one holds 12 pixels)
+constexpr int kTfLH = kTfUH - 1, kTfLW = kTfUW - 1;        // 5 x 17 of them put a given sub-pixel inside the halo: a wave's live pixels
+constexpr int kTfNL = kTfLH * kTfLW;                       // 85
+constexpr int kTfNF = (kTfNL + 31) / 32;                   // 32-pixel fragments of GEMM 1: 3 (the last one holds 21 pixels)
+static_assert(4 * kTfNL == kTfNHP, "the four sub-pixels' live pixels cover the halo exactly once");
 static_assert(kTfTH * kTfTW == 256, "one thread per output pixel");
 constexpr int kTfRow = 64 + 8;                             // halfwords per halo pixel in LDS (padded: conflict-free fragments)
 constexpr int kTfPRow = 9;                                 // floats per pixel of the tap table (odd stride)
@@ -99,16 +106,19 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
   const int per_img = a.tiles_x * a.tiles_y;
   const int HH = 2 * a.H2, WW = 2 * a.W2;
   __syncthreads();
-  // where lane r of fragment nt stores its u1 pixel's sub-pixel `wave` inside the 10 x 34 halo (halfwords; -1: a dead slot or a
-  // position outside the halo): the same for every tile
+  // The wave's live pixels: p in [0, 85) is u1 pixel uy = (1 - sy) + p / 17, ux = (1 - sx) + p % 17 of the 6 x 18 under the tile,
+  // and its sub-pixel (sy, sx) is halo position hr = 2 uy + sy - 1 in [0, 10), hc = 2 ux + sx - 1 in [0, 34).
+  // u2_off: where lane r of fragment nt stores that value inside the 10 x 34 halo (halfwords; -1: one of the 11 surplus slots of
+  // the last fragment): the same for every tile
   int u2_off[kTfNF];
 #pragma unroll
   for (int nt = 0; nt < kTfNF; ++nt) {
     const int p = nt * 32 + (threadIdx.x & 31);
-    const int uy = p / kTfUW, ux = p - uy * kTfUW;
-    const int hr = 2 * uy + (int)(threadIdx.x >> 7) - 1, hc = 2 * ux + (int)((threadIdx.x >> 6) & 1) - 1;
-    const bool keep = p < kTfNU && hr >= 0 && hr < kTfHH && hc >= 0 && hc < kTfHW;
-    u2_off[nt] = keep ? (hr * kTfHW + hc) * kTfRow + 4 * (int)((threadIdx.x >> 5) & 1) : -1;
+    const int sy = threadIdx.x >> 7, sx = (threadIdx.x >> 6) & 1;
+    const int py = p / kTfLW;
+    const int uy = 1 - sy + py, ux = 1 - sx + (p - py * kTfLW);
+    const int hr = 2 * uy + sy - 1, hc = 2 * ux + sx - 1;
+    u2_off[nt] = p < kTfNL ? (hr * kTfHW + hc) * kTfRow + 4 * (int)((threadIdx.x >> 5) & 1) : -1;
   }
   // the slope is the same for every tile: the whole tile loop exists once per PReLU form
   auto run_tiles = [&](auto s01_c) {
@@ -136,12 +146,14 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
   {
     const int r = lane & 31, h = lane >> 5;
     const uint16_t* ub = reinterpret_cast<const uint16_t*>(a.u1.p) + (long long)b * a.u1.sb + h * 8;
+    const int sy = wave >> 1, sx = wave & 1;                // this wave's sub-pixel
     uint4 kf[kTfNF][4];
 #pragma unroll
     for (int nt = 0; nt < kTfNF; ++nt) {
       int p = nt * 32 + r;
-      p = p < kTfNU ? p : kTfNU - 1;
-      const int uy = p / kTfUW, ux = p - uy * kTfUW;
+      p = p < kTfNL ? p : kTfNL - 1;                         // surplus slots load a valid pixel and are never stored
+      const int py = p / kTfLW;
+      const int uy = 1 - sy + py, ux = 1 - sx + (p - py * kTfLW);
       int gy = (Y0 >> 1) - 1 + uy, gx = (X0 >> 1) - 1 + ux;
       gy = gy < 0 ? 0 : (gy > a.H2 - 1 ? a.H2 - 1 : gy);    // clamped pixels only feed halo positions outside the image,
       gx = gx < 0 ? 0 : (gx > a.W2 - 1 ? a.W2 - 1 : gx);    // which are stored as zeros below
@@ -149,7 +161,6 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) kf[nt][kk] = *reinterpret_cast<const uint4*>(up + kk * 16);
     }
-    const int sy = wave >> 1, sx = wave & 1;                // this wave's sub-pixel
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       float4 bq[4];
@@ -187,12 +198,12 @@ __global__ __launch_bounds__(256, 3) void tail_fused_kernel(TailArgs a) {
 #pragma unroll 1
       for (int nt = 0; nt < kTfNF; ++nt) {
         const int p = nt * 32 + r;
-        const int uy = p / kTfUW, ux = p - uy * kTfUW;
+        const int py = p / kTfLW;
+        const int uy = 1 - sy + py, ux = 1 - sx + (p - py * kTfLW);
         const int hr = 2 * uy + sy - 1, hc = 2 * ux + sx - 1;
         const int Y = Y0 - 1 + hr, X = X0 - 1 + hc;
-        const bool keep = p < kTfNU && hr >= 0 && hr < kTfHH && hc >= 0 && hc < kTfHW;
         const bool inside = Y >= 0 && Y < HH && X >= 0 && X < WW;
-        if (keep && !inside) {
+        if (p < kTfNL && !inside) {
 #pragma unroll
           for (int c8 = 0; c8 < 8; ++c8)
             *reinterpret_cast<uint2*>(u2_s + (hr * kTfHW + hc) * kTfRow + 8 * c8 + 4 * h) = make_uint2(0u, 0u);
@@ -295,7 +306,7 @@ static int tail_fused_launch(const fcvsr_view* u1, const void* w2, const float* 
   a.tiles_x = cdiv(2 * W2, kTfTW);
   a.tiles_y = cdiv(2 * H2, kTfTH);
   a.ntiles = B * a.tiles_x * a.tiles_y;
-  static int wgs[64] = {0};                                // three workgroups per CU (48 KB of LDS, 168 registers each)
+  static int wgs[64] = {0};                                // three workgroups per CU (set by the 48 KB of LDS; 142-150 registers)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   if (!wgs[dev]) {
