@@ -249,6 +249,10 @@ class Engine:
     def _new(dev, *shape, dtype=torch.float32):
         return torch.empty(*shape, device=dev, dtype=dtype)
 
+    def _new_like(self, t, dtype=None):
+        """A dense tensor of t's shape (and dtype unless given): every scratch and intermediate tensor of the forward comes from `_new`."""
+        return self._new(t.device, *t.shape, dtype=t.dtype if dtype is None else dtype)
+
     def _channel_sum(self, t):
         B, H, W, Cc = t.shape
         nblk = (H * W + 255) // 256
@@ -632,14 +636,14 @@ class Engine:
             check(L.fcvsr_gc_apply(r.data_ptr(), add.data_ptr(), t2[l].data_ptr(), Rl.data_ptr(), self._code(tdt), 0.2, B,
                                    H, W, n, st), "fcvsr_gc_apply")
             R.append(Rl)
-        dn = [torch.empty_like(R[l]) for l in (0, 1)]
-        up = [torch.empty_like(R[l]) for l in (1, 2)]
+        dn = [self._new_like(R[l]) for l in (0, 1)]
+        up = [self._new_like(R[l]) for l in (1, 2)]
         self._convg(pre + ".down.0", [dict(srcs=[R[l]], dst=dn[l]) for l in (0, 1)])
         self._convg(pre + ".up.0", [dict(srcs=[R[l]], dst=up[l - 1]) for l in (1, 2)])
         outs = []
         for l, x in enumerate(xs):
             B, H, W, _ = x.shape
-            y = torch.empty_like(x)
+            y = self._new_like(x)
             rs = 2.0 if l in (0, 2) else 1.0
             d = dn[l - 1] if l >= 1 else None
             u = up[l] if l <= 1 else None
@@ -671,18 +675,18 @@ class Engine:
                 and B * (H0 // 2) * (W0 // 2) * n * 4 < 2 ** 31):      # the shapes on which the 1x1 layers run the lean kernel
             return self._block_rcb_tail_fused(pre, xs, t2, rr, adds, tdt)
         P = [self._new(dev, B, xs[l].shape[1] // 2, xs[l].shape[2] // 2, n, dtype=tdt) for l in (0, 1)]
-        R = [torch.empty_like(t) for t in t2]
+        R = [self._new_like(t) for t in t2]
         al = (hip.GcApplyLevel * 3)()
         for l in range(3):
             al[l].r, al[l].add, al[l].z, al[l].out = rr[l].data_ptr(), adds[l].data_ptr(), t2[l].data_ptr(), R[l].data_ptr()
             al[l].pool = P[l].data_ptr() if l < 2 else None
             al[l].B, al[l].H, al[l].W = B, xs[l].shape[1], xs[l].shape[2]
         check(L.fcvsr_gc_apply_levels(al, 3, code, self._code(rr[0].dtype), 0.2, n, st), "fcvsr_gc_apply_levels")
-        dn = [torch.empty_like(P[l]) for l in (0, 1)]           # dn[l] lives at level l+1's resolution
-        up = [torch.empty_like(R[l]) for l in (1, 2)]
+        dn = [self._new_like(P[l]) for l in (0, 1)]           # dn[l] lives at level l+1's resolution
+        up = [self._new_like(R[l]) for l in (1, 2)]
         self._convg(pre + ".down.0", [dict(srcs=[P[l]], dst=dn[l]) for l in (0, 1)])
         self._convg(pre + ".up.0", [dict(srcs=[R[l]], dst=up[l - 1]) for l in (1, 2)])
-        outs = [torch.empty_like(x) for x in xs]
+        outs = [self._new_like(x) for x in xs]
         xl = (hip.XscaleLevel * 3)()
         for l in range(3):
             xl[l].x, xl[l].r, xl[l].out = xs[l].data_ptr(), R[l].data_ptr(), outs[l].data_ptr()
@@ -702,8 +706,8 @@ class Engine:
         B = xs[0].shape[0]
         wu, bu, _, _ = self._weights(pre + ".up.0", tdt)
         wd, bd, _, _ = self._weights(pre + ".down.0", tdt)
-        R1, U1, U2 = torch.empty_like(t2[1]), torch.empty_like(t2[1]), torch.empty_like(t2[2])
-        outs = [torch.empty_like(x) for x in xs]
+        R1, U1, U2 = self._new_like(t2[1]), self._new_like(t2[1]), self._new_like(t2[2])
+        outs = [self._new_like(x) for x in xs]
         a = hip.RcbTailArgs()
         for l in range(3):
             a.x[l], a.r[l], a.z[l] = xs[l].data_ptr(), rr[l].data_ptr(), t2[l].data_ptr()
@@ -721,13 +725,19 @@ class Engine:
             t = cur
             for k in range(3):
                 t = self._block_rcb(f"recorb1.body.{g}.body.{k}", t)
+                if self.taps is not None:
+                    for l in range(3):
+                        self._tap(f"sc.g{g}.k{k}.l{l}", t[l])
             last = g == m.SCGroupN - 1
             # the trunk may be 16-bit (trunk16); SCNetbk's outputs o0..o2 leave in out_dtype (their only readers are the MFMA
             # convolutions upconv_fuse, upconv1_L2 and upconv1_L3)
-            nxt = [torch.empty_like(c, dtype=out_dtype if last else c.dtype) for c in cur]
+            nxt = [self._new_like(c, dtype=out_dtype if last else c.dtype) for c in cur]
             # fold SCNetbk's outer skip (x + body(x), :817-821) into the last group conv's epilogue
             grp = [dict(srcs=[t[l]], dst=nxt[l], res=([cur[l], xs[l]] if last else [cur[l]])) for l in range(3)]
             self._convg(f"recorb1.body.{g}.conv", grp)
+            if self.taps is not None:                             # the last group's tensors are o0..o2 (outer skip folded in)
+                for l in range(3):
+                    self._tap(f"sc.g{g}.l{l}", nxt[l])
             cur = nxt
         return cur
 
@@ -904,6 +914,7 @@ class Engine:
         d2 = self._new(dev, B, H // 4, W // 4, n, dtype=tdt)
         self._conv("rconcat1", [d0], d1, stride=2)
         self._conv("rconcat2", [d1], d2, stride=2)
+        self._tap("d1", d1), self._tap("d2", d2)
         # In the 16-bit modes the three sources of upconv_fuse (o0, l2p, l3_2) are stored in the MFMA dtype: they are read only as
         # MFMA operands (also o1 / o2), and their producers round as upconv_fuse's staging of f32 sources would (bit-identical,
         # half the bytes).  l3_2 (n/16 channels) is stored with zero channels up to a multiple of 8 (16-bit sources are 16-byte

@@ -312,14 +312,26 @@ def block_rcb(p: Params, key: str, xs: List[Tensor]) -> List[Tensor]:
     ]
 
 
-def scnet(p: Params, key: str, xs: List[Tensor], G: int) -> List[Tensor]:
+def scnet(p: Params, key: str, xs: List[Tensor], G: int, taps: Optional[dict] = None) -> List[Tensor]:
+    """taps: sc.g{g}.k{k}.l{l} = BlockRCB outputs, sc.g{g}.l{l} = group outputs (the last group's include the outer skip: they
+    are o0..o2, the tensors the engine stores)."""
     cur = xs
     for g in range(G):
         t = cur
         for k in range(3):
             t = block_rcb(p, f"{key}.body.{g}.body.{k}", t)
+            if taps is not None:
+                for l in range(3):
+                    taps[f"sc.g{g}.k{k}.l{l}"] = t[l]
         cur = [c + _conv(p, f"{key}.body.{g}.conv", r) for c, r in zip(cur, t)]
-    return [x + r for x, r in zip(xs, cur)]
+        if taps is not None and g < G - 1:
+            for l in range(3):
+                taps[f"sc.g{g}.l{l}"] = cur[l]
+    outs = [x + r for x, r in zip(xs, cur)]
+    if taps is not None:
+        for l in range(3):
+            taps[f"sc.g{G - 1}.l{l}"] = outs[l]
+    return outs
 
 
 # ----------------------------------------------------------------------------------------------
@@ -353,7 +365,7 @@ def forward(p: Params, x: Tensor, taps: Optional[dict] = None) -> Tensor:
     d0 = mffr(p, "MFFRblock", a2, Q, taps)
     d1 = _conv(p, "rconcat1", d0, stride=2)
     d2 = _conv(p, "rconcat2", d1, stride=2)
-    o0, o1, o2 = scnet(p, "recorb1", [d0, d1, d2], G)
+    o0, o1, o2 = scnet(p, "recorb1", [d0, d1, d2], G, taps)
     a = p["lrelu.weight"]
     l3 = _prelu(_conv(p, "upconv1_L3", o2), a)
     l3_1 = pixel_shuffle2(l3)
@@ -367,6 +379,7 @@ def forward(p: Params, x: Tensor, taps: Optional[dict] = None) -> Tensor:
     base = F.interpolate(x[:, T // 2], scale_factor=4, mode="bilinear", align_corners=False)
     if taps is not None:
         taps["feat"] = feat
+        taps["d1"], taps["d2"] = d1, d2
         taps["sc.o0"], taps["sc.o1"], taps["sc.o2"] = o0, o1, o2
         taps["fz"] = fz
         taps["out"] = out + base
