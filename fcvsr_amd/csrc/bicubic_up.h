@@ -39,7 +39,8 @@ __device__ inline float up_sample(const unsigned short* p, long long off) {   //
 }
 __device__ inline float up_sample(const float* p, long long off) { return p[off]; }
 
-// np.around(np.clip(v, 0, peak)) for the integer forms; f32 as it is
+// np.around(np.clip(v, 0, peak)) for the integer forms; f32 as it is.  A NaN gives sample 0 because of the clamp order (fmaxf
+// drops it for the 0), and rintf is half to even: v is a sum of exact dyadic products, so ties are met and compared exactly.
 __device__ inline void up_result(float v, float& o) { o = v; }
 __device__ inline void up_result(float v, unsigned char& o) { o = (unsigned char)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
 __device__ inline void up_result(float v, unsigned short& o) { o = (unsigned short)rintf(fminf(fmaxf(v, 0.f), 1023.f)); }

@@ -30,7 +30,8 @@ __device__ __forceinline__ float sample_value(const float* tab, T k) {
 }
 
 // the out rule, in f32; `mode` is FCVSR_QUANT_TRUNCATE or FCVSR_QUANT_ROUND, known at compile time (quantise) or at run time
-// (score_common.h frame_sample)
+// (score_common.h frame_sample).  A NaN gives sample 0 because of the clamp order (fmaxf drops it for the 0 before fminf sees it),
+// and the samples equal the harness's at ties (v * PEAK == k + 0.5) because the product is one f32 multiply: no fma, no f64.
 template <int PEAK>
 __device__ __forceinline__ float quantised(float v, int mode) {
   const float q = fminf(fmaxf(v, 0.f), 1.f) * (float)PEAK;
