@@ -143,6 +143,13 @@ class SequenceScores:
     brisque_mean = None
     baseline_brisque = None
     baseline_brisque_mean = None
+    # tOF (tof=True): per frame f64 (0.0 at frame 0 and at shot starts), its mean over all frames and over the real pairs only
+    tof = None
+    tof_mean = None
+    tof_pairs_mean = None
+    baseline_tof = None
+    baseline_tof_mean = None
+    baseline_tof_pairs_mean = None
     # the scene cuts that were used (cuts=): a list of frame numbers, None without the keyword; a plain attribute as well
     cuts = None
     # the (first frame, box) changes of the active box (active=): None without the keyword; a plain attribute as well
@@ -154,7 +161,7 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
                       quantise: str = "truncate", crop_border: int = 4, convert_to=None, return_frames: bool = False,
                       ensemble: Optional[str] = None, niqe=None, baseline: Optional[str] = None, brisque=None,
                       cuts=None, cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None,
-                      active=None, static_tiles: bool = False) -> SequenceScores:
+                      active=None, static_tiles: bool = False, tof: bool = False) -> SequenceScores:
     """Super-resolve a sequence and score every frame against its HR frame on the device (counterpart of the reference's
     eval_seq + cal_psnr_ssim, test_LD_freqCVSR_S_22.py:48-123, metric/psnr_ssim.py:447-485).
 
@@ -197,8 +204,16 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
     ``active`` as in `super_resolve_sequence`: the composed frames are what is scored, resized and returned; the (first frame, box)
     changes of the run come back as `SequenceScores.active` (None without the keyword).
 
-    ``static_tiles`` as in `super_resolve_sequence`: the scores and frames are those of ``static_tiles=False``."""
+    ``static_tiles`` as in `super_resolve_sequence`: the scores and frames are those of ``static_tiles=False``.
+
+    ``tof=True`` adds tOF, the third metric of the reference's test configs (`harness.tof`: the mean distance between the Farneback
+    flow previous -> current frame of the ground truth and that of the SR frames; `SequenceScores.tof`, `.tof_mean` over all frames
+    as mmedit averages it, `.tof_pairs_mean` over the real pairs; `.baseline_tof*` with ``baseline``).  It is scored on the quantised
+    delivered frames, the last frame of a batch carried to the next; frame 0 scores 0.0, and so does the first frame of every shot
+    of ``cuts``.  C = 1, or C = 3 with ``convert_to="Y"`` (the flow works on one plane): anything else is a ValueError.  The flow
+    is `harness.tof.farneback_host`, a restatement of the cv2 call by reading: cv2 was never run against it."""
     from .device_metrics import frame_metrics
+    from .tof import frame_tof, sequence_summary
     from .resize import bicubic_upscale, check_output_shape, imresize
     N, C, H, W = lr.shape
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
@@ -210,6 +225,8 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
         check_output_shape(shape, H, W)
     Ho, Wo = (4 * H, 4 * W) if shape is None else shape
     brisque = check_scores(niqe, brisque, 10 if hr.dtype == torch.uint16 else 8, Ho, Wo)     # ValueError up front
+    if tof and not (C == 1 or (C == 3 and isinstance(convert_to, str) and convert_to.lower() == "y")):
+        raise ValueError(f'tof=True scores one plane: C = 1, or C = 3 with convert_to="Y", got C = {C}, convert_to = {convert_to!r}')
     if tuple(hr.shape) != (N, C, Ho, Wo):
         raise ValueError(f"hr must be (N,C,4H,4W) = {(N, C, Ho, Wo)}, got {tuple(hr.shape)}" if shape is None else
                          f"hr must be (N,C,Ho,Wo) = {(N, C, Ho, Wo)}, got {tuple(hr.shape)}")
@@ -228,18 +245,29 @@ def evaluate_sequence(model, lr: torch.Tensor, hr: torch.Tensor, *, num_frames: 
         frames, else the rule f32 frames are quantised by in the kernels; everything stays on the device.  result(): the row's
         `SequenceScores` entries, fetched once, and the frames that were kept."""
         col, p_dev, s_dev, kept = ScoreCollector(niqe, brisque, "Y" if C == 3 else None), [], [], []
+        t_dev, carry = [], [None, 0]                                  # tof: the last (frame, HR frame) of the batch before; frames seen
+
+        def score_tof(f, hr_b, q):
+            d = f if q is None else _quantised_dev(f, q, peak)        # the delivered integer frames
+            d, g = (d, hr_b) if C == 3 else (bits16(d[:, 0]), bits16(hr_b[:, 0]))
+            local = [c - carry[1] for c in (cuts or ()) if carry[1] <= c < carry[1] + len(d)]
+            t_dev.append(frame_tof(d, g, first=carry[0], cuts=local, rgb=C == 3))
+            carry[:] = [(d[-1], g[-1]), carry[1] + len(d)]
 
         def score(f, hr_b, q):
             p, s = frame_metrics(f, hr_b, crop_border=crop_border, quantise=q, convert_to=convert_to)
             p_dev.append(p)
             s_dev.append(s)
             col.add(col.features(f, q))
+            if tof:
+                score_tof(f, hr_b, q)
             if keep:
                 kept.append(frames_to_numpy(f) if q is None else _quantised(f, q, peak))
 
         def result():
             p, s = torch.cat(p_dev).cpu().numpy(), torch.cat(s_dev).cpu().numpy()
-            return {"psnr": p, "ssim": s, "psnr_mean": float(np.mean(p)), "ssim_mean": float(np.mean(s)), **col.stats()}, kept
+            flow = sequence_summary(torch.cat(t_dev).cpu().numpy(), cuts or ()) if t_dev else {}
+            return {"psnr": p, "ssim": s, "psnr_mean": float(np.mean(p)), "ssim_mean": float(np.mean(s)), **col.stats(), **flow}, kept
         return score, result
     score_sr, result_sr = scorer(return_frames)
     score_base, result_base = scorer(False)

@@ -135,8 +135,10 @@ def check_reference(reference, dst_given: bool, crop_border, baseline, bit_depth
 
 
 def scores_csv(stats: dict) -> str:
-    """One line per frame, ``frame,psnr_y,psnr_u,psnr_v,psnr_yuv,ssim_y``, from the stats of a run with ``reference=``."""
-    lines = ["frame," + ",".join(FRAME_KEYS)]
+    """One line per frame, ``frame,psnr_y,psnr_u,psnr_v,psnr_yuv,ssim_y``, from the stats of a run with ``reference=``; a run with
+    ``tof=True`` has the further column ``tof``."""
+    keys = FRAME_KEYS + (("tof",) if "tof" in stats else ())
+    lines = ["frame," + ",".join(keys)]
     for i in range(int(stats["reference_frames"])):
-        lines.append(f"{i}," + ",".join(repr(float(stats[k][i])) for k in FRAME_KEYS))
+        lines.append(f"{i}," + ",".join(repr(float(stats[k][i])) for k in keys))
     return "\n".join(lines) + "\n"

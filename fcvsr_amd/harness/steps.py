@@ -266,7 +266,7 @@ class ScoreCollector:
 
 
 def check_reference(reference, dst, *, crop_border, baseline, bit_depth: int, height: int, width: int, out_shape=None,
-                    reference_pix_fmt=None) -> Optional["ReferenceCollector"]:
+                    reference_pix_fmt=None, tof: bool = False) -> Optional["ReferenceCollector"]:
     """The ``reference=`` keyword and its companions (``crop_border``, ``baseline``, ``reference_pix_fmt``, and ``dst=None``, which
     needs it) of a run on `width` x `height` LR frames of `bit_depth` bits that delivers `out_shape` (None: the 4x frame), before
     any device or file work (`reference.check_reference` has the rules).  Returns the run's `ReferenceCollector`, None without the
@@ -276,10 +276,12 @@ def check_reference(reference, dst, *, crop_border, baseline, bit_depth: int, he
     Ho, Wo = (4 * height, 4 * width) if out_shape is None else out_shape
     crop = reference_mod.check_reference(reference, dst is not None, crop_border, baseline, bit_depth, Ho, Wo, reference_pix_fmt)
     if crop is None:
+        if tof:
+            raise ValueError("tof=True compares against the ground truth: it needs reference=")
         return None
     if baseline is not None and out_shape is not None:
         check_output_shape(out_shape, height, width)                  # the baseline goes from the LR frame straight to (Ho, Wo)
-    return ReferenceCollector(crop, bit_depth, Ho, Wo, baseline)
+    return ReferenceCollector(crop, bit_depth, Ho, Wo, baseline, bool(tof))
 
 
 # ---- full-reference scores -----------------------------------------------------------------------------------------------------
@@ -308,12 +310,19 @@ class ReferenceCollector:
     on the device with no host sync - the exact squared-error sums of the luma planes and of U and V together (`hip.plane_sse`, two
     calls), the luma SSIM (`device_metrics.frame_metrics`) and, with ``baseline``, the PSNR / SSIM of the baseline luma - and packs
     them into one int64 tensor of `words` rows of b (f64 values as their bits); `add` holds what it is given, that tensor or its
-    host copy where the caller downloads per group; `stats` makes the scores, one ``scores_from_sse`` for the run."""
+    host copy where the caller downloads per group; `stats` makes the scores, one ``scores_from_sse`` for the run.
 
-    def __init__(self, crop_border: int, bit_depth: int, height: int, width: int, baseline=None):
+    With `tof` (``tof=True``; `harness.tof` is the contract) `score` adds the tOF of every delivered luma plane against the ground
+    truth's - and of the baseline luma with ``baseline`` - as further rows of the same tensor: the groups arrive in frame order, and
+    the collector carries a copy of the last (delivered, ground truth) plane pair of a group to the next one."""
+
+    def __init__(self, crop_border: int, bit_depth: int, height: int, width: int, baseline=None, tof: bool = False):
         self.crop, self.bit_depth, self.height, self.width, self.baseline = int(crop_border), int(bit_depth), height, width, baseline
-        self.words = 4 if baseline is None else 6                     # sse_y, sse_u, sse_v, ssim_y (, baseline psnr_y, ssim_y)
+        self.tof = bool(tof)
+        # sse_y, sse_u, sse_v, ssim_y (, baseline psnr_y, ssim_y) (, tof (, baseline tof))
+        self.words = (4 if baseline is None else 6) + (0 if not self.tof else 1 if baseline is None else 2)
         self.held = []
+        self.carry, self.starts = None, []                            # tof: the last planes; per frame, whether it starts a shot
 
     def _read10(self, g: torch.Tensor) -> torch.Tensor:
         """Ground-truth samples of a 10-bit run as min(k, 1023) (the delivered ones never exceed it), on the int16 bits."""
@@ -322,9 +331,10 @@ class ReferenceCollector:
         b = hip.bits16(g)
         return torch.where((b < 0) | (b > 1023), torch.full_like(b, 1023), b).view(torch.uint16)
 
-    def score(self, y: torch.Tensor, uv: torch.Tensor, gy: torch.Tensor, guv: torch.Tensor, base=None) -> torch.Tensor:
+    def score(self, y: torch.Tensor, uv: torch.Tensor, gy: torch.Tensor, guv: torch.Tensor, base=None, cuts=()) -> torch.Tensor:
         """y (b,Ho,Wo), uv (2b,Ho/2,Wo/2: U planes, then V planes): the delivered planes; gy, guv: the ground truth's, laid out
-        alike; base: the baseline luma (b,Ho,Wo) with ``baseline``.  Returns the packed (words * b,) int64 device tensor."""
+        alike; base: the baseline luma (b,Ho,Wo) with ``baseline``; cuts: which of the b frames start a shot (0 .. b-1; read with
+        `tof` only).  Returns the packed (words * b,) int64 device tensor."""
         from .device_metrics import frame_metrics
         y, gy = _as_samples(y), self._read10(_as_samples(gy))
         parts = [hip.plane_sse(y, gy, self.crop), hip.plane_sse(uv, guv, self.crop // 2)]
@@ -332,6 +342,17 @@ class ReferenceCollector:
         if self.baseline is not None:
             parts += [m.view(torch.int64) for m in frame_metrics(_as_samples(base)[:, None], gy[:, None], crop_border=self.crop,
                                                                  quantise=None)]
+        if self.tof:
+            from .tof import frame_tof
+            cuts = sorted(int(c) for c in cuts)
+            prev = self.carry                                         # (y, gy (, base)) of the frame before this group, or None
+            self.starts += [(i in cuts) or (i == 0 and prev is None) for i in range(y.shape[0])]
+            parts.append(frame_tof(y, gy, first=None if prev is None else prev[:2], cuts=cuts).view(torch.int64))
+            if self.baseline is not None:
+                base = _as_samples(base)
+                parts.append(frame_tof(base, gy, first=None if prev is None else (prev[2], prev[1]), cuts=cuts).view(torch.int64))
+            last = (y, gy) if self.baseline is None else (y, gy, base)
+            self.carry = tuple(hip.bits16(t[-1]).clone() for t in last)                   # copies: the planes may lie in a ring
         return torch.cat(parts)
 
     def add(self, packed) -> None:
@@ -349,6 +370,13 @@ class ReferenceCollector:
             for k, name in ((4, "baseline_psnr_y"), (5, "baseline_ssim_y")):
                 out[name] = a[k].view(np.float64).copy()
                 out[name + "_mean"] = float(np.mean(out[name])) if out[name].size else float("nan")
+        if self.tof:
+            k0 = 4 if self.baseline is None else 6
+            pairs = ~np.array(self.starts[:a.shape[1]], dtype=bool)
+            for k, pre in ((k0, ""), (k0 + 1, "baseline_"))[:1 if self.baseline is None else 2]:
+                v = a[k].view(np.float64).copy()
+                out.update({pre + "tof": v, pre + "tof_mean": float(v.mean()) if v.size else float("nan"),
+                            pre + "tof_pairs_mean": float(v[pairs].mean()) if pairs.any() else float("nan")})
         return out
 
 

@@ -192,7 +192,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
                   ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0, tile=None,
                   tile_overlap=16, output_shape=None, max_frames: Optional[int] = None, active=None,
                   static_tiles: bool = False, reference=None, reference_pix_fmt: Optional[str] = None, crop_border: int = 4,
-                  baseline: Optional[str] = None) -> dict:
+                  baseline: Optional[str] = None, tof: bool = False) -> dict:
     """Super-resolve raw 4:2:0 video of any length from `src` to `dst` 4x, a chunk of frames at a time.
 
     `src`: a path, or any binary object with ``readinto`` (``sys.stdin.buffer``, a pipe, a socket file); it is never seeked or
@@ -237,7 +237,11 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
     its ``done`` event, one small pinned copy.  The ground truth must hold at least as many whole frames as the source: if it ends
     early every source frame is still written, and ValueError names both counts at the end; bytes beyond the last frame needed are
     left unread.  ``dst=None`` (needs ``reference``): no pack, no download, no write, ``bytes_written`` 0 - a pure evaluation
-    run."""
+    run.
+
+    ``tof=True`` (needs ``reference``) as in `harness.yuv.super_resolve_yuv420`: ``"tof"``, ``"tof_mean"``, ``"tof_pairs_mean"`` (and
+    ``"baseline_tof*"`` with ``baseline``), the same values as the file entry point gives; one plane pair is carried from group to
+    group on the device, and the values ride in the packed tensor of the group's other scores: no further host sync."""
     import torch
 
     from .. import hip
@@ -263,7 +267,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
             raise ValueError(f"colour is {colour.bit_depth}-bit, pix_fmt {pix_fmt!r} {bits}-bit")
     shape = _check_output_shape_420(output_shape, W, H, chroma=C == 1)
     ref = check_reference(reference, dst, crop_border=crop_border, baseline=baseline, bit_depth=bits, height=H, width=W,
-                          out_shape=shape, reference_pix_fmt=reference_pix_fmt)
+                          out_shape=shape, reference_pix_fmt=reference_pix_fmt, tof=tof)
     ref_fmt = out_pix_fmt if reference_pix_fmt is None else reference_pix_fmt
     brisque = check_scores(niqe, brisque, bits, 4 * H, 4 * W)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
@@ -410,7 +414,7 @@ def stream_yuv420(model, src, dst, width: int, height: int, *, pix_fmt: str = "y
             words = 0
             if scored:                                                                    # its host copy is read after `done`
                 base = None if baseline is None else baseline_luma(lrc, shape, None if C == 1 else colour)
-                packed = ref.score(ysr, uvsr, gy, guv, base)
+                packed = ref.score(ysr, uvsr, gy, guv, base, cuts=[i for i, c in enumerate(centres) if c in (plan.cuts or ())])
                 words = packed.numel()
                 score_pin[g & 1][:words].copy_(packed, non_blocking=True)
             if fout is not None:

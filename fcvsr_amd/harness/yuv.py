@@ -165,7 +165,7 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
                          quantise: str = "truncate", num_frames: int = 7, bit_depth: int = 8,
                          ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None, cut_threshold: float = 10.0,
                          tile=None, tile_overlap=16, output_shape=None, active=None, static_tiles: bool = False,
-                         reference: Optional[str] = None, crop_border: int = 4) -> dict:
+                         reference: Optional[str] = None, crop_border: int = 4, tof: bool = False) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height).
 
     `bit_depth` is 8 (one byte per sample, uint8) or 10 (two bytes per sample, uint16; `yuv_bit_depth` reads it off the file
@@ -209,10 +209,14 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
     (f64 (N,)), their ``*_mean``, ``"psnr_{y,u,v,yuv}_global"`` and ``"reference_frames"``; the file written is the same.  Luma is
     cropped by ``crop_border`` (even; the reference's 4), chroma by half of it.  ``dst=None`` (needs ``reference``): nothing is
     downloaded or written, ``"bytes_written"`` is 0.  This function takes no ``baseline=`` (the "Bicubic" video of a file is
-    `upscale_yuv420`'s); `harness.stream.stream_yuv420` scores the bicubic baseline next to the same numbers."""
+    `upscale_yuv420`'s); `harness.stream.stream_yuv420` scores the bicubic baseline next to the same numbers.
+
+    ``tof=True`` (needs ``reference``, ValueError without): the stats gain ``"tof"`` (f64 (N,)), ``"tof_mean"`` and
+    ``"tof_pairs_mean"``, the tOF of `harness.tof` of the delivered luma planes against the ground truth's, on the device: 0.0 at
+    frame 0 and at every frame of ``cuts``, the last plane pair of a group carried to the next.  The file written is the same."""
     shape = _check_output_shape_420(output_shape, width, height)
     ref = check_reference(reference, dst, crop_border=crop_border, baseline=None, bit_depth=bit_depth, height=height,
-                          width=width, out_shape=shape)
+                          width=width, out_shape=shape, tof=tof)
     brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
                               cuts=cuts, frame_dtype="uint8", channels=(1,), who="super_resolve_yuv420", active=active,
@@ -237,7 +241,8 @@ def super_resolve_yuv420(model, src: str, dst: str, width: int, height: int, *, 
             uv = to_device(np.concatenate([u[s:e], v[s:e]], 0), bit_depth, dev)           # (2b, H/2, W/2)
             planes = deliver_luma(sr[:, 0], uv, shape)                                    # resized on the device
             if ref is not None:
-                ref.add(ref.score(*planes, *_reference_planes(gt[s:e], Wo, Ho, bit_depth, dev)))
+                ref.add(ref.score(*planes, *_reference_planes(gt[s:e], Wo, Ho, bit_depth, dev),
+                                  cuts=[c - s for c in cuts or () if s <= c < e]))
             if fh is not None:
                 ysr, uvsr = (hip.frames_to_numpy(t) for t in planes)                      # downloaded
                 _write_frames(fh, ysr, uvsr[:e - s], uvsr[e - s:])
@@ -263,7 +268,7 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
                              ensemble: Optional[str] = None, niqe=None, brisque=None, cuts=None,
                              cut_threshold: float = 10.0, tile=None, tile_overlap=16, output_shape=None, active=None,
                              static_tiles: bool = False, reference: Optional[str] = None, crop_border: int = 4,
-                             baseline: Optional[str] = None) -> dict:
+                             baseline: Optional[str] = None, tof: bool = False) -> dict:
     """Super-resolve the I420 sequence `src` (width x height) 4x into the I420 file `dst` (4 width x 4 height) with an RGB model
     (`FCVSRNet`, `FCVSR_SNet`).
 
@@ -295,11 +300,12 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
     ``reference`` / ``crop_border`` / ``dst=None`` as in `super_resolve_yuv420`: the Y, U and V planes of the encoded frames are what
     is scored.  ``baseline="bicubic"`` (needs ``reference``) adds ``"baseline_psnr_y"`` / ``"baseline_ssim_y"`` and their means,
     without a model pass: `device_metrics.frame_metrics` of the luma of ``rgb_to_i420(imresize(decoded RGB LR frame, out="int"),
-    colour)`` against the ground truth's."""
+    colour)`` against the ground truth's.  ``tof=True`` as in `super_resolve_yuv420`, on the luma plane of the encoded frames; with
+    ``baseline`` it adds ``"baseline_tof"``, ``"baseline_tof_mean"`` and ``"baseline_tof_pairs_mean"``."""
     shape = _check_output_shape_420(output_shape, width, height, chroma=False)
     bit_depth = colour.bit_depth if isinstance(colour, ColourSpec) else 8
     ref = check_reference(reference, dst, crop_border=crop_border, baseline=baseline, bit_depth=bit_depth, height=height,
-                          width=width, out_shape=shape)
+                          width=width, out_shape=shape, tof=tof)
     brisque = check_scores(niqe, brisque, bit_depth, 4 * height, 4 * width)
     resolver = check_keywords(model, ensemble=ensemble, tile=tile, tile_overlap=tile_overlap, batch=batch, quantise=quantise,
                               cuts=cuts, frame_dtype="uint8", channels=(3,), who="super_resolve_yuv420_rgb", active=active,
@@ -331,7 +337,8 @@ def super_resolve_yuv420_rgb(model, src: str, dst: str, width: int, height: int,
                 ysr, usr, vsr = i420_planes(out, Ho, Wo)
                 base = None if baseline is None else baseline_luma(hip.bits16(x)[s:e, :, :H, :W].view(x.dtype), shape, colour)
                 ref.add(ref.score(ysr, torch.cat([hip.bits16(usr), hip.bits16(vsr)], 0),
-                                  *_reference_planes(gt[s:e], Wo, Ho, bit_depth, dev), base))
+                                  *_reference_planes(gt[s:e], Wo, Ho, bit_depth, dev), base,
+                                  cuts=[c - s for c in cuts or () if s <= c < e]))
             if fh is not None:
                 out = hip.frames_to_numpy(out)
                 fh.write(np.ascontiguousarray(out if out.dtype.itemsize == 1 else out.astype("<u2", copy=False)).tobytes())

@@ -251,13 +251,22 @@ SIGNATURES = {
     "fcvsr_surface_unpack": [_VP, _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],
     "fcvsr_surface_pack": [_VP, _VP, _VP, C.c_longlong, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _VP, _VP],
     "fcvsr_plane_sse": [_VP, _VP, _I, _I, _I, _I, C.c_longlong, C.c_longlong, _I, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_farneback_scratch_bytes": [_I] * 3,
+    "fcvsr_farneback_flow": [_VP, _VP, _I, _I, _I, _I, C.c_longlong, C.c_longlong, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_flow_epe_scratch_bytes": [_I] * 3,
+    "fcvsr_flow_epe": [_VP, _VP, _I, _I, _I, _VP, C.c_longlong, _VP, _VP],
+    "fcvsr_flow_level_image": [_VP, _I, _I, _I, _I, C.c_longlong, _I, _VP, _VP],
+    "fcvsr_flow_poly_exp": [_VP, _I, _I, _I, _VP, _VP],
+    "fcvsr_flow_matrices": [_VP, _VP, _VP, _I, _I, _I, _VP, _VP],
+    "fcvsr_flow_box_solve": [_VP, _I, _I, _I, _VP, _VP],
 }
 _RESTYPES = {"fcvsr_last_error": C.c_char_p, "fcvsr_last_conv_kernel": C.c_char_p, "fcvsr_last_fft_path": C.c_char_p,
              "fcvsr_conv2d_wgrad_scratch_elems": C.c_longlong,
              "fcvsr_conv2d_wgrad_mfma_scratch_elems": C.c_longlong, "fcvsr_colsum_scratch_elems": C.c_longlong,
              "fcvsr_wgrad_cout1_scratch_elems": C.c_longlong, "fcvsr_conv2d_wgrad_mfma_groups_scratch_elems": C.c_longlong,
              "fcvsr_frame_metrics_scratch_bytes": C.c_longlong, "fcvsr_niqe_scratch_bytes": C.c_longlong,
-             "fcvsr_brisque_scratch_bytes": C.c_longlong, "fcvsr_ffl_workspace_elems": C.c_longlong}
+             "fcvsr_brisque_scratch_bytes": C.c_longlong, "fcvsr_ffl_workspace_elems": C.c_longlong,
+             "fcvsr_farneback_scratch_bytes": C.c_longlong, "fcvsr_flow_epe_scratch_bytes": C.c_longlong}
 
 
 def lib() -> C.CDLL:
@@ -1059,6 +1068,150 @@ def plane_sse(a: torch.Tensor, b: torch.Tensor, crop: int = 0) -> torch.Tensor:
         check(lib().fcvsr_plane_sse(a.data_ptr(), b.data_ptr(), elem, P, h, w, a.stride(0), b.stride(0), crop, scratch.data_ptr(),
                                     scratch.numel() * 8, out.data_ptr(), stream_ptr()), "fcvsr_plane_sse")
     return out
+
+
+# ---- tOF: Farneback flow and the end-point distance (csrc/flow.hip; the contract is harness/tof.py) ---------------------------------
+
+FLOW_U8, FLOW_U16, FLOW_F32, FLOW_RGB8 = 0, 1, 2, 3     # enum fcvsr_flow_elem
+FLOW_R_CHANNELS = 8                                      # FCVSR_FLOW_R_CHANNELS: floats per pixel of a polynomial expansion, 5 live
+FLOW_SCRATCH_BYTES = 1 << 30                             # `farneback_flow` scores larger batches in chunks of planes under this scratch
+_FLOW_ELEM = {torch.uint8: FLOW_U8, torch.uint16: FLOW_U16, torch.float32: FLOW_F32}
+
+
+def _flow_planes(who: str, t, rgb: bool):
+    """(tensor with dense rows, elem code, h, w) of the (P,h,w) planes - (P,3,h,w) uint8 with `rgb` - of a flow entry point."""
+    dims = 4 if rgb else 3
+    if not isinstance(t, torch.Tensor) or t.dim() != dims or (rgb and (t.dtype != torch.uint8 or t.shape[1] != 3)):
+        raise ValueError(f"{who}: expected {'(P,3,h,w) uint8 RGB frames' if rgb else '(P,h,w) planes'}, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if t.dtype == torch.int16:
+        t = t.view(torch.uint16)
+    if t.dtype not in _FLOW_ELEM:
+        raise ValueError(f"{who}: planes are uint8, uint16 (or its int16 bits) or float32, got {t.dtype}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{who} runs on the HIP device only (the host path is harness.tof.farneback_host)")
+    h, w = t.shape[-2:]
+    if h < 2 or w < 2 or h > 16384 or w > 16384 or t.shape[0] > 65535:
+        raise ValueError(f"{who}: at most 65535 planes of 2 .. 16384 samples a side, got {tuple(t.shape)}")
+    dense = t.stride(-1) == 1 and t.stride(-2) == w and (not rgb or t.stride(1) == h * w) and (t.shape[0] < 2 or t.stride(0) >= 0)
+    if not dense:
+        t = bits16(t).contiguous()
+        t = t.view(torch.uint16) if t.dtype == torch.int16 else t
+    return t, (FLOW_RGB8 if rgb else _FLOW_ELEM[t.dtype]), h, w
+
+
+def farneback_flow(prev: torch.Tensor, next: torch.Tensor, *, rgb: bool = False, **params) -> torch.Tensor:
+    """fcvsr_farneback_flow: `prev` and `next` (P,h,w) uint8, uint16 (10-bit samples, read as min(k, 1023); int16 bits are taken as
+    uint16) or f32 planes of one dtype on the HIP device - with ``rgb=True`` (P,3,h,w) uint8 RGB frames, read as the float Y of
+    `harness.metrics` - -> f32 (P,h,w,2) on the device, the dense flow [dx, dy] of every pair (`harness.tof.farneback_host` is the
+    contract: cv2.calcOpticalFlowFarneback(prev, next, None, 0.5, 3, 15, 3, 5, 1.2, 0) restated by reading).  The keywords of that
+    call (``pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags``) are accepted at exactly these values; anything
+    else is a ValueError.  Planes with dense rows are read where they lie at any plane stride: ``x[:-1]`` and ``x[1:]`` of one
+    buffer need no copy.  The flow of a pair does not depend on the batch it is in.  No host sync."""
+    from .harness.tof import check_params
+    check_params(**params)
+    prev, elem, h, w = _flow_planes("farneback_flow", prev, rgb)
+    next, elem2, h2, w2 = _flow_planes("farneback_flow", next, rgb)
+    if elem != elem2 or prev.shape != next.shape or prev.device != next.device:
+        raise ValueError(f"prev and next must share dtype, shape and device, got {prev.dtype} {tuple(prev.shape)} on {prev.device} and "
+                         f"{next.dtype} {tuple(next.shape)} on {next.device}")
+    P = prev.shape[0]
+    out = torch.empty((P, h, w, 2), dtype=torch.float32, device=prev.device)
+    if P == 0:
+        return out
+    per = int(lib().fcvsr_farneback_scratch_bytes(1, h, w))
+    step = max(1, min(P, FLOW_SCRATCH_BYTES // per))
+    with torch.cuda.device(prev.device):
+        nbytes = int(lib().fcvsr_farneback_scratch_bytes(step, h, w))
+        scratch = torch.empty((nbytes // 4,), dtype=torch.float32, device=prev.device)
+        sp, sn = (prev.stride(0) if P > 1 else 0), (next.stride(0) if P > 1 else 0)
+        for i in range(0, P, step):
+            n = min(step, P - i)
+            check(lib().fcvsr_farneback_flow(prev[i:].data_ptr(), next[i:].data_ptr(), elem, n, h, w, sp, sn, scratch.data_ptr(), nbytes,
+                                             out[i:].data_ptr(), stream_ptr()), "fcvsr_farneback_flow")
+    return out
+
+
+def _f32_dense(who: str, shape_doc: str, dims: int, *tensors):
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != dims:
+            raise ValueError(f"{who}: expected float32 {shape_doc}, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"{who} runs on the HIP device only (the host path is in harness.tof)")
+    return [t.contiguous() for t in tensors]
+
+
+def flow_epe(flow_a: torch.Tensor, flow_b: torch.Tensor) -> torch.Tensor:
+    """fcvsr_flow_epe: two f32 (P,h,w,2) flow fields on the HIP device -> f64 (P,) on the device, per plane the mean over pixels of
+    sqrt(ddx^2 + ddy^2), each value in f32, added in f64 in a fixed order (`harness.tof.epe_host`).  Two launches, no host sync."""
+    a, b = _f32_dense("flow_epe", "(P,h,w,2) flows", 4, flow_a, flow_b)
+    if a.shape != b.shape or a.shape[3] != 2 or a.device != b.device or a.shape[1] < 1 or a.shape[2] < 1 or a.shape[0] > 65535:
+        raise ValueError(f"flow_epe: two (P,h,w,2) flows of one shape and device, got {tuple(a.shape)}, {tuple(b.shape)}")
+    P, h, w, _ = a.shape
+    out = torch.empty((P,), dtype=torch.float64, device=a.device)
+    if P == 0:
+        return out
+    with torch.cuda.device(a.device):
+        nbytes = int(lib().fcvsr_flow_epe_scratch_bytes(P, h, w))
+        scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=a.device)
+        check(lib().fcvsr_flow_epe(a.data_ptr(), b.data_ptr(), P, h, w, scratch.data_ptr(), nbytes, out.data_ptr(), stream_ptr()),
+              "fcvsr_flow_epe")
+    return out
+
+
+def flow_level_size(h: int, w: int, level: int):
+    from .harness.tof import level_geometry
+    return level_geometry(h, w, level)[2]
+
+
+def flow_level_image(planes: torch.Tensor, level: int, *, rgb: bool = False) -> torch.Tensor:
+    """fcvsr_flow_level_image: stage (a) of the flow, (P,h,w) planes -> f32 (P,hl,wl), `harness.tof.level_image_host`."""
+    planes, elem, h, w = _flow_planes("flow_level_image", planes, rgb)
+    if level not in (0, 1, 2, 3):
+        raise ValueError(f"level: 0 .. 3, got {level!r}")
+    hl, wl = flow_level_size(h, w, level)
+    P = planes.shape[0]
+    out = torch.empty((P, hl, wl), dtype=torch.float32, device=planes.device)
+    with torch.cuda.device(planes.device):
+        check(lib().fcvsr_flow_level_image(planes.data_ptr(), elem, P, h, w, planes.stride(0) if P > 1 else 0, level, out.data_ptr(),
+                                           stream_ptr()), "fcvsr_flow_level_image")
+    return out
+
+
+def flow_poly_exp(img: torch.Tensor) -> torch.Tensor:
+    """fcvsr_flow_poly_exp: stage (b), f32 (n,h,w) -> (n,h,w,8), channels (y, x, yy, xx, xy, 0, 0, 0); `harness.tof.poly_exp_host`."""
+    img, = _f32_dense("flow_poly_exp", "(n,h,w) images", 3, img)
+    n, h, w = img.shape
+    R = torch.empty((n, h, w, FLOW_R_CHANNELS), dtype=torch.float32, device=img.device)
+    with torch.cuda.device(img.device):
+        check(lib().fcvsr_flow_poly_exp(img.data_ptr(), n, h, w, R.data_ptr(), stream_ptr()), "fcvsr_flow_poly_exp")
+    return R
+
+
+def flow_matrices(R0: torch.Tensor, R1: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
+    """fcvsr_flow_matrices: stage (c) from a given flow, R0, R1 (P,h,w,8), flow (P,h,w,2) -> M (P,5,h,w); `harness.tof.matrices_host`."""
+    R0, R1, flow = _f32_dense("flow_matrices", "(P,h,w,8) expansions and a (P,h,w,2) flow", 4, R0, R1, flow)
+    P, h, w, _ = R0.shape
+    if R0.shape[3] != FLOW_R_CHANNELS or R1.shape != R0.shape or tuple(flow.shape) != (P, h, w, 2):
+        raise ValueError(f"flow_matrices: R0, R1 (P,h,w,8) and flow (P,h,w,2), got {tuple(R0.shape)}, {tuple(R1.shape)}, {tuple(flow.shape)}")
+    M = torch.empty((P, 5, h, w), dtype=torch.float32, device=R0.device)
+    with torch.cuda.device(R0.device):
+        check(lib().fcvsr_flow_matrices(R0.data_ptr(), R1.data_ptr(), flow.data_ptr(), P, h, w, M.data_ptr(), stream_ptr()),
+              "fcvsr_flow_matrices")
+    return M
+
+
+def flow_box_solve(M: torch.Tensor) -> torch.Tensor:
+    """fcvsr_flow_box_solve: one iteration of stage (d) without the matrix update, M (P,5,h,w) -> flow (P,h,w,2);
+    `harness.tof.box_solve_host`."""
+    M, = _f32_dense("flow_box_solve", "(P,5,h,w) matrices", 4, M)
+    P, c, h, w = M.shape
+    if c != 5:
+        raise ValueError(f"flow_box_solve: M (P,5,h,w), got {tuple(M.shape)}")
+    flow = torch.empty((P, h, w, 2), dtype=torch.float32, device=M.device)
+    with torch.cuda.device(M.device):
+        check(lib().fcvsr_flow_box_solve(M.data_ptr(), P, h, w, flow.data_ptr(), stream_ptr()), "fcvsr_flow_box_solve")
+    return flow
 
 
 def clip_batch(desc: torch.Tensor, s: int, out: torch.Tensor, dtype: torch.dtype = torch.uint8) -> torch.Tensor:

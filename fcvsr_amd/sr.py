@@ -73,6 +73,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--reference-pix-fmt", choices=PIX_FMTS, default=None, help="default: the output format (same bit depth)")
     p.add_argument("--crop-border", type=int, default=4, help="--reference: luma border left out of the scores (even; chroma half)")
     p.add_argument("--baseline", default=None, choices=("bicubic",), help="--reference: also score the bicubic up-scale of the luma")
+    p.add_argument("--tof", action="store_true", help="--reference: also score tOF, the Farneback-flow distance to the ground truth "
+                   "(a restatement of the cv2 call; column tof of --scores-log)")
     p.add_argument("--scores-only", action="store_true", help="--reference: evaluate only; DST is neither opened nor written")
     p.add_argument("--scores-log", default=None, metavar="FILE", help="--reference: one CSV line per frame, "
                    "frame,psnr_y,psnr_u,psnr_v,psnr_yuv,ssim_y, written at the end")
@@ -86,8 +88,8 @@ def main(argv=None) -> int:
     p = parser()
     a = p.parse_args(argv)
     if a.reference is None and (a.scores_only or a.scores_log is not None or a.baseline is not None
-                                or a.reference_pix_fmt is not None):
-        p.error("--scores-only, --scores-log, --baseline and --reference-pix-fmt need --reference")
+                                or a.reference_pix_fmt is not None or a.tof):
+        p.error("--scores-only, --scores-log, --baseline, --tof and --reference-pix-fmt need --reference")
     import torch
 
     from .arch import CVSR_freq, fcvsr_rgb
@@ -110,7 +112,7 @@ def main(argv=None) -> int:
                           tile_overlap=a.tile_overlap, cuts=a.cuts, cut_threshold=a.cut_threshold,
                           output_shape=None if a.output_size is None else (a.output_size[1], a.output_size[0]),
                           max_frames=a.max_frames, active=active, static_tiles=a.static_tiles, reference=a.reference,
-                          reference_pix_fmt=a.reference_pix_fmt, crop_border=a.crop_border, baseline=a.baseline)
+                          reference_pix_fmt=a.reference_pix_fmt, crop_border=a.crop_border, baseline=a.baseline, tof=a.tof)
     if a.dst == "-" and dst is not None:
         sys.stdout.buffer.flush()
     if a.scores_log is not None:

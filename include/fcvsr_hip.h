@@ -928,6 +928,39 @@ int fcvsr_surface_pack(const void* y, const void* u, const void* v, long long y_
 #define FCVSR_PLANE_SSE_ROWS 32
 int fcvsr_plane_sse(const void* a, const void* b, int elem_size, int P, int h, int w, long long a_stride, long long b_stride, int crop,
                     void* scratch, long long scratch_bytes, long long* out, void* stream);
+/* ---- tOF: dense Farneback flow and the end-point distance of two flows (csrc/flow.hip; the contract is fcvsr_amd/harness/tof.py,
+ * farneback_host: a restatement of cv2.calcOpticalFlowFarneback(prev, next, None, 0.5, 3, 15, 3, 5, 1.2, 0) by reading; cv2 was never
+ * run against it) -----------------------------------------------------------------------------------------------------------------
+ * prev, next: P planes each of h x w samples with dense rows, stride_prev / stride_next SAMPLES apart (planes[:-1] and planes[1:] of
+ * one buffer are the two arguments).  elem: FCVSR_FLOW_U8, _U16 (a sample above 1023 reads as 1023), _F32, or _RGB8: every "plane"
+ * is three dense uint8 planes R, G, B (3 h w samples) read as the float Y ((65.481 R + 128.553 G) + 24.966 B) / 255 + 16.
+ * flow_out: DEVICE f32 (P,h,w,2), [dx, dy] from prev to next.  All arithmetic is f32 in a fixed order that depends on neither P nor
+ * the launch geometry: the flow of a pair is the same bits in any batch.  No atomics, no host sync.  scratch: DEVICE, 16-byte
+ * aligned, at least fcvsr_farneback_scratch_bytes(P, h, w) bytes (-1 for sizes outside the limits below).
+ * Layouts: a polynomial expansion R is (images,h,w,FCVSR_FLOW_R_CHANNELS) f32, channels (y, x, yy, xx, xy, 0, 0, 0): one pixel is
+ * two 16-byte words, which is what the four-neighbour gather and the stores want; the matrices M are planar (P,5,h,w) f32 (g11, g12,
+ * g22, h1, h2), what the 15x15 box sums read row by row.
+ * FCVSR_E_ARG before any device call: another elem, P outside 0 .. 65535, h or w outside 2 .. 16384, a negative stride, a null or
+ * misaligned pointer, a scratch that is too small.  P = 0 writes nothing. */
+enum fcvsr_flow_elem { FCVSR_FLOW_U8 = 0, FCVSR_FLOW_U16 = 1, FCVSR_FLOW_F32 = 2, FCVSR_FLOW_RGB8 = 3 };
+#define FCVSR_FLOW_R_CHANNELS 8
+long long fcvsr_farneback_scratch_bytes(int P, int h, int w);
+int fcvsr_farneback_flow(const void* prev, const void* next, int elem, int P, int h, int w, long long stride_prev, long long stride_next,
+                         void* scratch, long long scratch_bytes, float* flow_out, void* stream);
+/* flow_a, flow_b: DEVICE f32 (P,h,w,2), dense.  out: DEVICE f64 (P), out[p] = the mean over pixels of sqrt(ddx^2 + ddy^2), each
+ * value in f32 (a correctly rounded square root), added in f64: fixed-order partial sums per workgroup, then a second launch.
+ * scratch: DEVICE, 8-byte aligned, at least fcvsr_flow_epe_scratch_bytes(P, h, w) bytes. */
+long long fcvsr_flow_epe_scratch_bytes(int P, int h, int w);
+int fcvsr_flow_epe(const float* flow_a, const float* flow_b, int P, int h, int w, void* scratch, long long scratch_bytes, double* out,
+                   void* stream);
+/* The stages of fcvsr_farneback_flow, one launch each, as the whole flow runs them (the tests pin each to the host contract).
+ * level_image: P planes -> out (P,hl,wl), the blurred and resized image of pyramid level `level` (0 .. 3; hl = round_half_even(h /
+ * 2^level)).  poly_exp: img (n,h,w) -> R (n,h,w,8).  matrices: R0, R1 (P,h,w,8), flow (P,h,w,2) -> M (P,5,h,w).  box_solve: M ->
+ * flow (P,h,w,2), the 15x15 box average and the 2x2 solve. */
+int fcvsr_flow_level_image(const void* src, int elem, int P, int h, int w, long long stride, int level, float* out, void* stream);
+int fcvsr_flow_poly_exp(const float* img, int n, int h, int w, float* R, void* stream);
+int fcvsr_flow_matrices(const float* R0, const float* R1, const float* flow, int P, int h, int w, float* M, void* stream);
+int fcvsr_flow_box_solve(const float* M, int P, int h, int w, float* flow, void* stream);
 #ifdef __cplusplus
 }
 #endif
